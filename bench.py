@@ -2,6 +2,7 @@
 """bench.py -- retrieval QPS of the fused HNSW-with-model-scoring traversal on MI355X.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   (+ the last timed step's answers as DIR/*.npy)
     python bench.py --gpus 8 ...            (spawns one rank per GPU itself), or
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -90,6 +91,9 @@ def parse():
     ap.add_argument("--index-cache", default=None, help="directory to cache built indices in")
     ap.add_argument("--stress-items", type=int, default=4_000_000,
                     help="items of the HBM-honest secondary workload: configs[4]'s shard at its own size (4M x 256-d bf16, ef=256)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (item ids, scores, status) as "
+                         "DIR/<name>.npy in float32 / float64 (rank 0; a seeded sample of rows beyond 64 MB)")
     ap.add_argument("--phase-ticks", action="store_true",
                     help="one extra instrumented launch: per-phase time attribution")
     return ap.parse_args()
@@ -207,6 +211,27 @@ def n_clusters_for(items, ef):
     ef = 64: 20 % of the requests valid; clusters of >= 30 ef items: 100 %).  256 clusters wherever they stay that
     large (1M items / ef = 128 and up: the round-1/2 corpora unchanged), fewer for small corpora / wide beams."""
     return int(min(256, max(1, items // (30 * ef))))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dump_dir, arrays, seed=2024):
+    """Write {name: array} as dump_dir/<name>.npy: integer and f64 arrays as float64 (item ids stay exact below 2^53),
+    the rest as float32.  When the rows together pass DUMP_LIMIT_BYTES, a fixed seeded sample of rows (the same for every
+    array, ascending) is written instead, with its row numbers as sample_rows.npy."""
+    os.makedirs(dump_dir, exist_ok=True)
+    out = {k: np.asarray(v) for k, v in arrays.items()}
+    out = {k: v.astype(np.float64 if v.dtype.kind in "iub" or v.dtype == np.float64 else np.float32) for k, v in out.items()}
+    n = len(next(iter(out.values())))
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, int(n * DUMP_LIMIT_BYTES // total) - 1)
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        out = {k: v[rows] for k, v in out.items()}
+        out["sample_rows"] = rows.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(dump_dir, k + ".npy"), v)
 
 
 def make_index(items, dim, ef, graph, noise, dtype, rank, dev, n_threads, cache_dir=None):
@@ -357,6 +382,12 @@ def run_workload(name, args, dev, rank, world, cfg, sharded=None, want_cpu=False
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
     host_enqueue_ms = [round((b - a) * 1e3, 3) for a, b in zip([t_start] + host_marks[:-1], host_marks)]
+    if cfg.get("dump_dir") and rank == 0:
+        # what a caller of the timed path receives from its last step (sharded: the merged answer over every shard)
+        arrays = {"item_ids": out[0].cpu().numpy(), "scores": out[1].cpu().numpy()}
+        if sharded is None:
+            arrays["status"] = r.status.cpu().numpy()
+        dump_outputs(cfg["dump_dir"], arrays)
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -861,7 +892,7 @@ def main():
     tag = f"{args.items}x{args.dim}{args.dtype}_ef{args.ef}_k{args.topk}_b{args.batch}_{args.scorer}_{args.graph}"
     if args.scorer == "mlp" and args.mlp_precision == "exact":
         tag += "_exact"  # (its own counters in profiles/pmc_latest.json)
-    prim = run_workload(tag, args, dev, rank, world, primary_cfg, sharded=sharded,
+    prim = run_workload(tag, args, dev, rank, world, dict(primary_cfg, dump_dir=args.dump_outputs), sharded=sharded,
                         want_cpu=not args.no_cpu_baseline, want_parity=True, want_recall=True)
 
     qps = prim["qps_end_to_end"]

@@ -3,6 +3,7 @@
 // in nann_device.h.  Reference citations are relative to /root/reference/.
 #include "nann_eval.h"
 #include "nann_attn.h"
+#include "nann_order_kernels.h"
 #include "host/nann_graphdef_text.h"
 #include "host/nann_blaze_options.h"
 #include "host/nann_npy.h"
@@ -703,22 +704,24 @@ typedef nann::ProjTableT<HipProjBackend> ProjTable;
 // Every knob of the planner is a field of nann_search_options (include/nann_hip.h, round 5); a field left at -1 takes the
 // PROCESS DEFAULT: what nann_set_traversal_mode / nann_set_search_reserve / nann_set_preprojection last stored, else the
 // environment read ONCE below (A/B tooling: NANN_PREPROJECT=0, NANN_SEARCH_SLOT_RESERVE=n, NANN_MLP_FORM=fused|phased,
-// NANN_PHASE_SMALL32=0), else the built-in value.  plan_search and the launchers only ever see the resolved struct.
+// NANN_PHASE_SMALL32=0, NANN_QUERY_ORDER=0), else the built-in value.  plan_search and the launchers only ever see the resolved struct.
 struct SearchOpt {
   int mode;        // nann_traversal_mode
   int reserve;     // workgroup slots the persistent grids leave free
   int preproject;  // 1: the MLP / attention scorers read their pre-projected tables
   int mlp_form;    // nann_mlp_form
   int small32;     // 1: at most one query per CU -> one 1024-thread workgroup per CU for the traversal (stages)
+  int order;       // 1: L2 hash-set plans run a batch larger than their slots in locality order (nann_order.h)
 };
 static std::atomic<int> g_traversal_mode{-1}, g_slot_reserve{-1}, g_preproject{-1};
 static const SearchOpt& env_defaults() {
   static const SearchOpt d = [] {
-    SearchOpt o{NANN_TRAVERSAL_AUTO, 0, 1, NANN_MLP_FORM_AUTO, 1};
+    SearchOpt o{NANN_TRAVERSAL_AUTO, 0, 1, NANN_MLP_FORM_AUTO, 1, 1};
     if (const char* e = std::getenv("NANN_PREPROJECT")) o.preproject = !(e[0] == '0' && e[1] == 0);
     if (const char* e = std::getenv("NANN_SEARCH_SLOT_RESERVE")) o.reserve = std::max(0, std::atoi(e));
     if (const char* e = std::getenv("NANN_MLP_FORM")) o.mlp_form = std::string(e) == "fused" ? NANN_MLP_FORM_FUSED : std::string(e) == "phased" ? NANN_MLP_FORM_PHASED : NANN_MLP_FORM_AUTO;
     if (const char* e = std::getenv("NANN_PHASE_SMALL32")) o.small32 = !(e[0] == '0');
+    if (const char* e = std::getenv("NANN_QUERY_ORDER")) o.order = !(e[0] == '0');
     return o;
   }();
   return d;
@@ -779,8 +782,15 @@ struct nann_index {
   bool probe_valid = false;
   int probe_ef = 0, probe_queries = 0;
   float probe_new_per_row_mean = 0.0f, probe_new_per_row_q90 = 0.0f, probe_new_per_row_max = 0.0f;
+  // the pivots of the batch order (nann_order.h): f32 [d][n_pivots] rows, then their squared norms (kOrderMaxPivots
+  // floats); n_pivots < 2: no order
+  float* pivots = nullptr;
+  int n_pivots = 0;
 };
 static void probe_index(nann_index* ix);  // (defined behind search_impl)
+static void choose_pivots(nann_index* ix, const std::vector<int32_t>& enter);
+static int launch_order(const nann_index* ix, const float* q, int n, int32_t* key, int32_t* perm, unsigned int* heads,
+                        hipStream_t st);
 
 extern "C" {
 
@@ -1858,6 +1868,7 @@ int nann_index_create(const nann_index_desc* desc, nann_index** out) {
     ix->owns = true;
     dd.on_device = 1;
   }
+  choose_pivots(ix, ep_host);  // the batch order's pivots (never fails the creation: without them, input order)
   probe_index(ix);  // what a beam visits on this graph: 64 queries, one small launch (never fails the creation)
   *out = ix;
   return NANN_OK;
@@ -1867,6 +1878,7 @@ void nann_index_destroy(nann_index* ix) {
   if (!ix) return;
   ProjCache::drop_index(ix->uid);  // the scorers' pre-projected tables of this index go with it (retired, then freed)
   for (void* p : ix->owned) (void)hipFree(p);
+  if (ix->pivots) (void)hipFree(ix->pivots);
   delete ix;
 }
 
@@ -2109,7 +2121,8 @@ int nann_search_workspace_bytes(const nann_index* ix, const int32_t level_topn[6
   SearchPlan p;
   const int rc = plan_search(ix, level_topn, n_queries, -1, &p, resolve_options(nullptr));  // (kind "any": the widest plan, whatever the options)
   if (rc) return rc;
-  *nbytes = (int64_t)(256 + p.slot_bytes * (unsigned long long)std::max(p.slots, p.fb_slots) + kPhaseTail);
+  *nbytes = (int64_t)(256 + p.slot_bytes * (unsigned long long)std::max(p.slots, p.fb_slots) + kPhaseTail +
+                      order_ws_bytes(n_queries));
   return NANN_OK;
 }
 
@@ -2257,12 +2270,31 @@ static int search_impl(const nann_index* ix, const nann_scorer* scorer, const na
   HIP_TRY(hipMemsetAsync(workspace, 0, 256, st));  // WsHeader: query queues, hand-back counter
   const int dt = ix->desc.emb_dtype;
   const bool hashed = p.vis == VIS_LDS_HASH || p.vis == VIS_LDS_HASH32;
+  // L2 hash-set plans with more queries than slots: the main launch takes the batch in locality order (nann_order.h);
+  // the rerun launch, the MLP / attention scorers and the bitmap plans keep input order.  The order lives behind the
+  // slots, at the last 256-byte boundary that leaves order_ws_bytes(n) behind it (nann_search_workspace_bytes counts
+  // them); a workspace sized without them runs in input order.
+  const unsigned long long slots_end = 256 + p.slot_bytes * (unsigned long long)std::max(p.slots, p.fb_slots) + kPhaseTail;
+  const unsigned long long order_off = ((unsigned long long)workspace_bytes - order_ws_bytes(n_queries)) & ~255ull;
+  if (opt.order && hashed && !attn && kind == NANN_SCORER_L2 && ix->n_pivots >= 2 && n_queries > p.slots &&
+      (unsigned long long)workspace_bytes >= ((slots_end + 255) & ~255ull) + order_ws_bytes(n_queries)) {
+    unsigned char* ow = static_cast<unsigned char*>(workspace) + order_off;
+    unsigned int* heads = reinterpret_cast<unsigned int*>(ow);
+    int32_t* perm = reinterpret_cast<int32_t*>(ow + kOrderSegs * kOrderHeadStride * 4);
+    int32_t* key = perm + n_queries;
+    rc = launch_order(ix, q, (int)n_queries, key, perm, heads, st);
+    if (rc) return rc;
+    a.perm = perm;
+    a.xheads = heads;
+  }
   // main launch, then -- hash-set plans -- the rerun of the queries whose set could have overflowed on the bitmap
   // kernel (its workgroups leave at once when there is none)
   auto both = [&](auto&& launch_on) -> int {
     int r2 = launch_on(p.vis, p.nt, p.slots, p.lds_bytes);
     if (!r2 && hashed) {
       a.redo = 1;
+      a.perm = nullptr;
+      a.xheads = nullptr;
       r2 = launch_on(p.fb_vis, kNT, p.fb_slots, p.fb_lds_bytes);
     }
     if (cache) projection_used(*cache, tab, st);
@@ -2350,6 +2382,82 @@ __global__ void k_probe_queries(const void* emb, int dt, int d, long long n_item
     }
     q[(size_t)j * d + k] = v;
   }
+}
+
+// ---- the pivots of the batch order ------------------------------------------------------------------------------------
+// Farthest-point sample of the enter points (the graph's upper levels, spread over the corpus by construction): P of
+// them, P = order_pivots(n_enter, d).  Their rows are gathered to f32 once on the NULL stream (blocking, like the probe).
+__global__ void k_order_gather(const void* emb, int dt, int d, const int32_t* rows, int m, float* out) {
+  for (int k = threadIdx.x; k < d; k += blockDim.x) out[(size_t)blockIdx.x * d + k] = order_row_elem(emb, dt, (size_t)rows[blockIdx.x] * d + k);
+}
+
+// key and order kernels on `st`: key[n] (scratch), perm[n], the segment heads zeroed
+static int launch_order(const nann_index* ix, const float* q, int n, int32_t* key, int32_t* perm, unsigned int* heads,
+                        hipStream_t st) {
+  const int d = ix->desc.d, P = ix->n_pivots;
+  const size_t lds = ((size_t)d * P + kOrderMaxPivots + (size_t)kOrderKeyQueries * d) * 4;
+  if (lds > 48 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_order_key), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_order_key, dim3((unsigned)((n + kOrderKeyQueries - 1) / kOrderKeyQueries)), dim3(256), lds, st,
+                     ix->pivots, d, P, q, n, key);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_order_perm, dim3(1), dim3(kOrderSortThreads), 0, st, key, n, P, perm, heads);
+  HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+static void choose_pivots(nann_index* ix, const std::vector<int32_t>& enter) {
+  const int d = ix->desc.d;
+  const int P = order_pivots((int64_t)enter.size(), d);
+  if (P < 2) return;
+  constexpr size_t kMaxCand = 1024;  // candidates: the enter points, strided down to at most this many
+  const size_t E = enter.size(), m = std::min(E, kMaxCand);
+  std::vector<int32_t> cand(m);
+  for (size_t i = 0; i < m; ++i) cand[i] = enter[i * E / m];
+  int32_t* rows = nullptr;
+  float* buf = nullptr;
+  std::vector<float> x(m * (size_t)d);
+  bool ok = hipMalloc(&rows, m * 4) == hipSuccess && hipMalloc(&buf, m * (size_t)d * 4) == hipSuccess &&
+            hipMemcpy(rows, cand.data(), m * 4, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_order_gather, dim3((unsigned)m), dim3(128), 0, nullptr, ix->desc.item_embs, ix->desc.emb_dtype, d, rows, (int)m, buf);
+    ok = hipGetLastError() == hipSuccess && hipMemcpy(x.data(), buf, x.size() * 4, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  if (buf) (void)hipFree(buf);
+  if (rows) (void)hipFree(rows);
+  if (!ok) return;
+  std::vector<size_t> piv;
+  std::vector<double> dist(m, INFINITY);
+  size_t cur = 0;
+  for (int p = 0; p < P; ++p) {
+    piv.push_back(cur);
+    size_t far = cur;
+    for (size_t i = 0; i < m; ++i) {
+      double s = 0.0;
+      for (int k = 0; k < d; ++k) { const double t = (double)x[i * d + k] - (double)x[cur * d + k]; s += t * t; }
+      dist[i] = std::min(dist[i], s);
+      if (dist[i] > dist[far]) far = i;
+    }
+    if (dist[far] <= 0.0) break;  // (fewer distinct rows than P)
+    cur = far;
+  }
+  if (piv.size() < 2) return;
+  const size_t np = piv.size();
+  std::vector<float> t((size_t)d * np + kOrderMaxPivots, 0.0f);  // [d][np], then the norms
+  for (size_t p = 0; p < np; ++p) {
+    float s = 0.0f;
+    for (int k = 0; k < d; ++k) {
+      const float v = x[piv[p] * d + k];
+      t[(size_t)k * np + p] = v;
+      s += v * v;
+    }
+    t[(size_t)d * np + p] = s;
+  }
+  float* dev = nullptr;
+  if (hipMalloc(&dev, t.size() * 4) != hipSuccess) return;
+  if (hipMemcpy(dev, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dev); return; }
+  ix->pivots = dev;
+  ix->n_pivots = (int)piv.size();
 }
 
 static void probe_index(nann_index* ix) {
@@ -2521,8 +2629,8 @@ int nann_search_model_workspace_bytes(const nann_index* ix, const nann_model* m,
   SearchPlan p;
   const int rc = plan_search(ix, level_topn, n_queries, m->kind == NANN_MODEL_ATTENTION ? kKindAttn : -1, &p, resolve_options(nullptr));
   if (rc) return rc;
-  *nbytes = (int64_t)(256 + p.slot_bytes * (unsigned long long)std::max(p.slots, p.fb_slots) + kPhaseTail + 256 +
-                      model_query_bytes(m, n_queries));
+  *nbytes = (int64_t)(256 + p.slot_bytes * (unsigned long long)std::max(p.slots, p.fb_slots) + kPhaseTail +
+                      order_ws_bytes(n_queries) + 256 + model_query_bytes(m, n_queries));
   return NANN_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <type_traits>
 #include "../../include/nann_hip.h"
 #include "nann_device.h"
+#include "nann_order.h"
 #include "nann_mlp.h"
 #include "nann_mlp2.h"
 #include "nann_mlp3.h"
@@ -139,6 +140,10 @@ struct SearchArgs {
   int redo;                // 1: fallback launch, only queries with status NANN_ERR_CAPACITY
   int phase;               // kScorerMlpPhase: which traversal stage this launch runs (0: up to the entry layer's scoring call,
                            // p = 1..5: from behind round p - 1's scoring call up to round p's, 5: to the end); nann_mlp6.h
+  // locality order of the batch (nann_order.h): perm holds the query indices by nearest pivot, cut into kOrderSegs
+  // contiguous segments; xheads[s * kOrderHeadStride] is segment s's next position.  Null: input order, one counter.
+  const int32_t* perm = nullptr;
+  unsigned int* xheads = nullptr;
 };
 
 static_assert(PH_COUNT == NANN_NUM_PHASES, "phase list out of sync with include/nann_hip.h");
@@ -642,13 +647,29 @@ __global__ __launch_bounds__(NT, ((VIS == VIS_LDS_HASH && (SC == NANN_SCORER_L2 
   }
 
   // queries are pulled from one device-wide counter: a slot that finishes early takes
-  // the next request instead of idling until the slowest slot is done
+  // the next request instead of idling until the slowest slot is done.  With a locality order (a.perm) there is one
+  // counter per XCD instead: a slot works through its own XCD's segment of the ordered batch (neighbouring queries
+  // share rows in that XCD's L2), then takes from the other segments in a fixed rotation -- placement only ever
+  // decides speed: every position of every segment is handed out exactly once, whatever the XCD mapping
+  int seg = 0;  // (thread 0) segments [xcd, xcd + seg) are known empty
+  unsigned int xcd = 0;
+  if (a.perm && threadIdx.x == 0) xcd = xcc_id() % kOrderSegs;
   for (;;) {
     __syncthreads();
     if (threadIdx.x == 0) {
-      int qn = (int)atomicAdd(queue, 1u);
-      if (a.redo)  // skip the queries that are done
-        while (qn < a.n_queries && a.status[qn] != NANN_ERR_CAPACITY) qn = (int)atomicAdd(queue, 1u);
+      int qn = a.n_queries;
+      if (a.perm) {
+        for (; seg < kOrderSegs; ++seg) {
+          const unsigned int s = (xcd + (unsigned int)seg) % kOrderSegs;
+          const int lo = order_seg_begin(a.n_queries, (int)s), n = order_seg_begin(a.n_queries, (int)s + 1) - lo;
+          const int pos = (int)atomicAdd(&a.xheads[s * kOrderHeadStride], 1u);
+          if (pos < n) { qn = a.perm[lo + pos]; break; }
+        }
+      } else {
+        qn = (int)atomicAdd(queue, 1u);
+        if (a.redo)  // skip the queries that are done
+          while (qn < a.n_queries && a.status[qn] != NANN_ERR_CAPACITY) qn = (int)atomicAdd(queue, 1u);
+      }
       misc[0] = qn;
     }
     if (threadIdx.x < 3 * NANN_NUM_ROUNDS) s_ctr[threadIdx.x] = 0;

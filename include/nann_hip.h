@@ -204,8 +204,18 @@ typedef struct {
  *   switched off) the kernels that read the embedding rows run instead: same results for EXACT_F32, same tolerance for
  *   SPLIT_F16.  nann_score (stand-alone rows, no index) runs all three layers on the matrix cores.
  *   DEFAULT    (0, what a zero-initialised descriptor asks for) SPLIT_F16 when the weights meet its
- *              precondition, else EXACT_F32: 1e-5 is the contract, bit-exactness is opt-in. */
-enum nann_mlp_precision { NANN_MLP_PRECISION_DEFAULT = 0, NANN_MLP_SPLIT_F16 = 1, NANN_MLP_EXACT_F32 = 2 };
+ *              precondition, else EXACT_F32: 1e-5 is the contract, bit-exactness is opt-in.
+ *   CERTIFIED  ids, scores, out_index and counters BIT-identical to EXACT_F32 (and so to the oracle) for every weight
+ *              set EXACT_F32 accepts: no |w| or activation precondition.  In the pipeline of phases (nann_search_plan
+ *              .phased) a round is scored by an f16 filter -- one v_mfma_f32_32x32x16_f16 per fragment, an approximate
+ *              score and a rigorous bound on its distance to the exact one -- and only the rows whose bound interval
+ *              reaches the round's k-th largest lower bound are rescored exactly (csrc/nann_mlp6.h); a row the filter
+ *              cannot bound (f16 overflow, non-finite values) is always rescored.  Everywhere else CERTIFIED runs the
+ *              EXACT_F32 kernels: the planner's non-phased plans, the bitmap rerun of handed-back queries,
+ *              preprojection = 0, nann_score, nann_search_eval*; mlp_form = FUSED is taken as PHASED.  Rows rescored
+ *              per round: nann_search_refined.  MLP scorers only (nann_attn_scorer_create rejects it). */
+enum nann_mlp_precision { NANN_MLP_PRECISION_DEFAULT = 0, NANN_MLP_SPLIT_F16 = 1, NANN_MLP_EXACT_F32 = 2,
+                          NANN_MLP_CERTIFIED = 3 };
 int nann_scorer_create(const nann_scorer_desc* desc /*[host]*/, nann_scorer** out);
 void nann_scorer_destroy(nann_scorer* s);
 
@@ -261,7 +271,7 @@ int nann_score(const nann_scorer* scorer, const float* q, const void* table,
  *                nann_graphdef.h), batch norm folded to scale / shift, and handed to the hand-written kernels
  *                (nann_attn_desc).  A graph that is not that model -> NANN_ERR_UNSUPPORTED naming what is
  *                missing; a file that parses as neither -> NANN_ERR_IO.  An optional `<file>.precision` beside it
- *                holds "split" | "exact".
+ *                holds "split" | "exact" (| "certified": MLP only).
  *   a DIRECTORY  of .npy weight files, for scorers that have no frozen graph in the reference (BASELINE's L2
  *                and MLP) and for hosts that hold the model as arrays:
  *                  scorer.txt   one word: l2 | mlp | attention
@@ -269,7 +279,7 @@ int nann_score(const nann_scorer* scorer, const float* q, const void* table,
  *                  attention    wq1 bq1 aq wq2 bq2 wk1 bk1 ak wk2 bk2  w0..w3  b0..b2  bn_scale0..2  bn_shift0..2
  *                               alpha0..2                                                    (nann_attn_desc)
  *                  precision.txt (optional, mlp / attention): "split" (default: split-f16 operands on the 16-bit
- *                               MFMA) | "exact" (f32-input MFMA)
+ *                               MFMA) | "exact" (f32-input MFMA) | "certified" (mlp only: NANN_MLP_CERTIFIED)
  *                Every tensor is checked against the element count (d, seq_len) imply: NANN_ERR_SHAPE_MISMATCH.
  * nann_model_forward is forward() of build_opt_graph.py:91-107 for ONE user: user_seq f16
  * [seq_len, d] (l2 / mlp: its non-pad mean is the query vector; attention: [seq_len, 64]),
@@ -466,6 +476,10 @@ int nann_search_opt(const nann_index* ix, const nann_scorer* scorer, const float
                     int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan, nann_stream_t stream);
 /* queries of the LAST search on `workspace` that were rerun on the bitmap kernel (phased MLP: of its last chunk) */
 int nann_search_reruns(const void* workspace, int64_t* n_rerun, nann_stream_t stream);
+/* rows the LAST search on `workspace` rescored exactly, per round, summed over its queries (NANN_MLP_CERTIFIED in the
+ * pipeline of phases; counters' S_r counts every scored row, rescored or not).  0 for rounds no filter ran: other
+ * precisions and scorers, and the plans on which CERTIFIED runs the exact kernels.  Synchronises `stream`. */
+int nann_search_refined(const void* workspace, int64_t out[NANN_NUM_ROUNDS], nann_stream_t stream);
 
 /* The serving signature in one call (build_opt_graph.py:151-159): comm_seq f16[n_queries, seq_len, E]
  * + level_topn -> top_k, scored by whatever model the BlazeXlaOp nodes of the graph name.  l2 / mlp:
@@ -642,7 +656,7 @@ typedef struct {
   const float* alpha[3];
   int32_t precision;  /* enum nann_mlp_precision: NANN_MLP_SPLIT_F16 (every f32 operand as hi + lo f16 on the
                        * 16-bit MFMA, 3x fewer matrix cycles; logits within ~1e-6 of the exact form; the default),
-                       * NANN_MLP_EXACT_F32 (f32-input MFMA) */
+                       * NANN_MLP_EXACT_F32 (f32-input MFMA); NANN_MLP_CERTIFIED is rejected (MLP scorers only) */
 } nann_attn_desc;
 int nann_attn_scorer_create(const nann_attn_desc* desc /*[host]*/, nann_attn_scorer** out);
 void nann_attn_scorer_destroy(nann_attn_scorer* s);

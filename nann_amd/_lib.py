@@ -19,7 +19,7 @@ STATUS_NAMES = {
 }
 F16, BF16, F32, I32, I64, F64 = 0, 1, 2, 3, 4, 5
 SCORER_L2, SCORER_MLP = 0, 1
-MLP_DEFAULT, MLP_SPLIT_F16, MLP_EXACT_F32 = 0, 1, 2
+MLP_DEFAULT, MLP_SPLIT_F16, MLP_EXACT_F32, MLP_CERTIFIED = 0, 1, 2, 3
 NUM_ROUNDS = 5
 NUM_PHASES = 19
 PHASE_NAMES = ("zero", "walk", "expand", "score", "topk", "other", "tk_load", "tk_search",
@@ -34,7 +34,7 @@ SYMBOLS = [
     "nann_group_gather_fill", "nann_group_gather_unique_scratch_bytes", "nann_group_gather_unique", "nann_bitmap_ref_difference", "nann_bloom_filter_difference", "nann_gather_rows", "nann_topk",
     "nann_scorer_create", "nann_scorer_destroy", "nann_user_seq_mean", "nann_score",
     "nann_index_create", "nann_index_destroy", "nann_index_info", "nann_index_probe_info", "nann_search_workspace_bytes",
-    "nann_search", "nann_search_v", "nann_search_ex", "nann_search_opt", "nann_search_options_init", "nann_search_reruns", "nann_search_model_opt", "nann_set_traversal_mode", "nann_set_search_reserve", "nann_search_model_workspace_bytes",
+    "nann_search", "nann_search_v", "nann_search_ex", "nann_search_opt", "nann_search_options_init", "nann_search_reruns", "nann_search_refined", "nann_search_model_opt", "nann_set_traversal_mode", "nann_set_search_reserve", "nann_search_model_workspace_bytes",
     "nann_search_model", "nann_search_model_v",
     "nann_scorer_prepare", "nann_scorer_release", "nann_scorer_table_bytes", "nann_set_preprojection",
     "nann_model_prepare", "nann_model_release", "nann_model_table_bytes", "nann_search_eval_workspace_bytes", "nann_search_eval", "nann_search_eval_ex", "nann_search_eval_model",

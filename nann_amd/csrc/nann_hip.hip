@@ -12,10 +12,12 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -758,6 +760,7 @@ struct nann_scorer {
   float* dev_weights = nullptr;  // MLP weights block in HBM
   uint4* dev_packed = nullptr;   // split-f16 planes in MFMA A-fragment order
   float4* dev_packed_x = nullptr;  // W2 as f32 A fragments (exact form, layer 2 resident in LDS)
+  float* dev_cert = nullptr;       // certified form: the filter's c_j (certified_bound)
   MlpParams mlp = {};
   mutable ProjCache proj;
 };
@@ -1222,6 +1225,48 @@ static void pack_split_weights(const float* w1, const float* w2, int d, int h1, 
           }
 }
 
+// The certified form's bound constants (derivation above mlp_filter_vectors, nann_mlp6.h): c_j = sum_m w_jm |w3_m| M_m with
+// w_jm = |W2_jm| widened where the f16 plane's error is not within u16 relative, K1 2^-7 and K0; all rounded up to f32.
+static void certified_bound(const float* w2, const float* b2, const float* alpha2, const float* w3, int h1, int h2,
+                            std::vector<float>* c, float* k1s, float* k0) {
+  const double u = std::ldexp(1.0, -24), u16 = std::ldexp(1.0, -11), eta = std::ldexp(1.0, -13);
+  auto gam = [&](double n, double unit) { return n * unit / (1.0 - n * unit); };
+  const double g257 = gam(h1 + 1, u), gp257 = gam(h1 + 1, 2 * u), g129 = gam(h2 + 1, u);
+  const double a1 = u16 * (2 + u16) + gp257 * (1 + u16) * (1 + u16) + g257;
+  const double K1 = a1 + (3 * u * (1 + u) + g129 * (1 + 3 * u * (1 + u))) * (1 + g257 + a1) + (u + g129 * (1 + u)) * (1 + g257);
+  const double zeta = eta / 128.0 * (1 + gp257) * (1 + u16);
+  std::vector<double> wm(h2);
+  double sb = 0.0;
+  for (int m = 0; m < h2; ++m) {
+    wm[m] = std::fabs((double)w3[m]) * std::max(1.0, std::fabs((double)alpha2[m]));
+    sb += wm[m] * std::fabs((double)b2[m]);
+  }
+  auto up = [](double v) {  // the f32 at or above v
+    float f = (float)v;
+    if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
+    return f;
+  };
+  c->assign(h1, 0.0f);
+  double sc = 0.0;
+  for (int j = 0; j < h1; ++j) {
+    double cj = 0.0;
+    for (int m = 0; m < h2; ++m) {
+      const double w = w2[(size_t)j * h2 + m], sw = w * 128.0;
+      const double hv = (double)f16_bits_to_f32(f32_to_f16_rne((float)sw));
+      double e = std::fabs(hv - sw);
+      if (hv != 0.0 && std::fabs(hv) < std::ldexp(1.0, -14)) e = std::max(e, std::fabs(sw));  // subnormal: maybe flushed
+      e /= 128.0;
+      const double wide = std::fabs(w) + std::max(0.0, e - u16 * std::fabs(w)) / u16;
+      cj += wide * wm[m];
+    }
+    (*c)[j] = up(cj);
+    sc += cj;
+  }
+  constexpr double kMargin = 1.001;  // the kernel's f32 evaluation of B (two chains of 128 fmaf, an add, an fmaf)
+  *k1s = up(K1 * kMargin / 128.0);
+  *k0 = up((K1 * sb + 2 * zeta * sc) * kMargin + std::ldexp(1.0, -120));
+}
+
 int nann_scorer_create(const nann_scorer_desc* desc, nann_scorer** out) {
   if (!desc || !out) return fail(NANN_ERR_BAD_ARGUMENT, "nann_scorer_create: null argument");
   const int d = desc->d;
@@ -1266,11 +1311,21 @@ int nann_scorer_create(const nann_scorer_desc* desc, nann_scorer** out) {
     s->mlp.w2 = w + o_w2; s->mlp.b2 = w + o_b2; s->mlp.alpha2 = w + o_a2; s->mlp.w3 = w + o_w3;
     s->mlp.d = d; s->mlp.h1 = 256; s->mlp.h2 = 128;
     if (desc->precision != NANN_MLP_PRECISION_DEFAULT && desc->precision != NANN_MLP_EXACT_F32 &&
-        desc->precision != NANN_MLP_SPLIT_F16) {
+        desc->precision != NANN_MLP_SPLIT_F16 && desc->precision != NANN_MLP_CERTIFIED) {
       nann_scorer_destroy(s);
       return fail(NANN_ERR_BAD_ARGUMENT, "MLP scorer: unknown precision");
     }
-    if (desc->precision != NANN_MLP_EXACT_F32) {  // the pre-scaled weights must stay inside f16's range
+    if (desc->precision == NANN_MLP_CERTIFIED) {  // no precondition: rows the filter cannot bound are refined
+      std::vector<float> c;
+      certified_bound(desc->w2, desc->b2, desc->alpha2, desc->w3, 256, 128, &c, &s->mlp.k1s, &s->mlp.k0);
+      e = hipMalloc(reinterpret_cast<void**>(&s->dev_cert), c.size() * 4);
+      if (e == hipSuccess) e = hipMemcpy(s->dev_cert, c.data(), c.size() * 4, hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+        nann_scorer_destroy(s);
+        return fail(NANN_ERR_HIP, std::string("scorer weights: ") + hipGetErrorString(e));
+      }
+      s->mlp.cb = s->dev_cert;
+    } else if (desc->precision != NANN_MLP_EXACT_F32) {  // the pre-scaled weights must stay inside f16's range
       float wmax = 0.0f;
       for (size_t i2 = (size_t)d * h1; i2 < n_w1; ++i2) wmax = std::max(wmax, std::fabs(desc->w1[i2]));
       for (size_t i2 = 0; i2 < n_w2; ++i2) wmax = std::max(wmax, std::fabs(desc->w2[i2]));
@@ -1324,6 +1379,7 @@ void nann_scorer_destroy(nann_scorer* s) {
   if (s->dev_weights) (void)hipFree(s->dev_weights);
   if (s->dev_packed) (void)hipFree(s->dev_packed);
   if (s->dev_packed_x) (void)hipFree(s->dev_packed_x);
+  if (s->dev_cert) (void)hipFree(s->dev_cert);
   delete s;
 }
 
@@ -1444,6 +1500,11 @@ int nann_attn_scorer_create(const nann_attn_desc* desc, nann_attn_scorer** out) 
   const int d = desc->d, L = desc->seq_len;
   if (d != 64 && d != 128) return fail(NANN_ERR_UNSUPPORTED, "attention scorer: d must be 64 or 128");
   if (L <= 0 || L > kAttnLP) return fail(NANN_ERR_UNSUPPORTED, "attention scorer: seq_len must be in [1, 64]");
+  // (before any allocation; NANN_MLP_CERTIFIED is an MLP form: the attention model has no filter)
+  if (desc->precision != NANN_MLP_PRECISION_DEFAULT && desc->precision != NANN_MLP_EXACT_F32 &&
+      desc->precision != NANN_MLP_SPLIT_F16)
+    return fail(NANN_ERR_BAD_ARGUMENT, desc->precision == NANN_MLP_CERTIFIED ? "attention scorer: the certified precision is an MLP form"
+                                                                           : "attention scorer: unknown precision");
   if (desc->emb_dtype != NANN_F16 && desc->emb_dtype != NANN_BF16)
     return fail(NANN_ERR_UNSUPPORTED, "attention scorer: item rows must be f16 or bf16");
   const float* src[] = {desc->wq1, desc->bq1, desc->aq, desc->wq2, desc->bq2, desc->wk1, desc->bk1, desc->ak,
@@ -1482,11 +1543,6 @@ int nann_attn_scorer_create(const nann_attn_desc* desc, nann_attn_scorer** out) 
   P.d = d;
   P.L = L;
   s->emb_dtype = desc->emb_dtype;
-  if (desc->precision != NANN_MLP_PRECISION_DEFAULT && desc->precision != NANN_MLP_EXACT_F32 &&
-      desc->precision != NANN_MLP_SPLIT_F16) {
-    nann_attn_scorer_destroy(s);
-    return fail(NANN_ERR_BAD_ARGUMENT, "attention scorer: unknown precision");
-  }
   s->precision = desc->precision;  // DEFAULT is resolved below, once the weights have been looked at
   {  // the split-f16 planes (~0.5 MB) are always built; `precision` picks the kernels
     std::vector<uint16_t> packed;
@@ -1626,7 +1682,8 @@ static int read_precision(const std::string& dir, int32_t* precision) {
   if (!pf || !(pf >> prec)) return NANN_OK;
   if (prec == "split") *precision = NANN_MLP_SPLIT_F16;
   else if (prec == "exact") *precision = NANN_MLP_EXACT_F32;
-  else return fail(NANN_ERR_BAD_ARGUMENT, "precision.txt: expected exact or split, got '" + prec + "'");
+  else if (prec == "certified") *precision = NANN_MLP_CERTIFIED;
+  else return fail(NANN_ERR_BAD_ARGUMENT, "precision.txt: expected exact, split or certified, got '" + prec + "'");
   return NANN_OK;
 }
 
@@ -1675,7 +1732,8 @@ static int model_from_graphdef(const std::string& path, int32_t d, int32_t emb_d
     if (pf && (pf >> prec)) {
       if (prec == "split") ad.precision = NANN_MLP_SPLIT_F16;
       else if (prec == "exact") ad.precision = NANN_MLP_EXACT_F32;
-      else return fail(NANN_ERR_BAD_ARGUMENT, path + ".precision: expected exact or split, got '" + prec + "'");
+      else if (prec == "certified") ad.precision = NANN_MLP_CERTIFIED;
+      else return fail(NANN_ERR_BAD_ARGUMENT, path + ".precision: expected exact, split or certified, got '" + prec + "'");
     }
   }
   m->kind = NANN_MODEL_ATTENTION;
@@ -2205,10 +2263,14 @@ static int search_impl(const nann_index* ix, const nann_scorer* scorer, const na
   if (n_queries > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, "too many queries in one call");
   int rc = check_options(options);
   if (rc) return rc;
-  const SearchOpt opt = resolve_options(options);
+  SearchOpt opt = resolve_options(options);
   const int kind = attn ? kKindAttn : scorer->desc.kind;
   const bool mlp = !attn && kind == NANN_SCORER_MLP;
   const bool mlp_split = mlp && scorer->desc.precision == NANN_MLP_SPLIT_F16;
+  // certified: the filter lives in the pipeline of phases only -- a forced fused form is the phased one; every other plan
+  // runs the exact form's kernels
+  const bool mlp_cert = mlp && scorer->desc.precision == NANN_MLP_CERTIFIED;
+  if (mlp_cert && opt.mlp_form == NANN_MLP_FORM_FUSED) opt.mlp_form = NANN_MLP_FORM_PHASED;
   // the item-only part of the scorer, pre-projected per (scorer, index): found or built here (nann_*_prepare does it
   // ahead of traffic); without a table -- switched off, or no room in HBM -- the kernels that read the embedding rows run
   std::shared_ptr<ProjTable> tab;
@@ -2317,7 +2379,7 @@ static int search_impl(const nann_index* ix, const nann_scorer* scorer, const na
   }
   a.mlp = scorer->mlp;
   a.phase = 0;
-  const int exact = scorer->desc.kind == NANN_SCORER_MLP && scorer->desc.precision == NANN_MLP_EXACT_F32;
+  const int exact = scorer->desc.kind == NANN_SCORER_MLP && (scorer->desc.precision == NANN_MLP_EXACT_F32 || mlp_cert);
   if (mlp_res && p.phased) {
     // The default form of both precisions at beams that fit the 16K-slot set: the pipeline of phases (nann_mlp6.h).  Per
     // chunk of <= 1024 queries: traversal stage 0, then for every round its scoring launch and the
@@ -2337,13 +2399,17 @@ static int search_impl(const nann_index* ix, const nann_scorer* scorer, const na
       c.status = status + c0;
       if (counters) c.counters = counters + (size_t)c0 * 3 * NANN_NUM_ROUNDS;
       if (phase_ticks) c.phase_ticks = reinterpret_cast<long long*>(phase_ticks) + (size_t)c0 * NANN_NUM_PHASES;
-      if (c0) HIP_TRY(hipMemsetAsync(workspace, 0, 256, st));
+      if (c0 && mlp_cert) {  // (the certified form's refined counts add up over the chunks)
+        HIP_TRY(hipMemsetAsync(workspace, 0, offsetof(WsHeader, refined), st));
+        HIP_TRY(hipMemsetAsync(static_cast<unsigned char*>(workspace) + offsetof(WsHeader, pad2), 0, 256 - offsetof(WsHeader, pad2), st));
+      } else if (c0) HIP_TRY(hipMemsetAsync(workspace, 0, 256, st));
       const int slots = (int)std::min<int64_t>(c.n_queries, (int64_t)p.phase_slots);
       for (int ph = 0; ph <= NANN_NUM_ROUNDS && !rc; ++ph) {
         c.phase = ph;
         rc = launch_search_mlp_phase(p.phase_vis, slots, p.phase_lds_bytes, c, st);
         if (!rc && ph < NANN_NUM_ROUNDS) {
-          rc = launch_mlp_phase_score(exact, c, ph, p.phase_score_wgs, st);
+          rc = mlp_cert ? launch_mlp_phase_certified(c, ph, p.phase_score_wgs, st)
+                        : launch_mlp_phase_score(exact, c, ph, p.phase_score_wgs, st);
         }
       }
       if (!rc) {
@@ -2559,6 +2625,15 @@ int nann_search_reruns(const void* workspace, int64_t* n_rerun, nann_stream_t st
   HIP_TRY(hipMemcpyAsync(&v, static_cast<const unsigned char*>(workspace) + offsetof(WsHeader, n_redo), 4, hipMemcpyDeviceToHost, as_stream(stream)));
   HIP_TRY(hipStreamSynchronize(as_stream(stream)));
   *n_rerun = v;
+  return NANN_OK;
+}
+
+int nann_search_refined(const void* workspace, int64_t out[NANN_NUM_ROUNDS], nann_stream_t stream) {
+  if (!workspace || !out) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_refined: null argument");
+  unsigned long long v[NANN_NUM_ROUNDS] = {};
+  HIP_TRY(hipMemcpyAsync(v, static_cast<const unsigned char*>(workspace) + offsetof(WsHeader, refined), sizeof(v), hipMemcpyDeviceToHost, as_stream(stream)));
+  HIP_TRY(hipStreamSynchronize(as_stream(stream)));
+  for (int r = 0; r < NANN_NUM_ROUNDS; ++r) out[r] = (int64_t)v[r];
   return NANN_OK;
 }
 

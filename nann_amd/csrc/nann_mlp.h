@@ -46,6 +46,9 @@ struct MlpParams {  // device pointers
   const uint4* p2;  // [h1/32 tiles][2 chunks][h2/32 tiles][hi, lo][64 lanes] x 8 halves
   // exact form with W2 resident in LDS (nann_mlp5.h): f32 A fragments of v_mfma_f32_32x32x2_f32, four chain steps per 16 bytes
   const float4* p2x;  // [h1/32 tiles][h2/32 tiles][4][64 lanes] x 4 floats
+  // certified form (NANN_MLP_CERTIFIED, nann_mlp6.h): the filter's bound B = k1s sum_j |2^7 h1_j| cb[j] + k0
+  const float* cb;  // [h1] c_j = sum_m |W2_jm| |w3_m| max(1, |alpha2_m|), rounded up (nann_hip.hip certified_bound)
+  float k1s, k0;
 };
 
 constexpr int kMlpNT = 512;  // 8 wavefronts: 2 per SIMD -> 256 VGPRs each for the accumulators

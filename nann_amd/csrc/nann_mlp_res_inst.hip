@@ -1,6 +1,7 @@
 // nann_mlp_res_inst.hip -- the traversal with the MLP scorer's layer 2 resident in LDS (nann_mlp5.h): split-f16 and
 // exact f32, on the 16K-slot hash-set plan and on the HBM-bitmap plan (wide beams, large shards, and the rerun of
 // queries the set handed back).  An object of its own so that the four kernels compile next to the others.
+#include <cstddef>
 #include <cstdlib>
 
 #include "nann_search.h"
@@ -51,6 +52,30 @@ int launch_mlp_phase_score(int exact, const SearchArgs& a, int round, int workgr
   if (rc || !shadow) return rc;
   p.dry = 1;
   return exact ? launch(k_mlp_phase_score<true>) : launch(k_mlp_phase_score<false, NANN_PHASE_VAR>);
+}
+
+int launch_mlp_phase_certified(const SearchArgs& a, int round, int workgroups, hipStream_t st) {
+  if (a.n_queries > kPhaseChunk) return fail(NANN_ERR_BAD_ARGUMENT, "phased MLP traversal: chunks of at most 1024 queries");
+  unsigned long long off[9];
+  phase_offsets(a, off);
+  PhaseScoreArgs p;
+  p.ws = a.ws; p.slot_bytes = a.slot_bytes;
+  p.off_cand_ids = off[0]; p.off_cand_scores = off[1]; p.off_state = off[8];
+  p.enter = a.enter; p.proj = a.proj; p.n_items = a.n_items; p.n_queries = a.n_queries;
+  p.round = round; p.mlp = a.mlp; p.dry = 0;
+  p.off_raw = off[2]; p.max_raw = a.max_raw; p.t_r = a.t[round]; p.tq = a.tq;
+  p.refined = reinterpret_cast<unsigned long long*>(a.ws + offsetof(WsHeader, refined));
+  auto launch = [&](auto kern) -> int {
+    NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPhaseScoreLds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)workgroups), dim3(512), kPhaseScoreLds, st, p);
+    NANN_HIP_TRY(hipGetLastError());
+    return NANN_OK;
+  };
+  int rc = launch(k_mlp_phase_score<false, 0, 2>);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_mlp_phase_certify<kCertNT>, dim3((unsigned)a.n_queries), dim3(kCertNT), 0, st, p);
+  NANN_HIP_TRY(hipGetLastError());
+  return launch(k_mlp_phase_score<true, 0, 1>);
 }
 
 }  // namespace nann

@@ -594,10 +594,14 @@ struct WsHeader {
   unsigned int redo_queue;   // next query of the fallback launch
   unsigned int pad1[15];
   unsigned int n_redo;       // queries the hash-set kernel handed back (NANN_ERR_CAPACITY)
-  unsigned int pad2[15];
+  unsigned int pad2a;
+  unsigned long long refined[NANN_NUM_ROUNDS];  // certified MLP form: rows rescored exactly per round (k_mlp_phase_certify;
+                                                // kept over the chunks of a call: nann_search_refined)
+  unsigned int pad2[4];
   unsigned int pqueue[8];    // next query of traversal stage p of the phased MLP pipeline (nann_mlp6.h)
 };
 static_assert(sizeof(WsHeader) <= 256, "workspace header");
+static_assert(offsetof(WsHeader, refined) == 136 && offsetof(WsHeader, pqueue) == 192, "header regions the chunks of a certified call reset");
 
 // Second launch bound = waves per SIMD the register allocation must leave room for: the 16K-slot
 // hash-set kernel lives off TWO 512-thread workgroups per CU (16 waves = 4 per SIMD -> at most 128
@@ -765,6 +769,8 @@ int launch_search_mlp_res(int exact, int vis, int slots, size_t lds_bytes, const
 // the pipeline of phases (nann_mlp6.h): a traversal stage (a.phase), a round's scoring launch
 int launch_search_mlp_phase(int vis, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
 int launch_mlp_phase_score(int exact, const SearchArgs& a, int round, int workgroups, hipStream_t st);
+// the certified form's round: filter, certify and refine launches (nann_mlp6.h)
+int launch_mlp_phase_certified(const SearchArgs& a, int round, int workgroups, hipStream_t st);
 int launch_mlp_preproject(int dt, const void* emb, long long n_rows, int d, const float* w1, float* proj, hipStream_t st);
 // attention-scorer instantiations live in nann_attn_inst.hip: (vis, 512 threads) for vis in
 // {VIS_LDS_HASH (one workgroup per CU), VIS_LDS_BITMAP, VIS_HBM_BITMAP}

@@ -266,16 +266,16 @@ def top_k(values, k):
 _DT = {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16, torch.float32: _lib.F32}
 
 
-_PRECISION = {"split": _lib.MLP_SPLIT_F16, "exact": _lib.MLP_EXACT_F32}
+_PRECISION = {"split": _lib.MLP_SPLIT_F16, "exact": _lib.MLP_EXACT_F32, "certified": _lib.MLP_CERTIFIED}
 
 
 def _precision_code(precision):
-    """'split' | 'exact' -> nann_mlp_precision; anything else is an error (a typo must not silently select
-    the slower kernel)."""
+    """'split' | 'exact' | 'certified' -> nann_mlp_precision; anything else is an error (a typo must not silently
+    select the slower kernel).  'certified' is an MLP form: the attention scorer's creation rejects it."""
     try:
         return _PRECISION[precision]
     except KeyError:
-        raise ValueError(f"precision must be 'split' or 'exact', got {precision!r}") from None
+        raise ValueError(f"precision must be 'split', 'exact' or 'certified', got {precision!r}") from None
 
 
 class Scorer:
@@ -285,7 +285,8 @@ class Scorer:
     def __init__(self, kind, d, emb_dtype=torch.float16, weights=None, precision="split"):
         """precision (mlp): "split" (the default: north_star's contract is 1e-5) = split-f16 operands on the
         16-bit MFMA, scores within 1e-5 of the fp32 chain; "exact" = f32-input MFMA, scores bit-identical to
-        the oracle, ~3x slower (nann_mlp_precision)."""
+        the oracle, ~3x slower; "certified" = results bit-identical to "exact", the rows an f16 filter with a
+        rigorous error bound cannot rule out rescored exactly (nann_mlp_precision)."""
         if kind not in ("l2", "mlp"):
             raise ValueError(f"scorer kind must be 'l2' or 'mlp', got {kind!r}")
         self.kind, self.d, self.emb_dtype, self.precision = kind, d, emb_dtype, precision
@@ -382,7 +383,7 @@ def save_scorer_dir(path, kind, weights=None, precision=None):
     os.makedirs(path, exist_ok=True)
     with open(os.path.join(path, "scorer.txt"), "w") as f:
         f.write(kind + "\n")
-    if precision is not None:  # mlp / attention: "exact" | "split" (precision.txt, read by nann_model_load)
+    if precision is not None:  # mlp / attention: "exact" | "split" | "certified" (mlp; precision.txt, read by nann_model_load)
         with open(os.path.join(path, "precision.txt"), "w") as f:
             f.write(precision + "\n")
     if kind == "mlp":

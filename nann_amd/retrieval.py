@@ -162,6 +162,14 @@ class SearchResult:
         _check(lib().nann_search_reruns(_ptr(self._ws), C.byref(n), _stream()), "reruns")
         return n.value
 
+    def refined(self):
+        """rows of this call rescored exactly per round (precision="certified" in the pipeline of phases; zeros
+        elsewhere): a list of NUM_ROUNDS ints, to set against counters[:, 2, :].sum(0) (synchronises the stream;
+        read it before the next search on the same index reuses the workspace)"""
+        out = (C.c_int64 * _lib.NUM_ROUNDS)()
+        _check(lib().nann_search_refined(_ptr(self._ws), out, _stream()), "refined")
+        return list(out)
+
 
 def _level_topn_args(level_topn, b, dev):
     """level_topn as the C ABI takes it: uniform i32[6] -> (maxima, NULL); per query [B, 6] (the reference feeds

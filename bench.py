@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   (+ the last timed step's answers as DIR/*.npy)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full               (+ checks, CPU baselines, secondary workloads)
     python bench.py --gpus 8 ...            (spawns one rank per GPU itself), or
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -23,11 +24,16 @@ issued by the C ABI (nann_sharded_topk) and merged on the device.
 
 Prints ONE JSON line (rank 0).  `roofline` prices the traversal kernel's ALGORITHMIC bytes
 (SURVEY.md 8d formula over the kernel's own per-round counters, which the parity tests pin
-to the oracle's) against 8 TB/s HBM; `cpu_baseline` is the oracle (oracle/nann_oracle.c, a
-port of the reference's CPU op loops) timed on this box's cores.  At N = 1 the line also
-carries `secondary`: configs[2] (MLP scorer), an HBM-honest stress run (2M x 256-d bf16,
-ef=256: config 5's shard shape at half its size, table >> Infinity Cache) and the
-B in {1, 64, 1024} latency sweep.
+to the oracle's) against 8 TB/s HBM.
+
+A plain run does only what that line's headline needs: it sets up, warms up, times the steps,
+writes --dump-outputs and prints the line (`roofline` and `batch_latency_ms` come from the
+timed steps themselves).  Everything else runs with --full only: `parity` (the timed answers
+against the CPU oracle), `recall_at_k_vs_bruteforce`, `cpu_baseline` (the oracle --
+oracle/nann_oracle.c, a port of the reference's CPU op loops -- timed on the host's cores)
+and, at N = 1, `secondary`: configs[2] (MLP scorer), an HBM-honest stress run (4M x 256-d
+bf16, ef=256: config 5's shard shape, table >> Infinity Cache), the evaluation traversal,
+the attention model, the dense graph family and the B in {1, 64, 1024} latency sweep.
 """
 import argparse
 import json
@@ -47,7 +53,7 @@ F32_MFMA_PEAK_TF = 157.3  # f32-input MFMA dense peak
 F16_MFMA_PEAK_TF = 2500.0  # f16/bf16 MFMA dense peak (MI355X_MICROARCH.md)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -64,9 +70,12 @@ def parse():
                          "hnsw_cpu = the same algorithm by the host-side C++ builder (rounds 1-2: 16-30 s); synth = exact-search "
                          "insertion graph built with torch (round-1 default, ~2 min at 1M); knn = full-degree exact k-NN rows")
     ap.add_argument("--noise", type=float, default=1.0)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="primary workload only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check the answers against the CPU oracle and brute-force recall, time the "
+                         "CPU baselines and (one GPU, L2) run the secondary workloads; without it a run stops at the headline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline time budget")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary workloads")
     ap.add_argument("--merge", default="device", choices=["device", "host"])
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the N>1 run (nccl = RCCL; gloo + NANN_BENCH_SHARED_GPU=1: "
@@ -90,13 +99,13 @@ def parse():
     ap.add_argument("--traversal", default="auto", choices=["auto", "lds_bitmap", "hbm_bitmap", "lds_hash", "lds_hash32"])
     ap.add_argument("--index-cache", default=None, help="directory to cache built indices in")
     ap.add_argument("--stress-items", type=int, default=4_000_000,
-                    help="items of the HBM-honest secondary workload: configs[4]'s shard at its own size (4M x 256-d bf16, ef=256)")
+                    help="--full: items of the HBM-honest secondary workload: configs[4]'s shard at its own size (4M x 256-d bf16, ef=256)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (item ids, scores, status) as "
                          "DIR/<name>.npy in float32 / float64 (rank 0; a seeded sample of rows beyond 64 MB)")
     ap.add_argument("--phase-ticks", action="store_true",
                     help="one extra instrumented launch: per-phase time attribution")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def algorithmic_bytes(counters, d, emb_bytes, n_enter, k_out=200):
@@ -893,7 +902,7 @@ def main():
     if args.scorer == "mlp" and args.mlp_precision == "exact":
         tag += "_exact"  # (its own counters in profiles/pmc_latest.json)
     prim = run_workload(tag, args, dev, rank, world, dict(primary_cfg, dump_dir=args.dump_outputs), sharded=sharded,
-                        want_cpu=not args.no_cpu_baseline, want_parity=True, want_recall=True)
+                        want_cpu=args.full and not args.no_cpu_baseline, want_parity=args.full, want_recall=args.full)
 
     qps = prim["qps_end_to_end"]
     desc = (f"{args.items} items/GPU x {args.dim}-d {args.dtype}, M=32 graph from "
@@ -946,7 +955,7 @@ def main():
         if k in prim:
             result[k] = prim[k]
 
-    if rank == 0 and world == 1 and not args.no_secondary and args.scorer == "l2":
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and args.scorer == "l2":
         sec = {}
         try:
             sec["batch_sweep"] = batch_sweep(prim["_handles"], [args.ef] * 5 + [args.topk], [1, 64, 1024], args.dim, prim["n_enter"])

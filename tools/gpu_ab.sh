@@ -11,7 +11,7 @@ mkdir -p $OUT /tmp/idx
 cd /tmp && export TMPDIR=/tmp
 run() {  # name [env...]
   local name=$1; shift
-  env "$@" timeout 300 python $R/bench.py --index-cache /tmp/idx $FLAGS > $OUT/ab_${TAG}_$name.json 2> $OUT/ab_${TAG}_$name.err
+  env "$@" timeout 300 python $R/bench.py --full --index-cache /tmp/idx $FLAGS > $OUT/ab_${TAG}_$name.json 2> $OUT/ab_${TAG}_$name.err
   python - <<PY
 import json
 try:

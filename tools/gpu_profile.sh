@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT /tmp/idx /tmp/prof
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --index-cache /tmp/idx $*"
+BENCH="python $R/bench.py --full --index-cache /tmp/idx $*"
 
 # 1. plain bench (builds + caches the index), with per-phase attribution
 timeout 900 $BENCH --phase-ticks > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench rc=$?" >> $OUT/bench_$TAG.err

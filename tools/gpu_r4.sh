@@ -15,7 +15,7 @@ left() { echo $(( DEADLINE - ($(date +%s) - T0) )); }
 mkdir -p $OUT /tmp/idx /tmp/prof
 cd $R
 export TMPDIR=/tmp NANN_TEST_INDEX_CACHE=/tmp/idx
-BENCH="python $R/bench.py --index-cache /tmp/idx"
+BENCH="python $R/bench.py --full --index-cache /tmp/idx"
 show() {  # file label
 python - <<PY
 import json
@@ -287,7 +287,7 @@ open('$OUT/overlap_trace_$TAG.txt', 'w').write('\n'.join('%d %d %s' % r for r in
 PY
       ;;
     dry8)  # item 7b: the whole 8-rank flow of bench.py on ONE GPU (gloo, exchange staged through the host), merged parity vs the oracle
-      NANN_BENCH_SHARED_GPU=1 timeout 900 python bench.py --gpus 8 --dist-backend gloo --items 200000 --batch 1024 --steps 3 --warmup 1 --index-cache /tmp/idx --no-secondary --no-cpu-baseline > $OUT/bench_dry8_$TAG.json 2> $OUT/bench_dry8_$TAG.err
+      NANN_BENCH_SHARED_GPU=1 timeout 900 python bench.py --full --gpus 8 --dist-backend gloo --items 200000 --batch 1024 --steps 3 --warmup 1 --index-cache /tmp/idx --no-secondary --no-cpu-baseline > $OUT/bench_dry8_$TAG.json 2> $OUT/bench_dry8_$TAG.err
       tail -1 $OUT/bench_dry8_$TAG.json | cut -c1-900; tail -3 $OUT/bench_dry8_$TAG.err ;;
     bench_mlp_batches)  # configs[2] at batch 1024 / 2048 / 4096, steady state: the tail of a 4-queries-per-workgroup launch
       for B in 1024 2048 4096; do

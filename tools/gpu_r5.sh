@@ -11,7 +11,7 @@ left() { echo $(( DEADLINE - ($(date +%s) - T0) )); }
 mkdir -p $OUT /tmp/idx /tmp/prof
 cd $R
 export TMPDIR=/tmp NANN_TEST_INDEX_CACHE=/tmp/idx
-BENCH="python $R/bench.py --index-cache /tmp/idx"
+BENCH="python $R/bench.py --full --index-cache /tmp/idx"
 line() {  # file label: one line of a bench JSON
 python - <<PY
 import json

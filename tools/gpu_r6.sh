@@ -10,7 +10,7 @@ left() { echo $(( DEADLINE - ($(date +%s) - T0) )); }
 mkdir -p $OUT /tmp/idx /tmp/prof
 cd $R
 export TMPDIR=/tmp NANN_TEST_INDEX_CACHE=/tmp/idx
-BENCH="python $R/bench.py --index-cache /tmp/idx"
+BENCH="python $R/bench.py --full --index-cache /tmp/idx"
 for STEP in "$@"; do
   if [ $(left) -lt 45 ]; then echo "SKIP $STEP (deadline)"; continue; fi
   echo "=== $STEP (left $(left) s)"
@@ -35,7 +35,7 @@ print('value', d['value'], d['unit'], 'ms/step', d['ms_per_step'], 'roofline', j
 PY
       ;;
     replicas_dry)  # bench.py --gpus 2 --replicas with both ranks on the one GPU (gloo carries the barriers): the code path, not a rate
-      NANN_BENCH_SHARED_GPU=1 timeout 600 python bench.py --gpus 2 --replicas --dist-backend gloo --items 200000 --batch 1024 --steps 3 --warmup 1 --index-cache /tmp/idx --no-secondary --no-cpu-baseline > $OUT/bench_replicas_dry_$TAG.json 2> $OUT/bench_replicas_dry_$TAG.err
+      NANN_BENCH_SHARED_GPU=1 timeout 600 python bench.py --full --gpus 2 --replicas --dist-backend gloo --items 200000 --batch 1024 --steps 3 --warmup 1 --index-cache /tmp/idx --no-secondary --no-cpu-baseline > $OUT/bench_replicas_dry_$TAG.json 2> $OUT/bench_replicas_dry_$TAG.err
       python - <<PY
 import json
 try:

@@ -19,7 +19,7 @@ RC=$?; tail -3 $OUT/pytest_$TAG.log
 if [ $RC -ne 0 ]; then echo "GPU TESTS FAILED"; grep -E "^(E  |FAILED|ERROR)" $OUT/pytest_$TAG.log | head -30; fi
 timeout 60 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.log 2>&1; tail -1 $OUT/smoke_$TAG.log
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --index-cache /tmp/idx $EXTRA"
+BENCH="python $R/bench.py --full --index-cache /tmp/idx $EXTRA"
 show() {  # file label
 python - <<PY
 import json

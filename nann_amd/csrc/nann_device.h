@@ -1119,13 +1119,9 @@ __device__ __forceinline__ float l2_rows8_reduce_scatter(float (&a)[8]) {
 
 // 16-byte row loads per lane in flight in the scoring phase (8 = 128 KB per 1024-thread workgroup).
 // Measured on MI355X (profiles/r2a_variants.jsonl): 12 and 16 in flight, and a rolling window that
-// refills each slot as soon as it is reduced, are all slower (2.62 / 2.71 / 2.56 ms vs 2.56 ms).
-#ifndef NANN_SCORE_U
-#define NANN_SCORE_U 8
-#endif
-#ifndef NANN_SCORE_NT
-#define NANN_SCORE_NT 0
-#endif
+// refills each slot as soon as it is reduced, are all slower (2.62 / 2.71 / 2.56 ms vs 2.56 ms); so are
+// non-temporal row loads (profiles/rd5af_nontemporal_ab.txt).
+constexpr int kScoreU = 8;
 // wg_score_l2_part: scores[i] = -||q - table[ids[i]]||^2 for begin <= i < end, computed by
 // NWAVES wavefronts of the workgroup (this one is number wave_rel among them).  No barriers
 // inside, so a subset of the workgroup can run it.
@@ -1136,7 +1132,7 @@ template <int LPR, int DT, int NWAVES>
 __device__ __forceinline__ void wg_score_l2_part(const void* __restrict__ table, int d, const int32_t* ids,
                                                  int begin, int end, const float* qv, float* scores,
                                                  int wave_rel, bool near = false) {
-  constexpr int U = (DT == DT_F32) ? NANN_SCORE_U / 2 : NANN_SCORE_U;
+  constexpr int U = (DT == DT_F32) ? kScoreU / 2 : kScoreU;
   constexpr int GPW = 64 / LPR;      // rows per wavefront per load
   constexpr int RPI = NWAVES * GPW;  // rows per iteration of the participating wavefronts
   if (end <= begin) return;
@@ -1163,13 +1159,7 @@ __device__ __forceinline__ void wg_score_l2_part(const void* __restrict__ table,
       //  16 bytes of the row -- one vector instruction per row address)
       auto row = [&](int32_t v) -> uint4 {
         if constexpr (NEAR) {
-#if NANN_SCORE_NT  // measurement builds: the rows as non-temporal loads (a row is read once per query)
-          typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-          const u32x4_t r = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(static_cast<const unsigned char*>(table) + ((uint32_t)v | ((uint32_t)sub * 16u))));
-          return uint4{r.x, r.y, r.z, r.w};
-#else
           return *reinterpret_cast<const uint4*>(static_cast<const unsigned char*>(table) + ((uint32_t)v | ((uint32_t)sub * 16u)));
-#endif
         } else {
           return load_chunk<DT>(table, (size_t)v, d, sub).a;
         }

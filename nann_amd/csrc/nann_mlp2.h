@@ -114,10 +114,7 @@ __device__ __forceinline__ void split_tile(const f32x16& a1, const float (&beta)
 // wg_score_mlp_split2: scores[i] for candidates ids[i], i < n (ids == nullptr: row i).  All 256 threads; 4 wavefronts x
 // (32 + 32) candidates per pass.  wg_mlp2_stage_setup must have run for this query.  Rows outside [0, n_table_rows)
 // are read as row 0 (the caller reports them).
-// VAR (timing builds of tools/ubench_mlp2.hip only; the product instantiates VAR = 0): bit 0 = no PReLU / operand
-// split arithmetic, bit 1 = no weight staging (fetch, LDS stores, barrier), bit 2 = A fragments read from LDS once per
-// pass instead of per tile, bit 3 = no output layer.  Wrong scores, same control flow.
-template <int D, int DT, int VAR = 0>
+template <int D, int DT>
 __device__ __forceinline__ void wg_score_mlp_split2(const MlpParams& P, const void* __restrict__ table,
                                                     uint32_t n_table_rows, const int32_t* ids, int n,
                                                     Mlp2Scratch<D>* S, float* scores) {
@@ -185,9 +182,9 @@ __device__ __forceinline__ void wg_score_mlp_split2(const MlpParams& P, const vo
     // one hidden tile; LAST (compile time) = tile H1T - 1, after whose layer 1 the rows are dead and the next pass's are fetched
     auto tile = [&](int t, auto last_tag) {
       constexpr bool LAST = decltype(last_tag)::value;
-      const uint4* L1 = &S->buf[(VAR & 4) ? 0 : (t & 1)][0];
+      const uint4* L1 = &S->buf[t & 1][0];
       const uint4* L2 = L1 + Scr::kL1;
-      if constexpr (!(VAR & 2)) fetch_tile(LAST ? 0 : t + 1);  // the next tile (of this pass, or tile 0 for the next) from L2 underneath this one
+      fetch_tile(LAST ? 0 : t + 1);  // the next tile (of this pass, or tile 0 for the next) from L2 underneath this one
       f32x16 a1A, a1B;
       float beta[16];
 #pragma unroll
@@ -227,18 +224,7 @@ __device__ __forceinline__ void wg_score_mlp_split2(const MlpParams& P, const vo
         a1B = __builtin_amdgcn_mfma_f32_32x32x16_f16(W1[2 * kc], b, a1B, 0, 0, 0);
         a1B = __builtin_amdgcn_mfma_f32_32x32x16_f16(W1[2 * kc + 1], b, a1B, 0, 0, 0);
       }
-      if constexpr (VAR & 1) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          union { float f[4]; f16x8 h; } c;
-          c.f[0] = a1A[8 * q]; c.f[1] = a1A[8 * q + 1]; c.f[2] = a1A[8 * q + 2]; c.f[3] = a1A[8 * q + 3];
-          bhA[q] = c.h;
-          c.f[0] = a1A[8 * q + 4]; c.f[1] = a1A[8 * q + 5]; c.f[2] = a1A[8 * q + 6]; c.f[3] = a1A[8 * q + 7];
-          blA[q] = c.h;
-        }
-      } else {
-        split_tile(a1A, beta, bhA, blA);
-      }
+      split_tile(a1A, beta, bhA, blA);
       // pin: two MFMAs first (block A's last layer-1 result is still in the pipe), then VALU in groups of 8 per MFMA
       __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
 #pragma unroll
@@ -257,18 +243,7 @@ __device__ __forceinline__ void wg_score_mlp_split2(const MlpParams& P, const vo
           a2A[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W2[(q * H2T + mt) * 2], blA[q], a2A[mt], 0, 0, 0);
           a2A[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W2[(q * H2T + mt) * 2 + 1], bhA[q], a2A[mt], 0, 0, 0);
         }
-      if constexpr (VAR & 1) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          union { float f[4]; f16x8 h; } c;
-          c.f[0] = a1B[8 * q]; c.f[1] = a1B[8 * q + 1]; c.f[2] = a1B[8 * q + 2]; c.f[3] = a1B[8 * q + 3];
-          bhB[q] = c.h;
-          c.f[0] = a1B[8 * q + 4]; c.f[1] = a1B[8 * q + 5]; c.f[2] = a1B[8 * q + 6]; c.f[3] = a1B[8 * q + 7];
-          blB[q] = c.h;
-        }
-      } else {
-        split_tile(a1B, beta, bhB, blB);
-      }
+      split_tile(a1B, beta, bhB, blB);
       __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
 #pragma unroll
       for (int k = 2; k < 6 * H2T; ++k) {
@@ -285,24 +260,20 @@ __device__ __forceinline__ void wg_score_mlp_split2(const MlpParams& P, const vo
           a2B[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W2[(q * H2T + mt) * 2], blB[q], a2B[mt], 0, 0, 0);
           a2B[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W2[(q * H2T + mt) * 2 + 1], bhB[q], a2B[mt], 0, 0, 0);
         }
-      if constexpr (!(VAR & 2)) {
-        store_tile((t + 1) & 1);
+      store_tile((t + 1) & 1);
 #pragma unroll
-        for (int k = 0; k < PERT; ++k) {  // pin: the stores spread under the MFMAs, two MFMAs apart
-          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
+      for (int k = 0; k < PERT; ++k) {  // pin: the stores spread under the MFMAs, two MFMAs apart
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
       }
+      __builtin_amdgcn_sched_barrier(0);
+      __syncthreads();
     };
 #pragma unroll 1
     for (int t = 0; t < H1T - 1; ++t) tile(t, std::false_type{});
     tile(H1T - 1, std::true_type{});
     // PReLU of layer 2 and the bias-free output layer, both blocks from one read of the vectors
     float partA = 0.0f, partB = 0.0f;
-    if constexpr (VAR & 8) { partA = a2A[0][0] + a2A[1][1] + a2A[2][2] + a2A[3][3]; partB = a2B[0][0] + a2B[1][1] + a2B[2][2] + a2B[3][3]; }
-    else
 #pragma unroll
     for (int mt = 0; mt < H2T; ++mt)
 #pragma unroll

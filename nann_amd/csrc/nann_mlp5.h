@@ -30,15 +30,9 @@
 
 #include "nann_mlp3.h"
 
-#ifndef NANN_RES_XSKEW
-#define NANN_RES_XSKEW 32  // the same for the exact form (a tile = 64 f32 MFMAs of 64 cycles)
-#endif
-#ifndef NANN_RES_VAR
-#define NANN_RES_VAR 0  // timing builds only (tools/build_res_variant.py): bit 0 no split arithmetic, bit 1 no gathers, bit 2 no epilogue
-#endif
-
 namespace nann {
 
+constexpr int kMlpResXSkew = 32;  // s_sleep units between the SIMD partners of the exact form (a tile = 64 f32 MFMAs of 64 cycles)
 constexpr int kMlpResW2Bytes = 131072;                                // W2 resident: 8 hidden tiles x 16 KB
 constexpr int kMlpResW2Vec = kMlpResW2Bytes / 16;                     // uint4
 constexpr int kMlpResBytes = kMlpResW2Bytes + (int)sizeof(Mlp2Vectors);  // + the per-query vectors behind it
@@ -109,13 +103,14 @@ __device__ __forceinline__ void wg_mlp_res_leave(uint4* lds, const uint4* park, 
 // that arithmetic runs 76.8 instead of 96.9) --; +11..22 for the gathers of the table rows; the rest LDS reads, the
 // per-call weight load and the ragged last blocks of a call.
 //
-// The eight hidden tiles of a 32-row block are UNROLLED (NANN_RES_ROLLED = 1: two tiles per trip of a rolled loop, the
-// form of r4b): hipcc puts `s_waitcnt vmcnt(0)` at the head of a rolled loop that carries gathers in flight, i.e. every
-// trip waited for the gathers issued one tile earlier (a random 128-byte access takes 2-3 k cycles under this load, a
-// tile of a wavefront ~1.6 k).  Unrolled, the waits inside a block are exact (`vmcnt(4)`: this tile's four loads, not
-// the next tile's).  For the unrolled body to keep its registers the LDS addresses are formed from THREE opaque bases
-// (weights below / above the 64 KB an instruction's offset field reaches, and the vectors) + immediate offsets; left to
-// itself the compiler hoists ~60 address registers out of the block loop and spills them into it.
+// The eight hidden tiles of a 32-row block are UNROLLED (r4b's rolled loop, two tiles per trip, was removed: 96.9 cycles
+// per row, profiles/r4bcd_mlp_timing_builds.txt): hipcc puts `s_waitcnt vmcnt(0)` at the head of a rolled loop that
+// carries gathers in flight, i.e. every trip waited for the gathers issued one tile earlier (a random 128-byte access
+// takes 2-3 k cycles under this load, a tile of a wavefront ~1.6 k).  Unrolled, the waits inside a block are exact
+// (`vmcnt(4)`: this tile's four loads, not the next tile's).  For the unrolled body to keep its registers the LDS
+// addresses are formed from THREE opaque bases (weights below / above the 64 KB an instruction's offset field reaches,
+// and the vectors) + immediate offsets; left to itself the compiler hoists ~60 address registers out of the block loop
+// and spills them into it.
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4v* lds_u4_ptr;
@@ -141,16 +136,14 @@ __device__ __forceinline__ uint32_t lds_offset_of(const void* p) {  // a generic
 // pointer of the block behind it (this lane's row + 4 g floats; `row` again when there is none), and, when that block
 // belongs to another query, change = true and u_next = this lane's 16 bytes of that query's u x 2^7 (written to L.u_wr
 // behind the last read of the current u).  store(k, score): every lane, the block's score of its row (lanes g and g ^ 1
-// hold the same value).  VAR: timing builds (nann_mlp6.h NANN_PHASE_VAR; 16 = the PReLU decomposition priced in round 6).  KW3B >= 0: the packed output layer (below).
+// hold the same value).
 struct SplitPipeLds {  // opaque LDS byte addresses (an `asm volatile("" : "+v"(x))` behind each, see wg_score_mlp_res)
   uint32_t w_lo, w_hi;  // W2 fragments below / above 64 KB, + lane * 16
   uint32_t v_at;        // Mlp2Vectors, + g * 16
   uint32_t u_at;        // the current query's u x 2^7 [256], + g * 16 (the fused kernel: = v_at)
   uint32_t u_wr;        // where this lane writes its 16 bytes of the next query's u (fused kernel: unused)
-  const float* seed_base = nullptr;  // VAR & 16 only (round 6 pricing build): a table whose rows stand in for the second
-  uint32_t seed_rows = 0;            // pre-projected table of the PReLU decomposition, [seed_rows, 256] f32
 };
-template <int VAR, int KW3B, class Advance, class Store>
+template <class Advance, class Store>
 __device__ __forceinline__ void wave_mlp_split_pipeline(const SplitPipeLds& L, const float* row, int n_blocks,
                                                         Advance advance, Store store) {
   constexpr int H1T = 8, H2T = 4;
@@ -186,12 +179,6 @@ __device__ __forceinline__ void wave_mlp_split_pipeline(const SplitPipeLds& L, c
     // packed f32 forms by hand (left to itself hipcc scalarises about half of them; the vector pipe's issue slots
     // are what bounds this loop): x + u, min(., 0) per half (there is no packed f32 min), (alpha - 1) min + (x + u)
     const f32x2 xs = xp + up;
-    if constexpr ((VAR & 16) != 0) {
-      // pricing build of VERDICT r5 item 2: prelu(x) = a x + (1 - a) max(x, 0), the linear part precomputed per item (a second
-      // table, gathered below) and per query, so the activation beside the MFMAs is ONE v_max per element and no beta read
-      (void)bp;
-      return __builtin_elementwise_max(xs, f32x2{0.0f, 0.0f});
-    }
     const f32x2 m = __builtin_elementwise_min(xs, f32x2{0.0f, 0.0f});
     return __builtin_elementwise_fma(m, bp, xs);
   };
@@ -226,16 +213,6 @@ __device__ __forceinline__ void wave_mlp_split_pipeline(const SplitPipeLds& L, c
         const f32x4v v = vec4(kB2 + 32 * mt + 8 * rr);
         acc[mt][4 * rr] = v.x; acc[mt][4 * rr + 1] = v.y; acc[mt][4 * rr + 2] = v.z; acc[mt][4 * rr + 3] = v.w;
       }
-    f32x4v seed[(VAR & 16) ? 16 : 1];
-    if constexpr ((VAR & 16) != 0) {
-      // the item's linear part (a (.) P_i) W2: 128 f32 = 512 more bytes per scored row, issued at the top of the block, added to
-      // the accumulators behind its last MFMA (the products are linear in it).  Stand-in rows: another row of the table per row.
-      const uint32_t rid = (uint32_t)((row - L.seed_base) >> 8);
-      const uint32_t rid2 = (uint32_t)(((unsigned long long)rid * 2654435761ull + 12345ull) % L.seed_rows);
-      const float* srow = L.seed_base + (size_t)rid2 * 256 + ((row - L.seed_base) & 255);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) seed[i] = *reinterpret_cast<const f32x4v*>(srow + 8 * i);
-    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < H1T; ++t) {
@@ -252,77 +229,43 @@ __device__ __forceinline__ void wave_mlp_split_pipeline(const SplitPipeLds& L, c
         f32x2 hv[H2T] = {};
 #pragma unroll
         for (int mt = 0; mt < H2T; ++mt) {
-          if (!(VAR & 8)) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wf[2 * mt], bh, acc[mt], 0, 0, 0);
-          if (!(VAR & 4)) hv[mt] = convert_a(x[nbuf], q, mt);
+          acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wf[2 * mt], bh, acc[mt], 0, 0, 0);
+          hv[mt] = convert_a(x[nbuf], q, mt);
           __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int mt = 0; mt < H2T; ++mt) {
-          if (!(VAR & 8)) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wf[2 * mt], bl, acc[mt], 0, 0, 0);
-          if (!(VAR & 2)) Wf[2 * mt] = fragt(nt, nq * 2 * H2T + 2 * mt);
+          acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wf[2 * mt], bl, acc[mt], 0, 0, 0);
+          Wf[2 * mt] = fragt(nt, nq * 2 * H2T + 2 * mt);
           const int rr = 2 * nq + (mt & 1);  // u / beta of the next step's conversion (this step's were read above)
-          if (!(VAR & 4)) {
-            if (mt < 2) cu[mt & 1] = uvec4(32 * ct + 8 * rr); else if (!(VAR & 16)) cb[mt & 1] = vec4(kBeta1 + 32 * ct + 8 * rr);
-            convert_b(hv[mt], Bh[nbuf][q][mt], Bl[nbuf][q][mt]);
-          }
+          if (mt < 2) cu[mt & 1] = uvec4(32 * ct + 8 * rr); else cb[mt & 1] = vec4(kBeta1 + 32 * ct + 8 * rr);
+          convert_b(hv[mt], Bh[nbuf][q][mt], Bl[nbuf][q][mt]);
           __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int mt = 0; mt < H2T; ++mt) {
-          if (!(VAR & 8)) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wf[2 * mt + 1], bh, acc[mt], 0, 0, 0);
-          if (!(VAR & 2)) Wf[2 * mt + 1] = fragt(nt, nq * 2 * H2T + 2 * mt + 1);
-          if (q == 0 && !(VAR & 1))  // tile t + 2 (of the next block behind tile 5) into the buffer tile t was converted from
+          acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wf[2 * mt + 1], bh, acc[mt], 0, 0, 0);
+          Wf[2 * mt + 1] = fragt(nt, nq * 2 * H2T + 2 * mt + 1);
+          if (q == 0)  // tile t + 2 (of the next block behind tile 5) into the buffer tile t was converted from
             x[cbuf][mt] = *reinterpret_cast<const f32x4v*>((t + 2 >= H1T ? next : row) + 32 * ((t + 2) & (H1T - 1)) + 8 * mt);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
     }
-    if constexpr ((VAR & 16) != 0) {
+    // PReLU of layer 2 and the bias-free output layer: one chain, unit by unit (two packed-f32 dot products instead were
+    // 0.7 % slower and gave other bits: profiles/r4x_mlp_loop_ab.txt)
+    float part = 0.0f;
 #pragma unroll
-      for (int mt = 0; mt < H2T; ++mt)
+    for (int mt = 0; mt < H2T; ++mt)
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const f32x4v v = seed[4 * mt + rr];
-          acc[mt][4 * rr] += v.x; acc[mt][4 * rr + 1] += v.y; acc[mt][4 * rr + 2] += v.z; acc[mt][4 * rr + 3] += v.w;
+      for (int rr = 0; rr < 4; ++rr) {
+        const f32x4v be = vec4(kBeta2 + 32 * mt + 8 * rr), w3 = vec4(kW3 + 32 * mt + 8 * rr);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float xa = acc[mt][4 * rr + e];
+          part = __builtin_fmaf(__builtin_fmaf(neg_part(xa), be[e], xa), w3[e], part);
         }
-    }
-    // PReLU of layer 2 and the bias-free output layer
-    float part;
-    if constexpr (KW3B >= 0) {
-      // sum_j w3_j (x_j + beta2_j min(x_j, 0)) as two packed-f32 dot products, w3 . x and (w3 beta2) . min(x, 0) -- 2 vector
-      // instructions per unit instead of 3 (the caller staged w3 beta2 at float KW3B of the vectors)
-      f32x2 dot[4] = {};
-#pragma unroll
-      for (int mt = 0; mt < H2T; ++mt)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const f32x4v w3 = vec4(kW3 + 32 * mt + 8 * rr), wb = vec4(KW3B + 32 * mt + 8 * rr);
-#pragma unroll
-          for (int e = 0; e < 4; e += 2) {
-            const f32x2 xa = f32x2{acc[mt][4 * rr + e], acc[mt][4 * rr + e + 1]};
-            const f32x2 w3p = e ? f32x2{w3.z, w3.w} : f32x2{w3.x, w3.y}, wbp = e ? f32x2{wb.z, wb.w} : f32x2{wb.x, wb.y};
-            f32x2 m;
-            asm("v_min_f32 %0, 0, %1" : "=v"(m.x) : "v"(xa.x));
-            asm("v_min_f32 %0, 0, %1" : "=v"(m.y) : "v"(xa.y));
-            asm("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(dot[e >> 1]) : "v"(xa), "v"(w3p));
-            asm("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(dot[2 + (e >> 1)]) : "v"(m), "v"(wbp));
-          }
-        }
-      part = ((dot[0].x + dot[0].y) + (dot[1].x + dot[1].y)) + ((dot[2].x + dot[2].y) + (dot[3].x + dot[3].y));
-    } else {  // one chain, unit by unit (the fused kernel since round 4's first half)
-      part = 0.0f;
-#pragma unroll
-      for (int mt = 0; mt < H2T; ++mt)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const f32x4v be = vec4(kBeta2 + 32 * mt + 8 * rr), w3 = vec4(kW3 + 32 * mt + 8 * rr);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float xa = acc[mt][4 * rr + e];
-            part = __builtin_fmaf(__builtin_fmaf(neg_part(xa), be[e], xa), w3[e], part);
-          }
-        }
-    }
+      }
     const float other = __shfl_xor(part, 32);
     constexpr float kUnscale = 1.0f / (kSplit2Scale * kSplit2Scale);
     store(k, (part + other) * kUnscale);
@@ -370,7 +313,7 @@ __device__ __forceinline__ void wg_score_mlp_res(const float* __restrict__ proj,
     SplitPipeLds L;
     L.w_lo = w_lo; L.w_hi = w_hi; L.v_at = v_at; L.u_at = v_at; L.u_wr = 0u;  // (kU = 0: the query's u heads the vectors)
     int i_cur = 0;
-    wave_mlp_split_pipeline<0, -1>(
+    wave_mlp_split_pipeline(
         L, row_ptr(wave * 32 + cand), (nblk - wave + NW - 1) / NW,
         [&](int k, const float* row_k, const float*& next, bool&, float4&) {
           const int b = wave + k * NW;
@@ -408,7 +351,7 @@ __device__ __forceinline__ void wg_score_mlp_xres(const float* __restrict__ proj
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) p[rr] = *reinterpret_cast<const float4*>(row + 32 * t + 8 * rr);
   };
-  if (NANN_RES_XSKEW > 0 && wave >= NW / 2) __builtin_amdgcn_s_sleep(NANN_RES_XSKEW);  // SIMD partners half a tile apart (see the split form)
+  if (wave >= NW / 2) __builtin_amdgcn_s_sleep(kMlpResXSkew);  // SIMD partners half a tile apart (see the split form)
   auto load_ub = [&](int t, float4 (&ub)[8]) {
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
@@ -440,22 +383,16 @@ __device__ __forceinline__ void wg_score_mlp_xres(const float* __restrict__ proj
       for (int rr = 0; rr < 4; ++rr) {
         const float4 u = cur[rr], al = cur[4 + rr];
         constexpr float kInv = 1.0f / kSplit2Scale;  // the table holds 2^7 P: exact both ways
-#if (NANN_RES_VAR & 1)  // timing build: no layer-1 arithmetic
-        h[4 * rr + 0] = x[rr].x + u.x; h[4 * rr + 1] = x[rr].y + al.x; h[4 * rr + 2] = x[rr].z; h[4 * rr + 3] = x[rr].w;
-#else
         h[4 * rr + 0] = prelu(u.x + x[rr].x * kInv, al.x);
         h[4 * rr + 1] = prelu(u.y + x[rr].y * kInv, al.y);
         h[4 * rr + 2] = prelu(u.z + x[rr].z * kInv, al.z);
         h[4 * rr + 3] = prelu(u.w + x[rr].w * kInv, al.w);
-#endif
       }
       __builtin_amdgcn_sched_barrier(0);
-#if !(NANN_RES_VAR & 2)
       {
         const bool wrap = t + 2 >= H1T;
         load_tile(wrap ? next : row, wrap ? t + 2 - H1T : t + 2, x);
       }
-#endif
       load_ub((t + 1) & (H1T - 1), nxt);
       __builtin_amdgcn_sched_barrier(0);
       const float4* A = W2 + (size_t)t * (H2T * 4 * 64) + lane;
@@ -481,9 +418,6 @@ __device__ __forceinline__ void wg_score_mlp_xres(const float* __restrict__ proj
     row = next;
     // PReLU of layer 2 and the bias-free output layer: per-lane chain over its 64 outputs (wg_score_mlp's epilogue)
     float part = 0.0f;
-#if (NANN_RES_VAR & 4)  // timing build: no output chain
-    part = acc2[0][0] + acc2[1][1] + acc2[2][2] + acc2[3][3];
-#else
 #pragma unroll
     for (int mt = 0; mt < H2T; ++mt)
 #pragma unroll
@@ -491,7 +425,6 @@ __device__ __forceinline__ void wg_score_mlp_xres(const float* __restrict__ proj
         const int m = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * g;
         part = __fmaf_rn(prelu(acc2[mt][r], V->beta2[m]), V->w3[m], part);
       }
-#endif
     const float other = __shfl_xor(part, 32);
     const float p0 = g == 0 ? part : other, p1 = g == 0 ? other : part;
     if (g == 0 && i < n) scores[i] = p0 + p1;

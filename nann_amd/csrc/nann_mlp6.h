@@ -49,7 +49,6 @@ struct PhaseScoreArgs {
   uint32_t n_items;
   int n_queries;
   int round;
-  int dry;                      // timing launches (NANN_PHASE_SHADOW, tools/): everything but the store of the scores
   MlpParams mlp;
   // certified form only (k_mlp_phase_certify and the filter / refine instances of k_mlp_phase_score)
   unsigned long long off_raw;   // the slot's raw region: the filter's bounds, then the certify step's survivor list
@@ -58,18 +57,6 @@ struct PhaseScoreArgs {
   const int32_t* tq;
   unsigned long long* refined;  // WsHeader::refined[NANN_NUM_ROUNDS]
 };
-
-// timing builds (tools/build_res_variant.py -DNANN_PHASE_VAR=bits): the split-f16 scoring launch WITHOUT 1 = its gathers,
-// 2 = its W2 fragment reads, 4 = the PReLU / split arithmetic, 8 = the MFMAs; 16 = WITH the PReLU decomposition's cost (one v_max per
-// element, 512 more gathered bytes per row: nann_mlp5.h) -- run as a second, dry launch behind the real
-// one (NANN_PHASE_SHADOW=1), so that both see the same lists
-#ifndef NANN_PHASE_VAR
-#define NANN_PHASE_VAR 0
-#endif
-#ifndef NANN_PHASE_PACKED_EPI
-#define NANN_PHASE_PACKED_EPI 0  // 1: the scoring launch's output layer as two packed dot products (2 instead of 3 instructions per unit;
-                                 // measured 0.7 % slower, and other bits than the fused kernel's chain: profiles/r4x_*)
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------
 // The certified form (NANN_MLP_CERTIFIED): a round is scored by THREE launches, and its selection then runs as usual.
@@ -134,7 +121,7 @@ __device__ __forceinline__ void mlp_filter_vectors(const MlpParams& P, Mlp2Vecto
 // (wg_score_mlp_xres's arithmetic), else split-f16 (wg_score_mlp_res's).
 // CERT (the certified form, NANN_MLP_CERTIFIED; see the filter's comment below): 1 = EXACT over the rows the certify step
 // kept (PhaseState.ref_n, listed in the raw region when ref_list), scores scattered to their places; 2 = the f16 filter.
-template <bool EXACT, int VAR = 0, int CERT = 0>
+template <bool EXACT, int CERT = 0>
 __global__ __launch_bounds__(512, 2) void k_mlp_phase_score(PhaseScoreArgs a) {
   static_assert(CERT == 0 || (CERT == 1) == EXACT, "refine: exact f32; filter: f16");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -169,7 +156,6 @@ __global__ __launch_bounds__(512, 2) void k_mlp_phase_score(PhaseScoreArgs a) {
     if (EXACT) wg_mlp_xres_vectors<NT>(a.mlp, 0.0f, V);
     else if (CERT == 2) mlp_filter_vectors<NT>(a.mlp, V);
     else wg_mlp_res_vectors<NT>(a.mlp, 0.0f, V);
-    if (!EXACT && NANN_PHASE_PACKED_EPI && tid < 128) V->u[tid] = a.mlp.w3[tid] * (a.mlp.alpha2[tid] - 1.0f);  // (the same thread wrote the 0 above)
   }
   __syncthreads();
   int total = 0;
@@ -248,7 +234,6 @@ __global__ __launch_bounds__(512, 2) void k_mlp_phase_score(PhaseScoreArgs a) {
   auto vec4 = [&](int float_index) -> f32x4v { return *reinterpret_cast<lds_f4_ptr>(v_at + 4 * float_index); };
   auto uvec4 = [&](int float_index) -> f32x4v { return *reinterpret_cast<lds_f4_ptr>(u_at + 4 * float_index); };
   constexpr int kBeta1 = 256, kB2 = 512, kBeta2 = 640, kW3 = 768;  // Mlp2Vectors, in floats
-  constexpr int kW3b = 0;  // split-f16: w3 (alpha2 - 1), in the place of the fused kernel's per-workgroup u (here: one u per wavefront)
 
   if constexpr (CERT == 2) {
     // ---- the certified form's filter (comment above mlp_filter_vectors): one f16 product per fragment, tile by tile
@@ -333,7 +318,7 @@ __global__ __launch_bounds__(512, 2) void k_mlp_phase_score(PhaseScoreArgs a) {
       // widened by 2^-20 (|s| + B): s - B and s + B are then bounds after their own f32 rounding
       bnd = __builtin_fmaf(__builtin_fabsf(s), 0x1p-20f, bnd * (1.0f + 0x1p-20f));
       if (!(__builtin_isfinite(s) && __builtin_isfinite(bnd))) bnd = __builtin_inff();
-      if (g == 0 && i < cur.n && !a.dry) {
+      if (g == 0 && i < cur.n) {
         cur.out[i] = s;
         if (cur.bnd != nullptr) cur.bnd[i] = bnd;
       }
@@ -356,8 +341,7 @@ __global__ __launch_bounds__(512, 2) void k_mlp_phase_score(PhaseScoreArgs a) {
     SplitPipeLds L;
     L.w_lo = w_lo; L.w_hi = w_hi; L.v_at = v_at; L.u_at = u_at;
     L.u_wr = lds_offset_of(u_w) + (uint32_t)lane * 16u;
-    L.seed_base = a.proj; L.seed_rows = a.n_items;  // (read by the VAR & 16 pricing build only)
-    wave_mlp_split_pipeline<VAR, NANN_PHASE_PACKED_EPI ? kW3b : -1>(
+    wave_mlp_split_pipeline(
         L, row_ptr(cur, b_lo), b_hi - b_lo,
         [&](int k, const float* row, const float*& next, bool& change, float4& u_next) {  // the block behind block b_lo + k
           const int b = b_lo + k;
@@ -373,7 +357,7 @@ __global__ __launch_bounds__(512, 2) void k_mlp_phase_score(PhaseScoreArgs a) {
           i_cur = (b - cur.first) * 32 + cand;
         },
         [&](int, float score) {
-          if (g == 0 && i_cur < cur.n && !a.dry) cur.out[i_cur] = score;
+          if (g == 0 && i_cur < cur.n) cur.out[i_cur] = score;
           cur = nxt;
         });
     return;
@@ -451,7 +435,7 @@ __global__ __launch_bounds__(512, 2) void k_mlp_phase_score(PhaseScoreArgs a) {
       }
     const float other = __shfl_xor(part, 32);
     const float p0 = g == 0 ? part : other, p1 = g == 0 ? other : part;
-    if (g == 0 && i < cur.n && !a.dry) cur.out[(CERT == 1 && cur.list != nullptr) ? cur.list[i] : i] = p0 + p1;
+    if (g == 0 && i < cur.n) cur.out[(CERT == 1 && cur.list != nullptr) ? cur.list[i] : i] = p0 + p1;
     row = next;
     cur = nxt;
   }

@@ -282,10 +282,7 @@ __device__ __forceinline__ int search_one(const SearchArgs& a, int qi, const Slo
 
   // top-k ranks its selected pairs bin by bin (nann_device.h, round 6) in the L2 traversals: ~11 of a lone query's 144 us were the
   // all-pairs ranking (the register-starved MLP / attention kernels keep it: their selection is a percent of their time)
-#ifndef NANN_TOPK_BINS
-#define NANN_TOPK_BINS 1
-#endif
-  constexpr bool kTopkBins = NANN_TOPK_BINS && SC == NANN_SCORER_L2;
+  constexpr bool kTopkBins = SC == NANN_SCORER_L2;
   // The schedule of build_opt_graph.py:109-149 as six stages with ONE call site per
   // building block: stage 0 = entry layer (:111-112), 1 = level 1 (:114-127),
   // 2..4 = the three level-0 rounds (:129-141), 5 = final top-k (:143-149).

@@ -2,7 +2,7 @@
 """Timing / tuning builds of the resident-layer-2 MLP traversal (nann_amd/csrc/nann_mlp5.h): recompiles ONLY
 the translation unit nann_mlp_res_inst.hip lives in with extra -D flags and links it with the objects of the shipped build into
 nann_amd/_build/var_<name>/libnann_hip.so (load with NANN_HIP_LIB=...).  ~20 s per variant instead of a full rebuild.
-usage: tools/build_res_variant.py <name> [--unit nann_l2_inst.hip] [-DNANN_RES_PF=2] [-DNANN_RES_VAR=1] ...
+usage: tools/build_res_variant.py <name> [--unit nann_l2_inst.hip] [-DNANN_REPEAT_SCORE=2] ...
 (--unit: the FIRST translation unit that holds that source instead -- e.g. the f16 L2 traversal for the phase-repeat builds
 of nann_search.h, NANN_REPEAT_SCORE / NANN_REPEAT_TOPK)"""
 import os

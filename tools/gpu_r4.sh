@@ -307,14 +307,6 @@ PY
         F=$(find /tmp/prof/kt_ph_$P -name '*kernel_trace.csv' | head -1)
         echo "PHASED $P"; python tools/phase_trace.py $F 20 | tee $OUT/phase_trace_${P}_$TAG.txt
       done ;;
-    phase_vars)  # timing builds of the split-f16 scoring launch (nann_mlp6.h NANN_PHASE_VAR) as dry launches behind the real ones
-      for L in $R/nann_amd/_build/libnann_hip.so $R/nann_amd/_build/var_ph*/libnann_hip.so; do
-        V=$(basename $(dirname $L)); [ "$V" = "_build" ] && V=shipped
-        rm -rf /tmp/prof/kt_pv
-        ( cd /tmp && NANN_PHASE_SHADOW=1 NANN_HIP_LIB=$L timeout 200 rocprofv3 --kernel-trace --output-format csv -d /tmp/prof/kt_pv -o kt -- $BENCH --scorer mlp --mlp-precision split --batch 1024 --steps 20 --warmup 40 --no-secondary --no-cpu-baseline > $OUT/prof_kt_pv_${V}_$TAG.log 2>&1 )
-        F=$(find /tmp/prof/kt_pv -name '*kernel_trace.csv' | head -1)
-        echo "PHASEVAR $V"; python tools/phase_trace.py $F 12 | tee $OUT/phase_vars_${V}_$TAG.txt | grep -E "phase_score|sum of"
-      done ;;
     pmc_phased)  # counters of the pipeline of phases, per kernel (sums over all dispatches of the run; clock = GRBM cycles / duration)
       for P in ${PH_PRECISIONS:-split}; do
         S="--scorer mlp --mlp-precision $P --batch 1024 --steps 8 --warmup 24 --no-secondary --no-cpu-baseline"

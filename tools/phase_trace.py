@@ -12,13 +12,13 @@ from collections import defaultdict
 
 
 def short(name):
-    for key in ("k_mlp_phase_score", "k_mlp_phase_prefix", "k_search", "k_user_seq_mean", "k_mlp_preproject"):
+    for key in ("k_mlp_phase_score", "k_mlp_phase_certify", "k_search", "k_user_seq_mean", "k_mlp_preproject"):
         if key in name:
             if key == "k_search":
                 return "k_search<phase>" if ", 9," in name or ",9," in name else "k_search<fallback>"
-            if key == "k_mlp_phase_score":
+            if key == "k_mlp_phase_score":  # <EXACT, CERT>: CERT 2 = the certified form's filter, 1 = its refine
                 m = re.search(r"k_mlp_phase_score<(\w+), (\d+)>", name)
-                return key + ("<exact>" if m and m.group(1) == "true" else "") + ("/var%s" % m.group(2) if m and m.group(2) != "0" else "")
+                return key + ("<exact>" if m and m.group(1) == "true" else "") + {"1": "/refine", "2": "/filter"}.get(m.group(2) if m else "", "")
             return key
     return name[:40]
 

@@ -1,13 +1,15 @@
 // ubench_mlp2: where does a 256-row pass of the split-f16 MLP scorer's second mapping (nann_mlp2.h) spend its time?
 // The stand-alone scorer over random rows / random weights, in timing variants with parts compiled out (VAR bits of
 // wg_score_mlp_split2), each: wall us per pass per CU, shader ticks per pass (s_memtime of wave 0), tick rate.
-// build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -fno-fast-math -ffp-contract=off tools/ubench_mlp2.hip -o tools/_build/ubench_mlp2
+// RETIRED: its findings are DESIGN.md 4.2 facts 2-3 (profiles/r3b_ubench_mlp2_a.txt), and the VAR parameter it needs was
+// removed from wg_score_mlp_split2; to build it again, take nann_mlp2.h from git show 370122c:nann_amd/csrc/nann_mlp2.h.
+// build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -fno-fast-math -ffp-contract=off tools/rejected/ubench_mlp2.hip -o tools/_build/ubench_mlp2
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "rejected/nann_mlp3_streamed_layer2.h"
+#include "nann_mlp3_streamed_layer2.h"
 
 using namespace nann;
 

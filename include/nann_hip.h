@@ -481,6 +481,31 @@ int nann_search_reruns(const void* workspace, int64_t* n_rerun, nann_stream_t st
  * precisions and scorers, and the plans on which CERTIFIED runs the exact kernels.  Synchronises `stream`. */
 int nann_search_refined(const void* workspace, int64_t out[NANN_NUM_ROUNDS], nann_stream_t stream);
 
+/* ---- exhaustive search: test_all (NANN_impls/main.py:194-237) for a batch of queries ------------------------------
+ * Every item of the index scored for every query, then TopKV2 sorted=true per query (NANN_impls/nann/util.py:9-11 is the
+ * recall the reference computes against it): descending, ties -> lower internal row number, -0 and +0 tie.  The ground
+ * truth of every recall figure, as ONE call instead of a nann_score + nann_topk loop over the queries: a row is fetched
+ * once for a tile of queries, the selection runs on every CU (csrc/nann_scan.h).
+ *   q            f32[n_queries, d]
+ *   out_item_ids i64[n_queries, k] = item_ids[out_index]
+ *   out_scores   f32[n_queries, k] or NULL;  out_index i32[n_queries, k] (internal row numbers) or NULL
+ *   workspace    device, 256-byte aligned (else NANN_ERR_BAD_ARGUMENT), nann_search_all_workspace_bytes(...) bytes; smaller ->
+ *                NANN_ERR_CAPACITY.  Bounded: queries are processed in chunks inside the call -- the scores of a chunk take at
+ *                most max(512 MiB, one query's 4 B x n_items) at a time, never n_queries x n_items
+ *   options      NULL = defaults; only `preprojection` is read (-1: the process default)
+ * L2 scorer: every d and row dtype nann_score accepts, scores bit-identical to the oracle (DESIGN.md 2's order).  MLP scorer:
+ * scored from the pre-projected table of the (scorer, index) pair, found or built as in nann_search_opt -- EXACT_F32 and
+ * CERTIFIED (which runs the exact arithmetic here) bit-identical to the oracle, SPLIT_F16 within 1e-5 max(1, |s|); without a
+ * table NANN_ERR_CAPACITY (no room in HBM) or NANN_ERR_UNSUPPORTED (preprojection resolves to 0).
+ * k < 0 or n_queries < 0 -> NANN_ERR_BAD_ARGUMENT; k > n_items -> NANN_ERR_TOPK_K_GT_N, nothing launched (as nann_topk); k == 0 or
+ * n_queries == 0 -> NANN_OK, nothing written; k > 1024 -> NANN_ERR_UNSUPPORTED.  A query's answer does not depend on the batch
+ * it is in.  Asynchronous on `stream`, no host read-back, re-entrant on shared handles. */
+int nann_search_all_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k,
+                                    int64_t* nbytes);
+int nann_search_all(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                    int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                    const nann_search_options* options, nann_stream_t stream);
+
 /* The serving signature in one call (build_opt_graph.py:151-159): comm_seq f16[n_queries, seq_len, E]
  * + level_topn -> top_k, scored by whatever model the BlazeXlaOp nodes of the graph name.  l2 / mlp:
  * nann_user_seq_mean + nann_search.  attention: the per-user projection once per request

@@ -12,7 +12,7 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 # one after the other.  Round 5: 13 units -> 9: the three small host-facing files share one object, the
 # resident-layer-2 MLP kernels ride with the d = 64 MLP instances.  Round 6: 12 units -- the evaluation traversal's LDS forms are
 # units of their own, and the bf16 and f32 L2 instances are two again (their shared unit had become the longest: it alone bounded
-# a build from scratch at ~6 min on 8 cores).
+# a build from scratch at ~6 min on 8 cores).  The exhaustive search (nann_scan.h) is a unit of its own, the thirteenth.
 UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_comm.hip", {}), ("nann_hnsw_build.hip", {})]),
          ("nann_l2_f16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "0", "NANN_L2_NAME": "f16"})]),
          ("nann_l2_bf16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "1", "NANN_L2_NAME": "bf16"})]),
@@ -24,8 +24,9 @@ UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_comm.hip", {}), ("nann_hn
          ("nann_attn_split.o", [("nann_attn_split_inst.hip", {})]),
          ("nann_eval.o", [("nann_eval_inst.hip", {})]),
          ("nann_eval_lds.o", [("nann_eval_lds_inst.hip", {})]),
-         ("nann_eval_win.o", [("nann_eval_win_inst.hip", {})])]
-DEPS = ["nann_hip.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
+         ("nann_eval_win.o", [("nann_eval_win_inst.hip", {})]),
+         ("nann_scan.o", [("nann_scan_inst.hip", {})])]
+DEPS = ["nann_hip.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_scan_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
         "nann_attn.h", "nann_attn_kernels.h", "nann_search.h", "nann_order.h", "nann_order_kernels.h", os.path.join("host", "nann_graphdef.h"), os.path.join("host", "nann_graphdef_text.h"), os.path.join("host", "nann_blaze_options.h"), os.path.join("host", "nann_npy.h"), os.path.join("host", "nann_projcache.h"),
         os.path.join("..", "..", "include", "nann_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-fast-math", "-ffp-contract=off"]
@@ -101,6 +102,22 @@ def _check_occupancy(log_path):
             raise RuntimeError(f"{name}: occupancy {m.group(1)} waves/SIMD, the hash-set kernel needs 4")
 
 
+def _check_scan_scratch(log_path):
+    """The L2 scan of the exhaustive search (k_scan_l2, nann_scan.h) stages every byte of the table it reads through registers
+    into LDS.  When hipcc leaves that staging buffer in private memory the kernel still computes the same bits, with three times
+    the memory traffic and no other symptom (seen: ScratchSize 144 from an indexed uint4 array held across a barrier).  Refuse to
+    link a k_scan_l2 with a scratch frame."""
+    import re
+    name = None
+    for line in open(log_path, errors="replace"):
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and name and "k_scan_l2" in name and int(m.group(1)) != 0:
+            raise RuntimeError(f"{name}: {m.group(1)} bytes of scratch per lane, the scan kernel must have none")
+
+
 def unit_command(obj, parts, odir, extra_flags=(), save_temps=True):
     """Write the wrapper of a translation unit into `odir` and return the hipcc command that compiles it to odir/obj."""
     unit = os.path.join(odir, "unit.hip")
@@ -136,6 +153,7 @@ def _build_into(OUT_DIR, LIB, extra_flags, verbose, only=None):
             sys.stderr.write(open(os.path.join(odir, "compile.log")).read()[-6000:])
             raise subprocess.CalledProcessError(p.returncode, cmd)
         _check_occupancy(os.path.join(odir, "compile.log"))
+        _check_scan_scratch(os.path.join(odir, "compile.log"))
     # hipcc (ROCm 7.2) can place VGPR spill code ahead of the exec restore of a join block; the
     # lanes that were masked off then reload garbage (seen: top-k positions all -1).  Refuse
     # to ship an object with that pattern.

@@ -4,6 +4,7 @@
 #include "nann_eval.h"
 #include "nann_attn.h"
 #include "nann_order_kernels.h"
+#include "nann_scan.h"
 #include "host/nann_graphdef_text.h"
 #include "host/nann_blaze_options.h"
 #include "host/nann_npy.h"
@@ -2643,6 +2644,76 @@ int nann_search_v(const nann_index* ix, const nann_scorer* scorer, const float* 
                   int32_t* status, int32_t* counters, nann_stream_t stream) {
   return nann_search_opt(ix, scorer, q, n_queries, level_topn_max, level_topn, workspace, workspace_bytes, out_item_ids,
                          out_scores, out_index, status, counters, nullptr, nullptr, nullptr, stream);  // deprecated: thin wrapper
+}
+
+// ---- exhaustive search (nann_scan.h): test_all of main.py:194-237 for a batch ---------------------------------
+static int search_all_check(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k, const char* who) {
+  if (!ix || !scorer) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (n_queries < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_queries < 0");
+  const int d = ix->desc.d;
+  if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
+  if (scorer->desc.d != ix->desc.d || scorer->desc.emb_dtype != ix->desc.emb_dtype)
+    return fail(NANN_ERR_BAD_ARGUMENT, "scorer and index disagree on d / dtype");
+  if (k < 0) return fail(NANN_ERR_BAD_ARGUMENT, "Need k >= 0, got " + std::to_string(k));  // topk_op.cc:60-61
+  if (ix->desc.n_items < k)
+    return fail(NANN_ERR_TOPK_K_GT_N, "input must have at least k columns. Had " + std::to_string(ix->desc.n_items) +
+                                          ", needed " + std::to_string(k));
+  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
+  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  return NANN_OK;
+}
+
+int nann_search_all_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k,
+                                    int64_t* nbytes) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_workspace_bytes: null argument");
+  const int rc = search_all_check(ix, scorer, n_queries, k, "nann_search_all_workspace_bytes");
+  if (rc) return rc;
+  if (n_queries <= 0 || k == 0) { *nbytes = 0; return NANN_OK; }
+  *nbytes = (int64_t)scan_layout((long long)ix->desc.n_items, ix->desc.d, scorer->desc.kind, (long long)n_queries, k).total;
+  return NANN_OK;
+}
+
+int nann_search_all(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                    int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                    const nann_search_options* options, nann_stream_t stream) {
+  int rc = search_all_check(ix, scorer, n_queries, k, "nann_search_all");
+  if (rc) return rc;
+  if (n_queries <= 0 || k == 0) return NANN_OK;
+  if (!q || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all: null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  const SearchOpt opt = resolve_options(options);
+  const ScanLayout L = scan_layout((long long)ix->desc.n_items, ix->desc.d, scorer->desc.kind, (long long)n_queries, k);
+  if (!workspace || workspace_bytes < (int64_t)L.total)
+    return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_all_workspace_bytes()");
+  if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all: workspace must be 256-byte aligned");
+  hipStream_t st = as_stream(stream);
+  ScanArgs a = {};
+  a.emb = ix->desc.item_embs;
+  a.item_ids = ix->desc.item_ids;
+  a.n_items = (long long)ix->desc.n_items;
+  a.d = ix->desc.d;
+  a.dt = ix->desc.emb_dtype;
+  a.kind = scorer->desc.kind;
+  if (a.kind != NANN_SCORER_MLP)
+    return launch_scan(a, L, q, (long long)n_queries, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index, st);
+  // the MLP scores from the pre-projected table of the pair, obtained and released as search_impl does
+  if (!opt.preproject)
+    return fail(NANN_ERR_UNSUPPORTED, "nann_search_all: the MLP scan reads the pre-projected table and preprojection is switched off");
+  std::shared_ptr<ProjTable> tab;
+  rc = mlp_projection(scorer, ix, st, false, true, &tab);
+  if (rc) return rc;
+  if (!tab) return fail(NANN_ERR_CAPACITY, "nann_search_all: no room in HBM for the pre-projected table of this (scorer, index) pair");
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  a.proj = tab->table;
+  a.mlp = scorer->mlp;
+  a.exact = scorer->desc.precision == NANN_MLP_EXACT_F32 || scorer->desc.precision == NANN_MLP_CERTIFIED;
+  a.mlp_workgroups = di.cus;
+  rc = launch_scan(a, L, q, (long long)n_queries, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index, st);
+  projection_used(scorer->proj, tab, st);
+  return rc;
 }
 
 // ---- lifecycle of the pre-projected tables (ProjCache) -------------------------------------------------------

@@ -1,0 +1,102 @@
+// nann_scan_inst.hip -- the kernels of the exhaustive search (nann_scan.h): the L2 scan for every (d, row dtype), the MLP scan
+// in both precisions, the slab top-k and the merge; workspace layout and the launch sequence of a call.
+#define NANN_SCAN_IMPL
+#include "nann_scan.h"
+
+#include <algorithm>
+
+namespace nann {
+
+namespace {
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+constexpr size_t kScanScoreBytes = (size_t)512 << 20;  // most bytes of a chunk's score buffer -- or one query's scores (4 B x n_items) where that is more
+}  // namespace
+
+ScanLayout scan_layout(long long n_items, int d, int kind, long long n_queries, int k) {
+  ScanLayout L = {};
+  const int tq = kScanTileQueries;
+  long long chunk = std::min<long long>(kScanMaxChunk, (long long)(kScanScoreBytes / ((size_t)n_items * 4)));
+  chunk = std::max<long long>(1, std::min(chunk, n_queries));
+  if (kind == NANN_SCORER_L2 && chunk > tq) chunk -= chunk % tq;  // whole tiles of queries
+  L.chunk = (int)chunk;
+  L.n_slabs = scan_n_slabs(n_items);
+  const size_t cand = (size_t)L.chunk * L.n_slabs * k * 4;
+  const size_t qbytes = kind == NANN_SCORER_L2 ? (size_t)((L.chunk + tq - 1) / tq) * tq * d * 4 : (size_t)L.chunk * 256 * 4;
+  L.off_scores = 0;
+  L.off_cand_scores = up256((size_t)L.chunk * (size_t)n_items * 4);
+  L.off_cand_rows = L.off_cand_scores + up256(cand);
+  L.off_q = L.off_cand_rows + up256(cand);
+  L.total = L.off_q + up256(qbytes);
+  return L;
+}
+
+template <int LPR, int DT>
+static int launch_scan_l2_as(const ScanArgs& a, const float* qT, int n_q, float* scores, hipStream_t st) {
+  constexpr int TQ = kScanTileQueries;
+  const int tiles = (n_q + TQ - 1) / TQ;
+  const long long blocks = (a.n_items + kScanRows - 1) / kScanRows * tiles;
+  if (blocks > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, "nann_search_all: index too large for one launch");
+  hipLaunchKernelGGL((k_scan_l2<LPR, DT, TQ>), dim3((unsigned)blocks), dim3(kScanRows), 0, st, a.emb, a.n_items, qT, n_q, tiles, scores);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+template <int LPR>
+static int launch_scan_l2_dt(const ScanArgs& a, const float* qT, int n_q, float* scores, hipStream_t st) {
+  if (a.dt == NANN_F16) return launch_scan_l2_as<LPR, DT_F16>(a, qT, n_q, scores, st);
+  if (a.dt == NANN_BF16) return launch_scan_l2_as<LPR, DT_BF16>(a, qT, n_q, scores, st);
+  return launch_scan_l2_as<LPR, DT_F32>(a, qT, n_q, scores, st);
+}
+
+template <bool EXACT>
+static int launch_scan_mlp_as(const ScanArgs& a, const float* u, int n_q, float* scores, hipStream_t st) {
+  auto kern = k_scan_mlp<EXACT>;
+  NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kMlpResBytes));
+  const long long n_work = (a.n_items + kScanMlpRows - 1) / kScanMlpRows * n_q;
+  const unsigned grid = (unsigned)std::min<long long>(n_work, std::max(1, a.mlp_workgroups));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), (size_t)kMlpResBytes, st, a.mlp, a.proj, a.n_items, u, n_q, scores);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
+                int64_t* out_item_ids, float* out_scores, int32_t* out_index, hipStream_t st) {
+  float* scores = reinterpret_cast<float*>(ws + L.off_scores);
+  float* cand_scores = reinterpret_cast<float*>(ws + L.off_cand_scores);
+  int32_t* cand_rows = reinterpret_cast<int32_t*>(ws + L.off_cand_rows);
+  float* qbuf = reinterpret_cast<float*>(ws + L.off_q);
+  const int lpr = a.d / 8;
+  for (long long c0 = 0; c0 < n_queries; c0 += L.chunk) {
+    const int n_q = (int)std::min<long long>(L.chunk, n_queries - c0);
+    const float* qc = q + (size_t)c0 * a.d;
+    int rc;
+    if (a.kind == NANN_SCORER_L2) {
+      const int tq = kScanTileQueries;
+      const long long total = (long long)((n_q + tq - 1) / tq) * tq * a.d;
+      hipLaunchKernelGGL(k_scan_transpose_q, dim3((unsigned)std::min<long long>((total + 255) / 256, 1024)), dim3(256), 0, st, qc, n_q, a.d, tq, qbuf);
+      NANN_HIP_TRY(hipGetLastError());
+      switch (lpr) {
+        case 8: rc = launch_scan_l2_dt<8>(a, qbuf, n_q, scores, st); break;
+        case 16: rc = launch_scan_l2_dt<16>(a, qbuf, n_q, scores, st); break;
+        case 32: rc = launch_scan_l2_dt<32>(a, qbuf, n_q, scores, st); break;
+        case 64: rc = launch_scan_l2_dt<64>(a, qbuf, n_q, scores, st); break;
+        default: return fail(NANN_ERR_UNSUPPORTED, "nann_search_all: d must be 64, 128, 256 or 512");
+      }
+    } else {
+      hipLaunchKernelGGL(k_scan_mlp_u, dim3((unsigned)n_q), dim3(256), 0, st, a.mlp, qc, qbuf);
+      NANN_HIP_TRY(hipGetLastError());
+      rc = a.exact ? launch_scan_mlp_as<true>(a, qbuf, n_q, scores, st) : launch_scan_mlp_as<false>(a, qbuf, n_q, scores, st);
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_scan_slab_topk, dim3((unsigned)((long long)n_q * L.n_slabs)), dim3(kNT), 0, st, scores, a.n_items, L.n_slabs, k,
+                       cand_scores, cand_rows);
+    NANN_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_scan_merge, dim3((unsigned)n_q), dim3(kNT), 0, st, cand_scores, cand_rows, L.n_slabs * k, k, a.item_ids,
+                       out_item_ids + (size_t)c0 * k, out_scores ? out_scores + (size_t)c0 * k : nullptr,
+                       out_index ? out_index + (size_t)c0 * k : nullptr);
+    NANN_HIP_TRY(hipGetLastError());
+  }
+  return NANN_OK;
+}
+
+}  // namespace nann

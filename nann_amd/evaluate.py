@@ -89,33 +89,64 @@ def test(index, scorer, user_seqs, ground_truths, topk_eval=(200,), num_scoring_
     return {"precision": prec, "recall": rec, "f1": f1m}
 
 
-def test_all(index, scorer, user_seqs, ground_truths, topk_eval=(200,), num_test_batch=None):
+def _search_all_or_none(index, scorer, q, k):
+    """The brute-force top k of a batch in one call (retrieval.search_all) -> internal row numbers i32[B, k] on the host,
+    or None where the per-user loop has to run: an attention model, or an MLP scorer without its pre-projected table
+    (NANN_ERR_CAPACITY: no room in HBM; NANN_ERR_UNSUPPORTED: pre-projection switched off)."""
+    if isinstance(scorer, ops.Model) and scorer.kind == "attention":
+        return None
+    try:
+        return retrieval.search_all(index, scorer, q, k).index.cpu().numpy()
+    except ops.NannError as e:
+        if e.status in (102, 103):
+            return None
+        raise
+
+
+def test_all(index, scorer, user_seqs, ground_truths, topk_eval=(200,), num_test_batch=None, batched=False):
     """main.py:194-237: score EVERY item for each user, take the top max(topk_eval) (fast_argtopk,
-    util.py:9-11) -> the recall ceiling of the scorer itself."""
+    util.py:9-11) -> the recall ceiling of the scorer itself.  batched=True: all users in one retrieval.search_all call
+    instead of a blaze_score + top_k loop (an MLP scorer is then scored from its pre-projected table: with the split-f16
+    precision a near-tie may be ordered differently than by the loop's three-layer scorer)."""
     n = len(ground_truths) if num_test_batch is None else min(num_test_batch, len(ground_truths))
     prec, rec, f1m = defaultdict(AverageMeter), defaultdict(AverageMeter), defaultdict(AverageMeter)
     seqs = torch.as_tensor(np.asarray(user_seqs)).to(index.device)
+    rows = None
+    if batched and n > 0:
+        q = seqs[:n] if isinstance(scorer, ops.Model) else ops.user_seq_mean(seqs[:n])
+        rows = _search_all_or_none(index, scorer, q, max(topk_eval))
+    item_ids = index.item_ids.cpu().numpy() if rows is not None else None
     for u in range(n):
-        scores_all = _score_all(index, scorer, seqs[u])
-        _, idx = ops.top_k(scores_all, max(topk_eval))
-        ids = index.item_ids[idx.long()].cpu().numpy()
+        if rows is not None:
+            ids = item_ids[rows[u]]
+        else:
+            scores_all = _score_all(index, scorer, seqs[u])
+            _, idx = ops.top_k(scores_all, max(topk_eval))
+            ids = index.item_ids[idx.long()].cpu().numpy()
         for k in topk_eval:
             p, r, f = calc_pr(ground_truths[u], ids[:k])
             prec[k].update(p); rec[k].update(r); f1m[k].update(f)
     return {"precision": prec, "recall": rec, "f1": f1m}
 
 
-def recall_vs_bruteforce(index, scorer, q, level_topn, n_queries=None):
+def recall_vs_bruteforce(index, scorer, q, level_topn, n_queries=None, batched=False):
     """How much of the brute-force top-k (same scorer) the serving-graph traversal (nann_search) returns:
-    the recall@k figure bench.py reports."""
+    the recall@k figure bench.py reports.  batched=True: the brute force of all sampled queries is one
+    retrieval.search_all call (see test_all)."""
     r = retrieval.search(index, scorer, q, level_topn, want_counters=False)
     k = int(level_topn[5])
     st, got = r.status.cpu().numpy(), r.index.cpu().numpy()
+    n = q.shape[0] if n_queries is None else min(n_queries, q.shape[0])
+    rows = _search_all_or_none(index, scorer, q[:n], k) if batched and n > 0 else None
     hits = total = 0
-    for b in range(q.shape[0] if n_queries is None else min(n_queries, q.shape[0])):
+    for b in range(n):
         if st[b]:
             continue
-        _, bi = ops.top_k(ops.blaze_score(scorer, q[b], item_emb=index.item_embs), k)
-        hits += len(set(bi.cpu().tolist()) & set(got[b].tolist()))
+        if rows is not None:
+            truth = rows[b].tolist()
+        else:
+            _, bi = ops.top_k(ops.blaze_score(scorer, q[b], item_emb=index.item_embs), k)
+            truth = bi.cpu().tolist()
+        hits += len(set(truth) & set(got[b].tolist()))
         total += k
     return hits / max(total, 1)

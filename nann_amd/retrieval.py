@@ -6,6 +6,8 @@ per request.  Two equivalent executions of that schedule live here:
 
   * `search()`        one fused launch for a whole batch of queries
                       (nann_search in include/nann_hip.h) -- the product path;
+  * `search_all()`    its referee: every item scored for a batch of queries, top k
+                      per query (nann_search_all; main.py:194-237 `test_all`);
   * `search_per_op()` the same schedule spelled op by op with the drop-in ops
                       of nann_amd.ops, line for line against build_model(), so
                       that each op is exercised in the composition the
@@ -247,6 +249,45 @@ def search_model(index, model, comm_seq, level_topn, want_counters=True, options
                                            C.byref(options) if options is not None else None, C.byref(plan), _stream()), "search")
     return SearchResult(out_ids, out_scores, out_index, status, counters, None, _plan_dict(plan), ws,
                         slot_reserve=int(options.slot_reserve) if options is not None else None)
+
+
+class SearchAllResult:
+    """Outputs of search_all: the top k of EVERY item per query, TopKV2 order (device tensors)."""
+    __slots__ = ("item_ids", "scores", "index", "_ws")
+
+    def __init__(self, item_ids, scores, index, ws=None):
+        self.item_ids, self.scores, self.index, self._ws = item_ids, scores, index, ws
+
+
+def search_all(index, scorer, q, k, options=None):
+    """Exhaustive search for a batch (nann_search_all; the reference's test_all job, main.py:194-237): every item of
+    `index` scored for every query, top k per query -- descending, ties -> lower internal row number.  `scorer`:
+    ops.Scorer with q f32[B, d], or an ops.Model of kind l2 / mlp with q = comm_seq f16[B, seq_len, d] (its
+    ops.user_seq_mean is the query); an attention model raises NotImplementedError (score it user by user:
+    evaluate.test_all).  options: search_options(preprojection=...).  Asynchronous on torch's current stream.
+    An MLP scorer reads its pre-projected table; without one the call raises ops.NannError with status 103 (no room in
+    HBM) or 102 (pre-projection switched off)."""
+    dev = index.device
+    handle = scorer.handle
+    if isinstance(scorer, ops.Model):
+        if scorer.kind == "attention":
+            raise NotImplementedError("search_all: l2 / mlp scorers only; the attention model is scored user by user")
+        q = ops.user_seq_mean(q.to(dev))
+        handle = C.c_void_p(lib().nann_model_scorer(scorer.handle))  # (borrowed: the model owns it)
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    b, k = q.shape[0], int(k)
+    kk = max(k, 0)
+    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_all_workspace_bytes(index.handle, handle, b, k, C.byref(nbytes)), "search_all")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_all(index.handle, handle, _ptr(q), b, k, _ptr(out_ids), _ptr(out_scores), _ptr(out_index),
+                                     _ptr(ws), ws.numel(), C.byref(options) if options is not None else None, _stream()),
+               "search_all")
+    return SearchAllResult(out_ids, out_scores, out_index, ws)
 
 
 def prepare(index, scorer):

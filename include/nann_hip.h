@@ -536,6 +536,32 @@ int nann_model_prepare(const nann_model* m, const nann_index* ix, nann_stream_t 
 int nann_model_release(const nann_model* m, const nann_index* ix);
 int nann_model_table_bytes(const nann_model* m, const nann_index* ix, int64_t* table_bytes, int64_t* resident_bytes);
 
+/* ---- exhaustive search under a model: test_all (NANN_impls/main.py:194-237) with the serving signature's input ------
+ * nann_search_all for whatever model the node names, the reference's own attention + DNN model included: every item of the
+ * index scored for every user, then TopKV2 sorted=true per user (NANN_impls/nann/util.py:9-11): descending, ties -> lower
+ * internal row number, -0 and +0 tie.
+ *   comm_seq_f16 f16[n_users, seq_len, E], as nann_search_model_opt takes it
+ *   out_item_ids i64[n_users, k] = item_ids[out_index]
+ *   out_scores   f32[n_users, k] or NULL;  out_index i32[n_users, k] (internal row numbers) or NULL
+ *   workspace    device, 256-byte aligned (else NANN_ERR_BAD_ARGUMENT), nann_search_all_model_workspace_bytes(...) bytes; smaller
+ *                -> NANN_ERR_CAPACITY.  Bounded: users are processed in chunks of at most 128 inside the call -- the scores of a
+ *                chunk take at most max(512 MiB, one user's 4 B x n_items) at a time, never n_users x n_items; the attention
+ *                model adds the chunk's per-user side (nann_attn_prepare: 80 KB per user)
+ *   options      NULL = defaults; only `preprojection` is read (-1: the process default)
+ * l2 / mlp model: nann_user_seq_mean into the workspace, then nann_search_all with the model's own scorer (same bits).
+ * attention model: nann_attn_prepare per chunk of users, then every row scored from the pre-projected table of the (model,
+ * index) pair (csrc/nann_scan_attn_inst.hip), found or built as in nann_search_model_opt and released with the call's event --
+ * both precisions scan from the table: scores within 1e-5 max(1, |s|) of the oracle, and for the split-f16 precision
+ * bit-identical to what the hash-set traversal computes for the same (user, row); without a table NANN_ERR_CAPACITY (no room
+ * in HBM) or NANN_ERR_UNSUPPORTED (preprojection resolves to 0).  Model and index disagree on d / dtype -> NANN_ERR_BAD_ARGUMENT.
+ * k < 0 or n_users < 0 -> NANN_ERR_BAD_ARGUMENT; k > n_items -> NANN_ERR_TOPK_K_GT_N, nothing launched (as nann_topk); k == 0 or
+ * n_users == 0 -> NANN_OK, nothing written; k > 1024 -> NANN_ERR_UNSUPPORTED.  A user's answer does not depend on the batch
+ * it is in.  Asynchronous on `stream`, no host read-back, re-entrant on shared handles. */
+int nann_search_all_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, int64_t* nbytes);
+int nann_search_all_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                          const nann_search_options* options, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

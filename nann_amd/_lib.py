@@ -38,7 +38,7 @@ SYMBOLS = [
     "nann_search_model", "nann_search_model_v",
     "nann_scorer_prepare", "nann_scorer_release", "nann_scorer_table_bytes", "nann_set_preprojection",
     "nann_model_prepare", "nann_model_release", "nann_model_table_bytes", "nann_search_eval_workspace_bytes", "nann_search_eval", "nann_search_eval_ex", "nann_search_eval_model",
-    "nann_search_all_workspace_bytes", "nann_search_all",
+    "nann_search_all_workspace_bytes", "nann_search_all", "nann_search_all_model_workspace_bytes", "nann_search_all_model",
     "nann_merge_topk", "nann_merge_topk_host",
     "nann_attn_scorer_create", "nann_attn_scorer_destroy", "nann_attn_prepare", "nann_attn_score",
     "nann_blaze_options_parse", "nann_model_load", "nann_model_destroy", "nann_model_kind", "nann_model_scorer", "nann_model_workspace_bytes", "nann_model_forward",
@@ -120,6 +120,13 @@ def lib():
         L.nann_search_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
         L.nann_search_all.restype = C.c_int
+        # (ix, model, n_users, k, *nbytes) / (ix, model, comm_seq_f16, n_users, k, out_item_ids, out_scores, out_index, workspace,
+        #  workspace_bytes, options, stream)
+        L.nann_search_all_model_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+        L.nann_search_all_model_workspace_bytes.restype = C.c_int
+        L.nann_search_all_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
+        L.nann_search_all_model.restype = C.c_int
         _LIB = L
     return _LIB
 

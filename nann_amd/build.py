@@ -12,7 +12,8 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 # one after the other.  Round 5: 13 units -> 9: the three small host-facing files share one object, the
 # resident-layer-2 MLP kernels ride with the d = 64 MLP instances.  Round 6: 12 units -- the evaluation traversal's LDS forms are
 # units of their own, and the bf16 and f32 L2 instances are two again (their shared unit had become the longest: it alone bounded
-# a build from scratch at ~6 min on 8 cores).  The exhaustive search (nann_scan.h) is a unit of its own, the thirteenth.
+# a build from scratch at ~6 min on 8 cores).  The exhaustive search (nann_scan.h) is a unit of its own, the thirteenth; its scan
+# under the attention model (k_scan_attn), which instantiates the attention block scorers, the fourteenth.
 UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_comm.hip", {}), ("nann_hnsw_build.hip", {})]),
          ("nann_l2_f16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "0", "NANN_L2_NAME": "f16"})]),
          ("nann_l2_bf16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "1", "NANN_L2_NAME": "bf16"})]),
@@ -25,8 +26,9 @@ UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_comm.hip", {}), ("nann_hn
          ("nann_eval.o", [("nann_eval_inst.hip", {})]),
          ("nann_eval_lds.o", [("nann_eval_lds_inst.hip", {})]),
          ("nann_eval_win.o", [("nann_eval_win_inst.hip", {})]),
-         ("nann_scan.o", [("nann_scan_inst.hip", {})])]
-DEPS = ["nann_hip.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_scan_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
+         ("nann_scan.o", [("nann_scan_inst.hip", {})]),
+         ("nann_scan_attn.o", [("nann_scan_attn_inst.hip", {})])]
+DEPS = ["nann_hip.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
         "nann_attn.h", "nann_attn_kernels.h", "nann_search.h", "nann_order.h", "nann_order_kernels.h", os.path.join("host", "nann_graphdef.h"), os.path.join("host", "nann_graphdef_text.h"), os.path.join("host", "nann_blaze_options.h"), os.path.join("host", "nann_npy.h"), os.path.join("host", "nann_projcache.h"),
         os.path.join("..", "..", "include", "nann_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-fast-math", "-ffp-contract=off"]
@@ -118,6 +120,28 @@ def _check_scan_scratch(log_path):
             raise RuntimeError(f"{name}: {m.group(1)} bytes of scratch per lane, the scan kernel must have none")
 
 
+def _check_scan_attn(log_path):
+    """The split-f16 scan under the attention model (k_scan_attn<false>, nann_scan_attn_inst.hip) keeps 150 KB of a CU's LDS for
+    one 512-thread workgroup: two wavefronts per SIMD, which the kernel reaches only within 256 VGPRs, and it has no slack for
+    spills -- a scratch frame there goes to memory once per 32-row block, between the MFMAs.  Neither changes a bit of its
+    answers.  Refuse to link a split-form k_scan_attn with a scratch frame or fewer than 2 waves per SIMD (the f32 form,
+    k_scan_attn<true>, is the parity form and is not held to this)."""
+    import re
+    name = None
+    for line in open(log_path, errors="replace"):
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+        if not (name and "k_scan_attnILb0E" in name):
+            continue
+        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and int(m.group(1)) != 0:
+            raise RuntimeError(f"{name}: {m.group(1)} bytes of scratch per lane, the split-form attention scan must have none")
+        m = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", line)
+        if m and int(m.group(1)) < 2:
+            raise RuntimeError(f"{name}: occupancy {m.group(1)} waves/SIMD, the split-form attention scan needs 2")
+
+
 def unit_command(obj, parts, odir, extra_flags=(), save_temps=True):
     """Write the wrapper of a translation unit into `odir` and return the hipcc command that compiles it to odir/obj."""
     unit = os.path.join(odir, "unit.hip")
@@ -154,6 +178,7 @@ def _build_into(OUT_DIR, LIB, extra_flags, verbose, only=None):
             raise subprocess.CalledProcessError(p.returncode, cmd)
         _check_occupancy(os.path.join(odir, "compile.log"))
         _check_scan_scratch(os.path.join(odir, "compile.log"))
+        _check_scan_attn(os.path.join(odir, "compile.log"))
     # hipcc (ROCm 7.2) can place VGPR spill code ahead of the exec restore of a join block; the
     # lanes that were masked off then reload garbage (seen: top-k positions all -1).  Refuse
     # to ship an object with that pattern.

@@ -359,7 +359,13 @@ __device__ __forceinline__ void wg_score_attn_proj(const AttnParams& P, const ui
 // (nann_mlp5.h's scheme), W2 (32 KB) in the place of the two slice buffers, the sequence / W1a / W3 fragments and the
 // vectors where they were.  No slice ring, no barrier inside a call: a wavefront takes every eighth 32-candidate block
 // and runs at its own pace (the proj form met at six barriers per 256 candidates).  Same arithmetic, same scores.
-template <int NT>
+//
+// LOAD: which of the resident blocks this call brings in.  The traversal loads everything at the head of every call (the
+// default).  The exhaustive scan (k_scan_attn, nann_scan_attn_inst.hip) scores many (block of rows, user) items per
+// launch: a prologue call with kAttnResShared and n = 0 places what every user shares -- W2, W1a, W3, the vectors: 78 KB
+// -- once per launch, and an item's call with kAttnResUser loads only that user's keys and sequence (72 KB).
+constexpr int kAttnResShared = 1, kAttnResUser = 2, kAttnResAll = kAttnResShared | kAttnResUser;
+template <int NT, int LOAD = kAttnResAll>
 __device__ __forceinline__ void wg_score_attn_res(const AttnParams& P, const uint4* __restrict__ kt,
                                                   const uint4* __restrict__ ua, const float* __restrict__ proj,
                                                   long long n_table_rows, const int32_t* indices, long long n,
@@ -373,12 +379,23 @@ __device__ __forceinline__ void wg_score_attn_res(const AttnParams& P, const uin
   float* pv = slice_f + kAttnSlice;                // the small vectors, in LDS
   uint4* res = reinterpret_cast<uint4*>(slice_f + kAttnSlice + kAttnVecFloats);  // [kAttnResidentU4]
   __syncthreads();
-  for (int k = tid; k < PV_COUNT / 4; k += NT)
-    reinterpret_cast<float4*>(pv)[k] = reinterpret_cast<const float4*>(P.pvec)[k];
-  for (int k = tid; k < kAttnResidentU4; k += NT)
-    res[k] = k < R_W1 ? ua[k] : k < R_W3 ? P.pw1a[k - R_W1] : P.pw3[k - R_W3];
-  for (int k = tid; k < 4096; k += NT) keys[k] = kt[k];   // q_ tiles 2 s, 2 s + 1 at keys + 1024 s
-  for (int k = tid; k < 2048; k += NT) w2[k] = P.pw2[k];
+  if constexpr (LOAD == kAttnResAll) {
+    for (int k = tid; k < PV_COUNT / 4; k += NT)
+      reinterpret_cast<float4*>(pv)[k] = reinterpret_cast<const float4*>(P.pvec)[k];
+    for (int k = tid; k < kAttnResidentU4; k += NT)
+      res[k] = k < R_W1 ? ua[k] : k < R_W3 ? P.pw1a[k - R_W1] : P.pw3[k - R_W3];
+    for (int k = tid; k < 4096; k += NT) keys[k] = kt[k];   // q_ tiles 2 s, 2 s + 1 at keys + 1024 s
+    for (int k = tid; k < 2048; k += NT) w2[k] = P.pw2[k];
+  } else if constexpr (LOAD == kAttnResShared) {
+    for (int k = tid; k < PV_COUNT / 4; k += NT)
+      reinterpret_cast<float4*>(pv)[k] = reinterpret_cast<const float4*>(P.pvec)[k];
+    for (int k = R_W1 + tid; k < kAttnResidentU4; k += NT) res[k] = k < R_W3 ? P.pw1a[k - R_W1] : P.pw3[k - R_W3];
+    for (int k = tid; k < 2048; k += NT) w2[k] = P.pw2[k];
+  } else {
+    static_assert(LOAD == kAttnResUser, "LOAD: shared, user or both");
+    for (int k = tid; k < R_W1; k += NT) res[k] = ua[k];
+    for (int k = tid; k < 4096; k += NT) keys[k] = kt[k];
+  }
   __syncthreads();
   const float att_scale = (1.0f / sqrtf(256.0f)) / (kAttnWS * kAttnHS);  // model_util.py:89-91, and the operand scales
 

@@ -2852,6 +2852,93 @@ int nann_model_table_bytes(const nann_model* m, const nann_index* ix, int64_t* t
   return table_bytes_impl(m->scorer, m->kind == NANN_MODEL_ATTENTION ? m->attn : nullptr, ix, table_bytes, resident_bytes);
 }
 
+// ---- exhaustive search with the serving signature's input: test_all under whatever model the node names -------
+// l2 / mlp: [q f32[n_users, d] | the workspace of nann_search_all].  attention: the ScanLayout scheme with the chunk's
+// kt / upad in the place of the queries (nann_scan.h, kScanAttn).
+static size_t search_all_model_q_bytes(const nann_model* m, int64_t n_users) {
+  return ((size_t)n_users * (size_t)m->d * 4 + 255) & ~(size_t)255;
+}
+static int search_all_model_check(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, const char* who) {
+  if (!ix || !m) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (n_users < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_users < 0");
+  if (m->d != ix->desc.d || m->emb_dtype != ix->desc.emb_dtype)
+    return fail(NANN_ERR_BAD_ARGUMENT, "model and index disagree on d / dtype");
+  if (m->kind != NANN_MODEL_ATTENTION) return search_all_check(ix, m->scorer, n_users, k, who);
+  if (k < 0) return fail(NANN_ERR_BAD_ARGUMENT, "Need k >= 0, got " + std::to_string(k));  // topk_op.cc:60-61
+  if (ix->desc.n_items < k)
+    return fail(NANN_ERR_TOPK_K_GT_N, "input must have at least k columns. Had " + std::to_string(ix->desc.n_items) +
+                                          ", needed " + std::to_string(k));
+  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
+  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  return NANN_OK;
+}
+
+int nann_search_all_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, int64_t* nbytes) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_model_workspace_bytes: null argument");
+  const int rc = search_all_model_check(ix, m, n_users, k, "nann_search_all_model_workspace_bytes");
+  if (rc) return rc;
+  if (n_users <= 0 || k == 0) { *nbytes = 0; return NANN_OK; }
+  if (m->kind == NANN_MODEL_ATTENTION)
+    *nbytes = (int64_t)scan_layout((long long)ix->desc.n_items, ix->desc.d, kScanAttn, (long long)n_users, k).total;
+  else
+    *nbytes = (int64_t)(search_all_model_q_bytes(m, n_users) +
+                        scan_layout((long long)ix->desc.n_items, ix->desc.d, m->scorer->desc.kind, (long long)n_users, k).total);
+  return NANN_OK;
+}
+
+int nann_search_all_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                          const nann_search_options* options, nann_stream_t stream) {
+  int rc = search_all_model_check(ix, m, n_users, k, "nann_search_all_model");
+  if (rc) return rc;
+  if (n_users <= 0 || k == 0) return NANN_OK;
+  if (!comm_seq_f16 || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_model: null argument");
+  int64_t need = 0;
+  rc = nann_search_all_model_workspace_bytes(ix, m, n_users, k, &need);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < need)
+    return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_all_model_workspace_bytes()");
+  if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_model: workspace must be 256-byte aligned");
+  if (m->kind != NANN_MODEL_ATTENTION) {  // the query is the mean of the sequence (nann_search_model), then nann_search_all
+    const size_t qb = search_all_model_q_bytes(m, n_users);
+    float* q = static_cast<float*>(workspace);
+    rc = nann_user_seq_mean(comm_seq_f16, n_users, m->seq_len, m->d, q, stream);
+    if (rc) return rc;
+    return nann_search_all(ix, m->scorer, q, n_users, k, out_item_ids, out_scores, out_index, static_cast<unsigned char*>(workspace) + qb,
+                           workspace_bytes - (int64_t)qb, options, stream);
+  }
+  rc = check_options(options);
+  if (rc) return rc;
+  const SearchOpt opt = resolve_options(options);
+  // both precisions scan the pre-projected table of the pair, obtained and released as search_impl does
+  if (!opt.preproject)
+    return fail(NANN_ERR_UNSUPPORTED, "nann_search_all_model: the attention scan reads the pre-projected table and preprojection is switched off");
+  hipStream_t st = as_stream(stream);
+  const nann_attn_scorer* at = m->attn;
+  std::shared_ptr<ProjTable> tab;
+  rc = attn_projection(at, ix, st, false, true, &tab);
+  if (rc) return rc;
+  if (!tab) return fail(NANN_ERR_CAPACITY, "nann_search_all_model: no room in HBM for the pre-projected table of this (model, index) pair");
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  const ScanLayout L = scan_layout((long long)ix->desc.n_items, ix->desc.d, kScanAttn, (long long)n_users, k);
+  ScanArgs a = {};
+  a.item_ids = ix->desc.item_ids;
+  a.n_items = (long long)ix->desc.n_items;
+  a.d = ix->desc.d;
+  a.dt = ix->desc.emb_dtype;
+  a.kind = kScanAttn;
+  a.exact = at->precision != NANN_MLP_SPLIT_F16;
+  a.proj = tab->table;
+  a.attn = at->P;
+  a.mlp_workgroups = di.cus;
+  rc = launch_scan(a, L, static_cast<const float*>(comm_seq_f16), (long long)n_users, k, static_cast<unsigned char*>(workspace),
+                   out_item_ids, out_scores, out_index, st);
+  projection_used(at->proj, tab, st);
+  return rc;
+}
+
 // ---- the evaluation graph's traversal (nann_eval.h) ----------------------------------------
 }  // extern "C"
 

@@ -3,8 +3,9 @@
 // fetched once for a TILE of queries.
 //
 // Three steps per chunk of queries (the chunk bounds the workspace: no buffer of n_queries x n_items elements exists):
-//   1. scores f32[chunk, n_items]: k_scan_l2 (vector arithmetic, below) or k_scan_mlp (the block functions of nann_mlp5.h on
-//      the pre-projected table, identity row list);
+//   1. scores f32[chunk, n_items]: k_scan_l2 (vector arithmetic, below), k_scan_mlp (the block functions of nann_mlp5.h on
+//      the pre-projected table, identity row list) or, for the attention model (nann_search_all_model), k_scan_attn (the
+//      resident block scorers of nann_attn_proj.h / nann_attn_kernels.h on the model's table; nann_scan_attn_inst.hip);
 //   2. k_scan_slab_topk: the row range is cut into balanced slabs of 8192..16384 rows (wg_topk keeps that many keys in
 //      registers; a corpus of at most 16384 rows is one slab); one workgroup per (query, slab) keeps the slab's top k as
 //      (score, row number), TopKV2 order;
@@ -38,11 +39,15 @@ struct ScanArgs {
   const int64_t* item_ids;
   long long n_items;
   int d, dt;
-  int kind, exact;          // nann_scorer_kind; MLP: the exact f32 form (also the certified precision) or split-f16
+  int kind, exact;          // nann_scorer_kind or kScanAttn; MLP / attention: the exact f32 form (also the MLP's certified precision) or split-f16
   MlpParams mlp;
-  int mlp_workgroups;       // resident workgroups of k_scan_mlp (one per CU)
+  int mlp_workgroups;       // resident workgroups of k_scan_mlp / k_scan_attn (one per CU)
+  AttnParams attn;          // kScanAttn: the model; `proj` is its table, and launch_scan's `q` the users' sequences
+                            // f16[n_queries, attn.L, kAttnE], from which each chunk's kt / upad are prepared into the workspace
 };
-// workspace layout of a call: [scores chunk x n_items | cand scores | cand rows | qT or u]; chunk = queries scored per pass
+constexpr int kScanAttn = 100;  // ScanArgs::kind of the attention model (no nann_scorer_kind: it has a handle type of its own)
+constexpr size_t kScanAttnUserBytes = (size_t)(256 * kAttnLP + kAttnLP * kAttnE) * 4;  // kt 64 KB + upad 16 KB (nann_attn_prepare)
+// workspace layout of a call: [scores chunk x n_items | cand scores | cand rows | qT, u or kt + upad]; chunk = queries scored per pass
 struct ScanLayout {
   int chunk, n_slabs;
   size_t off_scores, off_cand_scores, off_cand_rows, off_q, total;
@@ -50,6 +55,8 @@ struct ScanLayout {
 ScanLayout scan_layout(long long n_items, int d, int kind, long long n_queries, int k);
 int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, hipStream_t st);
+// scores f32[n_q, n_items] of the attention model for the users whose kt / upad lie one after the other (nann_scan_attn_inst.hip)
+int launch_scan_attn(const ScanArgs& a, const float* kt, const float* upad, int n_q, float* scores, hipStream_t st);
 
 }  // namespace nann
 

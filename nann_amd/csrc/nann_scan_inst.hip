@@ -21,7 +21,8 @@ ScanLayout scan_layout(long long n_items, int d, int kind, long long n_queries, 
   L.chunk = (int)chunk;
   L.n_slabs = scan_n_slabs(n_items);
   const size_t cand = (size_t)L.chunk * L.n_slabs * k * 4;
-  const size_t qbytes = kind == NANN_SCORER_L2 ? (size_t)((L.chunk + tq - 1) / tq) * tq * d * 4 : (size_t)L.chunk * 256 * 4;
+  const size_t qbytes = kind == NANN_SCORER_L2 ? (size_t)((L.chunk + tq - 1) / tq) * tq * d * 4
+                        : kind == kScanAttn ? (size_t)L.chunk * kScanAttnUserBytes : (size_t)L.chunk * 256 * 4;
   L.off_scores = 0;
   L.off_cand_scores = up256((size_t)L.chunk * (size_t)n_items * 4);
   L.off_cand_rows = L.off_cand_scores + up256(cand);
@@ -70,7 +71,14 @@ int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long lon
     const int n_q = (int)std::min<long long>(L.chunk, n_queries - c0);
     const float* qc = q + (size_t)c0 * a.d;
     int rc;
-    if (a.kind == NANN_SCORER_L2) {
+    if (a.kind == kScanAttn) {  // the chunk's users: kt [n_q][256][64] then upad [n_q][64][64], as the traversal takes them
+      const uint16_t* seq = reinterpret_cast<const uint16_t*>(q) + (size_t)c0 * a.attn.L * kAttnE;
+      float* kt = qbuf;
+      float* upad = qbuf + (size_t)n_q * 256 * kAttnLP;
+      rc = a.exact ? launch_attn_prepare(st, a.attn, seq, n_q, kt, upad) : launch_attn_prepare_split(st, a.attn, seq, n_q, kt, upad);
+      if (rc) return rc;
+      rc = launch_scan_attn(a, kt, upad, n_q, scores, st);
+    } else if (a.kind == NANN_SCORER_L2) {
       const int tq = kScanTileQueries;
       const long long total = (long long)((n_q + tq - 1) / tq) * tq * a.d;
       hipLaunchKernelGGL(k_scan_transpose_q, dim3((unsigned)std::min<long long>((total + 255) / 256, 1024)), dim3(256), 0, st, qc, n_q, a.d, tq, qbuf);

@@ -89,13 +89,17 @@ def test(index, scorer, user_seqs, ground_truths, topk_eval=(200,), num_scoring_
     return {"precision": prec, "recall": rec, "f1": f1m}
 
 
-def _search_all_or_none(index, scorer, q, k):
+def _search_all_or_none(index, scorer, q, k, model_scan=False):
     """The brute-force top k of a batch in one call (retrieval.search_all) -> internal row numbers i32[B, k] on the host,
-    or None where the per-user loop has to run: an attention model, or an MLP scorer without its pre-projected table
+    or None where the per-user loop has to run: an attention model (unless model_scan: then one
+    retrieval.search_all_model call), or an MLP scorer / attention model without its pre-projected table
     (NANN_ERR_CAPACITY: no room in HBM; NANN_ERR_UNSUPPORTED: pre-projection switched off)."""
-    if isinstance(scorer, ops.Model) and scorer.kind == "attention":
+    attention = isinstance(scorer, ops.Model) and scorer.kind == "attention"
+    if attention and not model_scan:
         return None
     try:
+        if attention:
+            return retrieval.search_all_model(index, scorer, q, k).index.cpu().numpy()
         return retrieval.search_all(index, scorer, q, k).index.cpu().numpy()
     except ops.NannError as e:
         if e.status in (102, 103):
@@ -103,18 +107,21 @@ def _search_all_or_none(index, scorer, q, k):
         raise
 
 
-def test_all(index, scorer, user_seqs, ground_truths, topk_eval=(200,), num_test_batch=None, batched=False):
+def test_all(index, scorer, user_seqs, ground_truths, topk_eval=(200,), num_test_batch=None, batched=False, model_scan=False):
     """main.py:194-237: score EVERY item for each user, take the top max(topk_eval) (fast_argtopk,
     util.py:9-11) -> the recall ceiling of the scorer itself.  batched=True: all users in one retrieval.search_all call
     instead of a blaze_score + top_k loop (an MLP scorer is then scored from its pre-projected table: with the split-f16
-    precision a near-tie may be ordered differently than by the loop's three-layer scorer)."""
+    precision a near-tie may be ordered differently than by the loop's three-layer scorer).  model_scan=True (with
+    batched=True): an attention ops.Model is scored by one retrieval.search_all_model call too, from its pre-projected table
+    (within the scorer's 1e-5 of the loop's rows form); without a table (status 102 / 103) the loop runs.  With the default an
+    attention model is scored user by user whatever `batched` says."""
     n = len(ground_truths) if num_test_batch is None else min(num_test_batch, len(ground_truths))
     prec, rec, f1m = defaultdict(AverageMeter), defaultdict(AverageMeter), defaultdict(AverageMeter)
     seqs = torch.as_tensor(np.asarray(user_seqs)).to(index.device)
     rows = None
     if batched and n > 0:
         q = seqs[:n] if isinstance(scorer, ops.Model) else ops.user_seq_mean(seqs[:n])
-        rows = _search_all_or_none(index, scorer, q, max(topk_eval))
+        rows = _search_all_or_none(index, scorer, q, max(topk_eval), model_scan=model_scan)
     item_ids = index.item_ids.cpu().numpy() if rows is not None else None
     for u in range(n):
         if rows is not None:

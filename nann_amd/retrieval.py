@@ -8,6 +8,8 @@ per request.  Two equivalent executions of that schedule live here:
                       (nann_search in include/nann_hip.h) -- the product path;
   * `search_all()`    its referee: every item scored for a batch of queries, top k
                       per query (nann_search_all; main.py:194-237 `test_all`);
+  * `search_all_model()` the same under any ops.Model, the reference's attention +
+                      DNN model included, from `comm_seq` (nann_search_all_model);
   * `search_per_op()` the same schedule spelled op by op with the drop-in ops
                       of nann_amd.ops, line for line against build_model(), so
                       that each op is exercised in the composition the
@@ -287,6 +289,34 @@ def search_all(index, scorer, q, k, options=None):
         _check(lib().nann_search_all(index.handle, handle, _ptr(q), b, k, _ptr(out_ids), _ptr(out_scores), _ptr(out_index),
                                      _ptr(ws), ws.numel(), C.byref(options) if options is not None else None, _stream()),
                "search_all")
+    return SearchAllResult(out_ids, out_scores, out_index, ws)
+
+
+def search_all_model(index, model, comm_seq, k, options=None):
+    """Exhaustive search under a model (nann_search_all_model; the reference's test_all job, main.py:194-237, which scores
+    its own attention + DNN model): every item of `index` scored for every user of comm_seq f16[B, seq_len, E], top k per
+    user -- descending, ties -> lower internal row number -> SearchAllResult.  `model`: an ops.Model of any kind (l2 / mlp:
+    the bits of search_all(index, model, comm_seq, k); attention: scored on the device from the model's pre-projected
+    table, split-f16 scores bit-identical to the traversal's); an ops.Scorer raises TypeError (search_all takes those).
+    options: search_options(preprojection=...).  Asynchronous on torch's current stream.  An attention or MLP model reads
+    its pre-projected table; without one the call raises ops.NannError with status 103 (no room in HBM) or 102
+    (pre-projection switched off)."""
+    if not isinstance(model, ops.Model):
+        raise TypeError("search_all_model: an ops.Model (an ops.Scorer goes through search_all)")
+    dev = index.device
+    seq = comm_seq.to(device=dev, dtype=torch.float16).contiguous()
+    b, k = seq.shape[0], int(k)
+    kk = max(k, 0)
+    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_all_model_workspace_bytes(index.handle, model.handle, b, k, C.byref(nbytes)), "search_all_model")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_all_model(index.handle, model.handle, _ptr(seq), b, k, _ptr(out_ids), _ptr(out_scores),
+                                           _ptr(out_index), _ptr(ws), ws.numel(),
+                                           C.byref(options) if options is not None else None, _stream()), "search_all_model")
     return SearchAllResult(out_ids, out_scores, out_index, ws)
 
 

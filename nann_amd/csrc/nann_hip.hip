@@ -794,7 +794,7 @@ struct nann_index {
 static void probe_index(nann_index* ix);  // (defined behind search_impl)
 static void choose_pivots(nann_index* ix, const std::vector<int32_t>& enter);
 static int launch_order(const nann_index* ix, const float* q, int n, int32_t* key, int32_t* perm, unsigned int* heads,
-                        hipStream_t st);
+                        unsigned int* header, hipStream_t st);
 
 extern "C" {
 
@@ -2330,13 +2330,13 @@ static int search_impl(const nann_index* ix, const nann_scorer* scorer, const na
   a.mlp = MlpParams{};
   a.attn = AttnParams{};
   a.kt = kt; a.upad = upad;
-  HIP_TRY(hipMemsetAsync(workspace, 0, 256, st));  // WsHeader: query queues, hand-back counter
   const int dt = ix->desc.emb_dtype;
   const bool hashed = p.vis == VIS_LDS_HASH || p.vis == VIS_LDS_HASH32;
   // L2 hash-set plans with more queries than slots: the main launch takes the batch in locality order (nann_order.h);
   // the rerun launch, the MLP / attention scorers and the bitmap plans keep input order.  The order lives behind the
   // slots, at the last 256-byte boundary that leaves order_ws_bytes(n) behind it (nann_search_workspace_bytes counts
-  // them); a workspace sized without them runs in input order.
+  // them); a workspace sized without them runs in input order.  WsHeader (query queues, hand-back counter) starts every
+  // call at zero: the order's last kernel clears it on its way, every other plan with a memset.
   const unsigned long long slots_end = 256 + p.slot_bytes * (unsigned long long)std::max(p.slots, p.fb_slots) + kPhaseTail;
   const unsigned long long order_off = ((unsigned long long)workspace_bytes - order_ws_bytes(n_queries)) & ~255ull;
   if (opt.order && hashed && !attn && kind == NANN_SCORER_L2 && ix->n_pivots >= 2 && n_queries > p.slots &&
@@ -2345,10 +2345,12 @@ static int search_impl(const nann_index* ix, const nann_scorer* scorer, const na
     unsigned int* heads = reinterpret_cast<unsigned int*>(ow);
     int32_t* perm = reinterpret_cast<int32_t*>(ow + kOrderSegs * kOrderHeadStride * 4);
     int32_t* key = perm + n_queries;
-    rc = launch_order(ix, q, (int)n_queries, key, perm, heads, st);
+    rc = launch_order(ix, q, (int)n_queries, key, perm, heads, static_cast<unsigned int*>(workspace), st);
     if (rc) return rc;
     a.perm = perm;
     a.xheads = heads;
+  } else {
+    HIP_TRY(hipMemsetAsync(workspace, 0, 256, st));
   }
   // main launch, then -- hash-set plans -- the rerun of the queries whose set could have overflowed on the bitmap
   // kernel (its workgroups leave at once when there is none)
@@ -2458,9 +2460,10 @@ __global__ void k_order_gather(const void* emb, int dt, int d, const int32_t* ro
   for (int k = threadIdx.x; k < d; k += blockDim.x) out[(size_t)blockIdx.x * d + k] = order_row_elem(emb, dt, (size_t)rows[blockIdx.x] * d + k);
 }
 
-// key and order kernels on `st`: key[n] (scratch), perm[n], the segment heads zeroed
+// key and order kernels on `st`: key[n] (scratch), perm[n], the segment heads and the workspace header zeroed
+static_assert(sizeof(WsHeader) <= kOrderHeaderWords * 4 && kOrderHeaderWords * 4 == 256, "k_order_perm clears the header");
 static int launch_order(const nann_index* ix, const float* q, int n, int32_t* key, int32_t* perm, unsigned int* heads,
-                        hipStream_t st) {
+                        unsigned int* header, hipStream_t st) {
   const int d = ix->desc.d, P = ix->n_pivots;
   const size_t lds = ((size_t)d * P + kOrderMaxPivots + (size_t)kOrderKeyQueries * d) * 4;
   if (lds > 48 * 1024)
@@ -2468,7 +2471,7 @@ static int launch_order(const nann_index* ix, const float* q, int n, int32_t* ke
   hipLaunchKernelGGL(k_order_key, dim3((unsigned)((n + kOrderKeyQueries - 1) / kOrderKeyQueries)), dim3(256), lds, st,
                      ix->pivots, d, P, q, n, key);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_order_perm, dim3(1), dim3(kOrderSortThreads), 0, st, key, n, P, perm, heads);
+  hipLaunchKernelGGL(k_order_perm, dim3(1), dim3(kOrderSortThreads), 0, st, key, n, P, perm, heads, header);
   HIP_TRY(hipGetLastError());
   return NANN_OK;
 }

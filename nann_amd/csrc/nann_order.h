@@ -22,7 +22,17 @@ constexpr int kOrderHeadStride = 32;   // head words 128 bytes apart (one cache 
 constexpr int kOrderMaxPivots = 128;
 constexpr int kOrderPivotLds = 64 * 1024;  // pivots * d * 4 bytes staged per key workgroup
 constexpr int kOrderKeyQueries = 16;   // queries per key workgroup (4 waves x 4)
+static_assert(kOrderKeyQueries % 4 == 0, "a key workgroup is 4 waves");
 constexpr int kOrderSortThreads = 1024;
+// k_order_perm's fast path: a batch of at most this many queries is sorted from registers with one scan over a
+// [key][run of 64 queries] count table (u16, 32 KB of LDS at 128 runs); larger batches go tile by tile
+constexpr int kOrderFastQueries = 8192;
+constexpr int kOrderFastRuns = kOrderFastQueries / 64;
+static_assert(kOrderFastQueries % kOrderSortThreads == 0 && kOrderFastQueries < 65536, "u16 prefixes, whole tiles");
+static_assert(kOrderMaxPivots * kOrderFastRuns == 16 * kOrderSortThreads, "the scan gives each thread 16 table entries");
+static_assert(kOrderMaxPivots == 128, "a key is seven bits (order_same_key)");
+// k_order_perm also zeroes the 256-byte header of the search workspace (WsHeader, nann_search.h) for the launch behind it
+constexpr int kOrderHeaderWords = 64;
 
 __host__ __device__ inline int order_seg_begin(int n, int s) { return (int)((long long)n * s / kOrderSegs); }
 

@@ -562,6 +562,69 @@ int nann_search_all_model(const nann_index* ix, const nann_model* m, const void*
                           int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
                           const nann_search_options* options, nann_stream_t stream);
 
+/* ---- filtered retrieval: a deny bitmap for every query and an exclusion list per query ------------------------------
+ * What a recommender removes before it answers: rows blocked for everybody (out of stock, withdrawn) and, per user, the
+ * rows that user has seen.  The reference has no such feature -- its serving graph returns the top_k of the traversal as it
+ * is -- so nothing here restates a line of it; the semantics below are this library's own.
+ * A filter is a plain struct, passed per call and BORROWED for the call: no handle, no process state.  NULL, or all three
+ * pointers NULL, denies nothing.  Malformed contents never fault: a listed row outside [0, n_items) denies nothing, every
+ * [splits[i], splits[i + 1]) is clamped to [0, n_excl] and an inverted range is empty.  struct_bytes: 0 or
+ * sizeof(nann_filter); n_excl < 0, or splits without rows while n_excl > 0 -> NANN_ERR_BAD_ARGUMENT. */
+typedef struct {
+  int32_t struct_bytes;
+  const uint32_t* deny_bits;        /* device, ceil(n_items / 32) words, or NULL: row r is denied for EVERY query when
+                                       bit (r & 31) of word (r >> 5) is set (idx_flag's convention); bits at or beyond
+                                       n_items in the last word are ignored */
+  const int64_t* excl_row_splits;   /* device i64[n_queries + 1], or NULL: query i excludes excl_rows[splits[i] .. splits[i+1]) */
+  const int32_t* excl_rows;         /* device i32[n_excl]: INTERNAL row numbers; any order, duplicates allowed */
+  int64_t n_excl;
+} nann_filter;
+
+/* Exhaustive search over the ALLOWED rows: nann_search_all / nann_search_all_model -- same arguments, checks and error codes --
+ * plus the filter and n_out (device i32[n_queries], or NULL).  Query i returns the top k of its allowed rows in TopKV2 order
+ * (descending, ties -> lower row), n_out[i] valid entries at the head of its row and zeros behind.  When every allowed row
+ * scores above -inf, n_out[i] = min(k, allowed rows of query i); an allowed row whose own score is -inf may be displaced by a
+ * denied one (denied rows are taken out by writing -inf over their scores between scoring and selection); NaN scores stay
+ * outside the contract, as for nann_topk.  The workspace adds 16 B x k per query of a chunk to the unfiltered one.
+ * Asynchronous, no host read-back, and a query's answer does not depend on its batch. */
+int nann_search_all_filtered_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k,
+                                             int64_t* nbytes);
+int nann_search_all_filtered(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                             int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
+                             int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                             int32_t* n_out, nann_stream_t stream);
+int nann_search_all_model_filtered_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k,
+                                                   int64_t* nbytes);
+int nann_search_all_model_filtered(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                   int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
+                                   int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                                   int32_t* n_out, nann_stream_t stream);
+
+/* The traversal, filtered at its final selection: nann_search_opt / nann_search_model_opt -- same arguments, checks and error
+ * codes -- plus the filter, k and n_out (device i32[n_queries], or NULL).  level_topn_max[5] is the FETCH WIDTH F: the inner
+ * search runs unchanged at F into a staging area of the workspace (16 B x F per query, counted by the _workspace_bytes
+ * functions), and query i's answer is the first k allowed entries of what the unfiltered call returns for it at its own
+ * level_topn[i][5], order kept: outputs are [n_queries, k], n_out[i] entries at the head of row i and zeros behind.  Denied
+ * rows still guide the walk -- a graph search needs them to stay connected -- but are not returned.  F as wide as the pool,
+ * min(level_topn[1] + ... + level_topn[4], 1024), ranks the whole pool; F obeys the limits of level_topn[5] (at most 1024; a
+ * query whose level_topn[5] exceeds its pool fails as it does unfiltered).  k outside [0, F] -> NANN_ERR_BAD_ARGUMENT.  A
+ * query with status[i] != 0 gets n_out[i] = 0 and zeros.  counters, status, plan, nann_search_reruns and nann_search_refined
+ * report what the inner search reported. */
+int nann_search_filtered_workspace_bytes(const nann_index* ix, const int32_t level_topn[6] /*[host]*/, int64_t n_queries,
+                                         int64_t* nbytes);
+int nann_search_filtered(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                         const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                         int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status, int32_t* counters,
+                         int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
+                         const nann_filter* filter, int32_t k, int32_t* n_out, nann_stream_t stream);
+int nann_search_model_filtered_workspace_bytes(const nann_index* ix, const nann_model* m, const int32_t level_topn[6],
+                                               int64_t n_queries, int64_t* nbytes);
+int nann_search_model_filtered(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_queries,
+                               const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                               int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                               int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan,
+                               const nann_filter* filter, int32_t k, int32_t* n_out, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

@@ -39,6 +39,9 @@ SYMBOLS = [
     "nann_scorer_prepare", "nann_scorer_release", "nann_scorer_table_bytes", "nann_set_preprojection",
     "nann_model_prepare", "nann_model_release", "nann_model_table_bytes", "nann_search_eval_workspace_bytes", "nann_search_eval", "nann_search_eval_ex", "nann_search_eval_model",
     "nann_search_all_workspace_bytes", "nann_search_all", "nann_search_all_model_workspace_bytes", "nann_search_all_model",
+    "nann_search_all_filtered_workspace_bytes", "nann_search_all_filtered", "nann_search_all_model_filtered_workspace_bytes",
+    "nann_search_all_model_filtered", "nann_search_filtered_workspace_bytes", "nann_search_filtered",
+    "nann_search_model_filtered_workspace_bytes", "nann_search_model_filtered",
     "nann_merge_topk", "nann_merge_topk_host",
     "nann_attn_scorer_create", "nann_attn_scorer_destroy", "nann_attn_prepare", "nann_attn_score",
     "nann_blaze_options_parse", "nann_model_load", "nann_model_destroy", "nann_model_kind", "nann_model_scorer", "nann_model_workspace_bytes", "nann_model_forward",
@@ -58,6 +61,12 @@ class SearchPlan(C.Structure):
     _fields_ = [("visited_set", C.c_int32), ("fallback_visited_set", C.c_int32), ("threads", C.c_int32),
                 ("workgroups", C.c_int32), ("phased", C.c_int32), ("table", C.c_int32),
                 ("est_visited", C.c_float), ("worst_visited", C.c_float)]
+
+
+class Filter(C.Structure):
+    """nann_filter: a deny bitmap for every query and an exclusion list per query (device pointers, borrowed per call)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("deny_bits", C.c_void_p), ("excl_row_splits", C.c_void_p),
+                ("excl_rows", C.c_void_p), ("n_excl", C.c_int64)]
 
 
 class ScorerDesc(C.Structure):
@@ -127,6 +136,28 @@ def lib():
         L.nann_search_all_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
         L.nann_search_all_model.restype = C.c_int
+        # the filtered twins: the same lists, then (filter, n_out, stream) in the place of (stream)
+        for name, twin in (("nann_search_all_filtered", L.nann_search_all), ("nann_search_all_model_filtered", L.nann_search_all_model)):
+            fn = getattr(L, name)
+            fn.argtypes = twin.argtypes[:-1] + [C.POINTER(Filter), C.c_void_p, C.c_void_p]
+            fn.restype = C.c_int
+            wb = getattr(L, name + "_workspace_bytes")
+            wb.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+            wb.restype = C.c_int
+        # (ix, scorer | model, q, n_queries, level_topn_max, level_topn, workspace, workspace_bytes, out_item_ids, out_scores,
+        #  out_index, status, counters, [phase_ticks,] options, plan, filter, k, n_out, stream)
+        head = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int64,
+                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        tail = [C.POINTER(SearchOptions), C.POINTER(SearchPlan), C.POINTER(Filter), C.c_int32, C.c_void_p, C.c_void_p]
+        L.nann_search_filtered.argtypes = head + [C.c_void_p] + tail
+        L.nann_search_filtered.restype = C.c_int
+        L.nann_search_model_filtered.argtypes = head + tail
+        L.nann_search_model_filtered.restype = C.c_int
+        L.nann_search_filtered_workspace_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]
+        L.nann_search_filtered_workspace_bytes.restype = C.c_int
+        L.nann_search_model_filtered_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int64,
+                                                                 C.POINTER(C.c_int64)]
+        L.nann_search_model_filtered_workspace_bytes.restype = C.c_int
         _LIB = L
     return _LIB
 

@@ -1,0 +1,34 @@
+// nann_filter_inst.hip -- the kernels of filtered retrieval (nann_filter.h) and their launchers.
+#define NANN_FILTER_IMPL
+#include "nann_filter.h"
+
+namespace nann {
+
+int launch_filter_scatter(const FilterArgs& f, float* scores, long long q0, int n_q, hipStream_t st) {
+  if (n_q <= 0 || f.n_items <= 0) return NANN_OK;
+  if (f.deny_bits) {
+    const long long words = (f.n_items + 31) / 32;
+    const dim3 grid((unsigned)((words + kFilterNT - 1) / kFilterNT), (unsigned)((n_q + kFilterScatterQueries - 1) / kFilterScatterQueries));
+    hipLaunchKernelGGL(k_filter_scatter_bits, grid, dim3(kFilterNT), 0, st, f.deny_bits, f.n_items, n_q, scores);
+    NANN_HIP_TRY(hipGetLastError());
+  }
+  if (filter_has_lists(f)) {
+    hipLaunchKernelGGL(k_filter_scatter_lists, dim3((unsigned)n_q), dim3(kFilterNT), 0, st, f, q0, scores);
+    NANN_HIP_TRY(hipGetLastError());
+  }
+  return NANN_OK;
+}
+
+int launch_filter_compact(const FilterArgs& f, const int32_t* in_rows, const float* in_scores, int in_stride, int n_in,
+                          const int32_t* tq, const int32_t* status, long long q0, long long n_q, int k, const int64_t* item_ids,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* n_out, hipStream_t st) {
+  if (n_q <= 0) return NANN_OK;
+  if (n_q > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, "too many queries in one call");
+  if (k < 0 || in_stride < 0 || in_stride > kMaxK) return fail(NANN_ERR_BAD_ARGUMENT, "filter: a ranked list holds at most 1024 entries");
+  hipLaunchKernelGGL(k_filter_compact, dim3((unsigned)n_q), dim3(kFilterNT), 0, st, f, in_rows, in_scores, in_stride, n_in, tq, status,
+                     q0, k, item_ids, out_item_ids, out_scores, out_index, n_out);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+}  // namespace nann

@@ -2676,9 +2676,32 @@ int nann_search_all_workspace_bytes(const nann_index* ix, const nann_scorer* sco
   return NANN_OK;
 }
 
-int nann_search_all(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
-                    int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
-                    const nann_search_options* options, nann_stream_t stream) {
+}  // extern "C"
+
+// ---- filtered retrieval (nann_filter.h) -------------------------------------------------------------------------------
+// the caller's nann_filter as the kernels take it; NULL denies nothing
+static int resolve_filter(const nann_filter* f, const nann_index* ix, FilterArgs* out) {
+  *out = FilterArgs{};
+  out->n_items = (long long)ix->desc.n_items;
+  if (!f) return NANN_OK;
+  if (f->struct_bytes != 0 && f->struct_bytes != (int32_t)sizeof(nann_filter)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: struct_bytes");
+  if (f->n_excl < 0) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: n_excl < 0");
+  if (f->excl_row_splits && f->n_excl > 0 && !f->excl_rows) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: excl_row_splits without excl_rows");
+  out->deny_bits = f->deny_bits;
+  if (f->excl_row_splits && f->n_excl > 0) {
+    out->splits = f->excl_row_splits;
+    out->rows = f->excl_rows;
+    out->n_excl = (long long)f->n_excl;
+  }
+  return NANN_OK;
+}
+
+// nann_search_all and, filtered, nann_search_all_filtered: the same checks and launches; a filtered call keeps the staging
+// area of its final selection behind the unfiltered workspace
+static int search_all_impl(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                           int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                           const nann_search_options* options, bool filtered, const nann_filter* filter, int32_t* n_out,
+                           nann_stream_t stream) {
   int rc = search_all_check(ix, scorer, n_queries, k, "nann_search_all");
   if (rc) return rc;
   if (n_queries <= 0 || k == 0) return NANN_OK;
@@ -2687,11 +2710,22 @@ int nann_search_all(const nann_index* ix, const nann_scorer* scorer, const float
   if (rc) return rc;
   const SearchOpt opt = resolve_options(options);
   const ScanLayout L = scan_layout((long long)ix->desc.n_items, ix->desc.d, scorer->desc.kind, (long long)n_queries, k);
-  if (!workspace || workspace_bytes < (int64_t)L.total)
+  ScanFilter sf = {};
+  if (filtered) {
+    rc = resolve_filter(filter, ix, &sf.f);
+    if (rc) return rc;
+  }
+  const int64_t need = (int64_t)(L.total + (filtered ? scan_filter_stage_bytes(L.chunk, k) : 0));
+  if (!workspace || workspace_bytes < need)
     return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_all_workspace_bytes()");
   if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all: workspace must be 256-byte aligned");
   hipStream_t st = as_stream(stream);
   ScanArgs a = {};
+  if (filtered) {
+    sf.stage = static_cast<unsigned char*>(workspace) + L.total;
+    sf.n_out = n_out;
+    a.filter = &sf;
+  }
   a.emb = ix->desc.item_embs;
   a.item_ids = ix->desc.item_ids;
   a.n_items = (long long)ix->desc.n_items;
@@ -2717,6 +2751,31 @@ int nann_search_all(const nann_index* ix, const nann_scorer* scorer, const float
   rc = launch_scan(a, L, q, (long long)n_queries, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index, st);
   projection_used(scorer->proj, tab, st);
   return rc;
+}
+
+extern "C" {
+
+int nann_search_all(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                    int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                    const nann_search_options* options, nann_stream_t stream) {
+  return search_all_impl(ix, scorer, q, n_queries, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
+                         false, nullptr, nullptr, stream);
+}
+
+int nann_search_all_filtered_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k,
+                                             int64_t* nbytes) {
+  const int rc = nann_search_all_workspace_bytes(ix, scorer, n_queries, k, nbytes);
+  if (rc || n_queries <= 0 || k == 0) return rc;
+  *nbytes += (int64_t)scan_filter_stage_bytes(scan_layout((long long)ix->desc.n_items, ix->desc.d, scorer->desc.kind, (long long)n_queries, k).chunk, k);
+  return NANN_OK;
+}
+
+int nann_search_all_filtered(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                             int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
+                             int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                             int32_t* n_out, nann_stream_t stream) {
+  return search_all_impl(ix, scorer, q, n_queries, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
+                         true, filter, n_out, stream);
 }
 
 // ---- lifecycle of the pre-projected tables (ProjCache) -------------------------------------------------------
@@ -2876,28 +2935,31 @@ static int search_all_model_check(const nann_index* ix, const nann_model* m, int
   return NANN_OK;
 }
 
-int nann_search_all_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, int64_t* nbytes) {
+}  // extern "C"
+
+static int search_all_model_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, bool filtered, int64_t* nbytes) {
   if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_model_workspace_bytes: null argument");
   const int rc = search_all_model_check(ix, m, n_users, k, "nann_search_all_model_workspace_bytes");
   if (rc) return rc;
   if (n_users <= 0 || k == 0) { *nbytes = 0; return NANN_OK; }
-  if (m->kind == NANN_MODEL_ATTENTION)
-    *nbytes = (int64_t)scan_layout((long long)ix->desc.n_items, ix->desc.d, kScanAttn, (long long)n_users, k).total;
-  else
-    *nbytes = (int64_t)(search_all_model_q_bytes(m, n_users) +
-                        scan_layout((long long)ix->desc.n_items, ix->desc.d, m->scorer->desc.kind, (long long)n_users, k).total);
+  const int kind = m->kind == NANN_MODEL_ATTENTION ? kScanAttn : m->scorer->desc.kind;
+  const ScanLayout L = scan_layout((long long)ix->desc.n_items, ix->desc.d, kind, (long long)n_users, k);
+  *nbytes = (int64_t)((m->kind == NANN_MODEL_ATTENTION ? 0 : search_all_model_q_bytes(m, n_users)) + L.total +
+                      (filtered ? scan_filter_stage_bytes(L.chunk, k) : 0));
   return NANN_OK;
 }
 
-int nann_search_all_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
-                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
-                          const nann_search_options* options, nann_stream_t stream) {
+// nann_search_all_model and, filtered, nann_search_all_model_filtered (see search_all_impl)
+static int search_all_model_impl(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
+                                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                                 const nann_search_options* options, bool filtered, const nann_filter* filter, int32_t* n_out,
+                                 nann_stream_t stream) {
   int rc = search_all_model_check(ix, m, n_users, k, "nann_search_all_model");
   if (rc) return rc;
   if (n_users <= 0 || k == 0) return NANN_OK;
   if (!comm_seq_f16 || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_model: null argument");
   int64_t need = 0;
-  rc = nann_search_all_model_workspace_bytes(ix, m, n_users, k, &need);
+  rc = search_all_model_bytes(ix, m, n_users, k, filtered, &need);
   if (rc) return rc;
   if (!workspace || workspace_bytes < need)
     return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_all_model_workspace_bytes()");
@@ -2907,8 +2969,8 @@ int nann_search_all_model(const nann_index* ix, const nann_model* m, const void*
     float* q = static_cast<float*>(workspace);
     rc = nann_user_seq_mean(comm_seq_f16, n_users, m->seq_len, m->d, q, stream);
     if (rc) return rc;
-    return nann_search_all(ix, m->scorer, q, n_users, k, out_item_ids, out_scores, out_index, static_cast<unsigned char*>(workspace) + qb,
-                           workspace_bytes - (int64_t)qb, options, stream);
+    return search_all_impl(ix, m->scorer, q, n_users, k, out_item_ids, out_scores, out_index, static_cast<unsigned char*>(workspace) + qb,
+                           workspace_bytes - (int64_t)qb, options, filtered, filter, n_out, stream);
   }
   rc = check_options(options);
   if (rc) return rc;
@@ -2927,6 +2989,14 @@ int nann_search_all_model(const nann_index* ix, const nann_model* m, const void*
   if (rc) return rc;
   const ScanLayout L = scan_layout((long long)ix->desc.n_items, ix->desc.d, kScanAttn, (long long)n_users, k);
   ScanArgs a = {};
+  ScanFilter sf = {};
+  if (filtered) {
+    rc = resolve_filter(filter, ix, &sf.f);
+    if (rc) return rc;
+    sf.stage = static_cast<unsigned char*>(workspace) + L.total;
+    sf.n_out = n_out;
+    a.filter = &sf;
+  }
   a.item_ids = ix->desc.item_ids;
   a.n_items = (long long)ix->desc.n_items;
   a.d = ix->desc.d;
@@ -2940,6 +3010,124 @@ int nann_search_all_model(const nann_index* ix, const nann_model* m, const void*
                    out_item_ids, out_scores, out_index, st);
   projection_used(at->proj, tab, st);
   return rc;
+}
+
+extern "C" {
+
+int nann_search_all_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, int64_t* nbytes) {
+  return search_all_model_bytes(ix, m, n_users, k, false, nbytes);
+}
+
+int nann_search_all_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                          const nann_search_options* options, nann_stream_t stream) {
+  return search_all_model_impl(ix, m, comm_seq_f16, n_users, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes,
+                               options, false, nullptr, nullptr, stream);
+}
+
+int nann_search_all_model_filtered_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k,
+                                                   int64_t* nbytes) {
+  return search_all_model_bytes(ix, m, n_users, k, true, nbytes);
+}
+
+int nann_search_all_model_filtered(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                   int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
+                                   int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                                   int32_t* n_out, nann_stream_t stream) {
+  return search_all_model_impl(ix, m, comm_seq_f16, n_users, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes,
+                               options, true, filter, n_out, stream);
+}
+
+// ---- the traversal, filtered at its final selection: the inner search at the fetch width F = level_topn_max[5] into a
+// staging area behind its own workspace (item ids i64[n, F], scores f32[n, F], rows i32[n, F]), then k_filter_compact --
+static size_t filter_stage_bytes(int64_t n_queries, int f) {
+  return ((size_t)std::max<int64_t>(n_queries, 0) * (size_t)std::max(f, 0) * 16 + 255) & ~(size_t)255;
+}
+static int64_t up256_i64(int64_t v) { return (v + 255) & ~255ll; }
+
+// the final selection of a filtered traversal on `stream`, behind the inner search
+static int filtered_select(const nann_index* ix, const nann_filter* filter, unsigned char* stage, int64_t n_queries, int f,
+                           const int32_t* level_topn, const int32_t* status, int32_t k, int64_t* out_item_ids, float* out_scores,
+                           int32_t* out_index, int32_t* n_out, hipStream_t st) {
+  FilterArgs fa;
+  const int rc = resolve_filter(filter, ix, &fa);
+  if (rc) return rc;
+  const float* s_scores = reinterpret_cast<const float*>(stage + (size_t)n_queries * f * 8);
+  const int32_t* s_rows = reinterpret_cast<const int32_t*>(stage + (size_t)n_queries * f * 12);
+  return launch_filter_compact(fa, s_rows, s_scores, f, f, level_topn, status, 0, n_queries, k, ix->desc.item_ids, out_item_ids,
+                               out_scores, out_index, n_out, st);
+}
+
+int nann_search_filtered_workspace_bytes(const nann_index* ix, const int32_t level_topn[6], int64_t n_queries, int64_t* nbytes) {
+  const int rc = nann_search_workspace_bytes(ix, level_topn, n_queries, nbytes);
+  if (rc) return rc;
+  *nbytes = up256_i64(*nbytes) + (int64_t)filter_stage_bytes(n_queries, level_topn[5]);
+  return NANN_OK;
+}
+
+int nann_search_filtered(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                         const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                         int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status, int32_t* counters,
+                         int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
+                         const nann_filter* filter, int32_t k, int32_t* n_out, nann_stream_t stream) {
+  if (!ix || !scorer || !level_topn_max || !out_item_ids || !status)
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_filtered: null argument");
+  const int f = level_topn_max[5];
+  if (k < 0 || k > f) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_filtered: k must lie in [0, level_topn_max[5]]");
+  if (n_queries <= 0) return NANN_OK;
+  FilterArgs probe;
+  int rc = resolve_filter(filter, ix, &probe);  // (a malformed filter fails the call before anything is launched)
+  if (rc) return rc;
+  int64_t inner = 0;
+  rc = nann_search_workspace_bytes(ix, level_topn_max, n_queries, &inner);
+  if (rc) return rc;
+  const int64_t stage_off = up256_i64(inner);
+  if (!workspace || workspace_bytes < stage_off + (int64_t)filter_stage_bytes(n_queries, f))
+    return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_filtered_workspace_bytes()");
+  unsigned char* stage = static_cast<unsigned char*>(workspace) + stage_off;
+  rc = nann_search_opt(ix, scorer, q, n_queries, level_topn_max, level_topn, workspace, inner, reinterpret_cast<int64_t*>(stage),
+                       reinterpret_cast<float*>(stage + (size_t)n_queries * f * 8),
+                       reinterpret_cast<int32_t*>(stage + (size_t)n_queries * f * 12), status, counters, phase_ticks, options, plan,
+                       stream);
+  if (rc) return rc;
+  return filtered_select(ix, filter, stage, n_queries, f, level_topn, status, k, out_item_ids, out_scores, out_index, n_out,
+                         as_stream(stream));
+}
+
+int nann_search_model_filtered_workspace_bytes(const nann_index* ix, const nann_model* m, const int32_t level_topn[6],
+                                               int64_t n_queries, int64_t* nbytes) {
+  const int rc = nann_search_model_workspace_bytes(ix, m, level_topn, n_queries, nbytes);
+  if (rc) return rc;
+  *nbytes = up256_i64(*nbytes) + (int64_t)filter_stage_bytes(n_queries, level_topn[5]);
+  return NANN_OK;
+}
+
+int nann_search_model_filtered(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_queries,
+                               const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                               int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                               int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan,
+                               const nann_filter* filter, int32_t k, int32_t* n_out, nann_stream_t stream) {
+  if (!ix || !m || !comm_seq_f16 || !level_topn_max || !out_item_ids || !status || !workspace)
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_model_filtered: null argument");
+  const int f = level_topn_max[5];
+  if (k < 0 || k > f) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_model_filtered: k must lie in [0, level_topn_max[5]]");
+  if (n_queries <= 0) return NANN_OK;
+  FilterArgs probe;
+  int rc = resolve_filter(filter, ix, &probe);
+  if (rc) return rc;
+  int64_t inner = 0;
+  rc = nann_search_model_workspace_bytes(ix, m, level_topn_max, n_queries, &inner);
+  if (rc) return rc;
+  const int64_t stage_off = up256_i64(inner);
+  if (workspace_bytes < stage_off + (int64_t)filter_stage_bytes(n_queries, f))
+    return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_model_filtered_workspace_bytes()");
+  unsigned char* stage = static_cast<unsigned char*>(workspace) + stage_off;
+  rc = nann_search_model_opt(ix, m, comm_seq_f16, n_queries, level_topn_max, level_topn, workspace, inner,
+                             reinterpret_cast<int64_t*>(stage), reinterpret_cast<float*>(stage + (size_t)n_queries * f * 8),
+                             reinterpret_cast<int32_t*>(stage + (size_t)n_queries * f * 12), status, counters, options, plan, stream);
+  if (rc) return rc;
+  return filtered_select(ix, filter, stage, n_queries, f, level_topn, status, k, out_item_ids, out_scores, out_index, n_out,
+                         as_stream(stream));
 }
 
 // ---- the evaluation graph's traversal (nann_eval.h) ----------------------------------------

@@ -28,9 +28,19 @@
 #pragma once
 #include <cstddef>
 
+#include "nann_filter.h"
 #include "nann_search.h"
 
 namespace nann {
+
+// a filtered call (nann_search_all_filtered): the filter, where the merge's k-wide lists of a chunk are staged -- item ids
+// i64[chunk, k], scores f32[chunk, k], rows i32[chunk, k] -- and the counts of the final rows
+struct ScanFilter {
+  FilterArgs f;
+  unsigned char* stage;
+  int32_t* n_out;  // i32[n_queries] or null
+};
+inline size_t scan_filter_stage_bytes(int chunk, int k) { return ((size_t)chunk * k * 16 + 255) & ~(size_t)255; }
 
 // ---- launchers (nann_scan_inst.hip) -----------------------------------------------------------------------------------
 struct ScanArgs {
@@ -44,6 +54,8 @@ struct ScanArgs {
   int mlp_workgroups;       // resident workgroups of k_scan_mlp / k_scan_attn (one per CU)
   AttnParams attn;          // kScanAttn: the model; `proj` is its table, and launch_scan's `q` the users' sequences
                             // f16[n_queries, attn.L, kAttnE], from which each chunk's kt / upad are prepared into the workspace
+  const ScanFilter* filter; // null: the unfiltered call.  Else -inf over the denied scores of every chunk before the slab top-k
+                            // (nann_filter.h), and k_filter_compact behind the merge writes the outputs
 };
 constexpr int kScanAttn = 100;  // ScanArgs::kind of the attention model (no nann_scorer_kind: it has a handle type of its own)
 constexpr size_t kScanAttnUserBytes = (size_t)(256 * kAttnLP + kAttnLP * kAttnE) * 4;  // kt 64 KB + upad 16 KB (nann_attn_prepare)

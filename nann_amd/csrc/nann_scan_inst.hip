@@ -96,9 +96,28 @@ int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long lon
       rc = a.exact ? launch_scan_mlp_as<true>(a, qbuf, n_q, scores, st) : launch_scan_mlp_as<false>(a, qbuf, n_q, scores, st);
     }
     if (rc) return rc;
+    if (a.filter) {  // the denied rows of this chunk leave the selection: exclusion lists go by the call's query number c0 + i
+      rc = launch_filter_scatter(a.filter->f, scores, c0, n_q, st);
+      if (rc) return rc;
+    }
     hipLaunchKernelGGL(k_scan_slab_topk, dim3((unsigned)((long long)n_q * L.n_slabs)), dim3(kNT), 0, st, scores, a.n_items, L.n_slabs, k,
                        cand_scores, cand_rows);
     NANN_HIP_TRY(hipGetLastError());
+    if (a.filter) {
+      // the merge's lists go to the staging area; the final rows are their allowed entries (a query with fewer than k allowed
+      // rows has denied ones, at -inf, in its list)
+      int64_t* s_ids = reinterpret_cast<int64_t*>(a.filter->stage);
+      float* s_scores = reinterpret_cast<float*>(s_ids + (size_t)L.chunk * k);
+      int32_t* s_rows = reinterpret_cast<int32_t*>(s_scores + (size_t)L.chunk * k);
+      hipLaunchKernelGGL(k_scan_merge, dim3((unsigned)n_q), dim3(kNT), 0, st, cand_scores, cand_rows, L.n_slabs * k, k, a.item_ids,
+                         s_ids, s_scores, s_rows);
+      NANN_HIP_TRY(hipGetLastError());
+      rc = launch_filter_compact(a.filter->f, s_rows, s_scores, k, k, nullptr, nullptr, c0, n_q, k, a.item_ids,
+                                 out_item_ids + (size_t)c0 * k, out_scores ? out_scores + (size_t)c0 * k : nullptr,
+                                 out_index ? out_index + (size_t)c0 * k : nullptr, a.filter->n_out ? a.filter->n_out + c0 : nullptr, st);
+      if (rc) return rc;
+      continue;
+    }
     hipLaunchKernelGGL(k_scan_merge, dim3((unsigned)n_q), dim3(kNT), 0, st, cand_scores, cand_rows, L.n_slabs * k, k, a.item_ids,
                        out_item_ids + (size_t)c0 * k, out_scores ? out_scores + (size_t)c0 * k : nullptr,
                        out_index ? out_index + (size_t)c0 * k : nullptr);

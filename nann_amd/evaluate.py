@@ -136,10 +136,28 @@ def test_all(index, scorer, user_seqs, ground_truths, topk_eval=(200,), num_test
     return {"precision": prec, "recall": rec, "f1": f1m}
 
 
-def recall_vs_bruteforce(index, scorer, q, level_topn, n_queries=None, batched=False):
+def recall_vs_bruteforce(index, scorer, q, level_topn, n_queries=None, batched=False, filter=None, k=None):
     """How much of the brute-force top-k (same scorer) the serving-graph traversal (nann_search) returns:
     the recall@k figure bench.py reports.  batched=True: the brute force of all sampled queries is one
-    retrieval.search_all call (see test_all)."""
+    retrieval.search_all call (see test_all).
+    filter (retrieval.make_filter): the filtered traversal (level_topn[5] is its fetch width, k -- default level_topn[5] --
+    its answer's width) against the filtered exhaustive search, one retrieval.search_all call; a query counts
+    min(k, n_out of its exhaustive answer) rows, the allowed rows there are to find."""
+    if filter is not None:
+        k = int(level_topn[5]) if k is None else int(k)
+        n = q.shape[0] if n_queries is None else min(n_queries, q.shape[0])
+        r = retrieval.search(index, scorer, q, level_topn, want_counters=False, filter=filter, k=k)
+        t = retrieval.search_all(index, scorer, q, k, filter=filter)
+        st, got, got_n = r.status.cpu().numpy(), r.index.cpu().numpy(), r.n_out.cpu().numpy()
+        truth, truth_n = t.index.cpu().numpy(), t.n_out.cpu().numpy()
+        hits = total = 0
+        for b in range(n):
+            if st[b]:
+                continue
+            hits += len(set(truth[b, :truth_n[b]].tolist()) & set(got[b, :got_n[b]].tolist()))
+            total += min(k, int(truth_n[b]))
+        return hits / max(total, 1)
+    assert k is None, "k: the answer's width of a filtered search"
     r = retrieval.search(index, scorer, q, level_topn, want_counters=False)
     k = int(level_topn[5])
     st, got = r.status.cpu().numpy(), r.index.cpu().numpy()

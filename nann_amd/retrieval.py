@@ -10,6 +10,9 @@ per request.  Two equivalent executions of that schedule live here:
                       per query (nann_search_all; main.py:194-237 `test_all`);
   * `search_all_model()` the same under any ops.Model, the reference's attention +
                       DNN model included, from `comm_seq` (nann_search_all_model);
+  * `make_filter()`   a deny bitmap for every query and an exclusion list per query; search(), search_model(),
+                      and search_all() take it as `filter=`, search_all_model_filtered() as an argument
+                      (the nann_*_filtered calls: the reference has no such feature);
   * `search_per_op()` the same schedule spelled op by op with the drop-in ops
                       of nann_amd.ops, line for line against build_model(), so
                       that each op is exercised in the composition the
@@ -149,11 +152,13 @@ def search_options(traversal=None, slot_reserve=None, preprojection=None, mlp_fo
 
 
 class SearchResult:
-    __slots__ = ("item_ids", "scores", "index", "status", "counters", "phase_ticks", "plan", "_ws", "slot_reserve")
+    __slots__ = ("item_ids", "scores", "index", "status", "counters", "phase_ticks", "plan", "_ws", "slot_reserve", "n_out")
 
-    def __init__(self, item_ids, scores, index, status, counters, phase_ticks=None, plan=None, ws=None, slot_reserve=None):
+    def __init__(self, item_ids, scores, index, status, counters, phase_ticks=None, plan=None, ws=None, slot_reserve=None,
+                 n_out=None):
         self.item_ids, self.scores, self.index, self.status, self.counters = (
             item_ids, scores, index, status, counters)
+        self.n_out = n_out  # filtered calls: i32[B], valid entries at the head of each row (None: an unfiltered call)
         self.phase_ticks = phase_ticks
         self.plan = plan  # dict: what the planner chose (nann_search_plan)
         self._ws = ws
@@ -197,16 +202,123 @@ def _plan_dict(p):
             "est_visited": round(float(p.est_visited), 1), "worst_visited": round(float(p.worst_visited), 1)}
 
 
-def search(index, scorer, q, level_topn, want_counters=True, want_phase_ticks=False, options=None):
+class Filter:
+    """What make_filter returns: the tensors of a nann_filter (they may live on the CPU: the bit layout is testable without a
+    GPU) and its ctypes struct, which borrows their memory.
+      deny_bits   i32[ceil(n_items / 32)] or None: row r is denied for every query when bit (r & 31) of word (r >> 5) is set
+      row_splits  i64[n_queries + 1] or None; rows i32[n_excl]: query i excludes rows[row_splits[i] : row_splits[i + 1]]"""
+    __slots__ = ("deny_bits", "row_splits", "rows", "n_queries", "n_items", "device", "struct")
+
+    def __init__(self, deny_bits, row_splits, rows, n_items, device):
+        self.deny_bits, self.row_splits, self.rows, self.n_items, self.device = deny_bits, row_splits, rows, n_items, device
+        self.n_queries = None if row_splits is None else int(row_splits.numel()) - 1
+        st = _lib.Filter()
+        st.struct_bytes = C.sizeof(_lib.Filter)
+        st.deny_bits = deny_bits.data_ptr() if deny_bits is not None else None
+        st.excl_row_splits = row_splits.data_ptr() if row_splits is not None else None
+        st.excl_rows = rows.data_ptr() if rows is not None and rows.numel() else None
+        st.n_excl = int(rows.numel()) if rows is not None else 0
+        self.struct = st
+
+
+def _sorted_item_ids(index):
+    """(item ids ascending, the row of each): built once per Index and cached on it"""
+    c = getattr(index, "_sorted_ids", None)
+    if c is None:
+        vals, perm = torch.sort(index.item_ids)
+        c = index._sorted_ids = (vals, perm)
+    return c
+
+
+def _rows_of_item_ids(index, ids):
+    """internal rows of item ids (any array-like) on the device of index.item_ids; an unknown id is dropped"""
+    vals, perm = _sorted_item_ids(index)
+    ids = torch.as_tensor(np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids, dtype=np.int64)).reshape(-1).to(vals.device)
+    if vals.numel() == 0 or ids.numel() == 0:
+        return ids[:0]
+    pos = torch.searchsorted(vals, ids).clamp_(max=vals.numel() - 1)
+    return perm[pos][vals[pos] == ids]
+
+
+def _i64(a):
+    return torch.as_tensor(np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.int64)).reshape(-1)
+
+
+def make_filter(index, deny_rows=None, deny_item_ids=None, exclude_rows=None, exclude_item_ids=None, device=None):
+    """A nann_filter for searches on `index`: rows denied for EVERY query (deny_rows: internal row numbers; deny_item_ids:
+    item ids) and, per query, a list of excluded rows (exclude_rows / exclude_item_ids: one 1-D array per query of the
+    batch the filter will be used with; both given: their union).  Item ids map to rows through a sorted copy of
+    index.item_ids, built once per Index (an unknown id denies nothing; of rows that share an item id one is found).  Rows
+    outside [0, n_items) deny nothing: deny_rows drops them here, the lists keep them and the kernels skip them.
+    device: where the tensors live (default: the index's; "cpu" builds the same bits without a GPU).  -> Filter."""
+    dev = torch.device(device if device is not None else index.device)
+    n = int(index.n_items)
+    deny = []
+    if deny_rows is not None:
+        deny.append(_i64(deny_rows))
+    if deny_item_ids is not None:
+        deny.append(_rows_of_item_ids(index, deny_item_ids).cpu().to(torch.int64))
+    bits = None
+    if deny:
+        r = torch.cat(deny)
+        r = r[(r >= 0) & (r < n)]
+        words = (n + 31) // 32
+        flags = torch.zeros(words * 32, dtype=torch.bool)
+        flags[r] = True
+        w = (flags.view(words, 32).to(torch.int64) << torch.arange(32, dtype=torch.int64)).sum(1)
+        bits = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32).to(dev).contiguous()
+    splits = rows = None
+    if exclude_rows is not None or exclude_item_ids is not None:
+        nq = len(exclude_rows if exclude_rows is not None else exclude_item_ids)
+        assert exclude_rows is None or exclude_item_ids is None or len(exclude_rows) == len(exclude_item_ids)
+        per = []
+        for i in range(nq):
+            parts = []
+            if exclude_rows is not None:
+                parts.append(_i64(exclude_rows[i]))
+            if exclude_item_ids is not None:
+                parts.append(_rows_of_item_ids(index, exclude_item_ids[i]).cpu().to(torch.int64))
+            per.append(torch.cat(parts))
+        lens = torch.tensor([0] + [int(p.numel()) for p in per], dtype=torch.int64)
+        splits = torch.cumsum(lens, 0).to(dev).contiguous()
+        flat = torch.cat(per) if per else torch.zeros(0, dtype=torch.int64)
+        assert flat.numel() == 0 or (int(flat.min()) >= -(1 << 31) and int(flat.max()) < (1 << 31)), "row numbers are 32-bit"
+        rows = flat.to(torch.int32).to(dev).contiguous()
+    return Filter(bits, splits, rows, n, dev)
+
+
+def pool_width(level_topn):
+    """The widest useful fetch width of a filtered search: the last stage of the traversal ranks a pool of level_topn[1] + ...
+    + level_topn[4] distinct rows, and a list holds at most 1024."""
+    return min(int(sum(int(x) for x in list(level_topn)[1:5])), 1024)
+
+
+def _filter_args(filter, b, index):
+    """(POINTER(nann_filter) or None) for a batch of b queries on `index`"""
+    if filter is None:
+        return None
+    assert filter.n_items == index.n_items, "the filter was made for another index"
+    assert filter.device == index.device, "the filter's tensors must live on the index's device"
+    assert filter.n_queries is None or filter.n_queries == b, "the filter's exclusion lists: one per query of the batch"
+    return C.byref(filter.struct)
+
+
+def search(index, scorer, q, level_topn, want_counters=True, want_phase_ticks=False, options=None, filter=None, k=None):
     """Fused execution of build_model()'s schedule for a batch of queries.
     q: f32[B, d] CUDA tensor (ops.user_seq_mean of `comm_seq`).  level_topn: i32[6] for the whole batch, or
     [B, 6] per query (nann_search_v; rows of the outputs are level_topn.max(0)[5] wide, zero behind a query's
     own k).  options: search_options(...) for this call (nann_search_opt).  Asynchronous: the returned tensors are valid
-    once the current stream reaches them.  status[b] != 0 marks a request the reference would have failed."""
+    once the current stream reaches them.  status[b] != 0 marks a request the reference would have failed.
+    filter (make_filter) and / or k: the filtered call (nann_search_filtered) -- level_topn[5] is then the FETCH WIDTH F
+    (pool_width(level_topn) ranks the whole pool), the outputs are [B, k] (k = F when not given): the first k allowed entries
+    of the unfiltered answer at F, result.n_out[b] of them at the head of row b and zeros behind."""
     q = q.to(device=index.device, dtype=torch.float32).contiguous()
     b = q.shape[0]
     dev = index.device
-    t, tq, k = _level_topn_args(level_topn, b, dev)
+    t, tq, k_fetch = _level_topn_args(level_topn, b, dev)
+    if filter is not None or k is not None:
+        return _search_filtered(index, scorer, q, None, t, tq, k_fetch, want_counters, want_phase_ticks, options, filter, k)
+    k = k_fetch
     out_ids = torch.empty((b, k), dtype=torch.int64, device=dev)
     out_scores = torch.empty((b, k), dtype=torch.float32, device=dev)
     out_index = torch.empty((b, k), dtype=torch.int32, device=dev)
@@ -226,15 +338,56 @@ def search(index, scorer, q, level_topn, want_counters=True, want_phase_ticks=Fa
                         slot_reserve=int(options.slot_reserve) if options is not None else None)
 
 
-def search_model(index, model, comm_seq, level_topn, want_counters=True, options=None):
+def _search_filtered(index, scorer, q, seq, t, tq, k_fetch, want_counters, want_phase_ticks, options, filter, k):
+    """nann_search_filtered (q) / nann_search_model_filtered (seq): the body of search / search_model with a filter or a k"""
+    dev = index.device
+    x = q if seq is None else seq
+    b = x.shape[0]
+    k = k_fetch if k is None else int(k)
+    kk = max(k, 0)
+    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
+    n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    counters = torch.zeros((b, 3, _lib.NUM_ROUNDS), dtype=torch.int32, device=dev) if want_counters else None
+    ticks = torch.zeros((b, _lib.NUM_PHASES), dtype=torch.int64, device=dev) if want_phase_ticks else None
+    assert not (want_phase_ticks and tq is not None), "phase ticks: uniform level_topn only"
+    nbytes = C.c_int64(0)
+    L = lib()
+    if seq is None:
+        _check(L.nann_search_filtered_workspace_bytes(index.handle, t, b, C.byref(nbytes)), "search")
+    else:
+        _check(L.nann_search_model_filtered_workspace_bytes(index.handle, scorer.handle, t, b, C.byref(nbytes)), "search")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    plan = _lib.SearchPlan()
+    opt = C.byref(options) if options is not None else None
+    fa = _filter_args(filter, b, index)
+    with torch.cuda.device(dev):
+        if seq is None:
+            _check(L.nann_search_filtered(index.handle, scorer.handle, _ptr(x), b, t, _ptr(tq), _ptr(ws), ws.numel(), _ptr(out_ids),
+                                          _ptr(out_scores), _ptr(out_index), _ptr(status), _ptr(counters), _ptr(ticks), opt,
+                                          C.byref(plan), fa, k, _ptr(n_out), _stream()), "search")
+        else:
+            _check(L.nann_search_model_filtered(index.handle, scorer.handle, _ptr(x), b, t, _ptr(tq), _ptr(ws), ws.numel(),
+                                                _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(status), _ptr(counters), opt,
+                                                C.byref(plan), fa, k, _ptr(n_out), _stream()), "search")
+    return SearchResult(out_ids, out_scores, out_index, status, counters, ticks, _plan_dict(plan), ws,
+                        slot_reserve=int(options.slot_reserve) if options is not None else None, n_out=n_out)
+
+
+def search_model(index, model, comm_seq, level_topn, want_counters=True, options=None, filter=None, k=None):
     """The serving signature (build_opt_graph.py:151-159) for a batch: comm_seq f16[B, seq_len, E] +
     level_topn (i32[6], or [B, 6] per request) -> SearchResult, scored by `model` (ops.Model: l2 / mlp / the
     reference's attention + DNN model -- the per-user projection runs once per request, then the fused traversal;
-    nann_search_model_opt)."""
+    nann_search_model_opt).  filter / k: as search() takes them (nann_search_model_filtered)."""
     seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
     b = seq.shape[0]
     dev = index.device
-    t, tq, k = _level_topn_args(level_topn, b, dev)
+    t, tq, k_fetch = _level_topn_args(level_topn, b, dev)
+    if filter is not None or k is not None:
+        return _search_filtered(index, model, None, seq, t, tq, k_fetch, want_counters, False, options, filter, k)
+    k = k_fetch
     out_ids = torch.empty((b, k), dtype=torch.int64, device=dev)
     out_scores = torch.empty((b, k), dtype=torch.float32, device=dev)
     out_index = torch.empty((b, k), dtype=torch.int32, device=dev)
@@ -254,21 +407,23 @@ def search_model(index, model, comm_seq, level_topn, want_counters=True, options
 
 
 class SearchAllResult:
-    """Outputs of search_all: the top k of EVERY item per query, TopKV2 order (device tensors)."""
-    __slots__ = ("item_ids", "scores", "index", "_ws")
+    """Outputs of search_all: the top k of EVERY item per query, TopKV2 order (device tensors).  A filtered call: the top k
+    of every ALLOWED item, n_out[b] valid entries at the head of row b and zeros behind (n_out is None unfiltered)."""
+    __slots__ = ("item_ids", "scores", "index", "_ws", "n_out")
 
-    def __init__(self, item_ids, scores, index, ws=None):
-        self.item_ids, self.scores, self.index, self._ws = item_ids, scores, index, ws
+    def __init__(self, item_ids, scores, index, ws=None, n_out=None):
+        self.item_ids, self.scores, self.index, self._ws, self.n_out = item_ids, scores, index, ws, n_out
 
 
-def search_all(index, scorer, q, k, options=None):
+def search_all(index, scorer, q, k, options=None, filter=None):
     """Exhaustive search for a batch (nann_search_all; the reference's test_all job, main.py:194-237): every item of
     `index` scored for every query, top k per query -- descending, ties -> lower internal row number.  `scorer`:
     ops.Scorer with q f32[B, d], or an ops.Model of kind l2 / mlp with q = comm_seq f16[B, seq_len, d] (its
     ops.user_seq_mean is the query); an attention model raises NotImplementedError (score it user by user:
     evaluate.test_all).  options: search_options(preprojection=...).  Asynchronous on torch's current stream.
     An MLP scorer reads its pre-projected table; without one the call raises ops.NannError with status 103 (no room in
-    HBM) or 102 (pre-projection switched off)."""
+    HBM) or 102 (pre-projection switched off).  filter (make_filter): the top k of the ALLOWED rows
+    (nann_search_all_filtered), result.n_out[b] of them -- the ground truth of a filtered search()."""
     dev = index.device
     handle = scorer.handle
     if isinstance(scorer, ops.Model):
@@ -283,6 +438,16 @@ def search_all(index, scorer, q, k, options=None):
     out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
     out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
     nbytes = C.c_int64(0)
+    if filter is not None:
+        n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+        _check(lib().nann_search_all_filtered_workspace_bytes(index.handle, handle, b, k, C.byref(nbytes)), "search_all")
+        ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _check(lib().nann_search_all_filtered(index.handle, handle, _ptr(q), b, k, _ptr(out_ids), _ptr(out_scores),
+                                                  _ptr(out_index), _ptr(ws), ws.numel(),
+                                                  C.byref(options) if options is not None else None,
+                                                  _filter_args(filter, b, index), _ptr(n_out), _stream()), "search_all")
+        return SearchAllResult(out_ids, out_scores, out_index, ws, n_out)
     _check(lib().nann_search_all_workspace_bytes(index.handle, handle, b, k, C.byref(nbytes)), "search_all")
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
@@ -300,7 +465,18 @@ def search_all_model(index, model, comm_seq, k, options=None):
     table, split-f16 scores bit-identical to the traversal's); an ops.Scorer raises TypeError (search_all takes those).
     options: search_options(preprojection=...).  Asynchronous on torch's current stream.  An attention or MLP model reads
     its pre-projected table; without one the call raises ops.NannError with status 103 (no room in HBM) or 102
-    (pre-projection switched off)."""
+    (pre-projection switched off).  With a filter: search_all_model_filtered."""
+    return _search_all_model(index, model, comm_seq, k, options, None)
+
+
+def search_all_model_filtered(index, model, comm_seq, k, filter, options=None):
+    """search_all_model over the ALLOWED rows (nann_search_all_model_filtered): `filter` as search_all takes it (make_filter),
+    result.n_out[b] valid entries at the head of row b and zeros behind.  A function of its own: search_all_model's argument
+    list is pinned by its callers."""
+    return _search_all_model(index, model, comm_seq, k, options, filter)
+
+
+def _search_all_model(index, model, comm_seq, k, options, filter):
     if not isinstance(model, ops.Model):
         raise TypeError("search_all_model: an ops.Model (an ops.Scorer goes through search_all)")
     dev = index.device
@@ -311,6 +487,17 @@ def search_all_model(index, model, comm_seq, k, options=None):
     out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
     out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
     nbytes = C.c_int64(0)
+    if filter is not None:
+        n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+        _check(lib().nann_search_all_model_filtered_workspace_bytes(index.handle, model.handle, b, k, C.byref(nbytes)),
+               "search_all_model")
+        ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _check(lib().nann_search_all_model_filtered(index.handle, model.handle, _ptr(seq), b, k, _ptr(out_ids), _ptr(out_scores),
+                                                        _ptr(out_index), _ptr(ws), ws.numel(),
+                                                        C.byref(options) if options is not None else None,
+                                                        _filter_args(filter, b, index), _ptr(n_out), _stream()), "search_all_model")
+        return SearchAllResult(out_ids, out_scores, out_index, ws, n_out)
     _check(lib().nann_search_all_model_workspace_bytes(index.handle, model.handle, b, k, C.byref(nbytes)), "search_all_model")
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):

@@ -625,6 +625,55 @@ int nann_search_model_filtered(const nann_index* ix, const nann_model* m, const 
                                int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan,
                                const nann_filter* filter, int32_t k, int32_t* n_out, nann_stream_t stream);
 
+/* ---- candidate-list search: exact top-k over per-query candidate rows ------------------------------------------------
+ * "Here are the rows I may, or want to, return for this user: score them and give me the best k" -- re-ranking a merged
+ * recall set, an allow-list (a category, a campaign, a seller's stock), the small-allowed-set end of filtered retrieval.  The
+ * reference has no such call -- its serving graph scores what its own traversal reaches -- so nothing here restates a line of
+ * it; the semantics below are this library's own.  The cost is proportional to the lists, not to the index.
+ * The lists are a plain struct, passed per call and BORROWED for the call: */
+typedef struct {
+  int32_t struct_bytes;        /* 0 or sizeof(nann_candidates) */
+  const int64_t* row_splits;   /* device i64[n_queries + 1]: query i's list is rows[row_splits[i] .. row_splits[i+1]) */
+  const int32_t* rows;         /* device i32[n_cand]: INTERNAL row numbers; any order; duplicates allowed */
+  int64_t n_cand;              /* [host] length of rows: sizes the workspace */
+} nann_candidates;
+/*   q            f32[n_queries, d]
+ *   out_item_ids i64[n_queries, k] = item_ids[out_index];  status i32[n_queries] -- both required
+ *   out_scores   f32[n_queries, k], out_index i32[n_queries, k] (internal row numbers), out_pos i32[n_queries, k] (the entry's
+ *                0-based position within query i's list: what a re-ranking host maps back with), n_out i32[n_queries] -- each
+ *                may be NULL
+ *   workspace    device, 256-byte aligned (else NANN_ERR_BAD_ARGUMENT), nann_search_candidates_workspace_bytes(...) bytes; smaller
+ *                -> NANN_ERR_CAPACITY.  4 B per candidate, 24 B per query, and 1 KB per query under the MLP scorer
+ *   options      NULL = defaults; only `preprojection` is read (-1: the process default), as in nann_search_all
+ * Results: query i returns the min(k, len_i) best-scoring entries of its own list in TopKV2 order -- scores descending, ties ->
+ * the lower position in the list, -0 and +0 tie; NaN scores stay outside the contract, as for nann_topk.  n_out[i] entries at the
+ * head of row i of every output and zeros behind.  A row listed twice is scored twice and can be returned twice: there is no
+ * dedup, and k may exceed n_items (no NANN_ERR_TOPK_K_GT_N here).  An empty list is no error: n_out = 0, status = 0.  A caller
+ * who passes each list in ascending row order without duplicates gets "the top k of the allowed rows" of
+ * nann_search_all_filtered.
+ * Failures are per query, never per call and never a fault.  Query i is WELL-FORMED iff 0 <= row_splits[i] <= row_splits[i+1] <=
+ * n_cand and row_splits[i] >= row_splits[j] for every j < i; any other query gets status[i] = NANN_ERR_INVALID_RAGGED_INPUT,
+ * n_out[i] = 0 and a zeroed row.  (The rule makes the ranges of well-formed queries pairwise disjoint -- an earlier well-formed
+ * query's end is an earlier split, hence <= this query's begin -- so the score buffer, addressed by list position, has one
+ * writer per element whatever the caller passes.)  A well-formed query that lists a row outside [0, n_items) gets status[i] =
+ * NANN_ERR_INDEX_OUT_OF_RANGE, n_out[i] = 0 and zeros.  No other query's answer changes in either case.
+ * L2 scorer: every d (64, 128, 256, 512) and row dtype nann_score accepts, scores bit-identical to the oracle on the gathered
+ * rows and so to nann_score with `indices`.  MLP scorer: scored from the pre-projected table of the (scorer, index) pair, found or
+ * built as in nann_search_all and released behind the call's event -- EXACT_F32 and CERTIFIED (which runs the exact arithmetic
+ * here) bit-identical to the oracle, SPLIT_F16 within 1e-5 max(1, |s|); without a table NANN_ERR_CAPACITY (no room in HBM) or
+ * NANN_ERR_UNSUPPORTED (preprojection resolves to 0).  The attention model is not served by this call.
+ * Nothing is launched for: null ix, scorer or cand, a struct_bytes mismatch, n_queries < 0, n_cand < 0, k < 0, rows == NULL with
+ * n_cand > 0, row_splits == NULL with n_queries > 0, scorer and index disagreeing on d / dtype -> NANN_ERR_BAD_ARGUMENT; k > 1024
+ * or n_cand > 2^31 - 1 -> NANN_ERR_UNSUPPORTED; n_queries == 0 or k == 0 -> NANN_OK, nothing written.  A query's answer does not
+ * depend on the batch it is in.  Asynchronous on `stream`, no host read-back (the lists' lengths are device data), re-entrant
+ * on shared handles. */
+int nann_search_candidates_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int64_t n_cand,
+                                           int32_t k, int64_t* nbytes);
+int nann_search_candidates(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                           const nann_candidates* cand, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                           int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
+                           const nann_search_options* options, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

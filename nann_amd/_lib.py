@@ -42,6 +42,7 @@ SYMBOLS = [
     "nann_search_all_filtered_workspace_bytes", "nann_search_all_filtered", "nann_search_all_model_filtered_workspace_bytes",
     "nann_search_all_model_filtered", "nann_search_filtered_workspace_bytes", "nann_search_filtered",
     "nann_search_model_filtered_workspace_bytes", "nann_search_model_filtered",
+    "nann_search_candidates_workspace_bytes", "nann_search_candidates",
     "nann_merge_topk", "nann_merge_topk_host",
     "nann_attn_scorer_create", "nann_attn_scorer_destroy", "nann_attn_prepare", "nann_attn_score",
     "nann_blaze_options_parse", "nann_model_load", "nann_model_destroy", "nann_model_kind", "nann_model_scorer", "nann_model_workspace_bytes", "nann_model_forward",
@@ -67,6 +68,11 @@ class Filter(C.Structure):
     """nann_filter: a deny bitmap for every query and an exclusion list per query (device pointers, borrowed per call)"""
     _fields_ = [("struct_bytes", C.c_int32), ("deny_bits", C.c_void_p), ("excl_row_splits", C.c_void_p),
                 ("excl_rows", C.c_void_p), ("n_excl", C.c_int64)]
+
+
+class Candidates(C.Structure):
+    """nann_candidates: a list of rows per query (device pointers, borrowed per call)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("row_splits", C.c_void_p), ("rows", C.c_void_p), ("n_cand", C.c_int64)]
 
 
 class ScorerDesc(C.Structure):
@@ -158,6 +164,14 @@ def lib():
         L.nann_search_model_filtered_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int64,
                                                                  C.POINTER(C.c_int64)]
         L.nann_search_model_filtered_workspace_bytes.restype = C.c_int
+        # (ix, scorer, n_queries, n_cand, k, *nbytes) / (ix, scorer, q, n_queries, k, cand, out_item_ids, out_scores, out_index,
+        #  out_pos, n_out, status, workspace, workspace_bytes, options, stream)
+        L.nann_search_candidates_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                                             C.POINTER(C.c_int64)]
+        L.nann_search_candidates_workspace_bytes.restype = C.c_int
+        L.nann_search_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Candidates)] + \
+                                            [C.c_void_p] * 7 + [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
+        L.nann_search_candidates.restype = C.c_int
         _LIB = L
     return _LIB
 

@@ -14,7 +14,8 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 # units of their own, and the bf16 and f32 L2 instances are two again (their shared unit had become the longest: it alone bounded
 # a build from scratch at ~6 min on 8 cores).  The exhaustive search (nann_scan.h) is a unit of its own, the thirteenth; its scan
 # under the attention model (k_scan_attn), which instantiates the attention block scorers, the fourteenth.  The kernels of filtered
-# retrieval (nann_filter.h: two scatters and the compaction), which touch no search kernel, the fifteenth.
+# retrieval (nann_filter.h: two scatters and the compaction), which touch no search kernel, the fifteenth.  The candidate-list search
+# (nann_cand.h: the plan, its scorers over a ragged batch of row lists and the per-query top-k) the sixteenth.
 UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_comm.hip", {}), ("nann_hnsw_build.hip", {})]),
          ("nann_l2_f16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "0", "NANN_L2_NAME": "f16"})]),
          ("nann_l2_bf16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "1", "NANN_L2_NAME": "bf16"})]),
@@ -29,8 +30,9 @@ UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_comm.hip", {}), ("nann_hn
          ("nann_eval_win.o", [("nann_eval_win_inst.hip", {})]),
          ("nann_scan.o", [("nann_scan_inst.hip", {})]),
          ("nann_scan_attn.o", [("nann_scan_attn_inst.hip", {})]),
-         ("nann_filter.o", [("nann_filter_inst.hip", {})])]
-DEPS = ["nann_hip.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_filter_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
+         ("nann_filter.o", [("nann_filter_inst.hip", {})]),
+         ("nann_cand.o", [("nann_cand_inst.hip", {})])]
+DEPS = ["nann_hip.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_filter_inst.hip", "nann_cand.h", "nann_cand_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
         "nann_attn.h", "nann_attn_kernels.h", "nann_search.h", "nann_order.h", "nann_order_kernels.h", os.path.join("host", "nann_graphdef.h"), os.path.join("host", "nann_graphdef_text.h"), os.path.join("host", "nann_blaze_options.h"), os.path.join("host", "nann_npy.h"), os.path.join("host", "nann_projcache.h"),
         os.path.join("..", "..", "include", "nann_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-fast-math", "-ffp-contract=off"]

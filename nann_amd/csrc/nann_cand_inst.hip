@@ -1,0 +1,90 @@
+// nann_cand_inst.hip -- the kernels of the candidate-list search (nann_cand.h): the plan, the L2 scorer for every (d, row
+// dtype), the MLP scorer in both precisions and the per-query top-k; workspace layout and the launch sequence of a call.
+#define NANN_CAND_IMPL
+#include "nann_cand.h"
+
+#include <algorithm>
+
+namespace nann {
+
+namespace {
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+}  // namespace
+
+CandLayout cand_layout(int kind, long long n_queries, long long n_cand) {
+  CandLayout L = {};
+  L.off_scores = 0;
+  L.off_plan = up256((size_t)n_cand * 4);
+  L.off_items = L.off_plan + up256((size_t)n_queries * sizeof(CandQuery));
+  L.off_u = L.off_items + up256((size_t)(n_queries + 1) * 8);
+  L.total = L.off_u + (kind == NANN_SCORER_MLP ? up256((size_t)n_queries * 256 * 4) : 0);
+  return L;
+}
+
+// the persistent grid of a scoring kernel: at most the work items the lengths can add up to, n_cand / C whole blocks and one
+// ragged block per query
+static unsigned cand_grid(long long n_queries, long long n_cand, int rows_per_item, int resident) {
+  const long long most = n_cand / rows_per_item + std::min(n_queries, n_cand);
+  return (unsigned)std::max<long long>(1, std::min<long long>(most, resident));
+}
+
+template <int LPR>
+static void launch_cand_l2(const CandArgs& a, const CandScoreArgs& s, unsigned grid, hipStream_t st) {
+  if (a.dt == NANN_F16) hipLaunchKernelGGL((k_cand_score_l2<LPR, DT_F16>), dim3(grid), dim3(kCandNT), 0, st, s);
+  else if (a.dt == NANN_BF16) hipLaunchKernelGGL((k_cand_score_l2<LPR, DT_BF16>), dim3(grid), dim3(kCandNT), 0, st, s);
+  else hipLaunchKernelGGL((k_cand_score_l2<LPR, DT_F32>), dim3(grid), dim3(kCandNT), 0, st, s);
+}
+
+template <bool EXACT>
+static int launch_cand_mlp(const CandArgs& a, const CandScoreArgs& s, unsigned grid, hipStream_t st) {
+  auto kern = k_cand_score_mlp<EXACT>;
+  NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kMlpResBytes));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), (size_t)kMlpResBytes, st, a.mlp, s);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
+                int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status,
+                hipStream_t st) {
+  const bool mlp = a.kind == NANN_SCORER_MLP;
+  const int rows_per_item = mlp ? kCandMlpRows : kCandRows;
+  CandScoreArgs s = {};
+  s.emb = a.emb;
+  s.proj = a.proj;
+  s.n_items = a.n_items;
+  s.d = a.d;
+  s.rows = a.rows;
+  s.q = q;
+  s.u = reinterpret_cast<const float*>(ws + L.off_u);
+  s.scores = reinterpret_cast<float*>(ws + L.off_scores);
+  s.plan = reinterpret_cast<CandQuery*>(ws + L.off_plan);
+  s.item_off = reinterpret_cast<const long long*>(ws + L.off_items);
+  s.n_queries = n_queries;
+  hipLaunchKernelGGL(k_cand_plan, dim3(1), dim3(kCandNT), 0, st, a.row_splits, n_queries, a.n_cand, rows_per_item, s.plan,
+                     reinterpret_cast<long long*>(ws + L.off_items));
+  NANN_HIP_TRY(hipGetLastError());
+  if (a.n_cand > 0 && mlp) {
+    hipLaunchKernelGGL(k_cand_mlp_u, dim3((unsigned)n_queries), dim3(256), 0, st, a.mlp, q, reinterpret_cast<float*>(ws + L.off_u));
+    NANN_HIP_TRY(hipGetLastError());
+    const unsigned grid = cand_grid(n_queries, a.n_cand, rows_per_item, std::max(1, a.cus));
+    const int rc = a.exact ? launch_cand_mlp<true>(a, s, grid, st) : launch_cand_mlp<false>(a, s, grid, st);
+    if (rc) return rc;
+  } else if (a.n_cand > 0) {
+    const unsigned grid = cand_grid(n_queries, a.n_cand, rows_per_item, std::max(1, a.cus) * 8);
+    switch (a.d / 8) {
+      case 8: launch_cand_l2<8>(a, s, grid, st); break;
+      case 16: launch_cand_l2<16>(a, s, grid, st); break;
+      case 32: launch_cand_l2<32>(a, s, grid, st); break;
+      case 64: launch_cand_l2<64>(a, s, grid, st); break;
+      default: return fail(NANN_ERR_UNSUPPORTED, "nann_search_candidates: d must be 64, 128, 256 or 512");
+    }
+    NANN_HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cand_topk, dim3((unsigned)n_queries), dim3(kNT), 0, st, s.plan, a.rows, s.scores, k, a.item_ids, out_item_ids,
+                     out_scores, out_index, out_pos, n_out, status);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+}  // namespace nann

@@ -5,6 +5,7 @@
 #include "nann_attn.h"
 #include "nann_order_kernels.h"
 #include "nann_scan.h"
+#include "nann_cand.h"
 #include "host/nann_graphdef_text.h"
 #include "host/nann_blaze_options.h"
 #include "host/nann_npy.h"
@@ -2776,6 +2777,89 @@ int nann_search_all_filtered(const nann_index* ix, const nann_scorer* scorer, co
                              int32_t* n_out, nann_stream_t stream) {
   return search_all_impl(ix, scorer, q, n_queries, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
                          true, filter, n_out, stream);
+}
+
+// ---- candidate-list search (nann_cand.h): the top k of every query's own list of rows ------------------------
+// the checks both entry points share; `who` names the caller in the message
+static int search_candidates_check(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int64_t n_cand, int32_t k,
+                                   const char* who) {
+  if (!ix || !scorer) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (n_queries < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_queries < 0");
+  if (n_cand < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_cand < 0");
+  if (k < 0) return fail(NANN_ERR_BAD_ARGUMENT, "Need k >= 0, got " + std::to_string(k));
+  const int d = ix->desc.d;
+  if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
+  if (scorer->desc.d != ix->desc.d || scorer->desc.emb_dtype != ix->desc.emb_dtype)
+    return fail(NANN_ERR_BAD_ARGUMENT, "scorer and index disagree on d / dtype");
+  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
+  if (n_cand > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": list positions are 32-bit");
+  if (n_queries > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many queries in one call");
+  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  return NANN_OK;
+}
+
+int nann_search_candidates_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int64_t n_cand,
+                                           int32_t k, int64_t* nbytes) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates_workspace_bytes: null argument");
+  const int rc = search_candidates_check(ix, scorer, n_queries, n_cand, k, "nann_search_candidates_workspace_bytes");
+  if (rc) return rc;
+  if (n_queries == 0 || k == 0) { *nbytes = 0; return NANN_OK; }
+  *nbytes = (int64_t)cand_layout(scorer->desc.kind, (long long)n_queries, (long long)n_cand).total;
+  return NANN_OK;
+}
+
+int nann_search_candidates(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                           const nann_candidates* cand, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                           int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
+                           const nann_search_options* options, nann_stream_t stream) {
+  if (!cand) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates: null argument");
+  if (cand->struct_bytes != 0 && cand->struct_bytes != (int32_t)sizeof(nann_candidates))
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: struct_bytes");
+  int rc = search_candidates_check(ix, scorer, n_queries, cand->n_cand, k, "nann_search_candidates");
+  if (rc) return rc;
+  if (cand->n_cand > 0 && !cand->rows) return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: rows is null while n_cand > 0");
+  if (n_queries > 0 && !cand->row_splits) return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: row_splits is null while n_queries > 0");
+  if (n_queries == 0 || k == 0) return NANN_OK;
+  if (!q || !out_item_ids || !status) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates: null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  const SearchOpt opt = resolve_options(options);
+  const CandLayout L = cand_layout(scorer->desc.kind, (long long)n_queries, (long long)cand->n_cand);
+  if (!workspace || workspace_bytes < (int64_t)L.total)
+    return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_candidates_workspace_bytes()");
+  if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates: workspace must be 256-byte aligned");
+  hipStream_t st = as_stream(stream);
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  CandArgs a = {};
+  a.emb = ix->desc.item_embs;
+  a.item_ids = ix->desc.item_ids;
+  a.n_items = (long long)ix->desc.n_items;
+  a.d = ix->desc.d;
+  a.dt = ix->desc.emb_dtype;
+  a.kind = scorer->desc.kind;
+  a.cus = di.cus;
+  a.row_splits = cand->row_splits;
+  a.rows = cand->rows;
+  a.n_cand = (long long)cand->n_cand;
+  if (a.kind != NANN_SCORER_MLP)
+    return launch_cand(a, L, q, (long long)n_queries, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index,
+                       out_pos, n_out, status, st);
+  // the MLP scores from the pre-projected table of the pair, obtained and released as nann_search_all does
+  if (!opt.preproject)
+    return fail(NANN_ERR_UNSUPPORTED, "nann_search_candidates: the MLP scorer reads the pre-projected table and preprojection is switched off");
+  std::shared_ptr<ProjTable> tab;
+  rc = mlp_projection(scorer, ix, st, false, true, &tab);
+  if (rc) return rc;
+  if (!tab) return fail(NANN_ERR_CAPACITY, "nann_search_candidates: no room in HBM for the pre-projected table of this (scorer, index) pair");
+  a.proj = tab->table;
+  a.mlp = scorer->mlp;
+  a.exact = scorer->desc.precision == NANN_MLP_EXACT_F32 || scorer->desc.precision == NANN_MLP_CERTIFIED;
+  rc = launch_cand(a, L, q, (long long)n_queries, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index,
+                   out_pos, n_out, status, st);
+  projection_used(scorer->proj, tab, st);
+  return rc;
 }
 
 // ---- lifecycle of the pre-projected tables (ProjCache) -------------------------------------------------------

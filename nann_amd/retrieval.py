@@ -507,6 +507,94 @@ def _search_all_model(index, model, comm_seq, k, options, filter):
     return SearchAllResult(out_ids, out_scores, out_index, ws)
 
 
+# candidates per work item of the scoring kernels of search_candidates (csrc/nann_cand.h: kCandRows, kCandMlpRows)
+CANDIDATE_BLOCK_ROWS = 1024
+CANDIDATE_MLP_BLOCK_ROWS = 4096
+
+
+class CandidateResult:
+    """Outputs of search_candidates (device tensors): per query the top min(k, len) of its own list, TopKV2 order, ties to
+    the lower position in the list -- n_out[b] valid entries at the head of row b of item_ids / scores / index (internal rows) /
+    pos (positions within the query's list) and zeros behind.  status[b]: 0, 3 (the query's range in row_splits is ill-formed)
+    or 5 (it lists a row outside the index); such a query has n_out[b] = 0."""
+    __slots__ = ("item_ids", "scores", "index", "pos", "n_out", "status", "_ws", "_lists")
+
+    def __init__(self, item_ids, scores, index, pos, n_out, status, ws=None, lists=None):
+        self.item_ids, self.scores, self.index, self.pos, self.n_out, self.status = item_ids, scores, index, pos, n_out, status
+        self._ws, self._lists = ws, lists
+
+
+def _rows_of_item_ids_kept(index, ids):
+    """_rows_of_item_ids with every position kept: the row of each item id, -1 for an unknown one"""
+    vals, perm = _sorted_item_ids(index)
+    ids = _i64(ids).to(vals.device)
+    if vals.numel() == 0 or ids.numel() == 0:
+        return torch.full_like(ids, -1)
+    pos = torch.searchsorted(vals, ids).clamp_(max=vals.numel() - 1)
+    return torch.where(vals[pos] == ids, perm[pos], torch.full_like(ids, -1))
+
+
+def _candidate_lists(index, candidates, candidate_item_ids):
+    """(row_splits i64[B + 1], rows i32[n_cand]) on the index's device"""
+    dev = index.device
+    given = candidates if candidates is not None else candidate_item_ids
+    if isinstance(given, tuple) and len(given) == 2 and all(isinstance(t, torch.Tensor) for t in given):
+        splits, flat = given[0].to(torch.int64), given[1].reshape(-1)
+    else:
+        per = [_i64(p) for p in given]
+        splits = torch.cumsum(torch.tensor([0] + [int(p.numel()) for p in per], dtype=torch.int64), 0)
+        flat = torch.cat(per) if per else torch.zeros(0, dtype=torch.int64)
+    if candidates is None:
+        flat = _rows_of_item_ids_kept(index, flat)
+    elif flat.dtype != torch.int32:
+        assert flat.numel() == 0 or (int(flat.min()) >= -(1 << 31) and int(flat.max()) < (1 << 31)), "row numbers are 32-bit"
+    return splits.to(dev).contiguous(), flat.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def search_candidates(index, scorer, q, candidates=None, candidate_item_ids=None, k=200, options=None):
+    """Candidate-list search (nann_search_candidates): query b brings a list of rows of its own, the rows are scored and the
+    best min(k, len) returned -- descending, ties -> lower position in the list; a row listed twice is scored and may be
+    returned twice -> CandidateResult.  The cost grows with the lists, not with the index.
+    candidates: one 1-D integer array of internal row numbers per query, or a (row_splits i64[B + 1], rows) pair of tensors;
+    candidate_item_ids: the same in item ids (exactly one of the two), mapped through the sorted copy of index.item_ids that
+    make_filter uses -- an unknown id becomes row -1 and fails its query alone (status 5).
+    `scorer`: ops.Scorer with q f32[B, d], or an ops.Model of kind l2 / mlp with q = comm_seq f16[B, seq_len, d]; an attention
+    model raises NotImplementedError.  options: search_options(preprojection=...).  An MLP scorer reads its pre-projected
+    table, as in search_all.  Asynchronous on torch's current stream."""
+    assert (candidates is None) != (candidate_item_ids is None), "candidates or candidate_item_ids, one of the two"
+    dev = index.device
+    handle = scorer.handle
+    if isinstance(scorer, ops.Model):
+        if scorer.kind == "attention":
+            raise NotImplementedError("search_candidates: l2 / mlp scorers only")
+        q = ops.user_seq_mean(q.to(dev))
+        handle = C.c_void_p(lib().nann_model_scorer(scorer.handle))  # (borrowed: the model owns it)
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    b, k = q.shape[0], int(k)
+    splits, rows = _candidate_lists(index, candidates, candidate_item_ids)
+    assert splits.numel() == b + 1, "one candidate list per query of the batch"
+    cand = _lib.Candidates()
+    cand.struct_bytes = C.sizeof(_lib.Candidates)
+    cand.row_splits = splits.data_ptr()
+    cand.rows = rows.data_ptr() if rows.numel() else None
+    cand.n_cand = int(rows.numel())
+    kk = max(k, 0)
+    out_ids = torch.zeros((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.zeros((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.zeros((b, kk), dtype=torch.int32, device=dev)
+    out_pos = torch.zeros((b, kk), dtype=torch.int32, device=dev)
+    n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+    status = torch.zeros(b, dtype=torch.int32, device=dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_candidates_workspace_bytes(index.handle, handle, b, cand.n_cand, k, C.byref(nbytes)), "search_candidates")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_candidates(index.handle, handle, _ptr(q), b, k, C.byref(cand), _ptr(out_ids), _ptr(out_scores),
+                                            _ptr(out_index), _ptr(out_pos), _ptr(n_out), _ptr(status), _ptr(ws), ws.numel(),
+                                            C.byref(options) if options is not None else None, _stream()), "search_candidates")
+    return CandidateResult(out_ids, out_scores, out_index, out_pos, n_out, status, ws, (splits, rows))
+
+
 def prepare(index, scorer):
     """Build the pre-projected table of (scorer | model, index) now and pin it (nann_scorer_prepare /
     nann_model_prepare): no request pays for it.  Returns (table_bytes, resident_bytes)."""

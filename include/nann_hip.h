@@ -661,7 +661,8 @@ typedef struct {
  * rows and so to nann_score with `indices`.  MLP scorer: scored from the pre-projected table of the (scorer, index) pair, found or
  * built as in nann_search_all and released behind the call's event -- EXACT_F32 and CERTIFIED (which runs the exact arithmetic
  * here) bit-identical to the oracle, SPLIT_F16 within 1e-5 max(1, |s|); without a table NANN_ERR_CAPACITY (no room in HBM) or
- * NANN_ERR_UNSUPPORTED (preprojection resolves to 0).  The attention model is not served by this call.
+ * NANN_ERR_UNSUPPORTED (preprojection resolves to 0).  The attention model is not served by this call: it has a handle type of
+ * its own, and nann_search_candidates_model below takes it.
  * Nothing is launched for: null ix, scorer or cand, a struct_bytes mismatch, n_queries < 0, n_cand < 0, k < 0, rows == NULL with
  * n_cand > 0, row_splits == NULL with n_queries > 0, scorer and index disagreeing on d / dtype -> NANN_ERR_BAD_ARGUMENT; k > 1024
  * or n_cand > 2^31 - 1 -> NANN_ERR_UNSUPPORTED; n_queries == 0 or k == 0 -> NANN_OK, nothing written.  A query's answer does not
@@ -673,6 +674,38 @@ int nann_search_candidates(const nann_index* ix, const nann_scorer* scorer, cons
                            const nann_candidates* cand, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
                            int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
                            const nann_search_options* options, nann_stream_t stream);
+
+/* ---- candidate-list search under a model: nann_search_candidates for whatever model the node names ---------------------
+ * nann_search_candidates with the serving signature's input, as nann_search_all_model is to nann_search_all: comm_seq_f16 is
+ * f16[n_users, seq_len, E] (what nann_search_model_opt and nann_search_all_model take), `cand` the same nann_candidates with
+ * one list per user, the outputs and the workspace rule the same.  Lists, ordering (TopKV2, ties -> the lower position in
+ * the list, -0 and +0 tie), counts (n_out[i] = min(k, len_i) entries at the head of row i, zeros behind), duplicates (no
+ * dedup; k may exceed n_items), empty lists (no error) and the per-user failures -- the WELL-FORMED rule on row_splits with
+ * status 3, a row outside [0, n_items) with status 5, a zeroed row for the failed user and no other user's answer changed --
+ * are word for word the contract of nann_search_candidates above.
+ * l2 / mlp model: nann_user_seq_mean into the head of the workspace, then nann_search_candidates with the model's own scorer
+ * (nann_model_scorer) -- the same bits.  Workspace: 4 d bytes per user, rounded up to 256, plus that call's.
+ * attention model (NANN_impls/nann/model/model.py:189-233, the model the reference ships): both precisions score from the
+ * pre-projected table of the (model, index) pair, found or built as in nann_search_all_model and released behind the call's
+ * event; without a table NANN_ERR_CAPACITY (no room in HBM) or NANN_ERR_UNSUPPORTED (preprojection resolves to 0).  Scores
+ * are within 1e-5 max(1, |s|) of the oracle and, in both precisions, bit-identical to what nann_search_all_model returns for
+ * the same (user, row) -- the same block functions on the same table row; for split-f16 those are the traversal's bits too.
+ * Workspace, each part rounded up to 256 bytes: scores f32[n_cand], 16 B per user (the plan), 8 B x (n_users + 1), and the
+ * per-user side of ONE CHUNK: min(n_users, 128) x 80 KB (kt 64 KB + upad 16 KB per user).  The per-user side is bounded: the
+ * users are processed in chunks of at most 128, a chunk's nann_attn_prepare and scoring launch enqueued one after the other
+ * on `stream`, so the workspace never exceeds 4 n_cand + 24 n_users + 10 MB (+ rounding) however many users a call brings.
+ * Nothing is launched for: null ix, m or cand, a struct_bytes mismatch, n_users < 0, n_cand < 0, k < 0, rows == NULL with
+ * n_cand > 0, row_splits == NULL with n_users > 0, model and index disagreeing on d / dtype, null comm_seq_f16 / out_item_ids /
+ * status when there is work, a workspace off the 256-byte grid -> NANN_ERR_BAD_ARGUMENT; k > 1024, n_cand > 2^31 - 1 or
+ * n_users > 2^31 - 1 -> NANN_ERR_UNSUPPORTED; a workspace smaller than ..._workspace_bytes() -> NANN_ERR_CAPACITY; n_users == 0
+ * or k == 0 -> NANN_OK, nothing written.  A user's answer does not depend on the batch it is in.  Asynchronous on `stream`, no
+ * host read-back, re-entrant on shared handles. */
+int nann_search_candidates_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int64_t n_cand,
+                                                 int32_t k, int64_t* nbytes);
+int nann_search_candidates_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
+                                 const nann_candidates* cand, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                 int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
+                                 const nann_search_options* options, nann_stream_t stream);
 
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind

@@ -43,6 +43,7 @@ SYMBOLS = [
     "nann_search_all_model_filtered", "nann_search_filtered_workspace_bytes", "nann_search_filtered",
     "nann_search_model_filtered_workspace_bytes", "nann_search_model_filtered",
     "nann_search_candidates_workspace_bytes", "nann_search_candidates",
+    "nann_search_candidates_model_workspace_bytes", "nann_search_candidates_model",
     "nann_merge_topk", "nann_merge_topk_host",
     "nann_attn_scorer_create", "nann_attn_scorer_destroy", "nann_attn_prepare", "nann_attn_score",
     "nann_blaze_options_parse", "nann_model_load", "nann_model_destroy", "nann_model_kind", "nann_model_scorer", "nann_model_workspace_bytes", "nann_model_forward",
@@ -172,6 +173,11 @@ def lib():
         L.nann_search_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Candidates)] + \
                                             [C.c_void_p] * 7 + [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
         L.nann_search_candidates.restype = C.c_int
+        # the model form: (ix, model, comm_seq_f16, ...) in the place of (ix, scorer, q, ...)
+        L.nann_search_candidates_model_workspace_bytes.argtypes = list(L.nann_search_candidates_workspace_bytes.argtypes)
+        L.nann_search_candidates_model_workspace_bytes.restype = C.c_int
+        L.nann_search_candidates_model.argtypes = list(L.nann_search_candidates.argtypes)
+        L.nann_search_candidates_model.restype = C.c_int
         _LIB = L
     return _LIB
 

@@ -15,7 +15,8 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 # a build from scratch at ~6 min on 8 cores).  The exhaustive search (nann_scan.h) is a unit of its own, the thirteenth; its scan
 # under the attention model (k_scan_attn), which instantiates the attention block scorers, the fourteenth.  The kernels of filtered
 # retrieval (nann_filter.h: two scatters and the compaction), which touch no search kernel, the fifteenth.  The candidate-list search
-# (nann_cand.h: the plan, its scorers over a ragged batch of row lists and the per-query top-k) the sixteenth.
+# (nann_cand.h: the plan, its scorers over a ragged batch of row lists and the per-query top-k) the sixteenth; its scorer under the
+# attention model (k_cand_score_attn), which instantiates the attention block scorers once more, the seventeenth.
 UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_comm.hip", {}), ("nann_hnsw_build.hip", {})]),
          ("nann_l2_f16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "0", "NANN_L2_NAME": "f16"})]),
          ("nann_l2_bf16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "1", "NANN_L2_NAME": "bf16"})]),
@@ -31,8 +32,9 @@ UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_comm.hip", {}), ("nann_hn
          ("nann_scan.o", [("nann_scan_inst.hip", {})]),
          ("nann_scan_attn.o", [("nann_scan_attn_inst.hip", {})]),
          ("nann_filter.o", [("nann_filter_inst.hip", {})]),
-         ("nann_cand.o", [("nann_cand_inst.hip", {})])]
-DEPS = ["nann_hip.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_filter_inst.hip", "nann_cand.h", "nann_cand_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
+         ("nann_cand.o", [("nann_cand_inst.hip", {})]),
+         ("nann_cand_attn.o", [("nann_cand_attn_inst.hip", {})])]
+DEPS = ["nann_hip.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_filter_inst.hip", "nann_cand.h", "nann_cand_inst.hip", "nann_cand_attn_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
         "nann_attn.h", "nann_attn_kernels.h", "nann_search.h", "nann_order.h", "nann_order_kernels.h", os.path.join("host", "nann_graphdef.h"), os.path.join("host", "nann_graphdef_text.h"), os.path.join("host", "nann_blaze_options.h"), os.path.join("host", "nann_npy.h"), os.path.join("host", "nann_projcache.h"),
         os.path.join("..", "..", "include", "nann_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-fast-math", "-ffp-contract=off"]
@@ -146,6 +148,26 @@ def _check_scan_attn(log_path):
             raise RuntimeError(f"{name}: occupancy {m.group(1)} waves/SIMD, the split-form attention scan needs 2")
 
 
+def _check_cand_attn(log_path):
+    """The split-form scorer of the candidate-list search under the attention model (k_cand_score_attn<false>,
+    nann_cand_attn_inst.hip) has the body and the 150 KB of LDS of k_scan_attn<false> and is held to the same: no scratch frame,
+    2 waves per SIMD."""
+    import re
+    name = None
+    for line in open(log_path, errors="replace"):
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+        if not (name and "k_cand_score_attnILb0E" in name):
+            continue
+        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and int(m.group(1)) != 0:
+            raise RuntimeError(f"{name}: {m.group(1)} bytes of scratch per lane, the split-form attention scorer must have none")
+        m = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", line)
+        if m and int(m.group(1)) < 2:
+            raise RuntimeError(f"{name}: occupancy {m.group(1)} waves/SIMD, the split-form attention scorer needs 2")
+
+
 def unit_command(obj, parts, odir, extra_flags=(), save_temps=True):
     """Write the wrapper of a translation unit into `odir` and return the hipcc command that compiles it to odir/obj."""
     unit = os.path.join(odir, "unit.hip")
@@ -183,6 +205,7 @@ def _build_into(OUT_DIR, LIB, extra_flags, verbose, only=None):
         _check_occupancy(os.path.join(odir, "compile.log"))
         _check_scan_scratch(os.path.join(odir, "compile.log"))
         _check_scan_attn(os.path.join(odir, "compile.log"))
+        _check_cand_attn(os.path.join(odir, "compile.log"))
     # hipcc (ROCm 7.2) can place VGPR spill code ahead of the exec restore of a join block; the
     # lanes that were masked off then reload garbage (seen: top-k positions all -1).  Refuse
     # to ship an object with that pattern.

@@ -19,15 +19,31 @@
 //   3. k_cand_topk (one workgroup per query): wg_topk over scores[begin, +len) with ids = rows + begin -- positions, rows,
 //      scores and item ids in one pass, its tie rule (lower position) is the contract's; zeros behind min(k, len) entries, and a
 //      whole row of zeros for a query with a status.
+//
+// Under a model (nann_search_candidates_model): an l2 / mlp model is the call above on the mean of the user's sequence.  The
+// attention model keeps steps 1 and 3 and scores with k_cand_score_attn (nann_cand_attn_inst.hip), k_scan_attn crossed with
+// k_cand_score_mlp: the users are taken in chunks of at most kCandAttnChunk, whose kt / upad (nann_attn_prepare) share one
+// buffer of the workspace; per chunk the persistent grid walks the work items of the chunk's users only,
+// [item_off[c0], item_off[c0 + n_q)), and an item is one call of the resident attention block scorers of nann_attn_proj.h /
+// nann_attn_kernels.h on the model's pre-projected table with ids = rows + begin and the keys of user qi - c0.
 #pragma once
 #include <cstddef>
 
+#include "nann_scan.h"
 #include "nann_search.h"
 
 namespace nann {
 
 constexpr int kCandRows = 1024;     // C: candidates of an L2 work item (unmeasured)
 constexpr int kCandMlpRows = 4096;  // candidates of an MLP work item: what k_scan_mlp gives the block scorers per call (kScanMlpRows)
+// R: candidates of a work item under the attention model (unmeasured).  A multiple of 256: eight wavefronts take 32
+// candidates each.  An item loads its user's keys (72 KB in the split form, from L2 / Infinity Cache: a chunk's keys are
+// 10 MB) against 1.5 KB of table per scored row, so 256 rows put 19 % on top of the table's bytes; what this call is for,
+// re-ranking a few hundred rows for tens of users, has a few dozen items at any R and its time is the time of ONE item --
+// one 32-candidate block per wavefront at 256, two at 512.  The smallest legal value serves that case; the long lists of a
+// large batch have items enough for every CU at any R and pay the 19 %.
+constexpr int kCandAttnRows = 256;
+constexpr int kCandAttnChunk = 128;  // most users whose kt / upad are resident at a time (kScanMaxChunk of the exhaustive scan)
 
 struct CandQuery {  // the plan of one query
   int32_t begin, len;  // its list: rows[begin, +len); len = 0 for an ill-formed query
@@ -56,6 +72,52 @@ CandLayout cand_layout(int kind, long long n_queries, long long n_cand);
 int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status,
                 hipStream_t st);
+// steps 1 and 3 on their own (nann_cand_inst.hip): launch_cand's, and the attention form's around its chunks
+int launch_cand_plan(const int64_t* row_splits, long long n_queries, long long n_cand, int rows_per_item, CandQuery* plan,
+                     long long* item_off, hipStream_t st);
+int launch_cand_topk(const CandQuery* plan, const int32_t* rows, const float* scores, long long n_queries, int k,
+                     const int64_t* item_ids, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos,
+                     int32_t* n_out, int32_t* status, hipStream_t st);
+
+// ---- the attention model (nann_cand_attn_inst.hip) ------------------------------------------------------------------
+struct CandAttnArgs {
+  AttnParams attn;
+  int exact;                // the f32 form or split-f16
+  const float* proj;        // the pre-projected table of (model, index)
+  const int64_t* item_ids;
+  long long n_items;
+  int cus;
+  const int64_t* row_splits;
+  const int32_t* rows;
+  long long n_cand;
+};
+// workspace layout of a call: [scores f32[n_cand] | plan CandQuery[n_users] | item_off i64[n_users + 1] | kt + upad of one chunk]
+struct CandAttnLayout {
+  int chunk;  // users per pass = min(n_users, kCandAttnChunk)
+  size_t off_scores, off_plan, off_items, off_user, total;
+};
+CandAttnLayout cand_attn_layout(long long n_users, long long n_cand);
+int launch_cand_attn(const CandAttnArgs& a, const CandAttnLayout& L, const void* comm_seq_f16, long long n_users, int k,
+                     unsigned char* ws, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos,
+                     int32_t* n_out, int32_t* status, hipStream_t st);
+
+// work item w of a scoring kernel: the query it belongs to (item_off[qi] <= w < item_off[qi + 1]), where its block starts in
+// `rows` / `scores` and how many candidates it holds.  Uniform over the workgroup.
+struct CandItem {
+  long long qi;
+  int begin, count;
+};
+__device__ __forceinline__ CandItem cand_item(const CandQuery* __restrict__ plan, const long long* __restrict__ item_off,
+                                              long long n_queries, long long w, int rows_per_item) {
+  long long lo = 0, hi = n_queries;  // item_off[lo] <= w < item_off[hi]
+  while (hi - lo > 1) {
+    const long long mid = lo + (hi - lo) / 2;
+    if (item_off[mid] <= w) lo = mid; else hi = mid;
+  }
+  const CandQuery p = plan[lo];
+  const int at = (int)(w - item_off[lo]) * rows_per_item;
+  return CandItem{lo, p.begin + at, min(rows_per_item, p.len - at)};
+}
 
 }  // namespace nann
 
@@ -114,24 +176,6 @@ __global__ __launch_bounds__(kCandNT) void k_cand_plan(const int64_t* __restrict
     items += tile_items;
   }
   if (threadIdx.x == 0) item_off[n_queries] = items;
-}
-
-// work item w of a scoring kernel: the query it belongs to (item_off[qi] <= w < item_off[qi + 1]), where its block starts in
-// `rows` / `scores` and how many candidates it holds.  Uniform over the workgroup.
-struct CandItem {
-  long long qi;
-  int begin, count;
-};
-__device__ __forceinline__ CandItem cand_item(const CandQuery* __restrict__ plan, const long long* __restrict__ item_off,
-                                              long long n_queries, long long w, int rows_per_item) {
-  long long lo = 0, hi = n_queries;  // item_off[lo] <= w < item_off[hi]
-  while (hi - lo > 1) {
-    const long long mid = lo + (hi - lo) / 2;
-    if (item_off[mid] <= w) lo = mid; else hi = mid;
-  }
-  const CandQuery p = plan[lo];
-  const int at = (int)(w - item_off[lo]) * rows_per_item;
-  return CandItem{lo, p.begin + at, min(rows_per_item, p.len - at)};
 }
 
 // what the scoring kernels take (by value)

@@ -44,6 +44,22 @@ static int launch_cand_mlp(const CandArgs& a, const CandScoreArgs& s, unsigned g
   return NANN_OK;
 }
 
+int launch_cand_plan(const int64_t* row_splits, long long n_queries, long long n_cand, int rows_per_item, CandQuery* plan,
+                     long long* item_off, hipStream_t st) {
+  hipLaunchKernelGGL(k_cand_plan, dim3(1), dim3(kCandNT), 0, st, row_splits, n_queries, n_cand, rows_per_item, plan, item_off);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+int launch_cand_topk(const CandQuery* plan, const int32_t* rows, const float* scores, long long n_queries, int k,
+                     const int64_t* item_ids, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos,
+                     int32_t* n_out, int32_t* status, hipStream_t st) {
+  hipLaunchKernelGGL(k_cand_topk, dim3((unsigned)n_queries), dim3(kNT), 0, st, plan, rows, scores, k, item_ids, out_item_ids,
+                     out_scores, out_index, out_pos, n_out, status);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
 int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status,
                 hipStream_t st) {
@@ -61,14 +77,13 @@ int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long lon
   s.plan = reinterpret_cast<CandQuery*>(ws + L.off_plan);
   s.item_off = reinterpret_cast<const long long*>(ws + L.off_items);
   s.n_queries = n_queries;
-  hipLaunchKernelGGL(k_cand_plan, dim3(1), dim3(kCandNT), 0, st, a.row_splits, n_queries, a.n_cand, rows_per_item, s.plan,
-                     reinterpret_cast<long long*>(ws + L.off_items));
-  NANN_HIP_TRY(hipGetLastError());
+  int rc = launch_cand_plan(a.row_splits, n_queries, a.n_cand, rows_per_item, s.plan, reinterpret_cast<long long*>(ws + L.off_items), st);
+  if (rc) return rc;
   if (a.n_cand > 0 && mlp) {
     hipLaunchKernelGGL(k_cand_mlp_u, dim3((unsigned)n_queries), dim3(256), 0, st, a.mlp, q, reinterpret_cast<float*>(ws + L.off_u));
     NANN_HIP_TRY(hipGetLastError());
     const unsigned grid = cand_grid(n_queries, a.n_cand, rows_per_item, std::max(1, a.cus));
-    const int rc = a.exact ? launch_cand_mlp<true>(a, s, grid, st) : launch_cand_mlp<false>(a, s, grid, st);
+    rc = a.exact ? launch_cand_mlp<true>(a, s, grid, st) : launch_cand_mlp<false>(a, s, grid, st);
     if (rc) return rc;
   } else if (a.n_cand > 0) {
     const unsigned grid = cand_grid(n_queries, a.n_cand, rows_per_item, std::max(1, a.cus) * 8);
@@ -81,10 +96,8 @@ int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long lon
     }
     NANN_HIP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_cand_topk, dim3((unsigned)n_queries), dim3(kNT), 0, st, s.plan, a.rows, s.scores, k, a.item_ids, out_item_ids,
-                     out_scores, out_index, out_pos, n_out, status);
-  NANN_HIP_TRY(hipGetLastError());
-  return NANN_OK;
+  return launch_cand_topk(s.plan, a.rows, s.scores, n_queries, k, a.item_ids, out_item_ids, out_scores, out_index, out_pos, n_out,
+                          status, st);
 }
 
 }  // namespace nann

@@ -3122,6 +3122,95 @@ int nann_search_all_model_filtered(const nann_index* ix, const nann_model* m, co
                                options, true, filter, n_out, stream);
 }
 
+// ---- candidate-list search under a model (nann_cand.h) ---------------------------------------------------------
+// l2 / mlp: [q f32[n_users, d] | the workspace of nann_search_candidates].  attention: CandAttnLayout.
+static int search_candidates_model_check(const nann_index* ix, const nann_model* m, int64_t n_users, int64_t n_cand, int32_t k,
+                                         const char* who) {
+  if (!ix || !m) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (n_users < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_users < 0");
+  if (n_cand < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_cand < 0");
+  if (k < 0) return fail(NANN_ERR_BAD_ARGUMENT, "Need k >= 0, got " + std::to_string(k));
+  if (m->d != ix->desc.d || m->emb_dtype != ix->desc.emb_dtype)
+    return fail(NANN_ERR_BAD_ARGUMENT, "model and index disagree on d / dtype");
+  if (m->kind != NANN_MODEL_ATTENTION) return search_candidates_check(ix, m->scorer, n_users, n_cand, k, who);
+  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
+  if (n_cand > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": list positions are 32-bit");
+  if (n_users > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many users in one call");
+  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  return NANN_OK;
+}
+// the one place both entry points take the size from (after the check; n_users > 0 and k > 0)
+static size_t search_candidates_model_bytes(const nann_model* m, int64_t n_users, int64_t n_cand) {
+  if (m->kind == NANN_MODEL_ATTENTION) return cand_attn_layout((long long)n_users, (long long)n_cand).total;
+  return search_all_model_q_bytes(m, n_users) + cand_layout(m->scorer->desc.kind, (long long)n_users, (long long)n_cand).total;
+}
+
+int nann_search_candidates_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int64_t n_cand,
+                                                 int32_t k, int64_t* nbytes) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates_model_workspace_bytes: null argument");
+  const int rc = search_candidates_model_check(ix, m, n_users, n_cand, k, "nann_search_candidates_model_workspace_bytes");
+  if (rc) return rc;
+  if (n_users == 0 || k == 0) { *nbytes = 0; return NANN_OK; }
+  *nbytes = (int64_t)search_candidates_model_bytes(m, n_users, n_cand);
+  return NANN_OK;
+}
+
+int nann_search_candidates_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
+                                 const nann_candidates* cand, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                 int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
+                                 const nann_search_options* options, nann_stream_t stream) {
+  if (!cand) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates_model: null argument");
+  if (cand->struct_bytes != 0 && cand->struct_bytes != (int32_t)sizeof(nann_candidates))
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: struct_bytes");
+  int rc = search_candidates_model_check(ix, m, n_users, cand->n_cand, k, "nann_search_candidates_model");
+  if (rc) return rc;
+  if (cand->n_cand > 0 && !cand->rows) return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: rows is null while n_cand > 0");
+  if (n_users > 0 && !cand->row_splits) return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: row_splits is null while n_users > 0");
+  if (n_users == 0 || k == 0) return NANN_OK;
+  if (!comm_seq_f16 || !out_item_ids || !status) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates_model: null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  const size_t need = search_candidates_model_bytes(m, n_users, cand->n_cand);
+  if (!workspace || workspace_bytes < (int64_t)need)
+    return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_candidates_model_workspace_bytes()");
+  if (reinterpret_cast<uintptr_t>(workspace) & 255u)
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates_model: workspace must be 256-byte aligned");
+  if (m->kind != NANN_MODEL_ATTENTION) {  // the query is the mean of the sequence (nann_search_model), then nann_search_candidates
+    const size_t qb = search_all_model_q_bytes(m, n_users);
+    float* q = static_cast<float*>(workspace);
+    rc = nann_user_seq_mean(comm_seq_f16, n_users, m->seq_len, m->d, q, stream);
+    if (rc) return rc;
+    return nann_search_candidates(ix, m->scorer, q, n_users, k, cand, out_item_ids, out_scores, out_index, out_pos, n_out, status,
+                                  static_cast<unsigned char*>(workspace) + qb, workspace_bytes - (int64_t)qb, options, stream);
+  }
+  // both precisions score from the pre-projected table of the pair, obtained and released as nann_search_all_model does
+  if (!resolve_options(options).preproject)
+    return fail(NANN_ERR_UNSUPPORTED, "nann_search_candidates_model: the attention model is scored from the pre-projected table and preprojection is switched off");
+  hipStream_t st = as_stream(stream);
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  const nann_attn_scorer* at = m->attn;
+  std::shared_ptr<ProjTable> tab;
+  rc = attn_projection(at, ix, st, false, true, &tab);
+  if (rc) return rc;
+  if (!tab) return fail(NANN_ERR_CAPACITY, "nann_search_candidates_model: no room in HBM for the pre-projected table of this (model, index) pair");
+  CandAttnArgs a = {};
+  a.attn = at->P;
+  a.exact = at->precision != NANN_MLP_SPLIT_F16;
+  a.proj = tab->table;
+  a.item_ids = ix->desc.item_ids;
+  a.n_items = (long long)ix->desc.n_items;
+  a.cus = di.cus;
+  a.row_splits = cand->row_splits;
+  a.rows = cand->rows;
+  a.n_cand = (long long)cand->n_cand;
+  rc = launch_cand_attn(a, cand_attn_layout((long long)n_users, a.n_cand), comm_seq_f16, (long long)n_users, k,
+                        static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index, out_pos, n_out, status, st);
+  projection_used(at->proj, tab, st);
+  return rc;
+}
+
 // ---- the traversal, filtered at its final selection: the inner search at the fetch width F = level_topn_max[5] into a
 // staging area behind its own workspace (item ids i64[n, F], scores f32[n, F], rows i32[n, F]), then k_filter_compact --
 static size_t filter_stage_bytes(int64_t n_queries, int f) {

@@ -59,6 +59,10 @@ struct ScanArgs {
 };
 constexpr int kScanAttn = 100;  // ScanArgs::kind of the attention model (no nann_scorer_kind: it has a handle type of its own)
 constexpr size_t kScanAttnUserBytes = (size_t)(256 * kAttnLP + kAttnLP * kAttnE) * 4;  // kt 64 KB + upad 16 KB (nann_attn_prepare)
+// dynamic LDS of a 512-thread workgroup that runs the resident attention block scorers (k_scan_attn, k_cand_score_attn)
+constexpr int kScanAttnSplitLds = 65536 + kAttnSplitScratch;      // keys + [W2 | vectors | resident fragments]
+constexpr int kScanAttnExactLds = 65536 + kAttnXResFloats * 4;    // keys f32 [256][64] + [upad | W1a | W2 | W3]
+static_assert(kScanAttnSplitLds <= 160 * 1024 && kScanAttnExactLds <= 160 * 1024, "one workgroup per CU");
 // workspace layout of a call: [scores chunk x n_items | cand scores | cand rows | qT, u or kt + upad]; chunk = queries scored per pass
 struct ScanLayout {
   int chunk, n_slabs;

@@ -22,10 +22,7 @@
 
 namespace nann {
 
-constexpr int kScanAttnRows = 4096;  // rows of a work item
-constexpr int kScanAttnSplitLds = 65536 + kAttnSplitScratch;      // keys + [W2 | vectors | resident fragments]
-constexpr int kScanAttnExactLds = 65536 + kAttnXResFloats * 4;    // keys f32 [256][64] + [upad | W1a | W2 | W3]
-static_assert(kScanAttnSplitLds <= 160 * 1024 && kScanAttnExactLds <= 160 * 1024, "one workgroup per CU");
+constexpr int kScanAttnRows = 4096;  // rows of a work item (the LDS sizes: kScanAttnSplitLds / kScanAttnExactLds, nann_scan.h)
 
 template <bool EXACT>
 __global__ __launch_bounds__(512) void k_scan_attn(AttnParams P, const float* __restrict__ proj, long long n_items,

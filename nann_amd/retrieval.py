@@ -13,6 +13,8 @@ per request.  Two equivalent executions of that schedule live here:
   * `make_filter()`   a deny bitmap for every query and an exclusion list per query; search(), search_model(),
                       and search_all() take it as `filter=`, search_all_model_filtered() as an argument
                       (the nann_*_filtered calls: the reference has no such feature);
+  * `search_candidates()` / `search_candidates_model()` the exact top k of every query's own list of rows, under a
+                      scorer / under any ops.Model, the attention model included (nann_search_candidates[_model]);
   * `search_per_op()` the same schedule spelled op by op with the drop-in ops
                       of nann_amd.ops, line for line against build_model(), so
                       that each op is exercised in the composition the
@@ -510,6 +512,7 @@ def _search_all_model(index, model, comm_seq, k, options, filter):
 # candidates per work item of the scoring kernels of search_candidates (csrc/nann_cand.h: kCandRows, kCandMlpRows)
 CANDIDATE_BLOCK_ROWS = 1024
 CANDIDATE_MLP_BLOCK_ROWS = 4096
+CANDIDATE_ATTN_BLOCK_ROWS = 256  # search_candidates_model under the attention model (kCandAttnRows)
 
 
 class CandidateResult:
@@ -559,7 +562,7 @@ def search_candidates(index, scorer, q, candidates=None, candidate_item_ids=None
     candidate_item_ids: the same in item ids (exactly one of the two), mapped through the sorted copy of index.item_ids that
     make_filter uses -- an unknown id becomes row -1 and fails its query alone (status 5).
     `scorer`: ops.Scorer with q f32[B, d], or an ops.Model of kind l2 / mlp with q = comm_seq f16[B, seq_len, d]; an attention
-    model raises NotImplementedError.  options: search_options(preprojection=...).  An MLP scorer reads its pre-projected
+    model raises NotImplementedError here (search_candidates_model serves every kind of model).  options: search_options(preprojection=...).  An MLP scorer reads its pre-projected
     table, as in search_all.  Asynchronous on torch's current stream."""
     assert (candidates is None) != (candidate_item_ids is None), "candidates or candidate_item_ids, one of the two"
     dev = index.device
@@ -593,6 +596,49 @@ def search_candidates(index, scorer, q, candidates=None, candidate_item_ids=None
                                             _ptr(out_index), _ptr(out_pos), _ptr(n_out), _ptr(status), _ptr(ws), ws.numel(),
                                             C.byref(options) if options is not None else None, _stream()), "search_candidates")
     return CandidateResult(out_ids, out_scores, out_index, out_pos, n_out, status, ws, (splits, rows))
+
+
+def search_candidates_model(index, model, comm_seq, candidates=None, candidate_item_ids=None, k=200, options=None):
+    """Candidate-list search under a model (nann_search_candidates_model): search_candidates for the users of comm_seq
+    f16[B, seq_len, E] -- user b brings a list of rows of its own, the rows are scored by `model` and the best min(k, len)
+    returned, descending, ties -> lower position in the list, no dedup -> CandidateResult.  candidates / candidate_item_ids: as
+    search_candidates takes them (exactly one of the two).  `model`: an ops.Model of any kind (l2 / mlp: the bits of
+    search_candidates(index, model, comm_seq, ...); attention: scored on the device from the model's pre-projected table, both
+    precisions bit-identical to search_all_model's score of the same (user, row)); an ops.Scorer raises TypeError
+    (search_candidates takes those).  options: search_options(preprojection=...).  Asynchronous on torch's current stream.  An
+    attention or MLP model reads its pre-projected table; without one the call raises ops.NannError with status 103 (no room
+    in HBM) or 102 (pre-projection switched off).  The workspace holds the keys of at most 128 users at a time, however many
+    the batch has."""
+    if not isinstance(model, ops.Model):
+        raise TypeError("search_candidates_model: an ops.Model (an ops.Scorer goes through search_candidates)")
+    assert (candidates is None) != (candidate_item_ids is None), "candidates or candidate_item_ids, one of the two"
+    dev = index.device
+    seq = comm_seq.to(device=dev, dtype=torch.float16).contiguous()
+    b, k = seq.shape[0], int(k)
+    splits, rows = _candidate_lists(index, candidates, candidate_item_ids)
+    assert splits.numel() == b + 1, "one candidate list per user of the batch"
+    cand = _lib.Candidates()
+    cand.struct_bytes = C.sizeof(_lib.Candidates)
+    cand.row_splits = splits.data_ptr()
+    cand.rows = rows.data_ptr() if rows.numel() else None
+    cand.n_cand = int(rows.numel())
+    kk = max(k, 0)
+    out_ids = torch.zeros((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.zeros((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.zeros((b, kk), dtype=torch.int32, device=dev)
+    out_pos = torch.zeros((b, kk), dtype=torch.int32, device=dev)
+    n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+    status = torch.zeros(b, dtype=torch.int32, device=dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_candidates_model_workspace_bytes(index.handle, model.handle, b, cand.n_cand, k, C.byref(nbytes)),
+           "search_candidates_model")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_candidates_model(index.handle, model.handle, _ptr(seq), b, k, C.byref(cand), _ptr(out_ids),
+                                                  _ptr(out_scores), _ptr(out_index), _ptr(out_pos), _ptr(n_out), _ptr(status),
+                                                  _ptr(ws), ws.numel(), C.byref(options) if options is not None else None,
+                                                  _stream()), "search_candidates_model")
+    return CandidateResult(out_ids, out_scores, out_index, out_pos, n_out, status, ws, (splits, rows, seq))
 
 
 def prepare(index, scorer):

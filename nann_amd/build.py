@@ -16,8 +16,10 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 # under the attention model (k_scan_attn), which instantiates the attention block scorers, the fourteenth.  The kernels of filtered
 # retrieval (nann_filter.h: two scatters and the compaction), which touch no search kernel, the fifteenth.  The candidate-list search
 # (nann_cand.h: the plan, its scorers over a ragged batch of row lists and the per-query top-k) the sixteenth; its scorer under the
-# attention model (k_cand_score_attn), which instantiates the attention block scorers once more, the seventeenth.
-UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_comm.hip", {}), ("nann_hnsw_build.hip", {})]),
+# attention model (k_cand_score_attn), which instantiates the attention block scorers once more, the seventeenth.  The host side of
+# the exhaustive and the candidate-list search (nann_flat.hip) is a source of nann_core.o, behind nann_hip.hip whose file-scope
+# types and helpers it uses.
+UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_flat.hip", {}), ("nann_comm.hip", {}), ("nann_hnsw_build.hip", {})]),
          ("nann_l2_f16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "0", "NANN_L2_NAME": "f16"})]),
          ("nann_l2_bf16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "1", "NANN_L2_NAME": "bf16"})]),
          ("nann_l2_f32.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "2", "NANN_L2_NAME": "f32"})]),
@@ -34,7 +36,7 @@ UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_comm.hip", {}), ("nann_hn
          ("nann_filter.o", [("nann_filter_inst.hip", {})]),
          ("nann_cand.o", [("nann_cand_inst.hip", {})]),
          ("nann_cand_attn.o", [("nann_cand_attn_inst.hip", {})])]
-DEPS = ["nann_hip.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_filter_inst.hip", "nann_cand.h", "nann_cand_inst.hip", "nann_cand_attn_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
+DEPS = ["nann_hip.hip", "nann_flat.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_filter_inst.hip", "nann_cand.h", "nann_cand_inst.hip", "nann_cand_attn_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
         "nann_attn.h", "nann_attn_kernels.h", "nann_search.h", "nann_order.h", "nann_order_kernels.h", os.path.join("host", "nann_graphdef.h"), os.path.join("host", "nann_graphdef_text.h"), os.path.join("host", "nann_blaze_options.h"), os.path.join("host", "nann_npy.h"), os.path.join("host", "nann_projcache.h"),
         os.path.join("..", "..", "include", "nann_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-fast-math", "-ffp-contract=off"]
@@ -95,77 +97,68 @@ def build(force=False, verbose=False, variant=None, extra_flags=()):
     return _build_into(out, os.path.join(out, "libnann_hip.so"), tuple(extra_flags), verbose)
 
 
-def _check_occupancy(log_path):
-    """The 16K-slot hash-set traversal with the L2 scorer (k_search<.., VIS=2, SC=0, 512>) only pays off with TWO workgroups per
-    CU = 4 waves per SIMD; one VGPR over 128 halves its occupancy without any other symptom (seen: 130
-    VGPRs -> 2.82 ms instead of 1.99 ms).  Refuse to link such an object."""
+# What the compiler's resource report (-Rpass-analysis=kernel-resource-usage, a unit's compile.log) must show before an object is
+# linked: (name, pattern of the mangled kernel name, most scratch bytes per lane or None, fewest waves per SIMD or None, the kernel
+# in the message's words).  None of these faults changes a bit of an answer; each only costs time, without any other symptom.
+RULES = [
+    # The 16K-slot hash-set traversal with the L2 scorer (k_search<.., VIS=2, SC=0, 512>) only pays off with TWO workgroups per
+    # CU = 4 waves per SIMD; one VGPR over 128 halves its occupancy (seen: 130 VGPRs -> 2.82 ms instead of 1.99 ms).
+    ("occupancy", r"k_searchILi\d+ELi\d+ELi2ELi0ELi512E", None, 4, "the hash-set kernel"),
+    # The L2 scan of the exhaustive search (k_scan_l2, nann_scan.h) stages every byte of the table it reads through registers into
+    # LDS.  When hipcc leaves that staging buffer in private memory the kernel still computes the same bits, with three times the
+    # memory traffic (seen: ScratchSize 144 from an indexed uint4 array held across a barrier).
+    ("scan_scratch", r"k_scan_l2", 0, None, "the scan kernel"),
+    # The split-f16 scan under the attention model (k_scan_attn<false>, nann_scan_attn_inst.hip) keeps 150 KB of a CU's LDS for one
+    # 512-thread workgroup: two wavefronts per SIMD, which the kernel reaches only within 256 VGPRs, and it has no slack for spills
+    # -- a scratch frame there goes to memory once per 32-row block, between the MFMAs.  (The f32 form, k_scan_attn<true>, is the
+    # parity form and is not held to this.)
+    ("scan_attn", r"k_scan_attnILb0E", 0, 2, "the split-form attention scan"),
+    # The split-form scorer of the candidate-list search under the attention model (k_cand_score_attn<false>,
+    # nann_cand_attn_inst.hip) has the body and the 150 KB of LDS of k_scan_attn<false> and is held to the same.
+    ("cand_attn", r"k_cand_score_attnILb0E", 0, 2, "the split-form attention scorer"),
+]
+
+
+def check_resources(log_path, rules=RULES):
+    """One walk over a resource report: refuse (RuntimeError) to link a kernel that breaks one of `rules`."""
     import re
     name = None
     for line in open(log_path, errors="replace"):
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             name = m.group(1)
-        m = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", line)
-        if m and name and re.search(r"k_searchILi\d+ELi\d+ELi2ELi0ELi512E", name) and int(m.group(1)) < 4:
-            raise RuntimeError(f"{name}: occupancy {m.group(1)} waves/SIMD, the hash-set kernel needs 4")
+        scratch = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+        waves = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", line)
+        if not name or not (scratch or waves):
+            continue
+        for _, pattern, most_scratch, fewest_waves, what in rules:
+            if not re.search(pattern, name):
+                continue
+            if scratch and most_scratch is not None and int(scratch.group(1)) > most_scratch:
+                raise RuntimeError(f"{name}: {scratch.group(1)} bytes of scratch per lane, {what} must have "
+                                   f"{'none' if most_scratch == 0 else 'at most %d' % most_scratch}")
+            if waves and fewest_waves is not None and int(waves.group(1)) < fewest_waves:
+                raise RuntimeError(f"{name}: occupancy {waves.group(1)} waves/SIMD, {what} needs {fewest_waves}")
+
+
+def _rule(name):
+    return [r for r in RULES if r[0] == name]
+
+
+def _check_occupancy(log_path):
+    check_resources(log_path, _rule("occupancy"))
 
 
 def _check_scan_scratch(log_path):
-    """The L2 scan of the exhaustive search (k_scan_l2, nann_scan.h) stages every byte of the table it reads through registers
-    into LDS.  When hipcc leaves that staging buffer in private memory the kernel still computes the same bits, with three times
-    the memory traffic and no other symptom (seen: ScratchSize 144 from an indexed uint4 array held across a barrier).  Refuse to
-    link a k_scan_l2 with a scratch frame."""
-    import re
-    name = None
-    for line in open(log_path, errors="replace"):
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and "k_scan_l2" in name and int(m.group(1)) != 0:
-            raise RuntimeError(f"{name}: {m.group(1)} bytes of scratch per lane, the scan kernel must have none")
+    check_resources(log_path, _rule("scan_scratch"))
 
 
 def _check_scan_attn(log_path):
-    """The split-f16 scan under the attention model (k_scan_attn<false>, nann_scan_attn_inst.hip) keeps 150 KB of a CU's LDS for
-    one 512-thread workgroup: two wavefronts per SIMD, which the kernel reaches only within 256 VGPRs, and it has no slack for
-    spills -- a scratch frame there goes to memory once per 32-row block, between the MFMAs.  Neither changes a bit of its
-    answers.  Refuse to link a split-form k_scan_attn with a scratch frame or fewer than 2 waves per SIMD (the f32 form,
-    k_scan_attn<true>, is the parity form and is not held to this)."""
-    import re
-    name = None
-    for line in open(log_path, errors="replace"):
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        if not (name and "k_scan_attnILb0E" in name):
-            continue
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and int(m.group(1)) != 0:
-            raise RuntimeError(f"{name}: {m.group(1)} bytes of scratch per lane, the split-form attention scan must have none")
-        m = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", line)
-        if m and int(m.group(1)) < 2:
-            raise RuntimeError(f"{name}: occupancy {m.group(1)} waves/SIMD, the split-form attention scan needs 2")
+    check_resources(log_path, _rule("scan_attn"))
 
 
 def _check_cand_attn(log_path):
-    """The split-form scorer of the candidate-list search under the attention model (k_cand_score_attn<false>,
-    nann_cand_attn_inst.hip) has the body and the 150 KB of LDS of k_scan_attn<false> and is held to the same: no scratch frame,
-    2 waves per SIMD."""
-    import re
-    name = None
-    for line in open(log_path, errors="replace"):
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        if not (name and "k_cand_score_attnILb0E" in name):
-            continue
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and int(m.group(1)) != 0:
-            raise RuntimeError(f"{name}: {m.group(1)} bytes of scratch per lane, the split-form attention scorer must have none")
-        m = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", line)
-        if m and int(m.group(1)) < 2:
-            raise RuntimeError(f"{name}: occupancy {m.group(1)} waves/SIMD, the split-form attention scorer needs 2")
+    check_resources(log_path, _rule("cand_attn"))
 
 
 def unit_command(obj, parts, odir, extra_flags=(), save_temps=True):
@@ -202,10 +195,7 @@ def _build_into(OUT_DIR, LIB, extra_flags, verbose, only=None):
         if p.wait() != 0:
             sys.stderr.write(open(os.path.join(odir, "compile.log")).read()[-6000:])
             raise subprocess.CalledProcessError(p.returncode, cmd)
-        _check_occupancy(os.path.join(odir, "compile.log"))
-        _check_scan_scratch(os.path.join(odir, "compile.log"))
-        _check_scan_attn(os.path.join(odir, "compile.log"))
-        _check_cand_attn(os.path.join(odir, "compile.log"))
+        check_resources(os.path.join(odir, "compile.log"))
     # hipcc (ROCm 7.2) can place VGPR spill code ahead of the exec restore of a join block; the
     # lanes that were masked off then reload garbage (seen: top-k positions all -1).  Refuse
     # to ship an object with that pattern.

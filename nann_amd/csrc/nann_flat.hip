@@ -1,0 +1,431 @@
+// nann_flat.hip -- the host side of the flat retrieval calls, the ones that do not walk the graph: the exhaustive search
+// (nann_search_all, nann_search_all_filtered, nann_search_all_model, nann_search_all_model_filtered; kernels in nann_scan.h)
+// and the candidate-list search (nann_search_candidates, nann_search_candidates_model; kernels in nann_cand.h), each with its
+// *_workspace_bytes.
+//
+// Compiled into nann_core.o behind nann_hip.hip, as ONE translation unit with it (build.py writes the wrapper), on the terms
+// nann_comm.hip lives there: this file uses nann_hip.hip's file-scope types and helpers directly -- nann_index, nann_scorer,
+// nann_model, fail, device_info, as_stream, check_options / resolve_options, mlp_projection / attn_projection /
+// projection_used -- and no header stands between the two.  resolve_filter is defined here; the filtered traversal in
+// nann_hip.hip calls it through a declaration.
+//
+// Every entry point is one walk over the steps below, each written once:
+//   flat_by            who scores the call, from a nann_scorer or a nann_model
+//   flat_check         the shape of the call (flat_cand_check: with the nann_candidates struct around it)
+//   flat_all_bytes     the size of a workspace, per family; the *_workspace_bytes calls and the searches both take it from
+//   flat_cand_bytes    here, staged query in front and filter staging behind included
+//   flat_workspace     the caller's workspace against that size
+//   flat_stage_mean    an l2 / mlp model: the mean of the sequence into the head of the workspace, the scorer form behind it
+//   flat_table         the pre-projected table of an MLP or attention pair; projection_used hands it back behind the launch
+//   flat_ids_of, flat_rows_of, flat_lists_of   the index's and the lists' fields into ScanArgs / CandArgs / CandAttnArgs
+// A new flat form is an entry point at the bottom that calls flat_all or flat_cand (or a third walk made of the same steps).
+//
+// The ORDER in which a call looks at its arguments is part of its contract -- with two faults present, which one the caller is
+// told -- and the families differ in it for no deeper reason than their history.  The walks keep every order as it was and say
+// where they branch for it (tests/test_flat_contract_gpu.py pins them).
+#include "nann_scan.h"
+#include "nann_cand.h"
+
+#include <memory>
+#include <string>
+
+using namespace nann;
+
+// ---- who scores a call ---------------------------------------------------------------------------------------------------
+struct FlatBy {
+  int kind = NANN_SCORER_L2;             // the scorer's nann_scorer_kind, or kScanAttn for the attention model
+  int exact = 0;                         // MLP / attention: the f32 form (also the MLP's certified precision), else split-f16
+  MlpParams mlp = {};                    // MLP
+  AttnParams attn = {};                  // attention
+  const nann_scorer* scorer = nullptr;   // l2 / mlp: the scorer, a model's own included
+  const nann_attn_scorer* at = nullptr;  // attention
+  ProjCache* cache = nullptr;            // MLP / attention: the cache the pair's pre-projected table belongs to
+  const nann_model* mean_of = nullptr;   // an l2 / mlp model: the query is the mean of its sequence, staged at the head of the workspace
+  const char* what = "scorer";           // the handle's word in a message,
+  const char* unit = "queries";          // and what it scores for
+  bool mismatch = false;                 // handle and index disagree on d / dtype: flat_check reports it at its place in the order
+};
+
+static int flat_by(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, const char* who, FlatBy* by) {
+  *by = FlatBy{};
+  if (!ix || !(scorer || m)) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  int d = 0, dt = 0;
+  if (m) {
+    by->what = "model";
+    by->unit = "users";
+    d = m->d;
+    dt = m->emb_dtype;
+    if (m->kind == NANN_MODEL_ATTENTION) {
+      by->kind = kScanAttn;
+      by->at = m->attn;
+      by->attn = m->attn->P;
+      by->exact = m->attn->precision != NANN_MLP_SPLIT_F16;
+      by->cache = &m->attn->proj;
+    } else {
+      scorer = m->scorer;
+      if (!scorer) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+      by->mean_of = m;
+    }
+  } else {
+    d = scorer->desc.d;
+    dt = scorer->desc.emb_dtype;
+  }
+  if (scorer) {
+    by->scorer = scorer;
+    by->kind = scorer->desc.kind;
+    if (by->kind == NANN_SCORER_MLP) {
+      by->mlp = scorer->mlp;
+      by->exact = scorer->desc.precision == NANN_MLP_EXACT_F32 || scorer->desc.precision == NANN_MLP_CERTIFIED;
+      by->cache = &scorer->proj;
+    }
+  }
+  by->mismatch = d != ix->desc.d || dt != ix->desc.emb_dtype;
+  return NANN_OK;
+}
+
+// ---- the shape of a call -------------------------------------------------------------------------------------------------
+static int flat_bad_k(int32_t k) { return fail(NANN_ERR_BAD_ARGUMENT, "Need k >= 0, got " + std::to_string(k)); }  // topk_op.cc:60-61
+
+// lists: the candidate family (n_cand rows in all).  The exhaustive family holds k against n_items as TopKV2 does, and names a
+// negative k behind a mismatched handle; the candidate family names it in front.
+static int flat_check(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, int32_t k, bool lists,
+                      int64_t n_cand, const char* who, FlatBy* by) {
+  const int rc = flat_by(ix, scorer, m, who, by);
+  if (rc) return rc;
+  if (n < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_" + by->unit + " < 0");
+  if (lists) {
+    if (n_cand < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_cand < 0");
+    if (k < 0) return flat_bad_k(k);
+  }
+  if (by->mismatch) return fail(NANN_ERR_BAD_ARGUMENT, std::string(by->what) + " and index disagree on d / dtype");
+  if (!lists) {
+    if (k < 0) return flat_bad_k(k);
+    if (ix->desc.n_items < k)  // topk_op.cc:67-71
+      return fail(NANN_ERR_TOPK_K_GT_N, "input must have at least k columns. Had " + std::to_string(ix->desc.n_items) +
+                                            ", needed " + std::to_string(k));
+  }
+  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
+  if (lists) {
+    if (n_cand > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": list positions are 32-bit");
+    if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many " + by->unit + " in one call");
+  }
+  // (the last two cannot fail for an index nann_index_create has made -- it takes these d only, and at most 2^31 - 1 rows --
+  // so their place in the order is free)
+  const int d = ix->desc.d;
+  if (by->kind != kScanAttn && !(d == 64 || d == 128 || d == 256 || d == 512))  // the forms that read embedding rows
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
+  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  return NANN_OK;
+}
+
+// the caller's nann_candidates, around the checks of the call
+static int flat_cand_check(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, int32_t k,
+                           const nann_candidates* cand, const char* who, FlatBy* by) {
+  if (!cand) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (cand->struct_bytes != 0 && cand->struct_bytes != (int32_t)sizeof(nann_candidates))
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: struct_bytes");
+  const int rc = flat_check(ix, scorer, m, n, k, true, cand->n_cand, who, by);
+  if (rc) return rc;
+  if (cand->n_cand > 0 && !cand->rows) return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: rows is null while n_cand > 0");
+  if (n > 0 && !cand->row_splits)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string("nann_candidates: row_splits is null while n_") + by->unit + " > 0");
+  return NANN_OK;
+}
+
+// the caller's nann_filter as the kernels take it; NULL denies nothing
+static int resolve_filter(const nann_filter* f, const nann_index* ix, FilterArgs* out) {
+  *out = FilterArgs{};
+  out->n_items = (long long)ix->desc.n_items;
+  if (!f) return NANN_OK;
+  if (f->struct_bytes != 0 && f->struct_bytes != (int32_t)sizeof(nann_filter)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: struct_bytes");
+  if (f->n_excl < 0) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: n_excl < 0");
+  if (f->excl_row_splits && f->n_excl > 0 && !f->excl_rows) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: excl_row_splits without excl_rows");
+  out->deny_bits = f->deny_bits;
+  if (f->excl_row_splits && f->n_excl > 0) {
+    out->splits = f->excl_row_splits;
+    out->rows = f->excl_rows;
+    out->n_excl = (long long)f->n_excl;
+  }
+  return NANN_OK;
+}
+
+// ---- the workspace -------------------------------------------------------------------------------------------------------
+// An l2 / mlp model: [q f32[n, d], the means | the workspace of the scorer form].  Exhaustive: the ScanLayout of the kind (the
+// attention model's has each chunk's kt / upad in the place of the queries; nann_scan.h), and behind it a filtered call's
+// staging area of its final selection.  Candidates: CandLayout, or CandAttnLayout under the attention model.
+static size_t flat_mean_bytes(const FlatBy& by, int64_t n) {
+  return by.mean_of ? ((size_t)n * (size_t)by.mean_of->d * 4 + 255) & ~(size_t)255 : 0;
+}
+static size_t flat_all_bytes(const nann_index* ix, const FlatBy& by, int64_t n, int32_t k, bool filtered, ScanLayout* L) {
+  *L = scan_layout((long long)ix->desc.n_items, ix->desc.d, by.kind, (long long)n, k);
+  return flat_mean_bytes(by, n) + L->total + (filtered ? scan_filter_stage_bytes(L->chunk, k) : 0);
+}
+static size_t flat_cand_bytes(const FlatBy& by, int64_t n, int64_t n_cand) {
+  if (by.kind == kScanAttn) return cand_attn_layout((long long)n, (long long)n_cand).total;
+  return flat_mean_bytes(by, n) + cand_layout(by.kind, (long long)n, (long long)n_cand).total;
+}
+
+// `form`: "" or "_filtered" -- `need` is what <who><form>_workspace_bytes gives
+static int flat_workspace(const void* workspace, int64_t workspace_bytes, size_t need, const char* who, const char* form) {
+  if (!workspace || workspace_bytes < (int64_t)need)
+    return fail(NANN_ERR_CAPACITY, std::string("workspace smaller than ") + who + form + "_workspace_bytes()");
+  if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": workspace must be 256-byte aligned");
+  return NANN_OK;
+}
+
+// An l2 / mlp model: the query is the mean of the sequence (nann_search_model), into the head of the workspace; *q, *workspace
+// and *workspace_bytes are then the scorer form's.
+static int flat_stage_mean(const FlatBy& by, const void* comm_seq_f16, int64_t n, const float** q, void** workspace,
+                           int64_t* workspace_bytes, nann_stream_t stream) {
+  float* mean = static_cast<float*>(*workspace);
+  const int rc = nann_user_seq_mean(comm_seq_f16, n, by.mean_of->seq_len, by.mean_of->d, mean, stream);
+  if (rc) return rc;
+  const size_t qb = flat_mean_bytes(by, n);
+  *q = mean;
+  *workspace = static_cast<unsigned char*>(*workspace) + qb;
+  *workspace_bytes -= (int64_t)qb;
+  return NANN_OK;
+}
+
+// ---- the pre-projected table ---------------------------------------------------------------------------------------------
+// The MLP scorer and the attention model score from the pre-projected table of their pair, obtained as search_impl does; the
+// caller hands it back with projection_used(*by.cache, ..) behind its launch.
+static int flat_table(const FlatBy& by, const nann_index* ix, const nann_search_options* options, hipStream_t st,
+                      const char* who, std::shared_ptr<ProjTable>* tab) {
+  if (!resolve_options(options).preproject)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": the " + by.what + " scores from its pre-projected table and preprojection is switched off");
+  const int rc = by.at ? attn_projection(by.at, ix, st, false, true, tab) : mlp_projection(by.scorer, ix, st, false, true, tab);
+  if (rc) return rc;
+  if (!*tab) return fail(NANN_ERR_CAPACITY, std::string(who) + ": no room in HBM for the pre-projected table of this (" + by.what + ", index) pair");
+  return NANN_OK;
+}
+
+// ---- the launch arguments ------------------------------------------------------------------------------------------------
+// ScanArgs, CandArgs and CandAttnArgs name what they share alike: every one the index's ids, the first two its rows as well,
+// the last two the caller's lists
+template <class A> static void flat_ids_of(const nann_index* ix, A* a) {
+  a->item_ids = ix->desc.item_ids;
+  a->n_items = (long long)ix->desc.n_items;
+}
+template <class A> static void flat_rows_of(const nann_index* ix, A* a) {
+  flat_ids_of(ix, a);
+  a->emb = ix->desc.item_embs;
+  a->d = ix->desc.d;
+  a->dt = ix->desc.emb_dtype;
+}
+template <class A> static void flat_lists_of(const nann_candidates* cand, int cus, A* a) {
+  a->cus = cus;
+  a->row_splits = cand->row_splits;
+  a->rows = cand->rows;
+  a->n_cand = (long long)cand->n_cand;
+}
+
+// ---- exhaustive search (nann_scan.h): test_all of main.py:194-237 for a batch, under a scorer or whatever model the node names
+// x: q f32[n, d] with a scorer, comm_seq f16[n, seq_len, E] with a model.  `who`: the entry point in a message; a filtered
+// call speaks under its unfiltered twin's name.
+static int flat_all_size(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, int32_t k, bool filtered,
+                         int64_t* nbytes, const char* who) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  const int rc = flat_check(ix, scorer, m, n, k, false, 0, who, &by);
+  if (rc) return rc;
+  ScanLayout L;
+  *nbytes = n == 0 || k == 0 ? 0 : (int64_t)flat_all_bytes(ix, by, n, k, filtered, &L);
+  return NANN_OK;
+}
+
+static int flat_all(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, const void* x, int64_t n, int32_t k,
+                    int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                    const nann_search_options* options, bool filtered, const nann_filter* filter, int32_t* n_out,
+                    nann_stream_t stream, const char* who) {
+  FlatBy by;
+  int rc = flat_check(ix, scorer, m, n, k, false, 0, who, &by);
+  if (rc) return rc;
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!x || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  ScanLayout L;
+  const size_t need = flat_all_bytes(ix, by, n, k, filtered, &L);
+  const char* form = filtered ? "_filtered" : "";
+  // a model form looks at its workspace before its options, a scorer form at its options and its filter first
+  if (m) {
+    rc = flat_workspace(workspace, workspace_bytes, need, who, form);
+    if (rc) return rc;
+    if (by.mean_of) {  // (the mean is on the stream before the scorer form has looked at the options)
+      const float* q = nullptr;
+      rc = flat_stage_mean(by, x, n, &q, &workspace, &workspace_bytes, stream);
+      if (rc) return rc;
+      return flat_all(ix, by.scorer, nullptr, q, n, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
+                      filtered, filter, n_out, stream, "nann_search_all");
+    }
+  }
+  rc = check_options(options);
+  if (rc) return rc;
+  ScanFilter sf = {};
+  if (!m) {
+    if (filtered) rc = resolve_filter(filter, ix, &sf.f);
+    if (rc) return rc;
+    rc = flat_workspace(workspace, workspace_bytes, need, who, form);
+    if (rc) return rc;
+  }
+  hipStream_t st = as_stream(stream);
+  ScanArgs a = {};
+  std::shared_ptr<ProjTable> tab;
+  if (by.cache) {
+    rc = flat_table(by, ix, options, st, who, &tab);
+    if (rc) return rc;
+    DeviceInfo di;
+    rc = device_info(&di);
+    if (rc) return rc;
+    a.proj = tab->table;
+    a.mlp_workgroups = di.cus;
+  }
+  if (m && filtered) rc = resolve_filter(filter, ix, &sf.f);  // (the attention model: its filter behind its table)
+  if (rc) return rc;
+  if (filtered) {  // the staging area of the final selection lies behind the unfiltered workspace
+    sf.stage = static_cast<unsigned char*>(workspace) + L.total;
+    sf.n_out = n_out;
+    a.filter = &sf;
+  }
+  flat_rows_of(ix, &a);
+  a.kind = by.kind;
+  a.exact = by.exact;
+  a.mlp = by.mlp;
+  a.attn = by.attn;
+  rc = launch_scan(a, L, static_cast<const float*>(x), (long long)n, k, static_cast<unsigned char*>(workspace), out_item_ids,
+                   out_scores, out_index, st);
+  if (tab) projection_used(*by.cache, tab, st);
+  return rc;
+}
+
+// ---- candidate-list search (nann_cand.h): the top k of every query's own list of rows, under a scorer or a model -------------
+static int flat_cand_size(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, int64_t n_cand,
+                          int32_t k, int64_t* nbytes, const char* who) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  const int rc = flat_check(ix, scorer, m, n, k, true, n_cand, who, &by);
+  if (rc) return rc;
+  *nbytes = n == 0 || k == 0 ? 0 : (int64_t)flat_cand_bytes(by, n, n_cand);
+  return NANN_OK;
+}
+
+static int flat_cand(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, const void* x, int64_t n, int32_t k,
+                     const nann_candidates* cand, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos,
+                     int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                     nann_stream_t stream, const char* who) {
+  FlatBy by;
+  int rc = flat_cand_check(ix, scorer, m, n, k, cand, who, &by);
+  if (rc) return rc;
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!x || !out_item_ids || !status) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  rc = check_options(options);  // (both forms of this family: the options, then the workspace)
+  if (rc) return rc;
+  rc = flat_workspace(workspace, workspace_bytes, flat_cand_bytes(by, n, cand->n_cand), who, "");
+  if (rc) return rc;
+  if (by.mean_of) {
+    const float* q = nullptr;
+    rc = flat_stage_mean(by, x, n, &q, &workspace, &workspace_bytes, stream);
+    if (rc) return rc;
+    return flat_cand(ix, by.scorer, nullptr, q, n, k, cand, out_item_ids, out_scores, out_index, out_pos, n_out, status, workspace,
+                     workspace_bytes, options, stream, "nann_search_candidates");
+  }
+  hipStream_t st = as_stream(stream);
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  std::shared_ptr<ProjTable> tab;
+  if (by.cache) rc = flat_table(by, ix, options, st, who, &tab);
+  if (rc) return rc;
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  if (by.at) {
+    CandAttnArgs a = {};
+    flat_ids_of(ix, &a);
+    flat_lists_of(cand, di.cus, &a);
+    a.attn = by.attn;
+    a.exact = by.exact;
+    a.proj = tab->table;
+    rc = launch_cand_attn(a, cand_attn_layout((long long)n, a.n_cand), x, (long long)n, k, ws, out_item_ids, out_scores, out_index,
+                          out_pos, n_out, status, st);
+  } else {
+    CandArgs a = {};
+    flat_rows_of(ix, &a);
+    flat_lists_of(cand, di.cus, &a);
+    a.kind = by.kind;
+    a.exact = by.exact;
+    a.mlp = by.mlp;
+    if (tab) a.proj = tab->table;
+    rc = launch_cand(a, cand_layout(by.kind, (long long)n, a.n_cand), static_cast<const float*>(x), (long long)n, k, ws, out_item_ids,
+                     out_scores, out_index, out_pos, n_out, status, st);
+  }
+  if (tab) projection_used(*by.cache, tab, st);
+  return rc;
+}
+
+// ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
+extern "C" {
+
+int nann_search_all_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k, int64_t* nbytes) {
+  return flat_all_size(ix, scorer, nullptr, n_queries, k, false, nbytes, "nann_search_all_workspace_bytes");
+}
+int nann_search_all(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                    int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                    const nann_search_options* options, nann_stream_t stream) {
+  return flat_all(ix, scorer, nullptr, q, n_queries, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
+                  false, nullptr, nullptr, stream, "nann_search_all");
+}
+int nann_search_all_filtered_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k,
+                                             int64_t* nbytes) {
+  return flat_all_size(ix, scorer, nullptr, n_queries, k, true, nbytes, "nann_search_all_workspace_bytes");
+}
+int nann_search_all_filtered(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                             int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
+                             int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                             int32_t* n_out, nann_stream_t stream) {
+  return flat_all(ix, scorer, nullptr, q, n_queries, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
+                  true, filter, n_out, stream, "nann_search_all");
+}
+
+int nann_search_all_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, int64_t* nbytes) {
+  return flat_all_size(ix, nullptr, m, n_users, k, false, nbytes, "nann_search_all_model_workspace_bytes");
+}
+int nann_search_all_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                          const nann_search_options* options, nann_stream_t stream) {
+  return flat_all(ix, nullptr, m, comm_seq_f16, n_users, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes,
+                  options, false, nullptr, nullptr, stream, "nann_search_all_model");
+}
+int nann_search_all_model_filtered_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k,
+                                                   int64_t* nbytes) {
+  return flat_all_size(ix, nullptr, m, n_users, k, true, nbytes, "nann_search_all_model_workspace_bytes");
+}
+int nann_search_all_model_filtered(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                   int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
+                                   int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                                   int32_t* n_out, nann_stream_t stream) {
+  return flat_all(ix, nullptr, m, comm_seq_f16, n_users, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes,
+                  options, true, filter, n_out, stream, "nann_search_all_model");
+}
+
+int nann_search_candidates_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int64_t n_cand,
+                                           int32_t k, int64_t* nbytes) {
+  return flat_cand_size(ix, scorer, nullptr, n_queries, n_cand, k, nbytes, "nann_search_candidates_workspace_bytes");
+}
+int nann_search_candidates(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                           const nann_candidates* cand, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                           int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
+                           const nann_search_options* options, nann_stream_t stream) {
+  return flat_cand(ix, scorer, nullptr, q, n_queries, k, cand, out_item_ids, out_scores, out_index, out_pos, n_out, status,
+                   workspace, workspace_bytes, options, stream, "nann_search_candidates");
+}
+int nann_search_candidates_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int64_t n_cand,
+                                                 int32_t k, int64_t* nbytes) {
+  return flat_cand_size(ix, nullptr, m, n_users, n_cand, k, nbytes, "nann_search_candidates_model_workspace_bytes");
+}
+int nann_search_candidates_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
+                                 const nann_candidates* cand, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                 int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
+                                 const nann_search_options* options, nann_stream_t stream) {
+  return flat_cand(ix, nullptr, m, comm_seq_f16, n_users, k, cand, out_item_ids, out_scores, out_index, out_pos, n_out, status,
+                   workspace, workspace_bytes, options, stream, "nann_search_candidates_model");
+}
+
+}  // extern "C"

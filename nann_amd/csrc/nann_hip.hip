@@ -2600,6 +2600,10 @@ static void probe_index(nann_index* ix) {
   ix->probe_new_per_row_max = (float)mx;
 }
 
+// the caller's nann_filter as the kernels take it (nann_flat.hip, behind this file in the unit, defines it and holds the flat
+// retrieval calls -- nann_search_all*, nann_search_candidates* -- that use it too)
+static int resolve_filter(const nann_filter* f, const nann_index* ix, FilterArgs* out);
+
 extern "C" {
 
 int nann_search_ex(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
@@ -2648,218 +2652,6 @@ int nann_search_v(const nann_index* ix, const nann_scorer* scorer, const float* 
                   int32_t* status, int32_t* counters, nann_stream_t stream) {
   return nann_search_opt(ix, scorer, q, n_queries, level_topn_max, level_topn, workspace, workspace_bytes, out_item_ids,
                          out_scores, out_index, status, counters, nullptr, nullptr, nullptr, stream);  // deprecated: thin wrapper
-}
-
-// ---- exhaustive search (nann_scan.h): test_all of main.py:194-237 for a batch ---------------------------------
-static int search_all_check(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k, const char* who) {
-  if (!ix || !scorer) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  if (n_queries < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_queries < 0");
-  const int d = ix->desc.d;
-  if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
-  if (scorer->desc.d != ix->desc.d || scorer->desc.emb_dtype != ix->desc.emb_dtype)
-    return fail(NANN_ERR_BAD_ARGUMENT, "scorer and index disagree on d / dtype");
-  if (k < 0) return fail(NANN_ERR_BAD_ARGUMENT, "Need k >= 0, got " + std::to_string(k));  // topk_op.cc:60-61
-  if (ix->desc.n_items < k)
-    return fail(NANN_ERR_TOPK_K_GT_N, "input must have at least k columns. Had " + std::to_string(ix->desc.n_items) +
-                                          ", needed " + std::to_string(k));
-  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
-  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
-  return NANN_OK;
-}
-
-int nann_search_all_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k,
-                                    int64_t* nbytes) {
-  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_workspace_bytes: null argument");
-  const int rc = search_all_check(ix, scorer, n_queries, k, "nann_search_all_workspace_bytes");
-  if (rc) return rc;
-  if (n_queries <= 0 || k == 0) { *nbytes = 0; return NANN_OK; }
-  *nbytes = (int64_t)scan_layout((long long)ix->desc.n_items, ix->desc.d, scorer->desc.kind, (long long)n_queries, k).total;
-  return NANN_OK;
-}
-
-}  // extern "C"
-
-// ---- filtered retrieval (nann_filter.h) -------------------------------------------------------------------------------
-// the caller's nann_filter as the kernels take it; NULL denies nothing
-static int resolve_filter(const nann_filter* f, const nann_index* ix, FilterArgs* out) {
-  *out = FilterArgs{};
-  out->n_items = (long long)ix->desc.n_items;
-  if (!f) return NANN_OK;
-  if (f->struct_bytes != 0 && f->struct_bytes != (int32_t)sizeof(nann_filter)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: struct_bytes");
-  if (f->n_excl < 0) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: n_excl < 0");
-  if (f->excl_row_splits && f->n_excl > 0 && !f->excl_rows) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: excl_row_splits without excl_rows");
-  out->deny_bits = f->deny_bits;
-  if (f->excl_row_splits && f->n_excl > 0) {
-    out->splits = f->excl_row_splits;
-    out->rows = f->excl_rows;
-    out->n_excl = (long long)f->n_excl;
-  }
-  return NANN_OK;
-}
-
-// nann_search_all and, filtered, nann_search_all_filtered: the same checks and launches; a filtered call keeps the staging
-// area of its final selection behind the unfiltered workspace
-static int search_all_impl(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
-                           int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
-                           const nann_search_options* options, bool filtered, const nann_filter* filter, int32_t* n_out,
-                           nann_stream_t stream) {
-  int rc = search_all_check(ix, scorer, n_queries, k, "nann_search_all");
-  if (rc) return rc;
-  if (n_queries <= 0 || k == 0) return NANN_OK;
-  if (!q || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all: null argument");
-  rc = check_options(options);
-  if (rc) return rc;
-  const SearchOpt opt = resolve_options(options);
-  const ScanLayout L = scan_layout((long long)ix->desc.n_items, ix->desc.d, scorer->desc.kind, (long long)n_queries, k);
-  ScanFilter sf = {};
-  if (filtered) {
-    rc = resolve_filter(filter, ix, &sf.f);
-    if (rc) return rc;
-  }
-  const int64_t need = (int64_t)(L.total + (filtered ? scan_filter_stage_bytes(L.chunk, k) : 0));
-  if (!workspace || workspace_bytes < need)
-    return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_all_workspace_bytes()");
-  if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all: workspace must be 256-byte aligned");
-  hipStream_t st = as_stream(stream);
-  ScanArgs a = {};
-  if (filtered) {
-    sf.stage = static_cast<unsigned char*>(workspace) + L.total;
-    sf.n_out = n_out;
-    a.filter = &sf;
-  }
-  a.emb = ix->desc.item_embs;
-  a.item_ids = ix->desc.item_ids;
-  a.n_items = (long long)ix->desc.n_items;
-  a.d = ix->desc.d;
-  a.dt = ix->desc.emb_dtype;
-  a.kind = scorer->desc.kind;
-  if (a.kind != NANN_SCORER_MLP)
-    return launch_scan(a, L, q, (long long)n_queries, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index, st);
-  // the MLP scores from the pre-projected table of the pair, obtained and released as search_impl does
-  if (!opt.preproject)
-    return fail(NANN_ERR_UNSUPPORTED, "nann_search_all: the MLP scan reads the pre-projected table and preprojection is switched off");
-  std::shared_ptr<ProjTable> tab;
-  rc = mlp_projection(scorer, ix, st, false, true, &tab);
-  if (rc) return rc;
-  if (!tab) return fail(NANN_ERR_CAPACITY, "nann_search_all: no room in HBM for the pre-projected table of this (scorer, index) pair");
-  DeviceInfo di;
-  rc = device_info(&di);
-  if (rc) return rc;
-  a.proj = tab->table;
-  a.mlp = scorer->mlp;
-  a.exact = scorer->desc.precision == NANN_MLP_EXACT_F32 || scorer->desc.precision == NANN_MLP_CERTIFIED;
-  a.mlp_workgroups = di.cus;
-  rc = launch_scan(a, L, q, (long long)n_queries, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index, st);
-  projection_used(scorer->proj, tab, st);
-  return rc;
-}
-
-extern "C" {
-
-int nann_search_all(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
-                    int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
-                    const nann_search_options* options, nann_stream_t stream) {
-  return search_all_impl(ix, scorer, q, n_queries, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
-                         false, nullptr, nullptr, stream);
-}
-
-int nann_search_all_filtered_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k,
-                                             int64_t* nbytes) {
-  const int rc = nann_search_all_workspace_bytes(ix, scorer, n_queries, k, nbytes);
-  if (rc || n_queries <= 0 || k == 0) return rc;
-  *nbytes += (int64_t)scan_filter_stage_bytes(scan_layout((long long)ix->desc.n_items, ix->desc.d, scorer->desc.kind, (long long)n_queries, k).chunk, k);
-  return NANN_OK;
-}
-
-int nann_search_all_filtered(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
-                             int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
-                             int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
-                             int32_t* n_out, nann_stream_t stream) {
-  return search_all_impl(ix, scorer, q, n_queries, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
-                         true, filter, n_out, stream);
-}
-
-// ---- candidate-list search (nann_cand.h): the top k of every query's own list of rows ------------------------
-// the checks both entry points share; `who` names the caller in the message
-static int search_candidates_check(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int64_t n_cand, int32_t k,
-                                   const char* who) {
-  if (!ix || !scorer) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  if (n_queries < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_queries < 0");
-  if (n_cand < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_cand < 0");
-  if (k < 0) return fail(NANN_ERR_BAD_ARGUMENT, "Need k >= 0, got " + std::to_string(k));
-  const int d = ix->desc.d;
-  if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
-  if (scorer->desc.d != ix->desc.d || scorer->desc.emb_dtype != ix->desc.emb_dtype)
-    return fail(NANN_ERR_BAD_ARGUMENT, "scorer and index disagree on d / dtype");
-  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
-  if (n_cand > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": list positions are 32-bit");
-  if (n_queries > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many queries in one call");
-  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
-  return NANN_OK;
-}
-
-int nann_search_candidates_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int64_t n_cand,
-                                           int32_t k, int64_t* nbytes) {
-  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates_workspace_bytes: null argument");
-  const int rc = search_candidates_check(ix, scorer, n_queries, n_cand, k, "nann_search_candidates_workspace_bytes");
-  if (rc) return rc;
-  if (n_queries == 0 || k == 0) { *nbytes = 0; return NANN_OK; }
-  *nbytes = (int64_t)cand_layout(scorer->desc.kind, (long long)n_queries, (long long)n_cand).total;
-  return NANN_OK;
-}
-
-int nann_search_candidates(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
-                           const nann_candidates* cand, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
-                           int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
-                           const nann_search_options* options, nann_stream_t stream) {
-  if (!cand) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates: null argument");
-  if (cand->struct_bytes != 0 && cand->struct_bytes != (int32_t)sizeof(nann_candidates))
-    return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: struct_bytes");
-  int rc = search_candidates_check(ix, scorer, n_queries, cand->n_cand, k, "nann_search_candidates");
-  if (rc) return rc;
-  if (cand->n_cand > 0 && !cand->rows) return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: rows is null while n_cand > 0");
-  if (n_queries > 0 && !cand->row_splits) return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: row_splits is null while n_queries > 0");
-  if (n_queries == 0 || k == 0) return NANN_OK;
-  if (!q || !out_item_ids || !status) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates: null argument");
-  rc = check_options(options);
-  if (rc) return rc;
-  const SearchOpt opt = resolve_options(options);
-  const CandLayout L = cand_layout(scorer->desc.kind, (long long)n_queries, (long long)cand->n_cand);
-  if (!workspace || workspace_bytes < (int64_t)L.total)
-    return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_candidates_workspace_bytes()");
-  if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates: workspace must be 256-byte aligned");
-  hipStream_t st = as_stream(stream);
-  DeviceInfo di;
-  rc = device_info(&di);
-  if (rc) return rc;
-  CandArgs a = {};
-  a.emb = ix->desc.item_embs;
-  a.item_ids = ix->desc.item_ids;
-  a.n_items = (long long)ix->desc.n_items;
-  a.d = ix->desc.d;
-  a.dt = ix->desc.emb_dtype;
-  a.kind = scorer->desc.kind;
-  a.cus = di.cus;
-  a.row_splits = cand->row_splits;
-  a.rows = cand->rows;
-  a.n_cand = (long long)cand->n_cand;
-  if (a.kind != NANN_SCORER_MLP)
-    return launch_cand(a, L, q, (long long)n_queries, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index,
-                       out_pos, n_out, status, st);
-  // the MLP scores from the pre-projected table of the pair, obtained and released as nann_search_all does
-  if (!opt.preproject)
-    return fail(NANN_ERR_UNSUPPORTED, "nann_search_candidates: the MLP scorer reads the pre-projected table and preprojection is switched off");
-  std::shared_ptr<ProjTable> tab;
-  rc = mlp_projection(scorer, ix, st, false, true, &tab);
-  if (rc) return rc;
-  if (!tab) return fail(NANN_ERR_CAPACITY, "nann_search_candidates: no room in HBM for the pre-projected table of this (scorer, index) pair");
-  a.proj = tab->table;
-  a.mlp = scorer->mlp;
-  a.exact = scorer->desc.precision == NANN_MLP_EXACT_F32 || scorer->desc.precision == NANN_MLP_CERTIFIED;
-  rc = launch_cand(a, L, q, (long long)n_queries, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index,
-                   out_pos, n_out, status, st);
-  projection_used(scorer->proj, tab, st);
-  return rc;
 }
 
 // ---- lifecycle of the pre-projected tables (ProjCache) -------------------------------------------------------
@@ -2996,219 +2788,6 @@ int nann_model_release(const nann_model* m, const nann_index* ix) {
 int nann_model_table_bytes(const nann_model* m, const nann_index* ix, int64_t* table_bytes, int64_t* resident_bytes) {
   if (!m) return fail(NANN_ERR_BAD_ARGUMENT, "nann_model_table_bytes: null model");
   return table_bytes_impl(m->scorer, m->kind == NANN_MODEL_ATTENTION ? m->attn : nullptr, ix, table_bytes, resident_bytes);
-}
-
-// ---- exhaustive search with the serving signature's input: test_all under whatever model the node names -------
-// l2 / mlp: [q f32[n_users, d] | the workspace of nann_search_all].  attention: the ScanLayout scheme with the chunk's
-// kt / upad in the place of the queries (nann_scan.h, kScanAttn).
-static size_t search_all_model_q_bytes(const nann_model* m, int64_t n_users) {
-  return ((size_t)n_users * (size_t)m->d * 4 + 255) & ~(size_t)255;
-}
-static int search_all_model_check(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, const char* who) {
-  if (!ix || !m) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  if (n_users < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_users < 0");
-  if (m->d != ix->desc.d || m->emb_dtype != ix->desc.emb_dtype)
-    return fail(NANN_ERR_BAD_ARGUMENT, "model and index disagree on d / dtype");
-  if (m->kind != NANN_MODEL_ATTENTION) return search_all_check(ix, m->scorer, n_users, k, who);
-  if (k < 0) return fail(NANN_ERR_BAD_ARGUMENT, "Need k >= 0, got " + std::to_string(k));  // topk_op.cc:60-61
-  if (ix->desc.n_items < k)
-    return fail(NANN_ERR_TOPK_K_GT_N, "input must have at least k columns. Had " + std::to_string(ix->desc.n_items) +
-                                          ", needed " + std::to_string(k));
-  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
-  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
-  return NANN_OK;
-}
-
-}  // extern "C"
-
-static int search_all_model_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, bool filtered, int64_t* nbytes) {
-  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_model_workspace_bytes: null argument");
-  const int rc = search_all_model_check(ix, m, n_users, k, "nann_search_all_model_workspace_bytes");
-  if (rc) return rc;
-  if (n_users <= 0 || k == 0) { *nbytes = 0; return NANN_OK; }
-  const int kind = m->kind == NANN_MODEL_ATTENTION ? kScanAttn : m->scorer->desc.kind;
-  const ScanLayout L = scan_layout((long long)ix->desc.n_items, ix->desc.d, kind, (long long)n_users, k);
-  *nbytes = (int64_t)((m->kind == NANN_MODEL_ATTENTION ? 0 : search_all_model_q_bytes(m, n_users)) + L.total +
-                      (filtered ? scan_filter_stage_bytes(L.chunk, k) : 0));
-  return NANN_OK;
-}
-
-// nann_search_all_model and, filtered, nann_search_all_model_filtered (see search_all_impl)
-static int search_all_model_impl(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
-                                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
-                                 const nann_search_options* options, bool filtered, const nann_filter* filter, int32_t* n_out,
-                                 nann_stream_t stream) {
-  int rc = search_all_model_check(ix, m, n_users, k, "nann_search_all_model");
-  if (rc) return rc;
-  if (n_users <= 0 || k == 0) return NANN_OK;
-  if (!comm_seq_f16 || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_model: null argument");
-  int64_t need = 0;
-  rc = search_all_model_bytes(ix, m, n_users, k, filtered, &need);
-  if (rc) return rc;
-  if (!workspace || workspace_bytes < need)
-    return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_all_model_workspace_bytes()");
-  if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_model: workspace must be 256-byte aligned");
-  if (m->kind != NANN_MODEL_ATTENTION) {  // the query is the mean of the sequence (nann_search_model), then nann_search_all
-    const size_t qb = search_all_model_q_bytes(m, n_users);
-    float* q = static_cast<float*>(workspace);
-    rc = nann_user_seq_mean(comm_seq_f16, n_users, m->seq_len, m->d, q, stream);
-    if (rc) return rc;
-    return search_all_impl(ix, m->scorer, q, n_users, k, out_item_ids, out_scores, out_index, static_cast<unsigned char*>(workspace) + qb,
-                           workspace_bytes - (int64_t)qb, options, filtered, filter, n_out, stream);
-  }
-  rc = check_options(options);
-  if (rc) return rc;
-  const SearchOpt opt = resolve_options(options);
-  // both precisions scan the pre-projected table of the pair, obtained and released as search_impl does
-  if (!opt.preproject)
-    return fail(NANN_ERR_UNSUPPORTED, "nann_search_all_model: the attention scan reads the pre-projected table and preprojection is switched off");
-  hipStream_t st = as_stream(stream);
-  const nann_attn_scorer* at = m->attn;
-  std::shared_ptr<ProjTable> tab;
-  rc = attn_projection(at, ix, st, false, true, &tab);
-  if (rc) return rc;
-  if (!tab) return fail(NANN_ERR_CAPACITY, "nann_search_all_model: no room in HBM for the pre-projected table of this (model, index) pair");
-  DeviceInfo di;
-  rc = device_info(&di);
-  if (rc) return rc;
-  const ScanLayout L = scan_layout((long long)ix->desc.n_items, ix->desc.d, kScanAttn, (long long)n_users, k);
-  ScanArgs a = {};
-  ScanFilter sf = {};
-  if (filtered) {
-    rc = resolve_filter(filter, ix, &sf.f);
-    if (rc) return rc;
-    sf.stage = static_cast<unsigned char*>(workspace) + L.total;
-    sf.n_out = n_out;
-    a.filter = &sf;
-  }
-  a.item_ids = ix->desc.item_ids;
-  a.n_items = (long long)ix->desc.n_items;
-  a.d = ix->desc.d;
-  a.dt = ix->desc.emb_dtype;
-  a.kind = kScanAttn;
-  a.exact = at->precision != NANN_MLP_SPLIT_F16;
-  a.proj = tab->table;
-  a.attn = at->P;
-  a.mlp_workgroups = di.cus;
-  rc = launch_scan(a, L, static_cast<const float*>(comm_seq_f16), (long long)n_users, k, static_cast<unsigned char*>(workspace),
-                   out_item_ids, out_scores, out_index, st);
-  projection_used(at->proj, tab, st);
-  return rc;
-}
-
-extern "C" {
-
-int nann_search_all_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, int64_t* nbytes) {
-  return search_all_model_bytes(ix, m, n_users, k, false, nbytes);
-}
-
-int nann_search_all_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
-                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
-                          const nann_search_options* options, nann_stream_t stream) {
-  return search_all_model_impl(ix, m, comm_seq_f16, n_users, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes,
-                               options, false, nullptr, nullptr, stream);
-}
-
-int nann_search_all_model_filtered_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k,
-                                                   int64_t* nbytes) {
-  return search_all_model_bytes(ix, m, n_users, k, true, nbytes);
-}
-
-int nann_search_all_model_filtered(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
-                                   int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
-                                   int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
-                                   int32_t* n_out, nann_stream_t stream) {
-  return search_all_model_impl(ix, m, comm_seq_f16, n_users, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes,
-                               options, true, filter, n_out, stream);
-}
-
-// ---- candidate-list search under a model (nann_cand.h) ---------------------------------------------------------
-// l2 / mlp: [q f32[n_users, d] | the workspace of nann_search_candidates].  attention: CandAttnLayout.
-static int search_candidates_model_check(const nann_index* ix, const nann_model* m, int64_t n_users, int64_t n_cand, int32_t k,
-                                         const char* who) {
-  if (!ix || !m) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  if (n_users < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_users < 0");
-  if (n_cand < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_cand < 0");
-  if (k < 0) return fail(NANN_ERR_BAD_ARGUMENT, "Need k >= 0, got " + std::to_string(k));
-  if (m->d != ix->desc.d || m->emb_dtype != ix->desc.emb_dtype)
-    return fail(NANN_ERR_BAD_ARGUMENT, "model and index disagree on d / dtype");
-  if (m->kind != NANN_MODEL_ATTENTION) return search_candidates_check(ix, m->scorer, n_users, n_cand, k, who);
-  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
-  if (n_cand > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": list positions are 32-bit");
-  if (n_users > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many users in one call");
-  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
-  return NANN_OK;
-}
-// the one place both entry points take the size from (after the check; n_users > 0 and k > 0)
-static size_t search_candidates_model_bytes(const nann_model* m, int64_t n_users, int64_t n_cand) {
-  if (m->kind == NANN_MODEL_ATTENTION) return cand_attn_layout((long long)n_users, (long long)n_cand).total;
-  return search_all_model_q_bytes(m, n_users) + cand_layout(m->scorer->desc.kind, (long long)n_users, (long long)n_cand).total;
-}
-
-int nann_search_candidates_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int64_t n_cand,
-                                                 int32_t k, int64_t* nbytes) {
-  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates_model_workspace_bytes: null argument");
-  const int rc = search_candidates_model_check(ix, m, n_users, n_cand, k, "nann_search_candidates_model_workspace_bytes");
-  if (rc) return rc;
-  if (n_users == 0 || k == 0) { *nbytes = 0; return NANN_OK; }
-  *nbytes = (int64_t)search_candidates_model_bytes(m, n_users, n_cand);
-  return NANN_OK;
-}
-
-int nann_search_candidates_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
-                                 const nann_candidates* cand, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
-                                 int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
-                                 const nann_search_options* options, nann_stream_t stream) {
-  if (!cand) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates_model: null argument");
-  if (cand->struct_bytes != 0 && cand->struct_bytes != (int32_t)sizeof(nann_candidates))
-    return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: struct_bytes");
-  int rc = search_candidates_model_check(ix, m, n_users, cand->n_cand, k, "nann_search_candidates_model");
-  if (rc) return rc;
-  if (cand->n_cand > 0 && !cand->rows) return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: rows is null while n_cand > 0");
-  if (n_users > 0 && !cand->row_splits) return fail(NANN_ERR_BAD_ARGUMENT, "nann_candidates: row_splits is null while n_users > 0");
-  if (n_users == 0 || k == 0) return NANN_OK;
-  if (!comm_seq_f16 || !out_item_ids || !status) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates_model: null argument");
-  rc = check_options(options);
-  if (rc) return rc;
-  const size_t need = search_candidates_model_bytes(m, n_users, cand->n_cand);
-  if (!workspace || workspace_bytes < (int64_t)need)
-    return fail(NANN_ERR_CAPACITY, "workspace smaller than nann_search_candidates_model_workspace_bytes()");
-  if (reinterpret_cast<uintptr_t>(workspace) & 255u)
-    return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates_model: workspace must be 256-byte aligned");
-  if (m->kind != NANN_MODEL_ATTENTION) {  // the query is the mean of the sequence (nann_search_model), then nann_search_candidates
-    const size_t qb = search_all_model_q_bytes(m, n_users);
-    float* q = static_cast<float*>(workspace);
-    rc = nann_user_seq_mean(comm_seq_f16, n_users, m->seq_len, m->d, q, stream);
-    if (rc) return rc;
-    return nann_search_candidates(ix, m->scorer, q, n_users, k, cand, out_item_ids, out_scores, out_index, out_pos, n_out, status,
-                                  static_cast<unsigned char*>(workspace) + qb, workspace_bytes - (int64_t)qb, options, stream);
-  }
-  // both precisions score from the pre-projected table of the pair, obtained and released as nann_search_all_model does
-  if (!resolve_options(options).preproject)
-    return fail(NANN_ERR_UNSUPPORTED, "nann_search_candidates_model: the attention model is scored from the pre-projected table and preprojection is switched off");
-  hipStream_t st = as_stream(stream);
-  DeviceInfo di;
-  rc = device_info(&di);
-  if (rc) return rc;
-  const nann_attn_scorer* at = m->attn;
-  std::shared_ptr<ProjTable> tab;
-  rc = attn_projection(at, ix, st, false, true, &tab);
-  if (rc) return rc;
-  if (!tab) return fail(NANN_ERR_CAPACITY, "nann_search_candidates_model: no room in HBM for the pre-projected table of this (model, index) pair");
-  CandAttnArgs a = {};
-  a.attn = at->P;
-  a.exact = at->precision != NANN_MLP_SPLIT_F16;
-  a.proj = tab->table;
-  a.item_ids = ix->desc.item_ids;
-  a.n_items = (long long)ix->desc.n_items;
-  a.cus = di.cus;
-  a.row_splits = cand->row_splits;
-  a.rows = cand->rows;
-  a.n_cand = (long long)cand->n_cand;
-  rc = launch_cand_attn(a, cand_attn_layout((long long)n_users, a.n_cand), comm_seq_f16, (long long)n_users, k,
-                        static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index, out_pos, n_out, status, st);
-  projection_used(at->proj, tab, st);
-  return rc;
 }
 
 // ---- the traversal, filtered at its final selection: the inner search at the fetch width F = level_topn_max[5] into a

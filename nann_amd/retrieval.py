@@ -434,29 +434,31 @@ def search_all(index, scorer, q, k, options=None, filter=None):
         q = ops.user_seq_mean(q.to(dev))
         handle = C.c_void_p(lib().nann_model_scorer(scorer.handle))  # (borrowed: the model owns it)
     q = q.to(device=dev, dtype=torch.float32).contiguous()
-    b, k = q.shape[0], int(k)
+    return _flat_all(index, handle, q, k, options, filter, "nann_search_all", "search_all")
+
+
+def _flat_all(index, handle, x, k, options, filter, symbol, what):
+    """The exhaustive family's call: `symbol` (with _filtered under a filter) for the b rows of x -- the queries of a scorer
+    `handle`, the sequences of a model one -- into fresh outputs and a workspace of the size its _workspace_bytes twin gives."""
+    dev = index.device
+    b, k = x.shape[0], int(k)
     kk = max(k, 0)
     out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
     out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
     out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
-    nbytes = C.c_int64(0)
+    n_out = None
     if filter is not None:
+        symbol += "_filtered"
         n_out = torch.zeros(b, dtype=torch.int32, device=dev)
-        _check(lib().nann_search_all_filtered_workspace_bytes(index.handle, handle, b, k, C.byref(nbytes)), "search_all")
-        ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _check(lib().nann_search_all_filtered(index.handle, handle, _ptr(q), b, k, _ptr(out_ids), _ptr(out_scores),
-                                                  _ptr(out_index), _ptr(ws), ws.numel(),
-                                                  C.byref(options) if options is not None else None,
-                                                  _filter_args(filter, b, index), _ptr(n_out), _stream()), "search_all")
-        return SearchAllResult(out_ids, out_scores, out_index, ws, n_out)
-    _check(lib().nann_search_all_workspace_bytes(index.handle, handle, b, k, C.byref(nbytes)), "search_all")
+    nbytes = C.c_int64(0)
+    _check(getattr(lib(), symbol + "_workspace_bytes")(index.handle, handle, b, k, C.byref(nbytes)), what)
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _check(lib().nann_search_all(index.handle, handle, _ptr(q), b, k, _ptr(out_ids), _ptr(out_scores), _ptr(out_index),
-                                     _ptr(ws), ws.numel(), C.byref(options) if options is not None else None, _stream()),
-               "search_all")
-    return SearchAllResult(out_ids, out_scores, out_index, ws)
+        tail = (_filter_args(filter, b, index), _ptr(n_out)) if filter is not None else ()
+        _check(getattr(lib(), symbol)(index.handle, handle, _ptr(x), b, k, _ptr(out_ids), _ptr(out_scores), _ptr(out_index),
+                                      _ptr(ws), ws.numel(), C.byref(options) if options is not None else None, *tail, _stream()),
+               what)
+    return SearchAllResult(out_ids, out_scores, out_index, ws, n_out)
 
 
 def search_all_model(index, model, comm_seq, k, options=None):
@@ -481,32 +483,8 @@ def search_all_model_filtered(index, model, comm_seq, k, filter, options=None):
 def _search_all_model(index, model, comm_seq, k, options, filter):
     if not isinstance(model, ops.Model):
         raise TypeError("search_all_model: an ops.Model (an ops.Scorer goes through search_all)")
-    dev = index.device
-    seq = comm_seq.to(device=dev, dtype=torch.float16).contiguous()
-    b, k = seq.shape[0], int(k)
-    kk = max(k, 0)
-    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
-    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
-    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
-    nbytes = C.c_int64(0)
-    if filter is not None:
-        n_out = torch.zeros(b, dtype=torch.int32, device=dev)
-        _check(lib().nann_search_all_model_filtered_workspace_bytes(index.handle, model.handle, b, k, C.byref(nbytes)),
-               "search_all_model")
-        ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _check(lib().nann_search_all_model_filtered(index.handle, model.handle, _ptr(seq), b, k, _ptr(out_ids), _ptr(out_scores),
-                                                        _ptr(out_index), _ptr(ws), ws.numel(),
-                                                        C.byref(options) if options is not None else None,
-                                                        _filter_args(filter, b, index), _ptr(n_out), _stream()), "search_all_model")
-        return SearchAllResult(out_ids, out_scores, out_index, ws, n_out)
-    _check(lib().nann_search_all_model_workspace_bytes(index.handle, model.handle, b, k, C.byref(nbytes)), "search_all_model")
-    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib().nann_search_all_model(index.handle, model.handle, _ptr(seq), b, k, _ptr(out_ids), _ptr(out_scores),
-                                           _ptr(out_index), _ptr(ws), ws.numel(),
-                                           C.byref(options) if options is not None else None, _stream()), "search_all_model")
-    return SearchAllResult(out_ids, out_scores, out_index, ws)
+    seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
+    return _flat_all(index, model.handle, seq, k, options, filter, "nann_search_all_model", "search_all_model")
 
 
 # candidates per work item of the scoring kernels of search_candidates (csrc/nann_cand.h: kCandRows, kCandMlpRows)
@@ -573,9 +551,17 @@ def search_candidates(index, scorer, q, candidates=None, candidate_item_ids=None
         q = ops.user_seq_mean(q.to(dev))
         handle = C.c_void_p(lib().nann_model_scorer(scorer.handle))  # (borrowed: the model owns it)
     q = q.to(device=dev, dtype=torch.float32).contiguous()
-    b, k = q.shape[0], int(k)
+    return _flat_candidates(index, handle, q, candidates, candidate_item_ids, k, options, "nann_search_candidates",
+                            "search_candidates", "query", ())
+
+
+def _flat_candidates(index, handle, x, candidates, candidate_item_ids, k, options, symbol, what, unit, keep):
+    """The candidate family's call: `symbol` for the b rows of x (queries or sequences, as _flat_all takes them) and their
+    lists, as nann_candidates.  The result keeps the lists' tensors alive, and `keep` with them."""
+    dev = index.device
+    b, k = x.shape[0], int(k)
     splits, rows = _candidate_lists(index, candidates, candidate_item_ids)
-    assert splits.numel() == b + 1, "one candidate list per query of the batch"
+    assert splits.numel() == b + 1, "one candidate list per %s of the batch" % unit
     cand = _lib.Candidates()
     cand.struct_bytes = C.sizeof(_lib.Candidates)
     cand.row_splits = splits.data_ptr()
@@ -589,13 +575,13 @@ def search_candidates(index, scorer, q, candidates=None, candidate_item_ids=None
     n_out = torch.zeros(b, dtype=torch.int32, device=dev)
     status = torch.zeros(b, dtype=torch.int32, device=dev)
     nbytes = C.c_int64(0)
-    _check(lib().nann_search_candidates_workspace_bytes(index.handle, handle, b, cand.n_cand, k, C.byref(nbytes)), "search_candidates")
+    _check(getattr(lib(), symbol + "_workspace_bytes")(index.handle, handle, b, cand.n_cand, k, C.byref(nbytes)), what)
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _check(lib().nann_search_candidates(index.handle, handle, _ptr(q), b, k, C.byref(cand), _ptr(out_ids), _ptr(out_scores),
-                                            _ptr(out_index), _ptr(out_pos), _ptr(n_out), _ptr(status), _ptr(ws), ws.numel(),
-                                            C.byref(options) if options is not None else None, _stream()), "search_candidates")
-    return CandidateResult(out_ids, out_scores, out_index, out_pos, n_out, status, ws, (splits, rows))
+        _check(getattr(lib(), symbol)(index.handle, handle, _ptr(x), b, k, C.byref(cand), _ptr(out_ids), _ptr(out_scores),
+                                      _ptr(out_index), _ptr(out_pos), _ptr(n_out), _ptr(status), _ptr(ws), ws.numel(),
+                                      C.byref(options) if options is not None else None, _stream()), what)
+    return CandidateResult(out_ids, out_scores, out_index, out_pos, n_out, status, ws, (splits, rows) + tuple(keep))
 
 
 def search_candidates_model(index, model, comm_seq, candidates=None, candidate_item_ids=None, k=200, options=None):
@@ -612,33 +598,9 @@ def search_candidates_model(index, model, comm_seq, candidates=None, candidate_i
     if not isinstance(model, ops.Model):
         raise TypeError("search_candidates_model: an ops.Model (an ops.Scorer goes through search_candidates)")
     assert (candidates is None) != (candidate_item_ids is None), "candidates or candidate_item_ids, one of the two"
-    dev = index.device
-    seq = comm_seq.to(device=dev, dtype=torch.float16).contiguous()
-    b, k = seq.shape[0], int(k)
-    splits, rows = _candidate_lists(index, candidates, candidate_item_ids)
-    assert splits.numel() == b + 1, "one candidate list per user of the batch"
-    cand = _lib.Candidates()
-    cand.struct_bytes = C.sizeof(_lib.Candidates)
-    cand.row_splits = splits.data_ptr()
-    cand.rows = rows.data_ptr() if rows.numel() else None
-    cand.n_cand = int(rows.numel())
-    kk = max(k, 0)
-    out_ids = torch.zeros((b, kk), dtype=torch.int64, device=dev)
-    out_scores = torch.zeros((b, kk), dtype=torch.float32, device=dev)
-    out_index = torch.zeros((b, kk), dtype=torch.int32, device=dev)
-    out_pos = torch.zeros((b, kk), dtype=torch.int32, device=dev)
-    n_out = torch.zeros(b, dtype=torch.int32, device=dev)
-    status = torch.zeros(b, dtype=torch.int32, device=dev)
-    nbytes = C.c_int64(0)
-    _check(lib().nann_search_candidates_model_workspace_bytes(index.handle, model.handle, b, cand.n_cand, k, C.byref(nbytes)),
-           "search_candidates_model")
-    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib().nann_search_candidates_model(index.handle, model.handle, _ptr(seq), b, k, C.byref(cand), _ptr(out_ids),
-                                                  _ptr(out_scores), _ptr(out_index), _ptr(out_pos), _ptr(n_out), _ptr(status),
-                                                  _ptr(ws), ws.numel(), C.byref(options) if options is not None else None,
-                                                  _stream()), "search_candidates_model")
-    return CandidateResult(out_ids, out_scores, out_index, out_pos, n_out, status, ws, (splits, rows, seq))
+    seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
+    return _flat_candidates(index, model.handle, seq, candidates, candidate_item_ids, k, options, "nann_search_candidates_model",
+                            "search_candidates_model", "user", (seq,))
 
 
 def prepare(index, scorer):

@@ -100,3 +100,15 @@ def test_deprecated_search_entry_points_only_forward():
         text = re.sub(r"//[^\n]*|#[^\n]*", "", open(os.path.join(ROOT, rel)).read())
         text = re.sub(r'""".*?"""', "", text, flags=re.S)
         assert not re.search(deprecated, text), rel
+
+
+def test_by_hand_build_recipe_names_every_unit():
+    """INTEGRATION.md section 2 builds the library by hand: every object of build.UNITS and every source one is made of has to
+    be named there, or the recipe links a library with undefined symbols."""
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = text[text.index("\n## 2. Build"):text.index("\n## 3. ")]
+    for obj, parts in build.UNITS:
+        assert obj in section, f"{obj} is a unit of build.UNITS and not in the by-hand recipe"
+        for src, _ in parts:
+            assert src in section, f"{src} (a source of {obj}) is not in the by-hand recipe"
+    assert "seventeen translation units" in section and len(build.UNITS) == 17

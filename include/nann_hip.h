@@ -54,7 +54,7 @@ enum nann_status {
 
 enum nann_dtype { NANN_F16 = 0, NANN_BF16 = 1, NANN_F32 = 2, NANN_I32 = 3, NANN_I64 = 4,
                   NANN_F64 = 5 };
-enum nann_scorer_kind { NANN_SCORER_L2 = 0, NANN_SCORER_MLP = 1 };
+enum nann_scorer_kind { NANN_SCORER_L2 = 0, NANN_SCORER_MLP = 1, NANN_SCORER_IP = 2 };
 
 typedef void* nann_stream_t; /* hipStream_t */
 
@@ -166,7 +166,22 @@ int nann_topk(const float* values, int64_t n_rows, int64_t n_cols, int32_t k,
  *          blaze_xla_kernel.cc:24-33, blaze_xla_predictor.cc:360-459) --------
  * A scorer holds what the frozen scoring GraphDef holds in the reference.
  * L2: s = -||q - x||^2.  MLP: x=[q;e] -> h1 -> PReLU -> h2 -> PReLU -> 1
- * (weights f32; [host] pointers, copied to HBM at creation). */
+ * (weights f32; [host] pointers, copied to HBM at creation).
+ * IP (NANN_SCORER_IP): s = sum_k q_k x_k, the inner product; larger is better, nothing is negated.  It takes no weights: h1, h2,
+ * precision and the weight pointers are ignored; every d and row dtype of L2.  Canonical order (the order every entry point
+ * sums in, so that one (q, row) has the same score bits whichever call produced them): for d = 8 L, chunk l runs
+ * acc = fmaf(q_k, x_k, acc) from +0 over its 8 elements in order, 16-bit rows widened to f32 exactly; the L partials are added
+ * in the xor butterfly with strides 1, 2, 4, ...; score = sum.  (L2's tree with the other term and without the final 0 - sum.)
+ * Accepted wherever an L2 scorer is -- nann_score, nann_search_opt and its deprecated forwards, nann_search_filtered,
+ * nann_search_all(_filtered), nann_search_candidates, and as an `ip` model directory by the *_model calls -- with the L2
+ * contract of each call otherwise unchanged (TopKV2 order, the -0 / +0 tie, status codes, batch independence; no table:
+ * nann_scorer_prepare / release / table_bytes as for L2).  NOT supported: nann_search_eval, nann_search_eval_ex and
+ * nann_search_eval_model return NANN_ERR_UNSUPPORTED for an IP scorer or model and launch nothing.
+ * The index is the caller's: nann_hnsw_build* and the Python builders link rows by L2 distance, and a graph built that way is a
+ * reasonable but not a tuned neighbourhood structure for inner-product search (rows of large norm attract queries from far
+ * away in L2 terms); recall under IP is the caller's to measure, against nann_search_all with the same scorer.
+ * Cosine similarity is not a kind of its own: normalise the rows (and the queries) and use either metric -- on unit vectors
+ * -||q - x||^2 = 2 <q, x> - 2 ranks as <q, x> does. */
 typedef struct nann_scorer nann_scorer;
 typedef struct nann_index nann_index;
 typedef struct {
@@ -274,7 +289,7 @@ int nann_score(const nann_scorer* scorer, const float* q, const void* table,
  *                holds "split" | "exact" (| "certified": MLP only).
  *   a DIRECTORY  of .npy weight files, for scorers that have no frozen graph in the reference (BASELINE's L2
  *                and MLP) and for hosts that hold the model as arrays:
- *                  scorer.txt   one word: l2 | mlp | attention
+ *                  scorer.txt   one word: l2 | ip | mlp | attention  (l2, ip: no further file)
  *                  mlp          w1 [2d,256]  b1  alpha1  w2 [256,128]  b2  alpha2  w3 [128]     (nann_scorer_desc)
  *                  attention    wq1 bq1 aq wq2 bq2 wk1 bk1 ak wk2 bk2  w0..w3  b0..b2  bn_scale0..2  bn_shift0..2
  *                               alpha0..2                                                    (nann_attn_desc)
@@ -282,15 +297,15 @@ int nann_score(const nann_scorer* scorer, const float* q, const void* table,
  *                               MFMA) | "exact" (f32-input MFMA) | "certified" (mlp only: NANN_MLP_CERTIFIED)
  *                Every tensor is checked against the element count (d, seq_len) imply: NANN_ERR_SHAPE_MISMATCH.
  * nann_model_forward is forward() of build_opt_graph.py:91-107 for ONE user: user_seq f16
- * [seq_len, d] (l2 / mlp: its non-pad mean is the query vector; attention: [seq_len, 64]),
+ * [seq_len, d] (l2 / ip / mlp: its non-pad mean is the query vector; attention: [seq_len, 64]),
  * item_emb [n, d] rows as BlazeXlaOp receives them (already gathered) -> f32 logits[n].
  * All pointers device; workspace = nann_model_workspace_bytes() bytes; asynchronous on stream. */
 typedef struct nann_model nann_model;
-enum nann_model_kind { NANN_MODEL_L2 = 0, NANN_MODEL_MLP = 1, NANN_MODEL_ATTENTION = 2 };
+enum nann_model_kind { NANN_MODEL_L2 = 0, NANN_MODEL_MLP = 1, NANN_MODEL_ATTENTION = 2, NANN_MODEL_IP = 3 };
 int nann_model_load(const char* dir /*[host]*/, int32_t d, int32_t emb_dtype, int32_t seq_len, nann_model** out);
 void nann_model_destroy(nann_model* m);
 int nann_model_kind(const nann_model* m);
-/* the l2 / mlp model as the scorer nann_search takes (borrowed; NULL for attention) */
+/* the l2 / ip / mlp model as the scorer nann_search takes (borrowed; NULL for attention) */
 const nann_scorer* nann_model_scorer(const nann_model* m);
 int nann_model_workspace_bytes(const nann_model* m, int64_t* nbytes);
 int nann_model_forward(const nann_model* m, const void* user_seq_f16, const void* item_emb, int64_t n,

@@ -18,7 +18,7 @@ STATUS_NAMES = {
     104: "IO", 105: "DTYPE_MISMATCH", 106: "SHAPE_MISMATCH",
 }
 F16, BF16, F32, I32, I64, F64 = 0, 1, 2, 3, 4, 5
-SCORER_L2, SCORER_MLP = 0, 1
+SCORER_L2, SCORER_MLP, SCORER_IP = 0, 1, 2
 MLP_DEFAULT, MLP_SPLIT_F16, MLP_EXACT_F32, MLP_CERTIFIED = 0, 1, 2, 3
 NUM_ROUNDS = 5
 NUM_PHASES = 19

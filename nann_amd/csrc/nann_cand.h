@@ -9,7 +9,7 @@
 //      the running maximum of splits[0 .. i].  An earlier well-formed query's end is an earlier split, hence <= this query's
 //      begin: the ranges of well-formed queries are pairwise disjoint whatever the caller passes, and a score buffer addressed by
 //      list position has one writer per element.  An ill-formed query gets status 3, length 0 and no work item.
-//   2. k_cand_score_l2 / k_cand_score_mlp (persistent grids): work item w = block w - item_off[i] of the query i with
+//   2. k_cand_score_l2 / k_cand_score_ip / k_cand_score_mlp (persistent grids): work item w = block w - item_off[i] of the query i with
 //      item_off[i] <= w < item_off[i + 1], found by bisection (no list of items is written: the plan stays one pass over the
 //      queries however long a list is).  L2: the block's <= kCandRows row numbers are staged into LDS and checked -- a row outside
 //      [0, n_items) becomes row 0 and flags its query with an atomic OR on the plan's status word -- then wg_score_l2_part
@@ -52,7 +52,7 @@ struct CandQuery {  // the plan of one query
 };
 
 struct CandArgs {
-  const void* emb;          // L2: the index's rows
+  const void* emb;          // L2, inner product: the index's rows
   const float* proj;        // MLP: the pre-projected table of (scorer, index)
   const int64_t* item_ids;
   long long n_items;
@@ -185,7 +185,7 @@ struct CandScoreArgs {
   long long n_items;
   int d;
   const int32_t* rows;
-  const float* q;             // L2: f32[n_queries, d]
+  const float* q;             // L2, inner product: f32[n_queries, d]
   const float* u;             // MLP: f32[n_queries, 256]
   float* scores;              // f32[n_cand], by list position
   CandQuery* plan;
@@ -217,6 +217,34 @@ __global__ __launch_bounds__(kCandNT) void k_cand_score_l2(CandScoreArgs a) {
     __syncthreads();
     if (a.n_items <= 0) continue;  // (no row 0 to stand in: every candidate of an empty index has flagged its query)
     wg_score_l2_part<LPR, DT, kCandNT / 64>(a.emb, a.d, ids, 0, it.count, qv, a.scores + it.begin, tid >> 6, (unsigned long long)a.n_items * (unsigned)(a.d * 2) <= 0xffffffffull && a.n_items <= (1u << 24));
+  }
+}
+
+// The inner product: the same items, the shared scorer with the other term.  (A kernel of its own and not a shared body: a body
+// behind a common device function cost k_cand_score_l2 a scalar register, and the L2 kernels stay as they were to the register.)
+template <int LPR, int DT>
+__global__ __launch_bounds__(kCandNT) void k_cand_score_ip(CandScoreArgs a) {
+  __shared__ int32_t ids[kCandRows];
+  __shared__ float qv[kMaxD];
+  const int tid = threadIdx.x;
+  const long long n_work = a.item_off[a.n_queries];
+  for (long long w = blockIdx.x; w < n_work; w += gridDim.x) {
+    const CandItem it = cand_item(a.plan, a.item_off, a.n_queries, w, kCandRows);
+    __syncthreads();  // (every wavefront has left the item before: its list and query may go)
+    bool bad = false;
+    for (int j = tid; j < it.count; j += kCandNT) {
+      int32_t r = a.rows[it.begin + j];
+      if ((uint32_t)r >= (uint32_t)a.n_items) {  // (n_items < 2^31: a negative row is out of range too)
+        bad = true;
+        r = 0;
+      }
+      ids[j] = r;
+    }
+    for (int e = tid; e < a.d; e += kCandNT) qv[e] = a.q[(size_t)it.qi * a.d + e];
+    if (bad) atomicOr(&a.plan[it.qi].status, NANN_ERR_INDEX_OUT_OF_RANGE);
+    __syncthreads();
+    if (a.n_items <= 0) continue;  // (no row 0 to stand in: every candidate of an empty index has flagged its query)
+    wg_score_l2_part<LPR, DT, kCandNT / 64, MT_IP>(a.emb, a.d, ids, 0, it.count, qv, a.scores + it.begin, tid >> 6, (unsigned long long)a.n_items * (unsigned)(a.d * 2) <= 0xffffffffull && a.n_items <= (1u << 24));
   }
 }
 

@@ -1,4 +1,4 @@
-// nann_cand_inst.hip -- the kernels of the candidate-list search (nann_cand.h): the plan, the L2 scorer for every (d, row
+// nann_cand_inst.hip -- the kernels of the candidate-list search (nann_cand.h): the plan, the L2 and inner-product scorers for every (d, row
 // dtype), the MLP scorer in both precisions and the per-query top-k; workspace layout and the launch sequence of a call.
 #define NANN_CAND_IMPL
 #include "nann_cand.h"
@@ -35,6 +35,13 @@ static void launch_cand_l2(const CandArgs& a, const CandScoreArgs& s, unsigned g
   else hipLaunchKernelGGL((k_cand_score_l2<LPR, DT_F32>), dim3(grid), dim3(kCandNT), 0, st, s);
 }
 
+template <int LPR>
+static void launch_cand_ip(const CandArgs& a, const CandScoreArgs& s, unsigned grid, hipStream_t st) {
+  if (a.dt == NANN_F16) hipLaunchKernelGGL((k_cand_score_ip<LPR, DT_F16>), dim3(grid), dim3(kCandNT), 0, st, s);
+  else if (a.dt == NANN_BF16) hipLaunchKernelGGL((k_cand_score_ip<LPR, DT_BF16>), dim3(grid), dim3(kCandNT), 0, st, s);
+  else hipLaunchKernelGGL((k_cand_score_ip<LPR, DT_F32>), dim3(grid), dim3(kCandNT), 0, st, s);
+}
+
 template <bool EXACT>
 static int launch_cand_mlp(const CandArgs& a, const CandScoreArgs& s, unsigned grid, hipStream_t st) {
   auto kern = k_cand_score_mlp<EXACT>;
@@ -63,7 +70,9 @@ int launch_cand_topk(const CandQuery* plan, const int32_t* rows, const float* sc
 int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status,
                 hipStream_t st) {
-  const bool mlp = a.kind == NANN_SCORER_MLP;
+  if (a.kind != NANN_SCORER_L2 && a.kind != NANN_SCORER_MLP && a.kind != NANN_SCORER_IP)
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates: unknown scorer kind");
+  const bool mlp = a.kind == NANN_SCORER_MLP, ip = a.kind == NANN_SCORER_IP;
   const int rows_per_item = mlp ? kCandMlpRows : kCandRows;
   CandScoreArgs s = {};
   s.emb = a.emb;
@@ -88,10 +97,10 @@ int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long lon
   } else if (a.n_cand > 0) {
     const unsigned grid = cand_grid(n_queries, a.n_cand, rows_per_item, std::max(1, a.cus) * 8);
     switch (a.d / 8) {
-      case 8: launch_cand_l2<8>(a, s, grid, st); break;
-      case 16: launch_cand_l2<16>(a, s, grid, st); break;
-      case 32: launch_cand_l2<32>(a, s, grid, st); break;
-      case 64: launch_cand_l2<64>(a, s, grid, st); break;
+      case 8: ip ? launch_cand_ip<8>(a, s, grid, st) : launch_cand_l2<8>(a, s, grid, st); break;
+      case 16: ip ? launch_cand_ip<16>(a, s, grid, st) : launch_cand_l2<16>(a, s, grid, st); break;
+      case 32: ip ? launch_cand_ip<32>(a, s, grid, st) : launch_cand_l2<32>(a, s, grid, st); break;
+      case 64: ip ? launch_cand_ip<64>(a, s, grid, st) : launch_cand_l2<64>(a, s, grid, st); break;
       default: return fail(NANN_ERR_UNSUPPORTED, "nann_search_candidates: d must be 64, 128, 256 or 512");
     }
     NANN_HIP_TRY(hipGetLastError());

@@ -1029,14 +1029,12 @@ __device__ __forceinline__ void chunk_to_float(const RowChunk<DT>& r, float x[8]
   }
 }
 
+// what a row's score is made of: MT_L2  -sum (q_k - x_k)^2, MT_IP  sum q_k x_k.  Both sum their d terms in the SAME tree (eight
+// terms per lane in order, then the xor butterfly over the row's lanes), so everything but the term and the final sign is shared.
+enum : int { MT_L2 = 0, MT_IP = 1 };
+
 template <int LPR>
-__device__ __forceinline__ float l2_finish(const float q[8], const float x[8]) {
-  float acc = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const float t = q[k] - x[k];
-    acc = __fmaf_rn(t, t, acc);
-  }
+__device__ __forceinline__ float row_butterfly(float acc) {
   // xor butterfly over the LPR lanes of the row.  Strides 1 and 2 are quad permutes; for
   // strides 4 and 8 the mirror patterns pair every lane with a lane of the partner group,
   // all of whose lanes already hold the same partial sum -- the same tree as p[l] + p[l^s].
@@ -1046,7 +1044,27 @@ __device__ __forceinline__ float l2_finish(const float q[8], const float x[8]) {
   if constexpr (LPR >= 16) acc = acc + dpp_f32<0x140>(acc);  // row_mirror           (l ^ 8)
   if constexpr (LPR >= 32) acc = acc + __shfl_xor(acc, 16);
   if constexpr (LPR >= 64) acc = acc + __shfl_xor(acc, 32);
-  return 0.0f - acc;
+  return acc;
+}
+
+template <int LPR>
+__device__ __forceinline__ float l2_finish(const float q[8], const float x[8]) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float t = q[k] - x[k];
+    acc = __fmaf_rn(t, t, acc);
+  }
+  return 0.0f - row_butterfly<LPR>(acc);
+}
+
+// The inner product in the same tree: the term is one fma, and the sum is the score (no negation).
+template <int LPR>
+__device__ __forceinline__ float ip_finish(const float q[8], const float x[8]) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) acc = __fmaf_rn(q[k], x[k], acc);
+  return row_butterfly<LPR>(acc);
 }
 
 // The same score from the 16 bytes of an f16 row as they were loaded: t_k = q_k - x_k is ONE v_fma_mix_f32 (x_k * -1 + q_k with
@@ -1076,6 +1094,29 @@ __device__ __forceinline__ float l2_lane_bf16(const float q[8], const uint4& a) 
     const float t1 = q[2 * i + 1] - __uint_as_float(w[i] & 0xffff0000u);
     acc = __fmaf_rn(t0, t0, acc);
     acc = __fmaf_rn(t1, t1, acc);
+  }
+  return acc;
+}
+// This lane's 8 terms of <q, x> from the 16 bytes of an f16 row: acc = x_k * q_k + acc is ONE v_fma_mix_f32 per element (the f16
+// operand widened inside the instruction, the product exact, one rounding: the bits of cvt + fmaf) -- 8 vector instructions per
+// chunk where l2_lane_f16 has 16.
+__device__ __forceinline__ float ip_lane_f16(const float q[8], const uint4& a) {
+  const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+  float acc = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[1,0,0]" : "+v"(acc) : "v"(w[i]), "v"(q[2 * i]));
+    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(acc) : "v"(w[i]), "v"(q[2 * i + 1]));
+  }
+  return acc;
+}
+__device__ __forceinline__ float ip_lane_bf16(const float q[8], const uint4& a) {
+  const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+  float acc = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    acc = __fmaf_rn(q[2 * i], __uint_as_float(w[i] << 16), acc);
+    acc = __fmaf_rn(q[2 * i + 1], __uint_as_float(w[i] & 0xffff0000u), acc);
   }
   return acc;
 }
@@ -1128,7 +1169,8 @@ constexpr int kScoreU = 8;
 // ids must be in range (the visited filter and index validation guarantee it on the fused path).
 // qv: f32[d] (LDS or global).  U row loads per lane are in flight at once (U * 16 KB per
 // workgroup), and the candidate ids of the next batch are fetched underneath them.
-template <int LPR, int DT, int NWAVES>
+// METRIC = MT_IP: scores[i] = <q, table[ids[i]]> instead -- the lane sums and the sign of the store change, nothing else.
+template <int LPR, int DT, int NWAVES, int METRIC = MT_L2>
 __device__ __forceinline__ void wg_score_l2_part(const void* __restrict__ table, int d, const int32_t* ids,
                                                  int begin, int end, const float* qv, float* scores,
                                                  int wave_rel, bool near = false) {
@@ -1181,13 +1223,16 @@ __device__ __forceinline__ void wg_score_l2_part(const void* __restrict__ table,
       ch[6] = row(dpp_i32<0x156>(idv));
       ch[7] = row(dpp_i32<0x157>(idv));
       idv = ids_of(begin + RPI * U);
-      auto lane_sum = [&](const uint4& c) -> float { return DT == DT_F16 ? l2_lane_f16(q, c) : l2_lane_bf16(q, c); };
+      auto lane_sum = [&](const uint4& c) -> float {
+        if constexpr (METRIC == MT_IP) return DT == DT_F16 ? ip_lane_f16(q, c) : ip_lane_bf16(q, c);
+        else return DT == DT_F16 ? l2_lane_f16(q, c) : l2_lane_bf16(q, c);
+      };
       auto finish = [&](float (&s)[U], int i0) {
         float mine = l2_rows8_reduce_scatter(s);
         if constexpr (LPR >= 32) mine = mine + __shfl_xor(mine, 16);
         if constexpr (LPR >= 64) mine = mine + __shfl_xor(mine, 32);
         const int i = i0 + out_at;
-        if (sub < U && i < end) scores[i] = 0.0f - mine;
+        if (sub < U && i < end) scores[i] = METRIC == MT_IP ? mine : 0.0f - mine;
       };
       int i0 = begin;
       for (; i0 + RPI * U < end; i0 += RPI * U) {
@@ -1229,17 +1274,18 @@ __device__ __forceinline__ void wg_score_l2_part(const void* __restrict__ table,
       const int i = i0 + u * RPI + slot;
       float x[8];
       chunk_to_float<DT>(ch[u], x);
-      const float s = l2_finish<LPR>(q, x);
+      float s;
+      if constexpr (METRIC == MT_IP) s = ip_finish<LPR>(q, x); else s = l2_finish<LPR>(q, x);
       if (sub == 0 && i < end) scores[i] = s;
     }
   }
 }
 
 // whole workgroup, i < n
-template <int LPR, int DT, int NTHREADS>
+template <int LPR, int DT, int NTHREADS, int METRIC = MT_L2>
 __device__ __forceinline__ void wg_score_l2(const void* __restrict__ table, int d, const int32_t* ids,
                                             int n, const float* qv, float* scores) {
-  wg_score_l2_part<LPR, DT, NTHREADS / 64>(table, d, ids, 0, n, qv, scores, local_tid() >> 6);
+  wg_score_l2_part<LPR, DT, NTHREADS / 64, METRIC>(table, d, ids, 0, n, qv, scores, local_tid() >> 6);
 }
 
 // ---------------------------------------------------------------------------

@@ -37,10 +37,10 @@ struct FlatBy {
   int exact = 0;                         // MLP / attention: the f32 form (also the MLP's certified precision), else split-f16
   MlpParams mlp = {};                    // MLP
   AttnParams attn = {};                  // attention
-  const nann_scorer* scorer = nullptr;   // l2 / mlp: the scorer, a model's own included
+  const nann_scorer* scorer = nullptr;   // l2 / ip / mlp: the scorer, a model's own included
   const nann_attn_scorer* at = nullptr;  // attention
   ProjCache* cache = nullptr;            // MLP / attention: the cache the pair's pre-projected table belongs to
-  const nann_model* mean_of = nullptr;   // an l2 / mlp model: the query is the mean of its sequence, staged at the head of the workspace
+  const nann_model* mean_of = nullptr;   // an l2 / ip / mlp model: the query is the mean of its sequence, staged at the head of the workspace
   const char* what = "scorer";           // the handle's word in a message,
   const char* unit = "queries";          // and what it scores for
   bool mismatch = false;                 // handle and index disagree on d / dtype: flat_check reports it at its place in the order
@@ -77,6 +77,8 @@ static int flat_by(const nann_index* ix, const nann_scorer* scorer, const nann_m
       by->mlp = scorer->mlp;
       by->exact = scorer->desc.precision == NANN_MLP_EXACT_F32 || scorer->desc.precision == NANN_MLP_CERTIFIED;
       by->cache = &scorer->proj;
+    } else if (by->kind != NANN_SCORER_L2 && by->kind != NANN_SCORER_IP) {  // (L2 and the inner product read the index's rows: no table)
+      return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": unknown scorer kind");
     }
   }
   by->mismatch = d != ix->desc.d || dt != ix->desc.emb_dtype;

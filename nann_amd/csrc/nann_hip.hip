@@ -669,6 +669,43 @@ __global__ __launch_bounds__(256) void k_score_l2(const void* table, long long n
   }
 }
 
+// The inner product <q, row> (NANN_SCORER_IP): k_score_l2 with ip_finish.  (A kernel of its own and not a shared body: routed
+// through a common device function, k_score_l2<64, *> came out of the register allocator two VGPRs wider than before.)
+template <int LPR, int DT>
+__global__ __launch_bounds__(256) void k_score_ip(const void* table, long long n_table_rows, int d,
+                                                  const int32_t* indices, long long n,
+                                                  const float* qv, float* scores, OpResult* res) {
+  constexpr int GPW = 64 / LPR;
+  const int lane = lane_id();
+  const int sub = lane % LPR, grp = lane / LPR;
+  float q[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) q[k] = qv[sub * 8 + k];
+  const long long wave_global = (long long)blockIdx.x * (blockDim.x >> 6) + wave_id();
+  const long long n_waves = (long long)gridDim.x * (blockDim.x >> 6);
+  for (long long i0 = wave_global * GPW; i0 < n; i0 += n_waves * GPW) {
+    const long long i = i0 + grp;
+    long long row = -1;
+    if (i < n) {
+      row = indices ? (long long)indices[i] : i;
+      if (row < 0 || row >= n_table_rows) {
+        if (sub == 0) atomicMin(reinterpret_cast<unsigned long long*>(&res->bad_i), (unsigned long long)i);
+        row = -1;
+      }
+    }
+    float x[8];
+    if (row >= 0) {
+      const RowChunk<DT> ch = load_chunk<DT>(table, (size_t)row, d, sub);
+      chunk_to_float<DT>(ch, x);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) x[k] = 0.0f;
+    }
+    const float s = ip_finish<LPR>(q, x);
+    if (sub == 0 && i < n) scores[i] = s;
+  }
+}
+
 // ===========================================================================
 // C ABI
 // ===========================================================================
@@ -1276,7 +1313,7 @@ int nann_scorer_create(const nann_scorer_desc* desc, nann_scorer** out) {
     return fail(NANN_ERR_UNSUPPORTED, "embedding dim must be 64, 128, 256 or 512");
   if (desc->emb_dtype != NANN_F16 && desc->emb_dtype != NANN_BF16 && desc->emb_dtype != NANN_F32)
     return fail(NANN_ERR_UNSUPPORTED, "embedding dtype must be f16, bf16 or f32");
-  if (desc->kind != NANN_SCORER_L2 && desc->kind != NANN_SCORER_MLP)
+  if (desc->kind != NANN_SCORER_L2 && desc->kind != NANN_SCORER_MLP && desc->kind != NANN_SCORER_IP)
     return fail(NANN_ERR_BAD_ARGUMENT, "unknown scorer kind");
   nann_scorer* s = new nann_scorer();
   s->desc = *desc;
@@ -1406,6 +1443,17 @@ int nann_user_seq_mean(const void* comm_seq_f16, int64_t n_queries, int32_t seq_
 }  // extern "C"
 
 template <int LPR>
+static void launch_score_ip(int dt, unsigned blocks, hipStream_t st, const void* table, long long nt, int d,
+                            const int32_t* idx, long long n, const float* q, float* out, OpResult* res) {
+  if (dt == NANN_F16)
+    hipLaunchKernelGGL((k_score_ip<LPR, DT_F16>), dim3(blocks), dim3(256), 0, st, table, nt, d, idx, n, q, out, res);
+  else if (dt == NANN_BF16)
+    hipLaunchKernelGGL((k_score_ip<LPR, DT_BF16>), dim3(blocks), dim3(256), 0, st, table, nt, d, idx, n, q, out, res);
+  else
+    hipLaunchKernelGGL((k_score_ip<LPR, DT_F32>), dim3(blocks), dim3(256), 0, st, table, nt, d, idx, n, q, out, res);
+}
+
+template <int LPR>
 static void launch_score(int dt, unsigned blocks, hipStream_t st, const void* table, long long nt, int d,
                          const int32_t* idx, long long n, const float* q, float* out, OpResult* res) {
   if (dt == NANN_F16)
@@ -1451,11 +1499,22 @@ int nann_score(const nann_scorer* scorer, const float* q, const void* table, int
   }
   const long long rows_per_block = 4 * (64 / lpr);
   const unsigned blocks = (unsigned)std::min<long long>((n + rows_per_block - 1) / rows_per_block, 8192);
-  switch (lpr) {
-    case 8: launch_score<8>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
-    case 16: launch_score<16>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
-    case 32: launch_score<32>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
-    default: launch_score<64>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
+  if (scorer->desc.kind == NANN_SCORER_IP) {
+    switch (lpr) {
+      case 8: launch_score_ip<8>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
+      case 16: launch_score_ip<16>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
+      case 32: launch_score_ip<32>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
+      default: launch_score_ip<64>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
+    }
+  } else if (scorer->desc.kind == NANN_SCORER_L2) {
+    switch (lpr) {
+      case 8: launch_score<8>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
+      case 16: launch_score<16>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
+      case 32: launch_score<32>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
+      default: launch_score<64>(dt, blocks, st, table, n_table_rows, d, indices, n, q, out_scores, rb->dev); break;
+    }
+  } else {
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_score: unknown scorer kind");
   }
   HIP_TRY(hipGetLastError());
   rc = fetch_result(rb, st);
@@ -1760,11 +1819,11 @@ int nann_model_load(const char* dir, int32_t d, int32_t emb_dtype, int32_t seq_l
   kf >> kind;
   std::vector<std::vector<char>> keep;
   int rc = NANN_OK;
-  if (kind == "l2" || kind == "mlp") {
+  if (kind == "l2" || kind == "mlp" || kind == "ip") {
     nann_scorer_desc sd = {};
-    sd.kind = kind == "l2" ? NANN_SCORER_L2 : NANN_SCORER_MLP;
+    sd.kind = kind == "l2" ? NANN_SCORER_L2 : kind == "ip" ? NANN_SCORER_IP : NANN_SCORER_MLP;
     sd.d = d; sd.emb_dtype = emb_dtype;
-    m->kind = kind == "l2" ? NANN_MODEL_L2 : NANN_MODEL_MLP;
+    m->kind = kind == "l2" ? NANN_MODEL_L2 : kind == "ip" ? NANN_MODEL_IP : NANN_MODEL_MLP;
     if (kind == "mlp") {
       sd.h1 = 256; sd.h2 = 128;
       const struct { const char* n; const float** p; int64_t cnt; } w[] = {
@@ -1795,7 +1854,7 @@ int nann_model_load(const char* dir, int32_t d, int32_t emb_dtype, int32_t seq_l
     if (!rc) rc = read_precision(D, &ad.precision);
     if (!rc) rc = nann_attn_scorer_create(&ad, &m->attn);
   } else {
-    rc = fail(NANN_ERR_UNSUPPORTED, "scorer.txt: expected l2, mlp or attention, got '" + kind + "'");
+    rc = fail(NANN_ERR_UNSUPPORTED, "scorer.txt: expected l2, ip, mlp or attention, got '" + kind + "'");
   }
   if (rc) { nann_model_destroy(m); return rc; }
   *out = m;
@@ -1967,7 +2026,8 @@ constexpr int64_t kPhaseTail = 8192;  // behind the slots: reserved (round 4's f
 
 static int bit_length(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
 
-constexpr int kKindAttn = 2;      // plan_search: the attention model (NANN_MODEL_ATTENTION); 0 / 1 = nann_scorer_kind
+constexpr int kKindAttn = 2;      // plan_search: the attention model (NANN_MODEL_ATTENTION); 0 / 1 = NANN_SCORER_L2 / NANN_SCORER_MLP.  These are
+                                  //   PLAN kinds, not nann_scorer_kind: the inner product (NANN_SCORER_IP, also 2) plans as L2 (search_impl)
 constexpr int kKindMlpSplit = 3;  //   the MLP scorer in split-f16 form (two slice buffers: the scratch of an attention plan)
 constexpr int kKindMlpRes = 4;    //   the MLP scorer, either precision, on the pre-projected table with layer 2 resident in LDS
                                   //   (nann_mlp5.h): 16K-slot set under the weights, or the HBM bitmap
@@ -2228,6 +2288,7 @@ static int attn_projection(const nann_attn_scorer* sc, const nann_index* ix, hip
 
 // L2 instantiations live in nann_l2_inst.hip (one object per row dtype), MLP ones in
 // nann_mlp_inst.hip (one per embedding dim): the heavy kernels compile in parallel.
+// kind: nann_scorer_kind
 static int launch_search_any(int lpr, int dt, int kind, int split, int vis, int nt, int slots, size_t lds_bytes,
                              const SearchArgs& a, hipStream_t st) {
   if (kind == NANN_SCORER_MLP) {
@@ -2236,6 +2297,12 @@ static int launch_search_any(int lpr, int dt, int kind, int split, int vis, int 
     if (lpr == 32) return launch_search_mlp_d256(dt, split, vis, slots, lds_bytes, a, st);
     return fail(NANN_ERR_UNSUPPORTED, "MLP scorer: d <= 256 only");
   }
+  if (kind == NANN_SCORER_IP) {
+    if (dt == NANN_F16) return launch_search_ip_f16(lpr, vis, nt, slots, lds_bytes, a, st);
+    if (dt == NANN_BF16) return launch_search_ip_bf16(lpr, vis, nt, slots, lds_bytes, a, st);
+    return launch_search_ip_f32(lpr, vis, nt, slots, lds_bytes, a, st);
+  }
+  if (kind != NANN_SCORER_L2) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search: unknown scorer kind");
   if (dt == NANN_F16) return launch_search_l2_f16(lpr, vis, nt, slots, lds_bytes, a, st);
   if (dt == NANN_BF16) return launch_search_l2_bf16(lpr, vis, nt, slots, lds_bytes, a, st);
   return launch_search_l2_f32(lpr, vis, nt, slots, lds_bytes, a, st);
@@ -2266,7 +2333,11 @@ static int search_impl(const nann_index* ix, const nann_scorer* scorer, const na
   int rc = check_options(options);
   if (rc) return rc;
   SearchOpt opt = resolve_options(options);
-  const int kind = attn ? kKindAttn : scorer->desc.kind;
+  // the inner product takes every plan L2 takes (the same traversal with another term in its scoring call): it plans as L2, and
+  // only the launch and the batch order (pivot distances: an L2 notion) tell the two apart
+  const bool ip = !attn && scorer->desc.kind == NANN_SCORER_IP;
+  const int kind = attn ? kKindAttn : ip ? NANN_SCORER_L2 : scorer->desc.kind;
+  if (!attn && kind != NANN_SCORER_L2 && kind != NANN_SCORER_MLP) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search: unknown scorer kind");
   const bool mlp = !attn && kind == NANN_SCORER_MLP;
   const bool mlp_split = mlp && scorer->desc.precision == NANN_MLP_SPLIT_F16;
   // certified: the filter lives in the pipeline of phases only -- a forced fused form is the phased one; every other plan
@@ -2340,7 +2411,7 @@ static int search_impl(const nann_index* ix, const nann_scorer* scorer, const na
   // call at zero: the order's last kernel clears it on its way, every other plan with a memset.
   const unsigned long long slots_end = 256 + p.slot_bytes * (unsigned long long)std::max(p.slots, p.fb_slots) + kPhaseTail;
   const unsigned long long order_off = ((unsigned long long)workspace_bytes - order_ws_bytes(n_queries)) & ~255ull;
-  if (opt.order && hashed && !attn && kind == NANN_SCORER_L2 && ix->n_pivots >= 2 && n_queries > p.slots &&
+  if (opt.order && hashed && !attn && !ip && kind == NANN_SCORER_L2 && ix->n_pivots >= 2 && n_queries > p.slots &&
       (unsigned long long)workspace_bytes >= ((slots_end + 255) & ~255ull) + order_ws_bytes(n_queries)) {
     unsigned char* ow = static_cast<unsigned char*>(workspace) + order_off;
     unsigned int* heads = reinterpret_cast<unsigned int*>(ow);
@@ -2430,7 +2501,7 @@ static int search_impl(const nann_index* ix, const nann_scorer* scorer, const na
       return launch_search_mlp_res(exact, vis, slots, lds, a, st);
     });
   return both([&](int vis, int nt, int slots, size_t lds) {
-    return launch_search_any(ix->desc.d / 8, dt, kind, mlp_split, vis, nt, slots, lds, a, st);
+    return launch_search_any(ix->desc.d / 8, dt, scorer->desc.kind, mlp_split, vis, nt, slots, lds, a, st);
   });
 }
 
@@ -2665,7 +2736,7 @@ static int table_width(const nann_scorer* s, const nann_attn_scorer* at) {
   return (s && s->desc.kind == NANN_SCORER_MLP) ? kMlpProjWidth : 0;
 }
 static int prepare_impl(const nann_scorer* s, const nann_attn_scorer* at, const nann_index* ix, hipStream_t st) {
-  if (table_width(s, at) == 0) return NANN_OK;  // L2: nothing to pre-project
+  if (table_width(s, at) == 0) return NANN_OK;  // L2, inner product: nothing to pre-project
   const int d = at ? at->P.d : s->desc.d, dt = at ? at->emb_dtype : s->desc.emb_dtype;
   if (d != ix->desc.d || dt != ix->desc.emb_dtype) return fail(NANN_ERR_BAD_ARGUMENT, "scorer and index disagree on d / dtype");
   std::shared_ptr<ProjTable> tab;
@@ -2926,13 +2997,18 @@ static int eval_impl(const nann_index* ix, const nann_scorer* scorer, const nann
                      int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* n_out, int32_t* status,
                      hipStream_t st, int32_t* counters = nullptr) {
   if (n_queries > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, "too many queries in one call");
+  // the evaluation traversal has an L2, an MLP and an attention form; anything else is refused before a launch or a write
+  if (!attn && scorer->desc.kind == NANN_SCORER_IP)
+    return fail(NANN_ERR_UNSUPPORTED, "nann_search_eval: the inner-product scorer (NANN_SCORER_IP) is not supported by the evaluation traversal");
+  if (!attn && scorer->desc.kind != NANN_SCORER_L2 && scorer->desc.kind != NANN_SCORER_MLP)
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_eval: unknown scorer kind");
   if (num_scoring[2] != 1) return fail(NANN_ERR_BAD_ARGUMENT, "num_scoring_per_level[2] must be 1 (model.py:347)");
   for (int l = 0; l < 3; ++l)
     if (top_k[l] < 1 || top_k[l] > kEvalMaxK || num_scoring[l] < 0)
       return fail(NANN_ERR_UNSUPPORTED, "top_k_per_level entries must be in [1, 2048]");
   if (topk_eval < 1 || topk_eval > kEvalMaxK) return fail(NANN_ERR_UNSUPPORTED, "topk_eval must be in [1, 2048]");
   EvalArgs a;
-  const bool l2 = !attn && scorer->desc.kind != NANN_SCORER_MLP;
+  const bool l2 = !attn && scorer->desc.kind == NANN_SCORER_L2;
   EvalPlan pl, sizing;
   int rc = eval_plan(ix, n_queries, l2, &pl);
   if (!rc) rc = eval_plan(ix, n_queries, false, &sizing);  // (the workspace the caller sized: nann_search_eval_workspace_bytes)
@@ -2972,7 +3048,7 @@ static int eval_impl(const nann_index* ix, const nann_scorer* scorer, const nann
   // measurement builds of nann_eval.h (-DNANN_EVAL_TICKS=1, tools/build_res_variant.py): per-phase ticks of the launch on stderr
   static const bool want_ticks = [] { const char* e = std::getenv("NANN_EVAL_TICKS"); return e && e[0] == '1'; }();
   a.ticks = nullptr;
-  if (want_ticks && !attn && scorer->desc.kind != NANN_SCORER_MLP) {
+  if (want_ticks && l2) {
     static unsigned long long* g_ticks = nullptr;
     if (!g_ticks) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g_ticks), 16 * 8));
     HIP_TRY(hipMemsetAsync(g_ticks, 0, 16 * 8, st));
@@ -3047,6 +3123,8 @@ int nann_search_eval_model(const nann_index* ix, const nann_model* m, const void
   if (n_queries <= 0) return NANN_OK;
   if (m->d != ix->desc.d || m->emb_dtype != ix->desc.emb_dtype)
     return fail(NANN_ERR_BAD_ARGUMENT, "model and index disagree on d / dtype");
+  if (m->kind == NANN_MODEL_IP)  // (before the mean of the users' sequences is launched)
+    return fail(NANN_ERR_UNSUPPORTED, "nann_search_eval_model: an inner-product model (NANN_MODEL_IP) is not supported by the evaluation traversal");
   int64_t need = 0;
   int rc = nann_search_eval_workspace_bytes(ix, m, n_queries, &need);
   if (rc) return rc;

@@ -3,7 +3,7 @@
 // fetched once for a TILE of queries.
 //
 // Three steps per chunk of queries (the chunk bounds the workspace: no buffer of n_queries x n_items elements exists):
-//   1. scores f32[chunk, n_items]: k_scan_l2 (vector arithmetic, below), k_scan_mlp (the block functions of nann_mlp5.h on
+//   1. scores f32[chunk, n_items]: k_scan_l2 or k_scan_ip (vector arithmetic, below), k_scan_mlp (the block functions of nann_mlp5.h on
 //      the pre-projected table, identity row list) or, for the attention model (nann_search_all_model), k_scan_attn (the
 //      resident block scorers of nann_attn_proj.h / nann_attn_kernels.h on the model's table; nann_scan_attn_inst.hip);
 //   2. k_scan_slab_topk: the row range is cut into balanced slabs of 8192..16384 rows (wg_topk keeps that many keys in
@@ -44,7 +44,7 @@ inline size_t scan_filter_stage_bytes(int chunk, int k) { return ((size_t)chunk 
 
 // ---- launchers (nann_scan_inst.hip) -----------------------------------------------------------------------------------
 struct ScanArgs {
-  const void* emb;          // L2: the index's rows
+  const void* emb;          // L2, inner product: the index's rows
   const float* proj;        // MLP: the pre-projected table of (scorer, index)
   const int64_t* item_ids;
   long long n_items;
@@ -111,7 +111,8 @@ __global__ __launch_bounds__(256) void k_scan_transpose_q(const float* __restric
   }
 }
 
-template <int LPR, int DT, int TQ>
+// METRIC = MT_IP (k_scan_ip): the chunk accumulates acc = fma(q_k, x_k, acc) instead, in the same order and the same tree.
+template <int LPR, int DT, int TQ, int METRIC = MT_L2>
 struct ScanL2 {
   static constexpr int NP = TQ / 2;                         // packed pairs of queries
   static constexpr int PJ = DT == DT_F32 ? 4 : 8;           // chunks of 8 elements per 128-byte panel
@@ -175,16 +176,16 @@ struct ScanL2 {
 #pragma unroll 1
     for (int k = 0; k < 8; ++k) {
       const f32x2 xk = f32x2{x, x};
-      f32x2 t[NP];
+      f32x2 t[NP];  // L2: the differences.  Inner product: the queries themselves, moved aside (scalar registers) while the next ones load
 #pragma unroll
-      for (int p = 0; p < NP; ++p) t[p] = qn[p] - xk;
+      for (int p = 0; p < NP; ++p) t[p] = METRIC == MT_IP ? qn[p] : qn[p] - xk;
       __builtin_amdgcn_sched_barrier(0);
       const int e = J * 8 + k + 1;
       load_q(e < D ? e : 0, qn);
       x = load_x(at, k + 1);  // (k = 7: the next chunk's first element or the row's padding; not used)
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int p = 0; p < NP; ++p) out[p] = __builtin_elementwise_fma(t[p], t[p], out[p]);
+      for (int p = 0; p < NP; ++p) out[p] = __builtin_elementwise_fma(t[p], METRIC == MT_IP ? xk : t[p], out[p]);
     }
   }
 
@@ -210,12 +211,10 @@ struct ScanL2 {
 
 // grid: (tiles of TQ queries) x (blocks of 256 rows), the tile index fastest -- the workgroups that run together share rows.
 // scores f32[n_q, n_items].
-template <int LPR, int DT, int TQ>
-__global__ __launch_bounds__(kScanRows) __attribute__((amdgpu_waves_per_eu(scan_waves(LPR), scan_waves(LPR)))) void k_scan_l2(const void* __restrict__ table, long long n_items,
-                                                       const float* __restrict__ qT, int n_q, int n_tiles,
-                                                       float* __restrict__ scores) {
-  __shared__ __attribute__((aligned(16))) unsigned char rows[kScanRows * kScanRowStride];
-  typedef ScanL2<LPR, DT, TQ> S;
+template <int LPR, int DT, int TQ, int METRIC>
+__device__ __forceinline__ void scan_rows(unsigned char* rows, const void* __restrict__ table, long long n_items,
+                                          const float* __restrict__ qT, int n_q, int n_tiles, float* __restrict__ scores) {
+  typedef ScanL2<LPR, DT, TQ, METRIC> S;
   const int tile = (int)(blockIdx.x % (unsigned)n_tiles);
   S s;
   s.table = static_cast<const unsigned char*>(table);
@@ -231,9 +230,26 @@ __global__ __launch_bounds__(kScanRows) __attribute__((amdgpu_waves_per_eu(scan_
 #pragma unroll
   for (int p = 0; p < S::NP; ++p) {
     const int qi = tile * TQ + 2 * p;
-    if (qi < n_q) scores[(size_t)qi * n_items + row] = 0.0f - sum[p].x;
-    if (qi + 1 < n_q) scores[(size_t)(qi + 1) * n_items + row] = 0.0f - sum[p].y;
+    if (qi < n_q) scores[(size_t)qi * n_items + row] = METRIC == MT_IP ? sum[p].x : 0.0f - sum[p].x;
+    if (qi + 1 < n_q) scores[(size_t)(qi + 1) * n_items + row] = METRIC == MT_IP ? sum[p].y : 0.0f - sum[p].y;
   }
+}
+
+template <int LPR, int DT, int TQ>
+__global__ __launch_bounds__(kScanRows) __attribute__((amdgpu_waves_per_eu(scan_waves(LPR), scan_waves(LPR)))) void k_scan_l2(const void* __restrict__ table, long long n_items,
+                                                       const float* __restrict__ qT, int n_q, int n_tiles,
+                                                       float* __restrict__ scores) {
+  __shared__ __attribute__((aligned(16))) unsigned char rows[kScanRows * kScanRowStride];
+  scan_rows<LPR, DT, TQ, MT_L2>(rows, table, n_items, qT, n_q, n_tiles, scores);
+}
+
+// the inner-product scan: scores[q][row] = <q, row>, everything else as k_scan_l2
+template <int LPR, int DT, int TQ>
+__global__ __launch_bounds__(kScanRows) __attribute__((amdgpu_waves_per_eu(scan_waves(LPR), scan_waves(LPR)))) void k_scan_ip(const void* __restrict__ table, long long n_items,
+                                                       const float* __restrict__ qT, int n_q, int n_tiles,
+                                                       float* __restrict__ scores) {
+  __shared__ __attribute__((aligned(16))) unsigned char rows[kScanRows * kScanRowStride];
+  scan_rows<LPR, DT, TQ, MT_IP>(rows, table, n_items, qT, n_q, n_tiles, scores);
 }
 
 // u[q][j] = b1[j] + sum_k q[k] W1[k][j]: the query's part of layer 1, once per query (what stage 0 of the pipeline of phases

@@ -1,4 +1,4 @@
-// nann_scan_inst.hip -- the kernels of the exhaustive search (nann_scan.h): the L2 scan for every (d, row dtype), the MLP scan
+// nann_scan_inst.hip -- the kernels of the exhaustive search (nann_scan.h): the L2 and inner-product scans for every (d, row dtype), the MLP scan
 // in both precisions, the slab top-k and the merge; workspace layout and the launch sequence of a call.
 #define NANN_SCAN_IMPL
 #include "nann_scan.h"
@@ -17,11 +17,12 @@ ScanLayout scan_layout(long long n_items, int d, int kind, long long n_queries, 
   const int tq = kScanTileQueries;
   long long chunk = std::min<long long>(kScanMaxChunk, (long long)(kScanScoreBytes / ((size_t)n_items * 4)));
   chunk = std::max<long long>(1, std::min(chunk, n_queries));
-  if (kind == NANN_SCORER_L2 && chunk > tq) chunk -= chunk % tq;  // whole tiles of queries
+  const bool flat = kind == NANN_SCORER_L2 || kind == NANN_SCORER_IP;  // the vector scans: tiles of queries, a transposed copy
+  if (flat && chunk > tq) chunk -= chunk % tq;  // whole tiles of queries
   L.chunk = (int)chunk;
   L.n_slabs = scan_n_slabs(n_items);
   const size_t cand = (size_t)L.chunk * L.n_slabs * k * 4;
-  const size_t qbytes = kind == NANN_SCORER_L2 ? (size_t)((L.chunk + tq - 1) / tq) * tq * d * 4
+  const size_t qbytes = flat ? (size_t)((L.chunk + tq - 1) / tq) * tq * d * 4
                         : kind == kScanAttn ? (size_t)L.chunk * kScanAttnUserBytes : (size_t)L.chunk * 256 * 4;
   L.off_scores = 0;
   L.off_cand_scores = up256((size_t)L.chunk * (size_t)n_items * 4);
@@ -31,22 +32,36 @@ ScanLayout scan_layout(long long n_items, int d, int kind, long long n_queries, 
   return L;
 }
 
-template <int LPR, int DT>
+template <int LPR, int DT, int METRIC>
 static int launch_scan_l2_as(const ScanArgs& a, const float* qT, int n_q, float* scores, hipStream_t st) {
   constexpr int TQ = kScanTileQueries;
   const int tiles = (n_q + TQ - 1) / TQ;
   const long long blocks = (a.n_items + kScanRows - 1) / kScanRows * tiles;
   if (blocks > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, "nann_search_all: index too large for one launch");
-  hipLaunchKernelGGL((k_scan_l2<LPR, DT, TQ>), dim3((unsigned)blocks), dim3(kScanRows), 0, st, a.emb, a.n_items, qT, n_q, tiles, scores);
+  if constexpr (METRIC == MT_IP)
+    hipLaunchKernelGGL((k_scan_ip<LPR, DT, TQ>), dim3((unsigned)blocks), dim3(kScanRows), 0, st, a.emb, a.n_items, qT, n_q, tiles, scores);
+  else
+    hipLaunchKernelGGL((k_scan_l2<LPR, DT, TQ>), dim3((unsigned)blocks), dim3(kScanRows), 0, st, a.emb, a.n_items, qT, n_q, tiles, scores);
   NANN_HIP_TRY(hipGetLastError());
   return NANN_OK;
 }
 
-template <int LPR>
+template <int LPR, int METRIC>
 static int launch_scan_l2_dt(const ScanArgs& a, const float* qT, int n_q, float* scores, hipStream_t st) {
-  if (a.dt == NANN_F16) return launch_scan_l2_as<LPR, DT_F16>(a, qT, n_q, scores, st);
-  if (a.dt == NANN_BF16) return launch_scan_l2_as<LPR, DT_BF16>(a, qT, n_q, scores, st);
-  return launch_scan_l2_as<LPR, DT_F32>(a, qT, n_q, scores, st);
+  if (a.dt == NANN_F16) return launch_scan_l2_as<LPR, DT_F16, METRIC>(a, qT, n_q, scores, st);
+  if (a.dt == NANN_BF16) return launch_scan_l2_as<LPR, DT_BF16, METRIC>(a, qT, n_q, scores, st);
+  return launch_scan_l2_as<LPR, DT_F32, METRIC>(a, qT, n_q, scores, st);
+}
+
+template <int METRIC>
+static int launch_scan_flat(const ScanArgs& a, const float* qT, int n_q, float* scores, hipStream_t st) {
+  switch (a.d / 8) {
+    case 8: return launch_scan_l2_dt<8, METRIC>(a, qT, n_q, scores, st);
+    case 16: return launch_scan_l2_dt<16, METRIC>(a, qT, n_q, scores, st);
+    case 32: return launch_scan_l2_dt<32, METRIC>(a, qT, n_q, scores, st);
+    case 64: return launch_scan_l2_dt<64, METRIC>(a, qT, n_q, scores, st);
+    default: return fail(NANN_ERR_UNSUPPORTED, "nann_search_all: d must be 64, 128, 256 or 512");
+  }
 }
 
 template <bool EXACT>
@@ -66,7 +81,6 @@ int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long lon
   float* cand_scores = reinterpret_cast<float*>(ws + L.off_cand_scores);
   int32_t* cand_rows = reinterpret_cast<int32_t*>(ws + L.off_cand_rows);
   float* qbuf = reinterpret_cast<float*>(ws + L.off_q);
-  const int lpr = a.d / 8;
   for (long long c0 = 0; c0 < n_queries; c0 += L.chunk) {
     const int n_q = (int)std::min<long long>(L.chunk, n_queries - c0);
     const float* qc = q + (size_t)c0 * a.d;
@@ -78,22 +92,18 @@ int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long lon
       rc = a.exact ? launch_attn_prepare(st, a.attn, seq, n_q, kt, upad) : launch_attn_prepare_split(st, a.attn, seq, n_q, kt, upad);
       if (rc) return rc;
       rc = launch_scan_attn(a, kt, upad, n_q, scores, st);
-    } else if (a.kind == NANN_SCORER_L2) {
+    } else if (a.kind == NANN_SCORER_L2 || a.kind == NANN_SCORER_IP) {
       const int tq = kScanTileQueries;
       const long long total = (long long)((n_q + tq - 1) / tq) * tq * a.d;
       hipLaunchKernelGGL(k_scan_transpose_q, dim3((unsigned)std::min<long long>((total + 255) / 256, 1024)), dim3(256), 0, st, qc, n_q, a.d, tq, qbuf);
       NANN_HIP_TRY(hipGetLastError());
-      switch (lpr) {
-        case 8: rc = launch_scan_l2_dt<8>(a, qbuf, n_q, scores, st); break;
-        case 16: rc = launch_scan_l2_dt<16>(a, qbuf, n_q, scores, st); break;
-        case 32: rc = launch_scan_l2_dt<32>(a, qbuf, n_q, scores, st); break;
-        case 64: rc = launch_scan_l2_dt<64>(a, qbuf, n_q, scores, st); break;
-        default: return fail(NANN_ERR_UNSUPPORTED, "nann_search_all: d must be 64, 128, 256 or 512");
-      }
-    } else {
+      rc = a.kind == NANN_SCORER_IP ? launch_scan_flat<MT_IP>(a, qbuf, n_q, scores, st) : launch_scan_flat<MT_L2>(a, qbuf, n_q, scores, st);
+    } else if (a.kind == NANN_SCORER_MLP) {
       hipLaunchKernelGGL(k_scan_mlp_u, dim3((unsigned)n_q), dim3(256), 0, st, a.mlp, qc, qbuf);
       NANN_HIP_TRY(hipGetLastError());
       rc = a.exact ? launch_scan_mlp_as<true>(a, qbuf, n_q, scores, st) : launch_scan_mlp_as<false>(a, qbuf, n_q, scores, st);
+    } else {
+      return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all: unknown scorer kind");
     }
     if (rc) return rc;
     if (a.filter) {  // the denied rows of this chunk leave the selection: exclusion lists go by the call's query number c0 + i

@@ -193,6 +193,10 @@ constexpr int mlp_res_reload_bytes(bool hash) { return hash ? 65536 : 32768; }
 static_assert(kPhaseScratch <= 32768, "the bitmap kernels' phase scratch lies over the first two weight tiles");
 constexpr int kScorerAttnRes = 11;   // split-f16 attention model on its table with everything a scoring call reads resident in LDS (nann_attn_proj.h)
 constexpr int kScorerAttnXProj = 10;  // the f32-MFMA attention model on the same pre-projected table (nann_attn_kernels.h, PROJ)
+constexpr int kScorerIp = 12;        // the inner product <q, x> (NANN_SCORER_IP): the L2 traversal with the other term in its scoring call
+// the scorers that read table rows directly and take the L2 traversal's choices (LDS score mirror, binned top-k ranking, two
+// workgroups per CU on the 16K-slot set)
+constexpr bool is_flat(int sc) { return sc == NANN_SCORER_L2 || sc == kScorerIp; }
 constexpr bool is_attn(int sc) { return sc == kScorerAttn || sc == kScorerAttnSplit || sc == kScorerAttnProj || sc == kScorerAttnXProj || sc == kScorerAttnRes; }
 
 // where a query's visited set lives
@@ -254,7 +258,7 @@ __device__ __forceinline__ int search_one(const SearchArgs& a, int qi, const Slo
   }
   // bitmap kernels, L2: candidate scores are mirrored in LDS for the selection; the MLP uses that
   // space for its weight slices (and its selection time is negligible next to the MFMAs)
-  float* lds_scores = (SC == NANN_SCORER_L2 && !HASH) ? reinterpret_cast<float*>(scratch + kLdsScoresOff) : nullptr;
+  float* lds_scores = (is_flat(SC) && !HASH) ? reinterpret_cast<float*>(scratch + kLdsScoresOff) : nullptr;
   PhaseTimer timer;
   timer.start(ticks, a.phase_ticks != nullptr);
   const SubTimer pt{ticks, a.phase_ticks != nullptr};
@@ -282,7 +286,7 @@ __device__ __forceinline__ int search_one(const SearchArgs& a, int qi, const Slo
 
   // top-k ranks its selected pairs bin by bin (nann_device.h, round 6) in the L2 traversals: ~11 of a lone query's 144 us were the
   // all-pairs ranking (the register-starved MLP / attention kernels keep it: their selection is a percent of their time)
-  constexpr bool kTopkBins = SC == NANN_SCORER_L2;
+  constexpr bool kTopkBins = is_flat(SC);
   // The schedule of build_opt_graph.py:109-149 as six stages with ONE call site per
   // building block: stage 0 = entry layer (:111-112), 1 = level 1 (:114-127),
   // 2..4 = the three level-0 rounds (:129-141), 5 = final top-k (:143-149).
@@ -432,12 +436,13 @@ __device__ __forceinline__ int search_one(const SearchArgs& a, int qi, const Slo
         return kPhasePending;
       }
       if constexpr (!PHASED) {
-      if constexpr (SC == NANN_SCORER_L2) {
-        wg_score_l2_part<LPR, DT, NT / 64>(a.emb, a.d, sc_ids, 0, sc_n, qv, sc_out, tid >> 6, (unsigned long long)a.n_items * (unsigned)(a.d * 2) <= 0xffffffffull && a.n_items <= (1u << 24));
+      if constexpr (is_flat(SC)) {
+        constexpr int METRIC = SC == kScorerIp ? MT_IP : MT_L2;
+        wg_score_l2_part<LPR, DT, NT / 64, METRIC>(a.emb, a.d, sc_ids, 0, sc_n, qv, sc_out, tid >> 6, (unsigned long long)a.n_items * (unsigned)(a.d * 2) <= 0xffffffffull && a.n_items <= (1u << 24));
 #if NANN_REPEAT_SCORE  // measurement builds (tools/build_res_variant.py --unit nann_l2_inst.hip): a phase run twice costs what it costs once
         for (int rep = 0; rep < NANN_REPEAT_SCORE; ++rep) {
           __syncthreads();
-          wg_score_l2_part<LPR, DT, NT / 64>(a.emb, a.d, sc_ids, 0, sc_n, qv, sc_out, tid >> 6, (unsigned long long)a.n_items * (unsigned)(a.d * 2) <= 0xffffffffull && a.n_items <= (1u << 24));
+          wg_score_l2_part<LPR, DT, NT / 64, METRIC>(a.emb, a.d, sc_ids, 0, sc_n, qv, sc_out, tid >> 6, (unsigned long long)a.n_items * (unsigned)(a.d * 2) <= 0xffffffffull && a.n_items <= (1u << 24));
         }
 #endif
         if (lds_scores != nullptr) {
@@ -604,7 +609,7 @@ static_assert(offsetof(WsHeader, refined) == 136 && offsetof(WsHeader, pqueue) =
 // hash-set kernel lives off TWO 512-thread workgroups per CU (16 waves = 4 per SIMD -> at most 128
 // VGPRs; at 130 the second workgroup silently stops fitting and the kernel runs at half occupancy).
 template <int LPR, int DT, int VIS, int SC, int NT>
-__global__ __launch_bounds__(NT, ((VIS == VIS_LDS_HASH && (SC == NANN_SCORER_L2 || SC == kScorerMlpPhase)) ? 2 : 1) * NT / 256) void k_search(SearchArgs a) {
+__global__ __launch_bounds__(NT, ((VIS == VIS_LDS_HASH && (is_flat(SC) || SC == kScorerMlpPhase)) ? 2 : 1) * NT / 256) void k_search(SearchArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool HASH = VIS == VIS_LDS_HASH || VIS == VIS_LDS_HASH32;
   constexpr int kScratchBytes = phase_scratch<VIS, SC, NT>();
@@ -756,6 +761,10 @@ inline int launch_search_bitmap(int vis, int slots, size_t lds_bytes, const Sear
 int launch_search_l2_f16(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
 int launch_search_l2_bf16(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
 int launch_search_l2_f32(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
+// inner-product instantiations live in nann_ip_inst.hip (one per row dtype, spread over light objects): the same four plans
+int launch_search_ip_f16(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
+int launch_search_ip_bf16(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
+int launch_search_ip_f32(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
 // MLP instantiations live in nann_mlp_inst.hip (one object per embedding dim): bitmap kernels, 512 threads
 int launch_search_mlp_d64(int dt, int split, int vis, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
 int launch_search_mlp_d128(int dt, int split, int vis, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);

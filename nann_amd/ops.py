@@ -278,21 +278,25 @@ def _precision_code(precision):
         raise ValueError(f"precision must be 'split', 'exact' or 'certified', got {precision!r}") from None
 
 
+_SCORER_KIND = {"l2": _lib.SCORER_L2, "mlp": _lib.SCORER_MLP, "ip": _lib.SCORER_IP}
+
+
 class Scorer:
     """What the frozen scoring GraphDef is to BlazeXlaOp (blaze_xla_kernel.cc:24-33):
-    kind 'l2' (s = -||q - x||^2) or 'mlp' (weights dict as synth.make_mlp_weights)."""
+    kind 'l2' (s = -||q - x||^2), 'ip' (s = <q, x>, the inner product: no weights) or 'mlp' (weights dict as
+    synth.make_mlp_weights)."""
 
     def __init__(self, kind, d, emb_dtype=torch.float16, weights=None, precision="split"):
         """precision (mlp): "split" (the default: north_star's contract is 1e-5) = split-f16 operands on the
         16-bit MFMA, scores within 1e-5 of the fp32 chain; "exact" = f32-input MFMA, scores bit-identical to
         the oracle, ~3x slower; "certified" = results bit-identical to "exact", the rows an f16 filter with a
         rigorous error bound cannot rule out rescored exactly (nann_mlp_precision)."""
-        if kind not in ("l2", "mlp"):
-            raise ValueError(f"scorer kind must be 'l2' or 'mlp', got {kind!r}")
+        if kind not in _SCORER_KIND:
+            raise ValueError(f"scorer kind must be 'l2', 'ip' or 'mlp', got {kind!r}")
         self.kind, self.d, self.emb_dtype, self.precision = kind, d, emb_dtype, precision
         desc = _lib.ScorerDesc()
         desc.precision = _precision_code(precision)
-        desc.kind = _lib.SCORER_L2 if kind == "l2" else _lib.SCORER_MLP
+        desc.kind = _SCORER_KIND[kind]
         desc.d = d
         desc.emb_dtype = _DT[emb_dtype]
         self._keep = {}
@@ -378,7 +382,8 @@ class AttnScorer:
 def save_scorer_dir(path, kind, weights=None, precision=None):
     """Write a scoring model as the weights directory BlazeXlaOp's `graph_def` attr names on this
     build (include/nann_hip.h, nann_model_load): scorer.txt + one .npy per weight tensor.
-    kind: "l2" | "mlp" (dict as synth.make_mlp_weights) | "attention" (dict as synth.make_attn_weights)."""
+    kind: "l2" | "ip" (neither has weights) | "mlp" (dict as synth.make_mlp_weights) | "attention" (dict as
+    synth.make_attn_weights)."""
     import os
     os.makedirs(path, exist_ok=True)
     with open(os.path.join(path, "scorer.txt"), "w") as f:
@@ -402,14 +407,14 @@ def save_scorer_dir(path, kind, weights=None, precision=None):
 class Model:
     """The scoring model a BlazeXlaOp node names (nann_model_load): `path` is what the op's `graph_def` attr
     holds -- the reference's frozen GraphDef FILE (convert_meta.py:361-398; blaze_xla_kernel.cc:156-180), read
-    without TensorFlow, or a weights DIRECTORY (save_scorer_dir) for the l2 / mlp scorers."""
+    without TensorFlow, or a weights DIRECTORY (save_scorer_dir) for the l2 / ip / mlp scorers."""
 
     def __init__(self, path, d, seq_len=50, emb_dtype=torch.float16):
         self.d, self.seq_len = d, seq_len
         self.handle = C.c_void_p(0)
         _check(lib().nann_model_load(path.encode(), C.c_int32(d), C.c_int32(_DT[emb_dtype]), C.c_int32(seq_len),
                                      C.byref(self.handle)), "BlazeXlaOp model")
-        self.kind = ("l2", "mlp", "attention")[lib().nann_model_kind(self.handle)]
+        self.kind = ("l2", "mlp", "attention", "ip")[lib().nann_model_kind(self.handle)]
         nb = C.c_int64(0)
         _check(lib().nann_model_workspace_bytes(self.handle, C.byref(nb)))
         self._ws_bytes = nb.value

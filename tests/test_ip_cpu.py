@@ -1,0 +1,248 @@
+"""CPU: the inner-product scorer (NANN_SCORER_IP) -- what the ABI, the Python layer and the build say about it without a
+device, and the test-side reference (ip_reference.py) that the GPU tests hold the kernels to."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import ip_reference as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _create(kind, d=64, dt=0):
+    from nann_amd import _lib
+    desc = _lib.ScorerDesc()
+    desc.kind, desc.d, desc.emb_dtype = kind, d, dt
+    h = C.c_void_p(0)
+    L = _lib.lib()
+    st = L.nann_scorer_create(C.byref(desc), C.byref(h))
+    if h.value:
+        L.nann_scorer_destroy(h)
+    return st, bool(h.value)
+
+
+# ---- the contract without a device ------------------------------------------------------------------------------------------
+def test_scorer_create_accepts_kind_2():
+    assert _create(2) == (0, True)
+    for d in (64, 128, 256, 512):
+        for dt in (0, 1, 2):
+            assert _create(2, d, dt) == (0, True), (d, dt)
+
+
+def test_scorer_create_rejects_unknown_kinds_and_dims():
+    from nann_amd import _lib
+    assert _create(3) == (7, False)   # NANN_ERR_BAD_ARGUMENT
+    assert _create(-1) == (7, False)
+    assert b"unknown scorer kind" in _lib.lib().nann_last_error()
+    assert _create(2, d=96) == (102, False)  # NANN_ERR_UNSUPPORTED
+
+
+def test_header_and_python_constants():
+    from nann_amd import _lib
+    text = open(os.path.join(ROOT, "include", "nann_hip.h")).read()
+    assert re.search(r"enum nann_scorer_kind \{[^}]*\bNANN_SCORER_IP = 2\b", text)
+    assert re.search(r"enum nann_model_kind \{[^}]*\bNANN_MODEL_IP = 3\b", text)
+    assert re.search(r"#define NANN_ABI_VERSION 6\b", text)
+    assert _lib.SCORER_IP == 2
+
+
+def test_python_scorer_kinds():
+    from nann_amd import ops
+    with pytest.raises(ValueError, match="'l2', 'ip' or 'mlp'"):
+        ops.Scorer("cosine", 64)
+    sc = ops.Scorer("ip", 64)
+    assert sc.kind == "ip" and sc.handle.value
+
+
+def test_model_directory_ip(tmp_path):
+    from nann_amd import _lib, ops
+    path = str(tmp_path / "ip_model")
+    ops.save_scorer_dir(path, "ip")
+    assert open(os.path.join(path, "scorer.txt")).read().split() == ["ip"]
+    assert sorted(os.listdir(path)) == ["scorer.txt"]
+    L = _lib.lib()
+    h = C.c_void_p(0)
+    assert L.nann_model_load(path.encode(), C.c_int32(128), C.c_int32(0), C.c_int32(50), C.byref(h)) == 0
+    try:
+        assert L.nann_model_kind(h) == 3  # NANN_MODEL_IP
+        L.nann_model_scorer.restype = C.c_void_p
+        assert L.nann_model_scorer(h)
+    finally:
+        L.nann_model_destroy(h)
+    m = ops.Model(path, 128)
+    assert m.kind == "ip"
+
+
+# ---- the build's rules --------------------------------------------------------------------------------------------------------
+IP_HASH = "remark: x:1:0: Function Name: _ZN4nann8k_searchILi16ELi0ELi2ELi12ELi512EEEvNS_10SearchArgsE\n"
+L2_HASH = "remark: x:1:0: Function Name: _ZN4nann8k_searchILi16ELi0ELi2ELi0ELi512EEEvNS_10SearchArgsE\n"
+IP_BITMAP = "remark: x:1:0: Function Name: _ZN4nann8k_searchILi16ELi0ELi1ELi12ELi1024EEEvNS_10SearchArgsE\n"
+SCAN_IP = "remark: x:1:0: Function Name: _ZN4nann9k_scan_ipILi16ELi0ELi16EEEvPKvxPKfiiPf\n"
+
+
+def _occ(n):
+    return "remark: x:1:0:     Occupancy [waves/SIMD]: %d\n" % n
+
+
+def _scr(n):
+    return "remark: x:1:0:     ScratchSize [bytes/lane]: %d\n" % n
+
+
+def test_build_refuses_an_ip_hash_kernel_at_half_occupancy(tmp_path):
+    from nann_amd import build
+    bad, good = tmp_path / "bad.log", tmp_path / "good.log"
+    bad.write_text(L2_HASH + _occ(4) + IP_HASH + _occ(2))
+    good.write_text(IP_BITMAP + _occ(2) + IP_HASH + _occ(4) + L2_HASH + _occ(4))
+    with pytest.raises(RuntimeError, match="occupancy 2"):
+        build._check_ip_occupancy(str(bad))
+    with pytest.raises(RuntimeError, match="inner-product hash-set kernel"):
+        build.check_resources(str(bad))
+    build._check_ip_occupancy(str(good))
+    build.check_resources(str(good))
+    build._check_occupancy(str(bad))  # (the L2 rule does not take the IP kernel for its own)
+
+
+def test_build_refuses_an_ip_scan_kernel_with_scratch(tmp_path):
+    from nann_amd import build
+    bad, good = tmp_path / "bad.log", tmp_path / "good.log"
+    bad.write_text(IP_BITMAP + _scr(64) + SCAN_IP + _scr(144))
+    good.write_text(SCAN_IP + _scr(0) + IP_BITMAP + _scr(64))
+    with pytest.raises(RuntimeError, match="scratch"):
+        build._check_scan_ip_scratch(str(bad))
+    with pytest.raises(RuntimeError, match="scratch"):
+        build.check_resources(str(bad))
+    build._check_scan_ip_scratch(str(good))
+    build._check_scan_scratch(str(bad))  # (the L2 scan's rule does not reach k_scan_ip)
+
+
+def _report(unit):
+    from nann_amd import _lib, build
+    _lib.lib()
+    log = os.path.join(build.OUT_DIR, unit, "compile.log")
+    return open(log).read() if os.path.exists(log) else None  # (a library named by NANN_HIP_LIB has no report beside it)
+
+
+def test_built_library_has_the_ip_kernels_within_their_rules():
+    from nann_amd import build
+    scan = _report("nann_scan.d")
+    if scan is None:
+        return
+    sizes = re.findall(r"Function Name: (\S*k_scan_ip\S*)(?:.*\n)*?.*ScratchSize \[bytes/lane\]: (\d+)", scan)
+    assert len(sizes) == 12 and all(int(b) == 0 for _, b in sizes), sizes  # 4 d x 3 row dtypes
+    n_hash = 0
+    for obj, parts in build.UNITS:
+        if not any(src == "nann_ip_inst.hip" for src, _ in parts):
+            continue
+        assert not obj.startswith("nann_l2_"), "the IP instances must not ride in the objects that bound the build"
+        text = _report(obj[:-2] + ".d")
+        occ = re.findall(r"Function Name: (\S*k_searchILi\d+ELi\d+ELi2ELi12ELi512E\S*)(?:.*\n)*?.*Occupancy \[waves/SIMD\]: (\d+)", text)
+        assert len(occ) == 4 and all(int(w) >= 4 for _, w in occ), occ  # LPR 8 / 16 / 32 / 64
+        n_hash += len(occ)
+        build.check_resources(os.path.join(build.OUT_DIR, obj[:-2] + ".d", "compile.log"))
+    assert n_hash == 12
+
+
+# ---- the reference itself ---------------------------------------------------------------------------------------------------
+def _corpus(n, d, dtype, seed):
+    """rows whose norms vary by 16x, in the table's dtype (bf16: bit patterns) + their f32 widening"""
+    x = R.scaled_rows(np.random.default_rng(seed).standard_normal((n, d)).astype(np.float32), seed + 1)
+    if dtype == "f16":
+        t = x.astype(np.float16)
+    elif dtype == "bf16":
+        t = R.to_bf16_bits(x)
+    else:
+        t = x
+    return t, R.widen(t)
+
+
+def test_fma32_is_correctly_rounded():
+    rng = np.random.default_rng(3)
+    q = rng.standard_normal(64).astype(np.float32)
+    for dtype in ("f16", "bf16", "f32"):
+        _, rows = _corpus(24, 64, dtype, 5)
+        got = R.ip_scores(q, rows)
+        exp = np.array([R.ip_score_exact(q, r) for r in rows], np.float32)
+        assert (got.view(np.uint32) == exp.view(np.uint32)).all(), dtype
+    # a sum whose f64 rounding lands exactly between two f32 although the sum itself lies below the middle:
+    # (2^-12 (1 + 2^-23)) (2^-12 (1 - 2^-23)) + (1 + 2^-23) = 1 + 2^-23 + 2^-24 - 2^-70.  Rounded twice it ties to even, 1 + 2^-22.
+    a = np.float32(2.0 ** -12 * (1 + 2.0 ** -23))
+    b = np.float32(2.0 ** -12 * (1 - 2.0 ** -23))
+    c = np.float32(1 + 2.0 ** -23)
+    twice = np.float32(np.float64(a) * np.float64(b) + np.float64(c))
+    assert twice == np.float32(1 + 2.0 ** -22)
+    assert R.fma32(np.array([a]), np.array([b]), np.array([c]))[0] == c
+
+
+def test_l2_restatement_equals_the_oracle(oracle):
+    """the tree and the fma of ip_reference against the one implementation of them the project already has"""
+    rng = np.random.default_rng(7)
+    for d in (64, 128, 256, 512):
+        t, rows = _corpus(200, d, "f16", d)
+        q = rng.standard_normal(d).astype(np.float32)
+        rc, s = oracle.score_rows(oracle.Scorer("l2", d, oracle.EMB_F16), q, t)
+        assert rc == 0
+        assert (R.l2_scores(q, rows).view(np.uint32) == np.asarray(s, np.float32).view(np.uint32)).all(), d
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16", "f32"])
+@pytest.mark.parametrize("d", [64, 128, 256, 512])
+def test_restated_order_is_within_the_fma_bound(d, dtype):
+    """Any order of d fused terms is within gamma_d sum|q_k x_k|, gamma_d ~ d 2^-24 (Higham, Accuracy and Stability, 3.1); the
+    limit here is twice that: d 2^-23 sum|q_k x_k|."""
+    rng = np.random.default_rng(d)
+    _, rows = _corpus(300, d, dtype, d + 11)
+    norms = np.linalg.norm(rows.astype(np.float64), axis=1)
+    assert norms.max() / norms.min() >= 8.0
+    for _ in range(3):
+        q = (rng.standard_normal(d) * 3.0).astype(np.float32)
+        got = R.ip_scores(q, rows).astype(np.float64)
+        prod = q.astype(np.float64)[None, :] * rows.astype(np.float64)
+        exact, mag = prod.sum(1), np.abs(prod).sum(1)
+        assert (np.abs(got - exact) <= d * 2.0 ** -23 * mag).all()
+
+
+def test_ip_and_l2_rank_this_corpus_differently(golden_dir):
+    """The serving schedule scored with the restated IP against the same schedule scored with L2, on a committed graph whose
+    rows are scaled: the data is what catches a kernel that quietly runs L2 arithmetic."""
+    z = dict(np.load(os.path.join(golden_dir, "small_l2_d64.npz")))
+    rows = R.scaled_rows(R.widen(z["item_embs"]), 17).astype(np.float16).astype(np.float32)
+    g = {"nb_values": [z["nb_values_0"], z["nb_values_1"]], "nb_row_splits": [z["nb_row_splits_0"], z["nb_row_splits_1"]],
+         "enter_points": z["enter_points"], "item_ids": z["item_ids"]}
+    t = z["level_topn"].tolist()
+    differ = ran = 0
+    for q in z["q"]:
+        try:
+            a = R.py_search(g, q, t, lambda ids: R.ip_scores(q, rows[np.asarray(ids)]))
+            b = R.py_search(g, q, t, lambda ids: R.l2_scores(q, rows[np.asarray(ids)]))
+        except R.Failed:
+            continue
+        ran += 1
+        assert a[2].tolist() != b[2].tolist()
+        differ += int(a[2][0] != b[2][0])
+    assert ran >= len(z["q"]) // 2 and 2 * differ > ran, (differ, ran)
+
+
+def test_schedule_restatement_equals_the_oracle(oracle, golden_dir):
+    """py_search with L2 scores is the oracle's schedule bit for bit (status codes of failing requests included): what lets the
+    GPU tests use it, with IP scores, as the traversal's reference"""
+    z = dict(np.load(os.path.join(golden_dir, "small_l2_d64.npz")))
+    ix = oracle.Index(z["item_embs"], z["item_ids"], [z["nb_values_0"], z["nb_values_1"]],
+                      [z["nb_row_splits_0"], z["nb_row_splits_1"]], z["enter_points"])
+    sc = oracle.Scorer("l2", 64, oracle.EMB_F16)
+    rows = R.widen(z["item_embs"])
+    g = {"nb_values": [z["nb_values_0"], z["nb_values_1"]], "nb_row_splits": [z["nb_row_splits_0"], z["nb_row_splits_1"]],
+         "enter_points": z["enter_points"], "item_ids": z["item_ids"]}
+    E = len(z["enter_points"])
+    for t in (z["level_topn"].tolist(), [E + 1, 4, 4, 4, 4, 4], [4, 4, 4, 4, 4, 17], [0, 4, 4, 4, 4, 4]):
+        for q in z["q"][:4]:
+            rc, ids, scores, idx, _ = oracle.search(ix, sc, q, t)
+            try:
+                pids, ps, pidx = R.py_search(g, q, t, lambda i: R.l2_scores(q, rows[np.asarray(i)]))
+            except R.Failed as e:
+                assert rc == e.status, t
+                continue
+            assert rc == 0
+            assert (ids == pids).all() and (idx == pidx).all() and (scores.view(np.uint32) == ps.view(np.uint32)).all()

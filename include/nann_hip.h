@@ -844,6 +844,60 @@ int nann_hnsw_build_device(const void* item_embs, int64_t n_items, int32_t d, in
 int nann_hnsw_build_device_ex(const void* item_embs, int64_t n_items, int32_t d, int32_t emb_dtype, int32_t M,
                               int32_t ef_construction, int32_t keep_pruned, const int32_t* levels /*[host]*/, int32_t* adj0,
                               int32_t* up_row, int32_t* adj_up, nann_stream_t stream);
+/* Append: n_new rows go into a graph that nann_hnsw_build_device(_ex) or an earlier append built -- what a second
+ * faiss.IndexHNSWFlat.add on a built index does -- at the cost of the new rows, not of the corpus.
+ *   item_embs  device [n_old + n_new, d]; its first n_old rows are the rows the graph was built on (not checked)
+ *   levels     [host] n_old + n_new: the old nodes' levels as the build had them, then nann_hnsw_draw_levels(n_new, M, seed)
+ *              with a seed of the caller's choosing
+ *   adj0, up_row, adj_up   the builder's arrays (device, the caller's), sized for n_old + n_new nodes and sum(levels - 1)
+ *              upper rows over ALL nodes, the old graph in their heads as the build left it.  Their tails are ignored on
+ *              entry and overwritten: -1 slots, up_row continuing the prefix rule.
+ *   d, emb_dtype, M, ef_construction, keep_pruned   the limits and the status codes of the build.
+ * The old graph is INPUT, and malformed input never faults: one pass over the old rows, before anything is written or
+ * searched, holds them to the rules the insertion relies on -- up_row[i] is what `levels` implies (-1 for one level, else the
+ * running sum of levels - 1); every entry lies in [-1, n_old); no entry follows a -1 (rows are dense prefixes, their length
+ * is the fill count the build keeps private and the append recomputes); an entry of a level-l row names a node with more
+ * than l levels (so no row is looked up that does not exist).  A graph that breaks one is refused with
+ * NANN_ERR_BAD_ARGUMENT, every array untouched, nann_last_error naming the first broken rule and the lowest node that
+ * breaks it.
+ * Insertion is the build's (the same kernels): new nodes by descending level, then ascending id; the entry point is the
+ * lowest id among the nodes with the most levels; a new node with MORE levels than the entry point goes in alone, is linked
+ * on the levels the graph has (its rows above stay empty) and is the entry point from then on.  A batch is at most
+ * min(16384, inserted / 4, ceil(n_new / 64)) nodes: batch mates do not see each other, and appended rows, unlike a build's
+ * random order, may all be neighbours (a new category) -- in one batch they get no links to one another and requests near
+ * them fail; in 64 batches recall there is that of a build in random order (measured; 8 and 32 fall short).
+ * Deterministic: the same inputs give the same arrays.
+ * OLD ROWS CHANGE: back-links append new ids to an old row while it has room and re-select a full row with the heuristic, so
+ * the old part of a row can only shrink.  A caller that keeps serving the old graph while appending appends to a COPY.
+ * Synchronous.  NANN_OK (n_new == 0: after the checks, nothing written); NANN_ERR_BAD_ARGUMENT (a null pointer, n_old < 1,
+ * n_new < 0, levels[i] < 1, a malformed graph); NANN_ERR_UNSUPPORTED (more than 2^31 - 1 nodes in total, d, dtype, M or
+ * ef_construction outside the build's limits); NANN_ERR_HIP. */
+int nann_hnsw_append_device(const void* item_embs, int64_t n_old, int64_t n_new, int32_t d, int32_t emb_dtype,
+                            int32_t M, int32_t ef_construction, int32_t keep_pruned,
+                            const int32_t* levels /*[host] n_old + n_new*/,
+                            int32_t* adj0, int32_t* up_row, int32_t* adj_up, nann_stream_t stream);
+/* Export on the device: the builder's arrays -> what nann_index_desc takes (on_device = 1), by the rule of
+ * build_hnsw_index.py:41-66 with start_level = 2 (the levels serving walks; any other value: NANN_ERR_UNSUPPORTED).  Two steps,
+ * as nann_group_gather_count / _fill, because the sizes depend on the data.  adj0, up_row, adj_up (device) and levels [host]
+ * as the build or an append left them, n nodes; all outputs are the caller's.
+ *   count  row_splits0, row_splits1: device i64[n + 1], the CSR offsets of level 0 and 1 (a node absent on level 1 has an empty
+ *          row); nnz [host] i64[2] = their last entries; *n_enter [host] = nodes with levels > 2.  Synchronises.
+ *   fill   values0 i32[nnz[0]], values1 i32[nnz[1]] (device): every non-negative slot of a row in slot order, the -1 slots
+ *          dropped wherever they stand; enter_points i32[n_enter] (device): the nodes with levels > 2, ascending.
+ *          row_splits0/1 and nnz [host] i64[2] are count's.  Synchronises.
+ * NANN_ERR_BAD_ARGUMENT: a null pointer, n < 1, levels[i] < 1, an up_row entry of a node with more than one level outside
+ * adj_up, nnz < 0 or a null values array with nnz > 0, row_splits (fill) that are not this graph's -- a row is written only where
+ * its span has the row's own length and lies inside values[0, nnz), rs[0] is 0 and rs[n] is nnz, so nothing is written
+ * outside the arrays.  NANN_ERR_UNSUPPORTED:
+ * n > 2^31 - 1, M outside [2, 32], start_level != 2.  NANN_ERR_HIP. */
+int nann_hnsw_export_count(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up,
+                           const int32_t* levels /*[host] n*/, int64_t n, int32_t M, int32_t start_level,
+                           int64_t* row_splits0, int64_t* row_splits1, int64_t* nnz /*[host] 2*/,
+                           int64_t* n_enter /*[host]*/, nann_stream_t stream);
+int nann_hnsw_export_fill(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up,
+                          const int32_t* levels /*[host] n*/, int64_t n, int32_t M, int32_t start_level,
+                          const int64_t* row_splits0, const int64_t* row_splits1, const int64_t* nnz /*[host] 2*/,
+                          int32_t* values0, int32_t* values1, int32_t* enter_points, nann_stream_t stream);
 
 /* ---- 8(f2): the reference's own scorer model behind the BlazeXlaOp contract -------------
  * NANN_impls/nann/model/model.py:189-233 + model_util.py:70-97: softmax attention of the candidate

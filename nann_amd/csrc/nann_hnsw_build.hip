@@ -26,6 +26,11 @@
 // neighbors_level_{l}_{values,row_splits}.npy / enter_points.npy exactly as build_hnsw_index.py:41-66 does.
 // Index CONTENTS are not a parity target (Faiss' own insertion order is thread-schedule dependent);
 // the structural invariants and recall are (tests/test_index_build.py, -m gpu).
+//
+// APPEND (nann_hnsw_append_device): the same batch loop started from a graph that exists -- the old rows are checked
+// once (k_hb_check: the rules the kernels rely on, and the rows' fill counts), then the new nodes go in as a build's
+// would; build and append share hb_insert.  EXPORT (nann_hnsw_export_count / _fill): the arrays -> the per-level CSR
+// and enter points nann_index_create takes, on the device (tests/test_index_append_gpu.py).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -471,6 +476,209 @@ int run_backlink(const HbGraph& g, int level, const uint32_t* dst, const uint32_
   return NANN_OK;
 }
 
+// ---- append: the old graph is INPUT -------------------------------------------------------------------------
+// k_hb_check reads every row of the old graph once, one wavefront per node, BEFORE anything is written or searched:
+// it holds the arrays to the four rules the insertion kernels rely on and recomputes the rows' fill counts (the
+// length of the dense prefix) into the call's scratch.  Rows are addressed through `up_expect` (what the host
+// derived from `levels`), never through a value read from the arrays, so the pass itself cannot leave them.
+// bad[r] = lowest node that breaks rule r (kHbNone: none).
+enum { kHbBadUpRow = 0, kHbBadRange, kHbBadHole, kHbBadLevel, kHbRules };
+constexpr int32_t kHbNone = 0x7fffffff;
+
+__global__ __launch_bounds__(kHbWaves * 64) void k_hb_check(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up,
+                                                            const int32_t* levels, const int32_t* up_expect, int n_old, int M,
+                                                            int32_t* cnt0, int32_t* cnt_up, int32_t* bad) {
+  const int lane = threadIdx.x & 63;
+  const size_t at = (size_t)blockIdx.x * kHbWaves + (threadIdx.x >> 6);
+  if (at >= (size_t)n_old) return;
+  const int node = (int)at;
+  const int lv = levels[node], ur = up_expect[node];
+  if (lane == 0 && up_row[node] != ur) atomicMin(&bad[kHbBadUpRow], node);
+  for (int l = 0; l < lv; ++l) {
+    const int cap = l == 0 ? 2 * M : M;
+    const int32_t* row = l == 0 ? adj0 + (size_t)node * 2 * M : adj_up + ((size_t)ur + (size_t)(l - 1)) * M;
+    const int e = lane < cap ? row[lane] : -1;
+    const bool in_range = e >= -1 && e < n_old;
+    const uint64_t used = __ballot(e != -1);
+    const int c = popc64(used);
+    const bool hole = used != (c >= 64 ? ~0ull : (1ull << c) - 1ull);
+    const bool low = in_range && e >= 0 && levels[e] <= l;  // a link to a node that has no row on this level
+    const bool any_out = __ballot(!in_range) != 0ull, any_low = __ballot(low) != 0ull;
+    if (lane == 0) {
+      if (any_out) atomicMin(&bad[kHbBadRange], node);
+      if (hole) atomicMin(&bad[kHbBadHole], node);
+      if (any_low) atomicMin(&bad[kHbBadLevel], node);
+      if (l == 0) cnt0[node] = c; else cnt_up[(size_t)ur + (size_t)(l - 1)] = c;
+    }
+  }
+}
+
+// ---- export: the builder's arrays -> the per-level CSR of build_hnsw_index.py:41-66 (start_level = 2) --------
+// One wavefront per node and level: the row's slots one per lane, ballot of the non-negative ones, popcount = the
+// row's length (count), prefix popcount = a kept slot's place (fill) -- the compaction of nann_filter.h.  A node
+// absent on level 1 has an empty row.  up_row is data: a value outside [0, n_up) raises *bad instead of being used.
+__device__ __forceinline__ int hb_export_slot(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up,
+                                              const int32_t* levels, int64_t n_up, int M, int node, int level, int lane, int* bad) {
+  if (level == 0) return lane < 2 * M ? adj0[(size_t)node * 2 * M + lane] : -1;
+  if (levels[node] < 2) return -1;
+  const int64_t r = up_row[node];
+  if (r < 0 || r >= n_up) {
+    if (lane == 0) *bad = 1;
+    return -1;
+  }
+  return lane < M ? adj_up[(size_t)r * M + lane] : -1;
+}
+
+__global__ __launch_bounds__(kHbWaves * 64) void k_hb_export_count(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up,
+                                                                   const int32_t* levels, int n, int64_t n_up, int M,
+                                                                   int64_t* len0, int64_t* len1, int* bad) {
+  const int lane = threadIdx.x & 63;
+  const size_t at = (size_t)blockIdx.x * kHbWaves + (threadIdx.x >> 6);
+  if (at >= (size_t)n) return;
+  const int node = (int)at;
+#pragma unroll
+  for (int level = 0; level < 2; ++level) {
+    const int e = hb_export_slot(adj0, up_row, adj_up, levels, n_up, M, node, level, lane, bad);
+    const int c = popc64(__ballot(e >= 0));
+    if (lane == 0) (level == 0 ? len0 : len1)[node] = c;
+  }
+}
+
+__global__ __launch_bounds__(kHbWaves * 64) void k_hb_export_fill(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up,
+                                                                  const int32_t* levels, int n, int64_t n_up, int M,
+                                                                  const int64_t* rs0, const int64_t* rs1, int64_t nnz0, int64_t nnz1,
+                                                                  int32_t* v0, int32_t* v1, int* bad) {
+  const int lane = threadIdx.x & 63;
+  const size_t at = (size_t)blockIdx.x * kHbWaves + (threadIdx.x >> 6);
+  if (at >= (size_t)n) return;
+  const int node = (int)at;
+#pragma unroll
+  for (int level = 0; level < 2; ++level) {
+    const int e = hb_export_slot(adj0, up_row, adj_up, levels, n_up, M, node, level, lane, bad);
+    const uint64_t keep = __ballot(e >= 0);
+    const int64_t* rs = level == 0 ? rs0 : rs1;
+    const int64_t first = rs[node], len = rs[node + 1] - first, nnz = level == 0 ? nnz0 : nnz1;
+    // row_splits of another graph: a row is written only where its span is its own length and lies inside values[0, nnz)
+    if (len != popc64(keep) || first < 0 || first > nnz - len || (node == 0 && first != 0) || (node == n - 1 && first + len != nnz)) {
+      if (lane == 0) *bad = 1;
+      continue;
+    }
+    if (e >= 0) (level == 0 ? v0 : v1)[first + popc64(keep & lanemask_lt(lane))] = e;
+  }
+}
+
+// ---- what build and append share: the scratch of a run and the batch loop ------------------------------------
+struct HbScratch {
+  std::vector<void*> owned;
+  int32_t *order = nullptr, *cnt0 = nullptr, *cnt_up = nullptr, *entry = nullptr, *run_first = nullptr, *run_len = nullptr;
+  uint32_t *pair_dst = nullptr, *pair_src = nullptr, *pair_dst2 = nullptr, *pair_src2 = nullptr;
+  int* n_runs = nullptr;
+  void* sort = nullptr;
+  size_t sort_bytes = 0;
+  int max_batch = 16384, pair_cap = 0;
+  ~HbScratch() { for (void* p : owned) (void)hipFree(p); }
+  // n_order: nodes this run inserts (+ the entry point of a build); n_nodes / up_rows: the whole graph's
+  int alloc(size_t n_order, size_t n_nodes, int64_t up_rows, int M, hipStream_t st) {
+    pair_cap = 2 * M;
+    int rc = dev_alloc(&order, n_order, &owned);
+    if (!rc) rc = dev_alloc(&cnt0, n_nodes, &owned);
+    if (!rc) rc = dev_alloc(&cnt_up, (size_t)std::max<int64_t>(up_rows, 1), &owned);
+    if (!rc) rc = dev_alloc(&entry, (size_t)max_batch, &owned);
+    if (!rc) rc = dev_alloc(&pair_dst, (size_t)max_batch * pair_cap, &owned);
+    if (!rc) rc = dev_alloc(&pair_src, (size_t)max_batch * pair_cap, &owned);
+    if (!rc) rc = dev_alloc(&pair_dst2, (size_t)max_batch * pair_cap, &owned);
+    if (!rc) rc = dev_alloc(&pair_src2, (size_t)max_batch * pair_cap, &owned);
+    if (!rc) rc = dev_alloc(&run_first, (size_t)max_batch * pair_cap, &owned);
+    if (!rc) rc = dev_alloc(&run_len, (size_t)max_batch * pair_cap, &owned);
+    if (!rc) rc = dev_alloc(&n_runs, 1, &owned);
+    if (rc) return rc;
+    hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, pair_dst, pair_dst2, pair_src, pair_src2, max_batch * pair_cap, 0, 32, st);
+    unsigned char* p;
+    if ((rc = dev_alloc(&p, sort_bytes, &owned))) return rc;
+    sort = p;
+    return NANN_OK;
+  }
+};
+
+int hb_hip_rc(hipError_t e, const char* what) {
+  return e == hipSuccess ? NANN_OK : fail(NANN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The batch loop.  order[pos0 .. n_order) (also on the device, s.order) go into the graph `g`, which holds `base` nodes
+// that are not in `order` (append: the old graph) and order[0 .. pos0) (build: the entry point); `entry` has `T` levels,
+// the most of any node in it.  Same level count inside a batch; a batch is at most a quarter of what is already in the
+// graph, <= 16384, <= batch_cap.  A node with MORE levels than the entry point (append only: a build inserts in descending
+// order) is a batch of its own, searched and linked on the levels the graph has, T - 1 .. 0; its rows above stay empty,
+// and it is the entry point from then on -- so no row is ever looked up on a level its node does not have.
+int hb_insert(const char* who, const HbGraph& g, int emb_dtype, const int32_t* levels, const std::vector<int32_t>& order, int pos0, int64_t base,
+              int entry, int T, int batch_cap, int ef, HbScratch& s, hipStream_t st) {
+  const int n_order = (int)order.size(), d = g.d, pair_cap = s.pair_cap;
+  std::vector<int32_t> h_entry((size_t)s.max_batch, entry);
+  auto search = [&](const HbBatch& b) -> int {
+#define HB_CASE(LPR_)                                                                \
+  return emb_dtype == NANN_F16 ? run_batch_level<LPR_, 0>(g, b, st) : run_batch_level<LPR_, 1>(g, b, st)
+    if (d == 64) HB_CASE(8);
+    if (d == 128) HB_CASE(16);
+    HB_CASE(32);
+#undef HB_CASE
+  };
+  auto backlink = [&](int level, int n_pairs) -> int {
+#define HB_CASE(LPR_)                                                                                                        \
+  return emb_dtype == NANN_F16 ? run_backlink<LPR_, 0>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st) \
+                               : run_backlink<LPR_, 1>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st)
+    if (d == 64) HB_CASE(8);
+    if (d == 128) HB_CASE(16);
+    HB_CASE(32);
+#undef HB_CASE
+  };
+  int rc;
+  int pos = pos0;
+  while (pos < n_order) {
+    const int lv = levels[order[(size_t)pos]];  // number of levels of the batch's nodes
+    int end = pos;
+    const int64_t quarter = std::max<int64_t>(1, (base + pos) / 4);
+    const int limit = lv > T ? 1 : (int)std::min<int64_t>(std::min(s.max_batch, batch_cap), quarter);
+    while (end < n_order && end - pos < limit && levels[order[(size_t)end]] == lv) ++end;
+    const int n = end - pos;
+    if ((rc = hb_hip_rc(hipMemcpyAsync(s.entry, h_entry.data(), (size_t)n * 4, hipMemcpyHostToDevice, st), "entry"))) return rc;
+    for (int level = T - 1; level >= 0; --level) {
+      HbBatch b;
+      b.nodes = s.order + pos; b.n = n; b.level = level;
+      b.link = level <= lv - 1;
+      b.ef = b.link ? ef : 1;
+      b.entry = s.entry; b.pair_dst = s.pair_dst; b.pair_src = s.pair_src; b.pair_cap = pair_cap;
+      if ((rc = search(b))) return rc;
+      if (!b.link) continue;
+      const int n_pairs = n * pair_cap;
+      if (hipcub::DeviceRadixSort::SortPairs(s.sort, s.sort_bytes, s.pair_dst, s.pair_dst2, s.pair_src, s.pair_src2, n_pairs, 0, 32, st) != hipSuccess)
+        return fail(NANN_ERR_HIP, std::string(who) + ": radix sort failed");
+      if ((rc = hb_hip_rc(hipMemsetAsync(s.n_runs, 0, 4, st), "n_runs"))) return rc;
+      hipLaunchKernelGGL(k_hb_runs, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, s.pair_dst2, n_pairs, s.run_first, s.run_len, s.n_runs);
+      if ((rc = backlink(level, n_pairs))) return rc;
+    }
+    if (lv > T) {
+      if ((rc = hb_hip_rc(hipStreamSynchronize(st), "entry"))) return rc;  // the enqueued copies of h_entry have been read
+      T = lv;
+      std::fill(h_entry.begin(), h_entry.end(), order[(size_t)pos]);
+    }
+    pos = end;
+  }
+  return hb_hip_rc(hipStreamSynchronize(st), who);
+}
+
+// the argument limits build and append share
+int hb_check_shape(const char* who, int64_t n_total, int32_t d, int32_t emb_dtype, int32_t M, int ef) {
+  const std::string w(who);
+  if (n_total > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, w + ": more than 2^31 - 1 items");
+  if (!(d == 64 || d == 128 || d == 256)) return fail(NANN_ERR_UNSUPPORTED, w + ": d must be 64, 128 or 256");
+  if (emb_dtype != NANN_F16 && emb_dtype != NANN_BF16) return fail(NANN_ERR_UNSUPPORTED, w + ": f16 or bf16 rows");
+  if (M < 2 || 2 * M > kHbMaxCand) return fail(NANN_ERR_UNSUPPORTED, w + ": 2 <= M <= 32");
+  if (ef > kHbMaxEf) return fail(NANN_ERR_UNSUPPORTED, w + ": ef_construction <= 40 in this build");
+  return NANN_OK;
+}
+
+constexpr int kHbAppendDiv = 64;  // an append goes in in at least this many batches (8 and 32 measured short)
+
 }  // namespace
 
 extern "C" {
@@ -503,12 +711,8 @@ int nann_hnsw_build_device_ex(const void* item_embs, int64_t n_items, int32_t d,
                               int32_t* up_row, int32_t* adj_up, nann_stream_t stream) {
   if (!item_embs || !levels || !adj0 || !up_row || n_items <= 0)
     return fail(NANN_ERR_BAD_ARGUMENT, "nann_hnsw_build_device: null argument");
-  if (n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, "nann_hnsw_build_device: more than 2^31 - 1 items");
-  if (!(d == 64 || d == 128 || d == 256)) return fail(NANN_ERR_UNSUPPORTED, "nann_hnsw_build_device: d must be 64, 128 or 256");
-  if (emb_dtype != NANN_F16 && emb_dtype != NANN_BF16) return fail(NANN_ERR_UNSUPPORTED, "nann_hnsw_build_device: f16 or bf16 rows");
-  if (M < 2 || 2 * M > kHbMaxCand) return fail(NANN_ERR_UNSUPPORTED, "nann_hnsw_build_device: 2 <= M <= 32");
   const int ef = ef_construction > 0 ? ef_construction : 40;
-  if (ef > kHbMaxEf) return fail(NANN_ERR_UNSUPPORTED, "nann_hnsw_build_device: ef_construction <= 40 in this build");
+  if (int rc0 = hb_check_shape("nann_hnsw_build_device", n_items, d, emb_dtype, M, ef)) return rc0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = (int)n_items;
   // ---- insertion order: top level first, ascending id inside a level (Faiss adds the highest levels first)
@@ -525,97 +729,198 @@ int nann_hnsw_build_device_ex(const void* item_embs, int64_t n_items, int32_t d,
   if (up_rows > 0 && !adj_up) return fail(NANN_ERR_BAD_ARGUMENT, "nann_hnsw_build_device: adj_up is null");
   std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return levels[a] > levels[b]; });
 
-  std::vector<void*> owned;
-  auto cleanup = [&](int rc) { for (void* p : owned) (void)hipFree(p); return rc; };
-  int32_t *d_order, *d_cnt0, *d_cnt_up, *d_entry, *d_run_first, *d_run_len;
-  uint32_t *d_pair_dst, *d_pair_src, *d_pair_dst2, *d_pair_src2;
-  int* d_n_runs;
-  const int max_batch = 16384, pair_cap = 2 * M;
-  int rc = dev_alloc(&d_order, (size_t)N, &owned);
-  if (!rc) rc = dev_alloc(&d_cnt0, (size_t)N, &owned);
-  if (!rc) rc = dev_alloc(&d_cnt_up, (size_t)std::max<int64_t>(up_rows, 1), &owned);
-  if (!rc) rc = dev_alloc(&d_entry, (size_t)max_batch, &owned);
-  if (!rc) rc = dev_alloc(&d_pair_dst, (size_t)max_batch * pair_cap, &owned);
-  if (!rc) rc = dev_alloc(&d_pair_src, (size_t)max_batch * pair_cap, &owned);
-  if (!rc) rc = dev_alloc(&d_pair_dst2, (size_t)max_batch * pair_cap, &owned);
-  if (!rc) rc = dev_alloc(&d_pair_src2, (size_t)max_batch * pair_cap, &owned);
-  if (!rc) rc = dev_alloc(&d_run_first, (size_t)max_batch * pair_cap, &owned);
-  if (!rc) rc = dev_alloc(&d_run_len, (size_t)max_batch * pair_cap, &owned);
-  if (!rc) rc = dev_alloc(&d_n_runs, 1, &owned);
-  if (rc) return cleanup(rc);
-  size_t sort_bytes = 0;
-  int key_bits = 1;
-  while ((1ll << key_bits) < n_items) ++key_bits;
-  hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_pair_dst, d_pair_dst2, d_pair_src, d_pair_src2, max_batch * pair_cap, 0, 32, st);
-  void* d_sort = nullptr;
-  {
-    unsigned char* p;
-    rc = dev_alloc(&p, sort_bytes, &owned);
-    if (rc) return cleanup(rc);
-    d_sort = p;
-  }
-  auto hip_rc = [&](hipError_t e, const char* what) { return e == hipSuccess ? NANN_OK : fail(NANN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-  if ((rc = hip_rc(hipMemcpyAsync(d_order, order.data(), (size_t)N * 4, hipMemcpyHostToDevice, st), "order")) ||
-      (rc = hip_rc(hipMemcpyAsync(up_row, h_up.data(), (size_t)N * 4, hipMemcpyHostToDevice, st), "up_row")) ||
-      (rc = hip_rc(hipMemsetAsync(adj0, 0xff, (size_t)N * 2 * M * 4, st), "adj0")) ||
-      (rc = hip_rc(hipMemsetAsync(d_cnt0, 0, (size_t)N * 4, st), "cnt0")) ||
-      (rc = hip_rc(hipMemsetAsync(d_cnt_up, 0, (size_t)std::max<int64_t>(up_rows, 1) * 4, st), "cnt_up")))
-    return cleanup(rc);
-  if (up_rows > 0 && (rc = hip_rc(hipMemsetAsync(adj_up, 0xff, (size_t)up_rows * M * 4, st), "adj_up"))) return cleanup(rc);
+  HbScratch s;
+  int rc = s.alloc((size_t)N, (size_t)N, up_rows, M, st);
+  if (rc) return rc;
+  if ((rc = hb_hip_rc(hipMemcpyAsync(s.order, order.data(), (size_t)N * 4, hipMemcpyHostToDevice, st), "order")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(up_row, h_up.data(), (size_t)N * 4, hipMemcpyHostToDevice, st), "up_row")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(adj0, 0xff, (size_t)N * 2 * M * 4, st), "adj0")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(s.cnt0, 0, (size_t)N * 4, st), "cnt0")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(s.cnt_up, 0, (size_t)std::max<int64_t>(up_rows, 1) * 4, st), "cnt_up")))
+    return rc;
+  if (up_rows > 0 && (rc = hb_hip_rc(hipMemsetAsync(adj_up, 0xff, (size_t)up_rows * M * 4, st), "adj_up"))) return rc;
 
   HbGraph g;
-  g.emb = item_embs; g.adj0 = adj0; g.cnt0 = d_cnt0; g.up_row = up_row; g.adj_up = adj_up; g.cnt_up = d_cnt_up;
+  g.emb = item_embs; g.adj0 = adj0; g.cnt0 = s.cnt0; g.up_row = up_row; g.adj_up = adj_up; g.cnt_up = s.cnt_up;
   g.n_items = N; g.d = d; g.M = M; g.keep_pruned = keep_pruned ? 1 : 0;
-  const int global_entry = order[0], top = levels[order[0]] - 1;  // level index of the entry point
-  std::vector<int32_t> h_entry((size_t)max_batch, global_entry);
+  // order[0] is the entry point: inserted with no links
+  return hb_insert("nann_hnsw_build_device", g, emb_dtype, levels, order, 1, 0, order[0], levels[order[0]], 0x7fffffff, ef, s, st);
+}
 
-  auto search = [&](const HbBatch& b) -> int {
-#define HB_CASE(LPR_)                                                                \
-  return emb_dtype == NANN_F16 ? run_batch_level<LPR_, 0>(g, b, st) : run_batch_level<LPR_, 1>(g, b, st)
-    if (d == 64) HB_CASE(8);
-    if (d == 128) HB_CASE(16);
-    HB_CASE(32);
-#undef HB_CASE
-  };
-  auto backlink = [&](int level, int n_pairs) -> int {
-#define HB_CASE(LPR_)                                                                                                        \
-  return emb_dtype == NANN_F16 ? run_backlink<LPR_, 0>(g, level, d_pair_dst2, d_pair_src2, d_run_first, d_run_len, d_n_runs, n_pairs, st) \
-                               : run_backlink<LPR_, 1>(g, level, d_pair_dst2, d_pair_src2, d_run_first, d_run_len, d_n_runs, n_pairs, st)
-    if (d == 64) HB_CASE(8);
-    if (d == 128) HB_CASE(16);
-    HB_CASE(32);
-#undef HB_CASE
-  };
-
-  // ---- batches: same top level inside a batch; a batch is at most a quarter of what is already in the graph
-  int pos = 1;  // order[0] is the entry point: inserted with no links
-  while (pos < N) {
-    const int lv = levels[order[(size_t)pos]];  // number of levels of the batch's nodes
-    int end = pos;
-    const int limit = std::min(max_batch, std::max(1, pos / 4));
-    while (end < N && end - pos < limit && levels[order[(size_t)end]] == lv) ++end;
-    const int n = end - pos;
-    if ((rc = hip_rc(hipMemcpyAsync(d_entry, h_entry.data(), (size_t)n * 4, hipMemcpyHostToDevice, st), "entry"))) return cleanup(rc);
-    for (int level = top; level >= 0; --level) {
-      HbBatch b;
-      b.nodes = d_order + pos; b.n = n; b.level = level;
-      b.link = level <= lv - 1;
-      b.ef = b.link ? ef : 1;
-      b.entry = d_entry; b.pair_dst = d_pair_dst; b.pair_src = d_pair_src; b.pair_cap = pair_cap;
-      if ((rc = search(b))) return cleanup(rc);
-      if (!b.link) continue;
-      const int n_pairs = n * pair_cap;
-      if (hipcub::DeviceRadixSort::SortPairs(d_sort, sort_bytes, d_pair_dst, d_pair_dst2, d_pair_src, d_pair_src2, n_pairs, 0, 32, st) != hipSuccess)
-        return cleanup(fail(NANN_ERR_HIP, "nann_hnsw_build_device: radix sort failed"));
-      if ((rc = hip_rc(hipMemsetAsync(d_n_runs, 0, 4, st), "n_runs"))) return cleanup(rc);
-      hipLaunchKernelGGL(k_hb_runs, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, d_pair_dst2, n_pairs, d_run_first, d_run_len, d_n_runs);
-      if ((rc = backlink(level, n_pairs))) return cleanup(rc);
-    }
-    pos = end;
+int nann_hnsw_append_device(const void* item_embs, int64_t n_old, int64_t n_new, int32_t d, int32_t emb_dtype, int32_t M,
+                            int32_t ef_construction, int32_t keep_pruned, const int32_t* levels, int32_t* adj0,
+                            int32_t* up_row, int32_t* adj_up, nann_stream_t stream) {
+  const char* who = "nann_hnsw_append_device";
+  if (!item_embs || !levels || !adj0 || !up_row || n_old < 1 || n_new < 0)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument, n_old < 1 or n_new < 0");
+  const int ef = ef_construction > 0 ? ef_construction : 40;
+  int rc = hb_check_shape(who, n_old > 0x7fffffffll - n_new ? 0x80000000ll : n_old + n_new, d, emb_dtype, M, ef);
+  if (rc) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int N0 = (int)n_old, N1 = (int)n_new, N = N0 + N1;
+  // ---- from `levels`: every node's first upper row, the old graph's entry point, the new nodes' order
+  std::vector<int32_t> h_up((size_t)N);
+  int64_t up_rows = 0, up_rows_old = 0;
+  int entry = 0;
+  for (int i = 0; i < N; ++i) {
+    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
+    if (i < N0 && levels[i] > levels[entry]) entry = i;  // the lowest id among the nodes with the most levels
+    h_up[(size_t)i] = levels[i] > 1 ? (int32_t)up_rows : -1;
+    up_rows += levels[i] - 1;
+    if (i == N0 - 1) up_rows_old = up_rows;
   }
-  rc = hip_rc(hipStreamSynchronize(st), "nann_hnsw_build_device");
-  (void)key_bits;
-  return cleanup(rc);
+  if (up_rows > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 upper rows");
+  if (up_rows > 0 && !adj_up) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": adj_up is null");
+  std::vector<int32_t> order((size_t)N1);
+  for (int i = 0; i < N1; ++i) order[(size_t)i] = N0 + i;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return levels[a] > levels[b]; });
+
+  HbScratch s;
+  if ((rc = s.alloc((size_t)std::max(N1, 1), (size_t)N, up_rows, M, st))) return rc;
+  // ---- the old graph is checked before anything is written: levels and the expected up_row go up, one pass, one flag back
+  int32_t *d_levels, *d_up, *d_bad;
+  if ((rc = dev_alloc(&d_levels, (size_t)N0, &s.owned)) || (rc = dev_alloc(&d_up, (size_t)N0, &s.owned)) ||
+      (rc = dev_alloc(&d_bad, (size_t)kHbRules, &s.owned)))
+    return rc;
+  int32_t h_bad[kHbRules] = {kHbNone, kHbNone, kHbNone, kHbNone};
+  if ((rc = hb_hip_rc(hipMemcpyAsync(d_levels, levels, (size_t)N0 * 4, hipMemcpyHostToDevice, st), "levels")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(d_up, h_up.data(), (size_t)N0 * 4, hipMemcpyHostToDevice, st), "up_row")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(d_bad, h_bad, sizeof(h_bad), hipMemcpyHostToDevice, st), "flag")))
+    return rc;
+  hipLaunchKernelGGL(k_hb_check, dim3((unsigned)((N0 + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, adj0, up_row, adj_up,
+                     d_levels, d_up, N0, M, s.cnt0, s.cnt_up, d_bad);
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_check")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, st), "flag")) ||
+      (rc = hb_hip_rc(hipStreamSynchronize(st), "k_hb_check")))
+    return rc;
+  static const char* const kRule[kHbRules] = {
+      "up_row differs from what levels implies (-1 for one level, else the running sum of levels - 1)",
+      "a row entry lies outside [-1, n_old)", "a row entry follows a -1 (rows are dense prefixes)",
+      "a row entry names a node that has no row on that level"};
+  for (int r = 0; r < kHbRules; ++r)
+    if (h_bad[r] != kHbNone)
+      return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": malformed graph, node " + std::to_string(h_bad[r]) + ": " + kRule[r]);
+  if (N1 == 0) return NANN_OK;
+  // ---- the tails: empty rows, the prefix rule continued
+  const int64_t up_new = up_rows - up_rows_old;
+  if ((rc = hb_hip_rc(hipMemcpyAsync(s.order, order.data(), (size_t)N1 * 4, hipMemcpyHostToDevice, st), "order")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(up_row + N0, h_up.data() + N0, (size_t)N1 * 4, hipMemcpyHostToDevice, st), "up_row")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(adj0 + (size_t)N0 * 2 * M, 0xff, (size_t)N1 * 2 * M * 4, st), "adj0")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(s.cnt0 + N0, 0, (size_t)N1 * 4, st), "cnt0")))
+    return rc;
+  if (up_new > 0 &&
+      ((rc = hb_hip_rc(hipMemsetAsync(adj_up + (size_t)up_rows_old * M, 0xff, (size_t)up_new * M * 4, st), "adj_up")) ||
+       (rc = hb_hip_rc(hipMemsetAsync(s.cnt_up + up_rows_old, 0, (size_t)up_new * 4, st), "cnt_up"))))
+    return rc;
+  HbGraph g;
+  g.emb = item_embs; g.adj0 = adj0; g.cnt0 = s.cnt0; g.up_row = up_row; g.adj_up = adj_up; g.cnt_up = s.cnt_up;
+  g.n_items = N; g.d = d; g.M = M; g.keep_pruned = keep_pruned ? 1 : 0;
+  const int batch_cap = std::max(1, (N1 + kHbAppendDiv - 1) / kHbAppendDiv);
+  return hb_insert(who, g, emb_dtype, levels, order, 0, n_old, entry, levels[entry], batch_cap, ef, s, st);
+}
+
+namespace {
+int hb_export_args(const char* who, const void* adj0, const void* up_row, const int32_t* levels, int64_t n, int32_t M,
+                   int32_t start_level) {
+  const std::string w(who);
+  if (!adj0 || !up_row || !levels || n < 1) return fail(NANN_ERR_BAD_ARGUMENT, w + ": null argument or n < 1");
+  if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, w + ": more than 2^31 - 1 items");
+  if (M < 2 || 2 * M > kHbMaxCand) return fail(NANN_ERR_UNSUPPORTED, w + ": 2 <= M <= 32");
+  if (start_level != 2) return fail(NANN_ERR_UNSUPPORTED, w + ": start_level must be 2 (the levels serving walks)");
+  return NANN_OK;
+}
+}  // namespace
+
+int nann_hnsw_export_count(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up, const int32_t* levels, int64_t n,
+                           int32_t M, int32_t start_level, int64_t* row_splits0, int64_t* row_splits1, int64_t* nnz,
+                           int64_t* n_enter, nann_stream_t stream) {
+  const char* who = "nann_hnsw_export_count";
+  int rc = hb_export_args(who, adj0, up_row, levels, n, M, start_level);
+  if (rc) return rc;
+  if (!row_splits0 || !row_splits1 || !nnz || !n_enter) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null output");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int N = (int)n;
+  int64_t n_up = 0, enter = 0;
+  for (int i = 0; i < N; ++i) {
+    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
+    n_up += levels[i] - 1;
+    enter += levels[i] > start_level;
+  }
+  if (n_up > 0 && !adj_up) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": adj_up is null");
+  std::vector<void*> owned;
+  auto cleanup = [&](int r) { for (void* p : owned) (void)hipFree(p); return r; };
+  int32_t* d_levels;
+  int64_t* d_len;
+  int* d_bad;
+  if ((rc = dev_alloc(&d_levels, (size_t)N, &owned)) || (rc = dev_alloc(&d_len, (size_t)N * 2, &owned)) ||
+      (rc = dev_alloc(&d_bad, 1, &owned)))
+    return cleanup(rc);
+  size_t scan_bytes = 0;
+  hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, d_len, row_splits0 + 1, N, st);
+  unsigned char* d_scan;
+  if ((rc = dev_alloc(&d_scan, scan_bytes, &owned))) return cleanup(rc);
+  if ((rc = hb_hip_rc(hipMemcpyAsync(d_levels, levels, (size_t)N * 4, hipMemcpyHostToDevice, st), "levels")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(d_bad, 0, 4, st), "flag")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(row_splits0, 0, 8, st), "row_splits")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(row_splits1, 0, 8, st), "row_splits")))
+    return cleanup(rc);
+  hipLaunchKernelGGL(k_hb_export_count, dim3((unsigned)((N + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, adj0, up_row,
+                     adj_up, d_levels, N, n_up, M, d_len, d_len + N, d_bad);
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_export_count"))) return cleanup(rc);
+  if (hipcub::DeviceScan::InclusiveSum(d_scan, scan_bytes, d_len, row_splits0 + 1, N, st) != hipSuccess ||
+      hipcub::DeviceScan::InclusiveSum(d_scan, scan_bytes, d_len + N, row_splits1 + 1, N, st) != hipSuccess)
+    return cleanup(fail(NANN_ERR_HIP, std::string(who) + ": scan failed"));
+  int h_bad = 0;
+  if ((rc = hb_hip_rc(hipMemcpyAsync(&nnz[0], row_splits0 + N, 8, hipMemcpyDeviceToHost, st), "nnz")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(&nnz[1], row_splits1 + N, 8, hipMemcpyDeviceToHost, st), "nnz")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st), "flag")) ||
+      (rc = hb_hip_rc(hipStreamSynchronize(st), who)))
+    return cleanup(rc);
+  if (h_bad) return cleanup(fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": an up_row entry lies outside adj_up"));
+  *n_enter = enter;
+  return cleanup(NANN_OK);
+}
+
+int nann_hnsw_export_fill(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up, const int32_t* levels, int64_t n,
+                          int32_t M, int32_t start_level, const int64_t* row_splits0, const int64_t* row_splits1,
+                          const int64_t* nnz, int32_t* values0, int32_t* values1, int32_t* enter_points, nann_stream_t stream) {
+  const char* who = "nann_hnsw_export_fill";
+  int rc = hb_export_args(who, adj0, up_row, levels, n, M, start_level);
+  if (rc) return rc;
+  if (!row_splits0 || !row_splits1 || !nnz) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null row_splits or nnz");
+  if (nnz[0] < 0 || nnz[1] < 0 || (nnz[0] > 0 && !values0) || (nnz[1] > 0 && !values1))
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": nnz < 0 or values is null");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int N = (int)n;
+  int64_t n_up = 0;
+  std::vector<int32_t> enter;
+  for (int i = 0; i < N; ++i) {
+    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
+    n_up += levels[i] - 1;
+    if (levels[i] > start_level) enter.push_back(i);
+  }
+  if ((n_up > 0 && !adj_up) || (!enter.empty() && !enter_points))
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": adj_up or enter_points is null");
+  std::vector<void*> owned;
+  auto cleanup = [&](int r) { for (void* p : owned) (void)hipFree(p); return r; };
+  int32_t* d_levels;
+  int* d_bad;
+  if ((rc = dev_alloc(&d_levels, (size_t)N, &owned)) || (rc = dev_alloc(&d_bad, 1, &owned))) return cleanup(rc);
+  if ((rc = hb_hip_rc(hipMemcpyAsync(d_levels, levels, (size_t)N * 4, hipMemcpyHostToDevice, st), "levels")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(d_bad, 0, 4, st), "flag")))
+    return cleanup(rc);
+  if (!enter.empty() &&
+      (rc = hb_hip_rc(hipMemcpyAsync(enter_points, enter.data(), enter.size() * 4, hipMemcpyHostToDevice, st), "enter_points")))
+    return cleanup(rc);
+  hipLaunchKernelGGL(k_hb_export_fill, dim3((unsigned)((N + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, adj0, up_row,
+                     adj_up, d_levels, N, n_up, M, row_splits0, row_splits1, nnz[0], nnz[1], values0, values1, d_bad);
+  int h_bad = 0;
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_export_fill")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st), "flag")) ||
+      (rc = hb_hip_rc(hipStreamSynchronize(st), who)))
+    return cleanup(rc);
+  if (h_bad) return cleanup(fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": row_splits are not this graph's (call nann_hnsw_export_count first)"));
+  return cleanup(NANN_OK);
 }
 
 }  // extern "C"

@@ -108,14 +108,38 @@ def build_and_save_index(embeddings, start_level, num_neighbors, output_dir, see
 
 
 # ---- construction on the device (csrc/nann_hnsw_build.hip) -----------------------------------------------------
+def _export_torch(levels, adj0, up_row, adj_up, m, start_level):
+    """build_hnsw_index.py:41-66 on the device builder's arrays, assembled with torch on the device -> numpy"""
+    import torch
+    n = len(levels)
+    lev = torch.as_tensor(levels, device=adj0.device)
+    out = {"levels": levels, "enter_points": np.nonzero(levels > start_level)[0],  # build_hnsw_index.py:45
+           "nb_values": [], "nb_row_splits": []}
+    for level in range(start_level):                                              # :49
+        if level == 0:
+            rows = adj0
+        else:  # row of node i on level l >= 1: up_row[i] + l - 1 (absent: an empty row, :53)
+            rows = torch.full((n, m), -1, dtype=torch.int32, device=adj0.device)
+            has = lev > level
+            rows[has] = adj_up[(up_row[has] + (level - 1)).long()]
+        keep = rows >= 0                                                          # :59 drop the -1 slots
+        rs = torch.zeros(n + 1, dtype=torch.int64, device=adj0.device)
+        torch.cumsum(keep.sum(1), 0, out=rs[1:])
+        out["nb_values"].append(rows[keep].to(torch.int64).cpu().numpy())         # :66 int64 on disk
+        out["nb_row_splits"].append(rs.cpu().numpy())
+    return out
+
+
 def build_hnsw_gpu(item_embs, num_neighbors=32, ef_construction=40, seed=0, start_level=2, want_raw=False,
-                   keep_pruned=False):
+                   keep_pruned=False, want_state=False):
     """HNSW(M) over the rows of `item_embs` (CUDA tensor f16 | bf16 [N, d], or a numpy f16 array) built ON THE GPU
     (nann_hnsw_build_device).  Returns the export of build_hnsw_index.py:41-66 -- {"enter_points", "nb_values"
     [start_level], "nb_row_splits"[start_level], "levels"} as numpy arrays (values int64 on disk) -- assembled with
     torch on the device; with want_raw also the Faiss-shaped raw arrays of build_hnsw().  keep_pruned: the selection
     heuristic's keepPrunedConnections switch (off in Faiss, hence in the reference's graphs): rows fill up to their cap --
-    the dense-graph family (mean level-0 degree ~55 of 64 instead of ~17)."""
+    the dense-graph family (mean level-0 degree ~55 of 64 instead of ~17).  want_state: also "state", the builder's own
+    arrays on the device (item_embs, adj0, up_row, adj_up) with levels, M, ef_construction and keep_pruned -- what
+    append_hnsw_gpu() grows and export_hnsw_gpu() turns into an Index without leaving the device."""
     import torch
     from . import _lib
     from .ops import _check, _ptr, _stream, _DT
@@ -136,21 +160,10 @@ def build_hnsw_gpu(item_embs, num_neighbors=32, ef_construction=40, seed=0, star
                                        C.c_int32(ef_construction), C.c_int32(1 if keep_pruned else 0),
                                        levels.ctypes.data_as(C.c_void_p), _ptr(adj0), _ptr(up_row), _ptr(adj_up), _stream()),
            "hnsw build")
-    lev = torch.as_tensor(levels, device=x.device)
-    out = {"levels": levels, "enter_points": np.nonzero(levels > start_level)[0],  # build_hnsw_index.py:45
-           "nb_values": [], "nb_row_splits": []}
-    for level in range(start_level):                                              # :49
-        if level == 0:
-            rows = adj0
-        else:  # row of node i on level l >= 1: up_row[i] + l - 1 (absent: an empty row, :53)
-            rows = torch.full((n, m), -1, dtype=torch.int32, device=x.device)
-            has = lev > level
-            rows[has] = adj_up[(up_row[has] + (level - 1)).long()]
-        keep = rows >= 0                                                          # :59 drop the -1 slots
-        rs = torch.zeros(n + 1, dtype=torch.int64, device=x.device)
-        torch.cumsum(keep.sum(1), 0, out=rs[1:])
-        out["nb_values"].append(rows[keep].to(torch.int64).cpu().numpy())         # :66 int64 on disk
-        out["nb_row_splits"].append(rs.cpu().numpy())
+    out = _export_torch(levels, adj0, up_row, adj_up, m, start_level)
+    if want_state:
+        out["state"] = {"item_embs": x, "adj0": adj0, "up_row": up_row, "adj_up": adj_up, "levels": levels, "M": m,
+                        "ef_construction": int(ef_construction), "keep_pruned": bool(keep_pruned)}
     if want_raw:
         cum = np.concatenate([[0], 2 * m + m * np.arange(int(levels.max()))]).astype(np.int32)
         offsets = np.zeros(n + 1, np.int64)
@@ -163,3 +176,67 @@ def build_hnsw_gpu(item_embs, num_neighbors=32, ef_construction=40, seed=0, star
                 nb[offsets[i] + cum[l]: offsets[i] + cum[l] + m] = au[ur[i] + l - 1]
         out["raw"] = {"levels": levels, "offsets": offsets, "neighbors": nb, "cum_nneighbor_per_level": cum}
     return out
+
+
+def append_hnsw_gpu(state, new_rows, seed, start_level=2, want_export=True):
+    """Append `new_rows` ([n_new, d], the dtype of the state's rows) to the graph of `state` (build_hnsw_gpu(want_state=True)
+    or an earlier append) ON THE GPU (nann_hnsw_append_device).  The rows are concatenated and the three arrays grown into NEW
+    tensors: the input state is left as it is, so an index still serving from it is safe (back-links rewrite old rows).  The
+    new nodes' levels are drawn with `seed`.  Returns what build_hnsw_gpu(want_state=True) returns, over the grown corpus;
+    want_export=False: {"levels", "state"} only, without the torch export and its copy to the host -- the live path, which goes
+    on with export_hnsw_gpu(state) on the device."""
+    import torch
+    from . import _lib
+    from .ops import _check, _ptr, _stream, _DT
+    L = _lib.lib()
+    x0, m = state["item_embs"], int(state["M"])
+    n_old, d = x0.shape
+    new = new_rows if isinstance(new_rows, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(new_rows))
+    new = new.to(device=x0.device).reshape(-1, d)
+    if new.dtype != x0.dtype:
+        raise ValueError(f"append_hnsw_gpu: rows are {new.dtype}, the graph's are {x0.dtype}")
+    n_new = new.shape[0]
+    x = torch.cat([x0, new]).contiguous()
+    new_levels = np.zeros(n_new, np.int32)
+    if n_new:
+        _check(L.nann_hnsw_draw_levels(C.c_int64(n_new), C.c_int32(m), C.c_uint64(seed), new_levels.ctypes.data_as(C.c_void_p),
+                                       None), "hnsw levels")
+    levels = np.ascontiguousarray(np.concatenate([np.asarray(state["levels"], np.int32), new_levels]))
+    n = n_old + n_new
+    n_up_old, n_up = int((levels[:n_old] - 1).sum()), int((levels.astype(np.int64) - 1).sum())
+    adj0 = torch.full((n, 2 * m), -1, dtype=torch.int32, device=x.device)
+    adj0[:n_old] = state["adj0"]
+    up_row = torch.full((n,), -1, dtype=torch.int32, device=x.device)
+    up_row[:n_old] = state["up_row"]
+    adj_up = torch.full((max(n_up, 1), m), -1, dtype=torch.int32, device=x.device)
+    adj_up[:n_up_old] = state["adj_up"][:n_up_old]
+    torch.cuda.synchronize()
+    _check(L.nann_hnsw_append_device(_ptr(x), n_old, n_new, d, _DT[x.dtype], m, int(state["ef_construction"]),
+                                     1 if state["keep_pruned"] else 0, levels.ctypes.data_as(C.c_void_p), _ptr(adj0),
+                                     _ptr(up_row), _ptr(adj_up), _stream()), "hnsw append")
+    out = _export_torch(levels, adj0, up_row, adj_up, m, start_level) if want_export else {"levels": levels}
+    out["state"] = {"item_embs": x, "adj0": adj0, "up_row": up_row, "adj_up": adj_up, "levels": levels, "M": m,
+                    "ef_construction": int(state["ef_construction"]), "keep_pruned": bool(state["keep_pruned"])}
+    return out
+
+
+def export_hnsw_gpu(state, start_level=2):
+    """The export of build_hnsw_index.py:41-66 ON THE DEVICE (nann_hnsw_export_count / _fill): {"enter_points" i32,
+    "nb_values" [i32 l0, l1], "nb_row_splits" [i64 l0, l1]} as device tensors -- what retrieval.Index(...) takes as they are,
+    so a grown graph reaches serving without a host round trip."""
+    import torch
+    from . import _lib
+    from .ops import _check, _ptr, _stream
+    L = _lib.lib()
+    adj0, up_row, adj_up, levels, m = state["adj0"], state["up_row"], state["adj_up"], state["levels"], int(state["M"])
+    levels = np.ascontiguousarray(levels, dtype=np.int32)
+    n, dev = len(levels), adj0.device
+    rs = [torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(2)]
+    nnz, n_enter = (C.c_int64 * 2)(), C.c_int64(0)
+    torch.cuda.synchronize()
+    head = (_ptr(adj0), _ptr(up_row), _ptr(adj_up), levels.ctypes.data_as(C.c_void_p), n, m, int(start_level), _ptr(rs[0]), _ptr(rs[1]))
+    _check(L.nann_hnsw_export_count(*head, nnz, C.byref(n_enter), _stream()), "hnsw export count")
+    vals = [torch.empty(max(int(nnz[l]), 1), dtype=torch.int32, device=dev)[:int(nnz[l])] for l in range(2)]
+    enter = torch.empty(max(n_enter.value, 1), dtype=torch.int32, device=dev)[:n_enter.value]
+    _check(L.nann_hnsw_export_fill(*head, nnz, _ptr(vals[0]), _ptr(vals[1]), _ptr(enter), _stream()), "hnsw export fill")
+    return {"enter_points": enter, "nb_values": vals, "nb_row_splits": rs}

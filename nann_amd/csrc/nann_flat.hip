@@ -6,11 +6,11 @@
 // Compiled into nann_core.o behind nann_hip.hip, as ONE translation unit with it (build.py writes the wrapper), on the terms
 // nann_comm.hip lives there: this file uses nann_hip.hip's file-scope types and helpers directly -- nann_index, nann_scorer,
 // nann_model, fail, device_info, as_stream, check_options / resolve_options, mlp_projection / attn_projection /
-// projection_used -- and no header stands between the two.  resolve_filter is defined here; the filtered traversal in
-// nann_hip.hip calls it through a declaration.
+// projection_used, ScoredBy / scored_by -- and no header stands between the two.  resolve_filter is defined here; the filtered
+// traversal (nann_traverse.hip, behind this file in the unit) uses it too.
 //
 // Every entry point is one walk over the steps below, each written once:
-//   flat_by            who scores the call, from a nann_scorer or a nann_model
+//   flat_by            who scores the call, from a nann_scorer or a nann_model: scored_by, and what the flat kernels take
 //   flat_check         the shape of the call (flat_cand_check: with the nann_candidates struct around it)
 //   flat_all_bytes     the size of a workspace, per family; the *_workspace_bytes calls and the searches both take it from
 //   flat_cand_bytes    here, staged query in front and filter staging behind included
@@ -32,56 +32,35 @@
 using namespace nann;
 
 // ---- who scores a call ---------------------------------------------------------------------------------------------------
-struct FlatBy {
-  int kind = NANN_SCORER_L2;             // the scorer's nann_scorer_kind, or kScanAttn for the attention model
-  int exact = 0;                         // MLP / attention: the f32 form (also the MLP's certified precision), else split-f16
-  MlpParams mlp = {};                    // MLP
-  AttnParams attn = {};                  // attention
-  const nann_scorer* scorer = nullptr;   // l2 / ip / mlp: the scorer, a model's own included
-  const nann_attn_scorer* at = nullptr;  // attention
-  ProjCache* cache = nullptr;            // MLP / attention: the cache the pair's pre-projected table belongs to
-  const nann_model* mean_of = nullptr;   // an l2 / ip / mlp model: the query is the mean of its sequence, staged at the head of the workspace
-  const char* what = "scorer";           // the handle's word in a message,
-  const char* unit = "queries";          // and what it scores for
-  bool mismatch = false;                 // handle and index disagree on d / dtype: flat_check reports it at its place in the order
+// ScoredBy (nann_hip.hip: the scorer or the attention scorer, mean_of, cache, what, mismatch), and what the flat kernels take
+struct FlatBy : ScoredBy {
+  int kind = NANN_SCORER_L2;     // the scorer's nann_scorer_kind, or kScanAttn for the attention model
+  int exact = 0;                 // MLP / attention: the f32 form (also the MLP's certified precision), else split-f16
+  MlpParams mlp = {};            // MLP
+  AttnParams attn = {};          // attention
+  const char* unit = "queries";  // what the handle scores for, in a message
 };
 
 static int flat_by(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, const char* who, FlatBy* by) {
   *by = FlatBy{};
   if (!ix || !(scorer || m)) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  int d = 0, dt = 0;
-  if (m) {
-    by->what = "model";
-    by->unit = "users";
-    d = m->d;
-    dt = m->emb_dtype;
-    if (m->kind == NANN_MODEL_ATTENTION) {
-      by->kind = kScanAttn;
-      by->at = m->attn;
-      by->attn = m->attn->P;
-      by->exact = m->attn->precision != NANN_MLP_SPLIT_F16;
-      by->cache = &m->attn->proj;
-    } else {
-      scorer = m->scorer;
-      if (!scorer) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-      by->mean_of = m;
-    }
+  static_cast<ScoredBy&>(*by) = scored_by(ix, scorer, m);
+  if (m) by->unit = "users";
+  if (by->at) {
+    by->kind = kScanAttn;
+    by->attn = by->at->P;
+    by->exact = by->at->precision != NANN_MLP_SPLIT_F16;
+  } else if (!by->scorer) {
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
   } else {
-    d = scorer->desc.d;
-    dt = scorer->desc.emb_dtype;
-  }
-  if (scorer) {
-    by->scorer = scorer;
-    by->kind = scorer->desc.kind;
+    by->kind = by->scorer->desc.kind;
     if (by->kind == NANN_SCORER_MLP) {
-      by->mlp = scorer->mlp;
-      by->exact = scorer->desc.precision == NANN_MLP_EXACT_F32 || scorer->desc.precision == NANN_MLP_CERTIFIED;
-      by->cache = &scorer->proj;
+      by->mlp = by->scorer->mlp;
+      by->exact = by->scorer->desc.precision == NANN_MLP_EXACT_F32 || by->scorer->desc.precision == NANN_MLP_CERTIFIED;
     } else if (by->kind != NANN_SCORER_L2 && by->kind != NANN_SCORER_IP) {  // (L2 and the inner product read the index's rows: no table)
       return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": unknown scorer kind");
     }
   }
-  by->mismatch = d != ix->desc.d || dt != ix->desc.emb_dtype;
   return NANN_OK;
 }
 

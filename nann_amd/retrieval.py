@@ -315,65 +315,46 @@ def search(index, scorer, q, level_topn, want_counters=True, want_phase_ticks=Fa
     (pool_width(level_topn) ranks the whole pool), the outputs are [B, k] (k = F when not given): the first k allowed entries
     of the unfiltered answer at F, result.n_out[b] of them at the head of row b and zeros behind."""
     q = q.to(device=index.device, dtype=torch.float32).contiguous()
-    b = q.shape[0]
-    dev = index.device
+    return _traverse(index, scorer, q, False, level_topn, want_counters, want_phase_ticks, options, filter, k)
+
+
+# (model form, filtered) -> (the call that sizes the workspace -- None: index.workspace --, the search call)
+_TRAVERSE_CALLS = {(False, False): (None, "nann_search_opt"), (True, False): ("nann_search_model_workspace_bytes", "nann_search_model_opt"),
+                   (False, True): ("nann_search_filtered_workspace_bytes", "nann_search_filtered"),
+                   (True, True): ("nann_search_model_filtered_workspace_bytes", "nann_search_model_filtered")}
+
+
+def _traverse(index, by, x, model, level_topn, want_counters, want_phase_ticks, options, filter, k):
+    """The traversal family's call (_TRAVERSE_CALLS) for the b rows of x -- queries of a scorer `by`, sequences of a model one; with
+    a filter or a k the _filtered twin -- into fresh outputs and a workspace of the size its _workspace_bytes twin gives."""
+    dev, b = index.device, x.shape[0]
     t, tq, k_fetch = _level_topn_args(level_topn, b, dev)
-    if filter is not None or k is not None:
-        return _search_filtered(index, scorer, q, None, t, tq, k_fetch, want_counters, want_phase_ticks, options, filter, k)
-    k = k_fetch
-    out_ids = torch.empty((b, k), dtype=torch.int64, device=dev)
-    out_scores = torch.empty((b, k), dtype=torch.float32, device=dev)
-    out_index = torch.empty((b, k), dtype=torch.int32, device=dev)
-    status = torch.empty(b, dtype=torch.int32, device=dev)
-    counters = torch.zeros((b, 3, _lib.NUM_ROUNDS), dtype=torch.int32, device=dev) if want_counters else None
-    ticks = (torch.zeros((b, _lib.NUM_PHASES), dtype=torch.int64, device=dev)
-             if want_phase_ticks else None)
-    ws = index.workspace(list(t), b)
-    plan = _lib.SearchPlan()
-    assert not (want_phase_ticks and tq is not None), "phase ticks: uniform level_topn only"
-    with torch.cuda.device(dev):
-        _check(lib().nann_search_opt(index.handle, scorer.handle, _ptr(q), C.c_int64(b), t, _ptr(tq), _ptr(ws),
-                                     C.c_int64(ws.numel()), _ptr(out_ids), _ptr(out_scores), _ptr(out_index),
-                                     _ptr(status), _ptr(counters), _ptr(ticks),
-                                     C.byref(options) if options is not None else None, C.byref(plan), _stream()), "search")
-    return SearchResult(out_ids, out_scores, out_index, status, counters, ticks, _plan_dict(plan), ws,
-                        slot_reserve=int(options.slot_reserve) if options is not None else None)
-
-
-def _search_filtered(index, scorer, q, seq, t, tq, k_fetch, want_counters, want_phase_ticks, options, filter, k):
-    """nann_search_filtered (q) / nann_search_model_filtered (seq): the body of search / search_model with a filter or a k"""
-    dev = index.device
-    x = q if seq is None else seq
-    b = x.shape[0]
-    k = k_fetch if k is None else int(k)
-    kk = max(k, 0)
+    filtered = filter is not None or k is not None
+    k = int(k) if filtered and k is not None else k_fetch
+    kk = max(k, 0) if filtered else k
     out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
     out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
     out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
-    n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+    n_out = torch.zeros(b, dtype=torch.int32, device=dev) if filtered else None
     status = torch.empty(b, dtype=torch.int32, device=dev)
     counters = torch.zeros((b, 3, _lib.NUM_ROUNDS), dtype=torch.int32, device=dev) if want_counters else None
     ticks = torch.zeros((b, _lib.NUM_PHASES), dtype=torch.int64, device=dev) if want_phase_ticks else None
     assert not (want_phase_ticks and tq is not None), "phase ticks: uniform level_topn only"
-    nbytes = C.c_int64(0)
-    L = lib()
-    if seq is None:
-        _check(L.nann_search_filtered_workspace_bytes(index.handle, t, b, C.byref(nbytes)), "search")
+    L, (size_call, search_call) = lib(), _TRAVERSE_CALLS[model, filtered]
+    if size_call is None:
+        ws = index.workspace(list(t), b)
     else:
-        _check(L.nann_search_model_filtered_workspace_bytes(index.handle, scorer.handle, t, b, C.byref(nbytes)), "search")
-    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+        nbytes = C.c_int64(0)
+        handles = (index.handle, by.handle) if model else (index.handle,)  # (a model form is sized for its model)
+        _check(getattr(L, size_call)(*handles, t, C.c_int64(b), C.byref(nbytes)), "search")
+        ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
     plan = _lib.SearchPlan()
-    opt = C.byref(options) if options is not None else None
-    fa = _filter_args(filter, b, index)
+    ticks_arg = () if model else (_ptr(ticks),)  # the model forms have no phase ticks
+    filter_args = (_filter_args(filter, b, index), k, _ptr(n_out)) if filtered else ()  # what the filtered forms end on
     with torch.cuda.device(dev):
-        if seq is None:
-            _check(L.nann_search_filtered(index.handle, scorer.handle, _ptr(x), b, t, _ptr(tq), _ptr(ws), ws.numel(), _ptr(out_ids),
-                                          _ptr(out_scores), _ptr(out_index), _ptr(status), _ptr(counters), _ptr(ticks), opt,
-                                          C.byref(plan), fa, k, _ptr(n_out), _stream()), "search")
-        else:
-            _check(L.nann_search_model_filtered(index.handle, scorer.handle, _ptr(x), b, t, _ptr(tq), _ptr(ws), ws.numel(),
-                                                _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(status), _ptr(counters), opt,
-                                                C.byref(plan), fa, k, _ptr(n_out), _stream()), "search")
+        _check(getattr(L, search_call)(index.handle, by.handle, _ptr(x), C.c_int64(b), t, _ptr(tq), _ptr(ws), C.c_int64(ws.numel()),
+                                       _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(status), _ptr(counters), *ticks_arg,
+                                       C.byref(options) if options is not None else None, C.byref(plan), *filter_args, _stream()), "search")
     return SearchResult(out_ids, out_scores, out_index, status, counters, ticks, _plan_dict(plan), ws,
                         slot_reserve=int(options.slot_reserve) if options is not None else None, n_out=n_out)
 
@@ -384,28 +365,7 @@ def search_model(index, model, comm_seq, level_topn, want_counters=True, options
     reference's attention + DNN model -- the per-user projection runs once per request, then the fused traversal;
     nann_search_model_opt).  filter / k: as search() takes them (nann_search_model_filtered)."""
     seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
-    b = seq.shape[0]
-    dev = index.device
-    t, tq, k_fetch = _level_topn_args(level_topn, b, dev)
-    if filter is not None or k is not None:
-        return _search_filtered(index, model, None, seq, t, tq, k_fetch, want_counters, False, options, filter, k)
-    k = k_fetch
-    out_ids = torch.empty((b, k), dtype=torch.int64, device=dev)
-    out_scores = torch.empty((b, k), dtype=torch.float32, device=dev)
-    out_index = torch.empty((b, k), dtype=torch.int32, device=dev)
-    status = torch.empty(b, dtype=torch.int32, device=dev)
-    counters = torch.zeros((b, 3, _lib.NUM_ROUNDS), dtype=torch.int32, device=dev) if want_counters else None
-    nbytes = C.c_int64(0)
-    _check(lib().nann_search_model_workspace_bytes(index.handle, model.handle, t, C.c_int64(b), C.byref(nbytes)))
-    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-    plan = _lib.SearchPlan()
-    with torch.cuda.device(dev):
-        _check(lib().nann_search_model_opt(index.handle, model.handle, _ptr(seq), C.c_int64(b), t, _ptr(tq), _ptr(ws),
-                                           C.c_int64(ws.numel()), _ptr(out_ids), _ptr(out_scores), _ptr(out_index),
-                                           _ptr(status), _ptr(counters),
-                                           C.byref(options) if options is not None else None, C.byref(plan), _stream()), "search")
-    return SearchResult(out_ids, out_scores, out_index, status, counters, None, _plan_dict(plan), ws,
-                        slot_reserve=int(options.slot_reserve) if options is not None else None)
+    return _traverse(index, model, seq, True, level_topn, want_counters, False, options, filter, k)
 
 
 class SearchAllResult:

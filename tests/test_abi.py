@@ -84,7 +84,7 @@ def test_cpp_serving_host_builds_against_the_header_alone():
 def test_deprecated_search_entry_points_only_forward():
     """ABI v6: ONE search operation = nann_search_opt / nann_search_model_opt.  The five spellings of rounds 1-5 stay exported
     for hosts built against v5, each as a single `return` of the canonical call; the hosts of this repo call the pair only."""
-    src = open(os.path.join(ROOT, "nann_amd", "csrc", "nann_hip.hip")).read()
+    src = open(os.path.join(ROOT, "nann_amd", "csrc", "nann_traverse.hip")).read()
     hdr = open(os.path.join(ROOT, "include", "nann_hip.h")).read()
     for name, target in (("nann_search", "nann_search_opt"), ("nann_search_v", "nann_search_opt"), ("nann_search_ex", "nann_search_opt"),
                          ("nann_search_model", "nann_search_model_opt"), ("nann_search_model_v", "nann_search_model_opt")):

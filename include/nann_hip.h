@@ -177,9 +177,12 @@ int nann_topk(const float* values, int64_t n_rows, int64_t n_cols, int32_t k,
  * contract of each call otherwise unchanged (TopKV2 order, the -0 / +0 tie, status codes, batch independence; no table:
  * nann_scorer_prepare / release / table_bytes as for L2).  NOT supported: nann_search_eval, nann_search_eval_ex and
  * nann_search_eval_model return NANN_ERR_UNSUPPORTED for an IP scorer or model and launch nothing.
- * The index is the caller's: nann_hnsw_build* and the Python builders link rows by L2 distance, and a graph built that way is a
- * reasonable but not a tuned neighbourhood structure for inner-product search (rows of large norm attract queries from far
- * away in L2 terms); recall under IP is the caller's to measure, against nann_search_all with the same scorer.
+ * The index is the caller's, and it should be linked by the metric it is searched with: nann_hnsw_build_device_metric and
+ * nann_hnsw_append_device_metric (the Python builders: metric="ip") link rows by dist(a, b) = -<a, b>.  The builders' other
+ * entry points link by L2 distance, and a graph built that way is a poor neighbourhood structure for inner-product search
+ * where the rows' norms carry information (rows of large norm attract queries from far away in L2 terms; measured on such a
+ * corpus, DESIGN.md 4.6: recall@50 0.25 on the L2-linked graph, 0.87 on the IP-linked one).  Recall under IP is the caller's
+ * to measure, against nann_search_all with the same scorer.
  * Cosine similarity is not a kind of its own: normalise the rows (and the queries) and use either metric -- on unit vectors
  * -||q - x||^2 = 2 <q, x> - 2 ranks as <q, x> does. */
 typedef struct nann_scorer nann_scorer;
@@ -876,6 +879,27 @@ int nann_hnsw_append_device(const void* item_embs, int64_t n_old, int64_t n_new,
                             int32_t M, int32_t ef_construction, int32_t keep_pruned,
                             const int32_t* levels /*[host] n_old + n_new*/,
                             int32_t* adj0, int32_t* up_row, int32_t* adj_up, nann_stream_t stream);
+/* Build and append with a metric: the arguments of nann_hnsw_build_device_ex / nann_hnsw_append_device and `metric`, a
+ * nann_scorer_kind, the kind of scorer the index will be searched with.  NANN_SCORER_L2: the calls above (which are these with
+ * L2).  NANN_SCORER_IP: rows are linked by dist(a, b) = -<a, b>, smaller is nearer (Faiss' IndexHNSWFlat(d, M,
+ * METRIC_INNER_PRODUCT)); greedy descent, the ef_construction beam, the selection heuristic (keep c iff dist(c, s) >=
+ * dist(c, base) for every kept s) with its keep_pruned switch and the back-links' re-selection run on that distance unchanged.
+ * Per lane acc = fmaf(a_k, b_k, acc) from +0 over its 8 elements, the partials added in the xor butterfly, dist = 0 - sum:
+ * deterministic, not a promise of the scorer's bits.  NANN_SCORER_MLP: NANN_ERR_UNSUPPORTED; any other value:
+ * NANN_ERR_BAD_ARGUMENT; both before anything is launched or written.  Every other limit, status code, the validation pass of
+ * an append, the batch rule and the determinism promise are those of the calls above.  Appending with another metric than the
+ * graph was built with is the caller's error and is not checked (neither are the old rows).  The export calls below do not
+ * depend on the metric.  Under IP with the default heuristic rows are sparse (mean level-0 degree 2-3 on the test corpus of
+ * DESIGN.md 4.6 against 3-4 for L2 on the same rows: a kept neighbour of large norm dominates most later candidates);
+ * keep_pruned is the switch for denser rows. */
+int nann_hnsw_build_device_metric(const void* item_embs, int64_t n_items, int32_t d, int32_t emb_dtype, int32_t M,
+                                  int32_t ef_construction, int32_t keep_pruned, int32_t metric,
+                                  const int32_t* levels /*[host]*/, int32_t* adj0, int32_t* up_row, int32_t* adj_up,
+                                  nann_stream_t stream);
+int nann_hnsw_append_device_metric(const void* item_embs, int64_t n_old, int64_t n_new, int32_t d, int32_t emb_dtype,
+                                   int32_t M, int32_t ef_construction, int32_t keep_pruned, int32_t metric,
+                                   const int32_t* levels /*[host] n_old + n_new*/,
+                                   int32_t* adj0, int32_t* up_row, int32_t* adj_up, nann_stream_t stream);
 /* Export on the device: the builder's arrays -> what nann_index_desc takes (on_device = 1), by the rule of
  * build_hnsw_index.py:41-66 with start_level = 2 (the levels serving walks; any other value: NANN_ERR_UNSUPPORTED).  Two steps,
  * as nann_group_gather_count / _fill, because the sizes depend on the data.  adj0, up_row, adj_up (device) and levels [host]

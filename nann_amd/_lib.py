@@ -50,6 +50,7 @@ SYMBOLS = [
     "nann_comm_get_unique_id", "nann_comm_create", "nann_comm_destroy", "nann_comm_ranks", "nann_comm_set_timing", "nann_comm_last_breakdown", "nann_comm_wait", "nann_comm_abort", "nann_sharded_topk_workspace_bytes",
     "nann_sharded_topk", "nann_hnsw_draw_levels", "nann_hnsw_build_device", "nann_hnsw_build_device_ex",
     "nann_hnsw_append_device", "nann_hnsw_export_count", "nann_hnsw_export_fill",
+    "nann_hnsw_build_device_metric", "nann_hnsw_append_device_metric",
 ]
 
 
@@ -182,6 +183,11 @@ def lib():
         # (item_embs, n_old, n_new, d, emb_dtype, M, ef_construction, keep_pruned, levels, adj0, up_row, adj_up, stream)
         L.nann_hnsw_append_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 5
         L.nann_hnsw_append_device.restype = C.c_int
+        # the metric forms: (..., keep_pruned, metric, levels, ...)
+        L.nann_hnsw_build_device_metric.argtypes = [C.c_void_p, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 5
+        L.nann_hnsw_build_device_metric.restype = C.c_int
+        L.nann_hnsw_append_device_metric.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 5
+        L.nann_hnsw_append_device_metric.restype = C.c_int
         # (adj0, up_row, adj_up, levels, n, M, start_level, row_splits0, row_splits1, ...): count (nnz, n_enter, stream),
         # fill (nnz, values0, values1, enter_points, stream)
         head = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]

@@ -12,6 +12,8 @@
 // reference and its insertion order is thread-schedule dependent, so index CONTENTS are not a
 // parity target ("parity unpinned at the index-build boundary"); the file layout
 // and the structural invariants are, and tests/test_index_build.py checks them plus recall.
+// nann_hnsw_build_metric: the same with dist(a, b) = -<a, b> (Faiss' METRIC_INNER_PRODUCT) for an
+// index that is searched with the inner-product scorer.
 //
 // Host code, plain C++17 + std::thread; C ABI at the bottom.
 #include <algorithm>
@@ -39,6 +41,7 @@ struct Hnsw {
   std::vector<int32_t> neighbors;    // -1 = empty slot
   int64_t entry_point = -1;
   int max_level = -1;
+  bool ip = false;                   // link rows by -<a, b> instead of squared L2
 
   int nb_at(int level) const { return level == 0 ? 2 * M : M; }
   int cum(int level) const { return level == 0 ? 0 : 2 * M + (level - 1) * M; }
@@ -48,6 +51,10 @@ struct Hnsw {
   float dist(const float* a, int64_t j) const {
     const float* b = x + j * d;
     float s = 0.f;
+    if (ip) {  // smaller is nearer, as Faiss negates the inner product
+      for (int k = 0; k < d; ++k) s += a[k] * b[k];
+      return -s;
+    }
     for (int k = 0; k < d; ++k) {
       const float t = a[k] - b[k];
       s += t * t;
@@ -224,11 +231,16 @@ extern "C" {
 // Call once with neighbors == nullptr to obtain *n_slots and *max_levels (levels and offsets are
 // filled), then again with the buffers.  seed fixes the level draw; with n_threads == 1 the
 // whole build is deterministic (nodes inserted by descending level, then ascending id).
-int nann_hnsw_build(const float* x, int64_t n, int32_t d, int32_t M, int32_t ef_construction,
-                    uint64_t seed, int32_t n_threads, int32_t* levels, int64_t* offsets,
-                    int32_t* neighbors, int64_t* n_slots, int32_t* cum_nneighbor, int32_t* max_levels) {
+// metric: a nann_scorer_kind of include/nann_hip.h -- 0 (L2) or 2 (inner product: dist = -<a, b>); 1 (a model) returns 102
+// (unsupported), any other value 7 (bad argument).
+int nann_hnsw_build_metric(const float* x, int64_t n, int32_t d, int32_t M, int32_t ef_construction,
+                           uint64_t seed, int32_t n_threads, int32_t metric, int32_t* levels, int64_t* offsets,
+                           int32_t* neighbors, int64_t* n_slots, int32_t* cum_nneighbor, int32_t* max_levels) {
   if (!x || n <= 0 || d <= 0 || M < 2 || !levels || !offsets || !n_slots || !max_levels) return 7;
+  if (metric == 1) return 102;
+  if (metric != 0 && metric != 2) return 7;
   Hnsw h;
+  h.ip = metric == 2;
   h.n = n; h.d = d; h.M = M; h.ef_construction = ef_construction > 0 ? ef_construction : 40; h.x = x;
   h.levels.resize((size_t)n);
   std::mt19937_64 rng(seed);
@@ -299,6 +311,12 @@ int nann_hnsw_build(const float* x, int64_t n, int32_t d, int32_t M, int32_t ef_
   }
   std::memcpy(neighbors, h.neighbors.data(), (size_t)*n_slots * 4);
   return 0;
+}
+
+int nann_hnsw_build(const float* x, int64_t n, int32_t d, int32_t M, int32_t ef_construction,
+                    uint64_t seed, int32_t n_threads, int32_t* levels, int64_t* offsets,
+                    int32_t* neighbors, int64_t* n_slots, int32_t* cum_nneighbor, int32_t* max_levels) {
+  return nann_hnsw_build_metric(x, n, d, M, ef_construction, seed, n_threads, 0, levels, offsets, neighbors, n_slots, cum_nneighbor, max_levels);
 }
 
 }  // extern "C"

@@ -31,6 +31,10 @@
 // once (k_hb_check: the rules the kernels rely on, and the rows' fill counts), then the new nodes go in as a build's
 // would; build and append share hb_insert.  EXPORT (nann_hnsw_export_count / _fill): the arrays -> the per-level CSR
 // and enter points nann_index_create takes, on the device (tests/test_index_append_gpu.py).
+//
+// METRIC (nann_hnsw_build_device_metric / nann_hnsw_append_device_metric): the same kernels with dist(a, b) = -<a, b>, for an
+// index that is searched with the inner-product scorer.  Algorithms 1-4 run on that distance unchanged; the beam's keys take
+// an order-preserving map of its bits (hb_key).  tests/test_index_build_ip_gpu.py.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -129,7 +133,8 @@ __device__ __forceinline__ void hb_load8(const void* emb, size_t r, int d, int s
   }
 }
 
-// squared L2 over the LPR lanes of a row group: every lane of the group returns the total
+// a lane's partial (8 squared differences, or 8 products) summed over the LPR lanes of a row group: every lane of the group
+// returns the total
 template <int LPR>
 __device__ __forceinline__ float hb_group_sum(float acc) {
 #pragma unroll
@@ -137,9 +142,32 @@ __device__ __forceinline__ float hb_group_sum(float acc) {
   return acc;
 }
 
-// distance key: squared distances are >= 0, so their f32 bit patterns order like the values
+// The metric rows are linked by (a template parameter of every kernel below): kHbL2 = squared L2, kHbIp = -<a, b> (Faiss'
+// convention for METRIC_INNER_PRODUCT: smaller is nearer).  The L2 instances are the code they were before the parameter.
+constexpr int kHbL2 = 0, kHbIp = 1;
+
+// distance key.  L2: squared distances are >= 0, so their f32 bit patterns order like the values.  IP: distances take both
+// signs, so the pattern goes through the order-preserving map of a radix sort -- all bits flipped when the sign bit is set,
+// else the sign bit set; -0 is made +0 first.  Either way kKeyInf (a NaN pattern no distance has) sorts last.
+template <int MT>
 __device__ __forceinline__ unsigned long long hb_key(float dist, int id) {
-  return ((unsigned long long)__float_as_uint(dist + 0.0f) << 32) | (uint32_t)id;
+  uint32_t u = __float_as_uint(dist + 0.0f);
+  if constexpr (MT == kHbIp) u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (uint32_t)id;
+}
+
+// the distance a key's upper half holds
+template <int MT>
+__device__ __forceinline__ float hb_key_dist(uint32_t u) {
+  if constexpr (MT == kHbIp) u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  return __uint_as_float(u);
+}
+
+// a group's sum -> the distance: L2 the sum of squares itself, IP 0 - <a, b>
+template <int MT>
+__device__ __forceinline__ float hb_dist_of_sum(float sum) {
+  if constexpr (MT == kHbIp) return 0.0f - sum;
+  return sum;
 }
 
 constexpr int kHbMaxEf = 40;  // ef_construction this build stages rows for (Faiss' default)
@@ -156,10 +184,10 @@ struct HbWaveLds {
 };
 
 // the selection heuristic (alg. 4 / Faiss shrink_neighbor_list) over candidates sorted ascending by distance to the
-// base: keep c iff it is closer to the base than to every candidate kept so far; at most `cap`.  cand_key: lane i =
-// i-th nearest (kKeyInf beyond n).  Rows are staged into `rows` (LDS, n x d halves).  Returns the keep mask
-// (bit i = candidate i kept; wave-uniform).
-template <int LPR, int DT>
+// base: keep c iff it is closer to the base than to every candidate kept so far (dist(c, s) >= dist(c, base) for every kept
+// s, in the kernel's metric); at most `cap`.  cand_key: lane i = i-th nearest (kKeyInf beyond n).  Rows are staged into
+// `rows` (LDS, n x d halves).  Returns the keep mask (bit i = candidate i kept; wave-uniform).
+template <int LPR, int DT, int MT>
 __device__ __forceinline__ uint64_t wave_select(const HbGraph& g, unsigned long long cand_key, int n, int cap,
                                                 uint16_t* rows, int lane) {
   constexpr int GPW = 64 / LPR;
@@ -177,7 +205,7 @@ __device__ __forceinline__ uint64_t wave_select(const HbGraph& g, unsigned long 
   uint64_t kept = 0;
   int n_kept = 0;
   for (int c = 0; c < n && n_kept < cap; ++c) {
-    const float dc = __uint_as_float((uint32_t)__shfl((int)(uint32_t)(cand_key >> 32), c));  // distance of c to the base
+    const float dc = hb_key_dist<MT>((uint32_t)__shfl((int)(uint32_t)(cand_key >> 32), c));  // distance of c to the base
     bool dominated = false;
     if (n_kept > 0) {
       // distances of c to the kept candidates, GPW pairs per step
@@ -206,12 +234,17 @@ __device__ __forceinline__ uint64_t wave_select(const HbGraph& g, unsigned long 
             float a, b;
             if (DT == 0) { a = half_bits_to_float(w[i] & 0xffffu); b = half_bits_to_float(w[i] >> 16); }
             else { a = bf16_bits_to_float(w[i] & 0xffffu); b = bf16_bits_to_float(w[i] >> 16); }
-            const float t0 = xc[2 * i] - a, t1 = xc[2 * i + 1] - b;
-            acc = __fmaf_rn(t0, t0, acc);
-            acc = __fmaf_rn(t1, t1, acc);
+            if constexpr (MT == kHbIp) {
+              acc = __fmaf_rn(xc[2 * i], a, acc);
+              acc = __fmaf_rn(xc[2 * i + 1], b, acc);
+            } else {
+              const float t0 = xc[2 * i] - a, t1 = xc[2 * i + 1] - b;
+              acc = __fmaf_rn(t0, t0, acc);
+              acc = __fmaf_rn(t1, t1, acc);
+            }
           }
         }
-        acc = hb_group_sum<LPR>(acc);
+        acc = hb_dist_of_sum<MT>(hb_group_sum<LPR>(acc));
         dominated = __ballot(s >= 0 && acc < dc) != 0ull;
         for (int k = 0; k < GPW && todo; ++k) todo &= todo - 1;  // the GPW bits just processed
       }
@@ -246,7 +279,7 @@ struct HbBatch {
   int pair_cap;
 };
 
-template <int LPR, int DT>
+template <int LPR, int DT, int MT>
 __global__ __launch_bounds__(kHbWaves * 64) void k_hb_search(HbGraph g, HbBatch b) {
   __shared__ __attribute__((aligned(16))) HbWaveLds<LPR * 8> lds_all[kHbWaves];
   constexpr int GPW = 64 / LPR;
@@ -264,8 +297,11 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_search(HbGraph g, HbBatch 
     hb_load8<DT>(g.emb, (size_t)id, g.d, sub, x);
     float acc = 0.0f;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { const float t = q[k] - x[k]; acc = __fmaf_rn(t, t, acc); }
-    return hb_group_sum<LPR>(acc);
+    for (int k = 0; k < 8; ++k) {
+      if constexpr (MT == kHbIp) acc = __fmaf_rn(q[k], x[k], acc);
+      else { const float t = q[k] - x[k]; acc = __fmaf_rn(t, t, acc); }
+    }
+    return hb_dist_of_sum<MT>(hb_group_sum<LPR>(acc));
   };
   auto visit = [&](int id) -> bool {  // true if the id was not in the set (and is now)
     uint32_t h = ((uint32_t)id * 2654435761u) >> 20;  // 12 bits
@@ -283,7 +319,7 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_search(HbGraph g, HbBatch 
   if (lane == 0) visit(ep);
   int n_vis = 1;
   // the beam: lane i = i-th best (distance, id); low bit of `expanded` per lane
-  unsigned long long beam = lane == 0 ? hb_key(d_ep, ep) : kKeyInf;
+  unsigned long long beam = lane == 0 ? hb_key<MT>(d_ep, ep) : kKeyInf;
   bool expanded = false;
   const int ef = b.ef;
   for (;;) {
@@ -314,7 +350,7 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_search(HbGraph g, HbBatch 
     }
     __builtin_amdgcn_wave_barrier();
     unsigned long long fresh_key = kKeyInf;
-    if (lane < n_new) fresh_key = hb_key(L.dist[lane], L.list[lane]);
+    if (lane < n_new) fresh_key = hb_key<MT>(L.dist[lane], L.list[lane]);
     // merge; a lane's `expanded` flag travels with its key: carry it in the key's bit 31 (ids are < 2^31)
     const unsigned long long tagged = beam == kKeyInf ? beam : (beam | (expanded ? 0x80000000ull : 0ull));
     const unsigned long long merged = wave_merge64(tagged, fresh_key, lane);
@@ -333,7 +369,7 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_search(HbGraph g, HbBatch 
   int32_t* cnt;
   int32_t* my_row = hb_row(g, u, b.level, &cap, &cnt);
   uint16_t* rows = reinterpret_cast<uint16_t*>(L.stage);  // the search is over: its table becomes row staging
-  const uint64_t kept = wave_select<LPR, DT>(g, beam, n_cand, cap, rows, lane);
+  const uint64_t kept = wave_select<LPR, DT, MT>(g, beam, n_cand, cap, rows, lane);
   const int n_kept = popc64(kept);
   const bool mine = (kept >> lane) & 1ull;
   const int pos = popc64(kept & lanemask_lt(lane));
@@ -365,7 +401,7 @@ __global__ void k_hb_runs(const uint32_t* dst, int n_pairs, int32_t* run_first, 
 // pair buffer is filled by batch position and the sort is stable).  Room left: append.  Full: re-select among the
 // row + the new link (Faiss add_link), one incoming link at a time.  The row lives in the lanes (lane i = link i)
 // and is written back once.
-template <int LPR, int DT>
+template <int LPR, int DT, int MT>
 __global__ __launch_bounds__(kHbWaves * 64) void k_hb_backlink(HbGraph g, int level, const uint32_t* pair_dst,
                                                                const uint32_t* pair_src, const int32_t* run_first,
                                                                const int32_t* run_len, const int* n_runs) {
@@ -407,8 +443,11 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_backlink(HbGraph g, int le
       hb_load8<DT>(g.emb, (size_t)id, g.d, sub, x);
       float acc = 0.0f;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) { const float t = qv[k] - x[k]; acc = __fmaf_rn(t, t, acc); }
-      acc = hb_group_sum<LPR>(acc);
+      for (int k = 0; k < 8; ++k) {
+        if constexpr (MT == kHbIp) acc = __fmaf_rn(qv[k], x[k], acc);
+        else { const float t = qv[k] - x[k]; acc = __fmaf_rn(t, t, acc); }
+      }
+      acc = hb_dist_of_sum<MT>(hb_group_sum<LPR>(acc));
       if (i < cap && sub == 0) dist[i] = acc;
       if (i == cap && sub == 0) dist[63] = cap == 64 ? dist[63] : acc;  // (placeholder slot; the extra's distance is re-derived below)
     }
@@ -419,12 +458,15 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_backlink(HbGraph g, int le
       hb_load8<DT>(g.emb, (size_t)s, g.d, sub, x);
       float acc = 0.0f;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) { const float t = qv[k] - x[k]; acc = __fmaf_rn(t, t, acc); }
-      d_extra = hb_group_sum<LPR>(acc);
+      for (int k = 0; k < 8; ++k) {
+        if constexpr (MT == kHbIp) acc = __fmaf_rn(qv[k], x[k], acc);
+        else { const float t = qv[k] - x[k]; acc = __fmaf_rn(t, t, acc); }
+      }
+      d_extra = hb_dist_of_sum<MT>(hb_group_sum<LPR>(acc));
     }
-    unsigned long long key = lane < cap ? hb_key(dist[lane], link) : kKeyInf;
+    unsigned long long key = lane < cap ? hb_key<MT>(dist[lane], link) : kKeyInf;
     key = wave_sort64(key, lane);
-    const unsigned long long extra = hb_key(d_extra, s);
+    const unsigned long long extra = hb_key<MT>(d_extra, s);
     const int before = popc64(__ballot(key < extra));  // the extra candidate's place in the ascending order
     const int src_lane = lane <= before ? lane : lane - 1;
     const unsigned long long from = ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(key >> 32), src_lane) << 32) |
@@ -432,7 +474,7 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_backlink(HbGraph g, int le
     unsigned long long cand = lane == before ? extra : from;
     const int n_cand = min(cap + 1, 64);
     if (lane >= n_cand) cand = kKeyInf;
-    const uint64_t kept = wave_select<LPR, DT>(g, cand, n_cand, cap, rows, lane);
+    const uint64_t kept = wave_select<LPR, DT, MT>(g, cand, n_cand, cap, rows, lane);
     const int n_kept = popc64(kept);
     __builtin_amdgcn_wave_barrier();
     if ((kept >> lane) & 1ull) ids[popc64(kept & lanemask_lt(lane))] = (int)(uint32_t)cand;
@@ -454,20 +496,20 @@ int dev_alloc(T** p, size_t n, std::vector<void*>* owned) {
   return NANN_OK;
 }
 
-template <int LPR, int DT>
+template <int LPR, int DT, int MT>
 int run_batch_level(const HbGraph& g, const HbBatch& b, hipStream_t st) {
   const unsigned blocks = (unsigned)((b.n + kHbWaves - 1) / kHbWaves);
-  hipLaunchKernelGGL((k_hb_search<LPR, DT>), dim3(blocks), dim3(kHbWaves * 64), 0, st, g, b);
+  hipLaunchKernelGGL((k_hb_search<LPR, DT, MT>), dim3(blocks), dim3(kHbWaves * 64), 0, st, g, b);
   HB_TRY(hipGetLastError());
   return NANN_OK;
 }
 
-template <int LPR, int DT>
+template <int LPR, int DT, int MT>
 int run_backlink(const HbGraph& g, int level, const uint32_t* dst, const uint32_t* src, const int32_t* rf, const int32_t* rl,
                  const int* n_runs, int max_runs, hipStream_t st) {
   const size_t per_wave = (size_t)kHbMaxCand * g.d * 2 + 1024;
   const size_t lds = per_wave * kHbWaves;
-  auto kern = k_hb_backlink<LPR, DT>;
+  auto kern = k_hb_backlink<LPR, DT, MT>;
   if (lds > 48 * 1024)
     HB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const unsigned blocks = (unsigned)((max_runs + kHbWaves - 1) / kHbWaves);
@@ -610,24 +652,29 @@ int hb_hip_rc(hipError_t e, const char* what) {
 // graph, <= 16384, <= batch_cap.  A node with MORE levels than the entry point (append only: a build inserts in descending
 // order) is a batch of its own, searched and linked on the levels the graph has, T - 1 .. 0; its rows above stay empty,
 // and it is the entry point from then on -- so no row is ever looked up on a level its node does not have.
-int hb_insert(const char* who, const HbGraph& g, int emb_dtype, const int32_t* levels, const std::vector<int32_t>& order, int pos0, int64_t base,
+int hb_insert(const char* who, const HbGraph& g, int emb_dtype, int metric, const int32_t* levels, const std::vector<int32_t>& order, int pos0, int64_t base,
               int entry, int T, int batch_cap, int ef, HbScratch& s, hipStream_t st) {
   const int n_order = (int)order.size(), d = g.d, pair_cap = s.pair_cap;
   std::vector<int32_t> h_entry((size_t)s.max_batch, entry);
   auto search = [&](const HbBatch& b) -> int {
-#define HB_CASE(LPR_)                                                                \
-  return emb_dtype == NANN_F16 ? run_batch_level<LPR_, 0>(g, b, st) : run_batch_level<LPR_, 1>(g, b, st)
-    if (d == 64) HB_CASE(8);
-    if (d == 128) HB_CASE(16);
+#define HB_CASE(LPR_)                                                                                      \
+  if (metric == NANN_SCORER_IP)                                                                            \
+    return emb_dtype == NANN_F16 ? run_batch_level<LPR_, 0, kHbIp>(g, b, st) : run_batch_level<LPR_, 1, kHbIp>(g, b, st); \
+  return emb_dtype == NANN_F16 ? run_batch_level<LPR_, 0, kHbL2>(g, b, st) : run_batch_level<LPR_, 1, kHbL2>(g, b, st)
+    if (d == 64) { HB_CASE(8); }
+    if (d == 128) { HB_CASE(16); }
     HB_CASE(32);
 #undef HB_CASE
   };
   auto backlink = [&](int level, int n_pairs) -> int {
 #define HB_CASE(LPR_)                                                                                                        \
-  return emb_dtype == NANN_F16 ? run_backlink<LPR_, 0>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st) \
-                               : run_backlink<LPR_, 1>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st)
-    if (d == 64) HB_CASE(8);
-    if (d == 128) HB_CASE(16);
+  if (metric == NANN_SCORER_IP)                                                                                              \
+    return emb_dtype == NANN_F16 ? run_backlink<LPR_, 0, kHbIp>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st) \
+                                 : run_backlink<LPR_, 1, kHbIp>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st); \
+  return emb_dtype == NANN_F16 ? run_backlink<LPR_, 0, kHbL2>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st) \
+                               : run_backlink<LPR_, 1, kHbL2>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st)
+    if (d == 64) { HB_CASE(8); }
+    if (d == 128) { HB_CASE(16); }
     HB_CASE(32);
 #undef HB_CASE
   };
@@ -677,6 +724,13 @@ int hb_check_shape(const char* who, int64_t n_total, int32_t d, int32_t emb_dtyp
   return NANN_OK;
 }
 
+// the metric of a build or an append: a nann_scorer_kind, checked before anything is launched or written
+int hb_check_metric(const char* who, int32_t metric) {
+  if (metric == NANN_SCORER_L2 || metric == NANN_SCORER_IP) return NANN_OK;
+  if (metric == NANN_SCORER_MLP) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": rows are linked by L2 or inner product, not by a model");
+  return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": metric must be NANN_SCORER_L2 or NANN_SCORER_IP");
+}
+
 constexpr int kHbAppendDiv = 64;  // an append goes in in at least this many batches (8 and 32 measured short)
 
 }  // namespace
@@ -703,14 +757,21 @@ int nann_hnsw_draw_levels(int64_t n_items, int32_t M, uint64_t seed, int32_t* le
 int nann_hnsw_build_device(const void* item_embs, int64_t n_items, int32_t d, int32_t emb_dtype, int32_t M,
                            int32_t ef_construction, const int32_t* levels, int32_t* adj0, int32_t* up_row,
                            int32_t* adj_up, nann_stream_t stream) {
-  return nann_hnsw_build_device_ex(item_embs, n_items, d, emb_dtype, M, ef_construction, 0, levels, adj0, up_row, adj_up, stream);
+  return nann_hnsw_build_device_metric(item_embs, n_items, d, emb_dtype, M, ef_construction, 0, NANN_SCORER_L2, levels, adj0, up_row, adj_up, stream);
 }
 
 int nann_hnsw_build_device_ex(const void* item_embs, int64_t n_items, int32_t d, int32_t emb_dtype, int32_t M,
                               int32_t ef_construction, int32_t keep_pruned, const int32_t* levels, int32_t* adj0,
                               int32_t* up_row, int32_t* adj_up, nann_stream_t stream) {
+  return nann_hnsw_build_device_metric(item_embs, n_items, d, emb_dtype, M, ef_construction, keep_pruned, NANN_SCORER_L2, levels, adj0, up_row, adj_up, stream);
+}
+
+int nann_hnsw_build_device_metric(const void* item_embs, int64_t n_items, int32_t d, int32_t emb_dtype, int32_t M,
+                                  int32_t ef_construction, int32_t keep_pruned, int32_t metric, const int32_t* levels,
+                                  int32_t* adj0, int32_t* up_row, int32_t* adj_up, nann_stream_t stream) {
   if (!item_embs || !levels || !adj0 || !up_row || n_items <= 0)
     return fail(NANN_ERR_BAD_ARGUMENT, "nann_hnsw_build_device: null argument");
+  if (int rcm = hb_check_metric("nann_hnsw_build_device", metric)) return rcm;
   const int ef = ef_construction > 0 ? ef_construction : 40;
   if (int rc0 = hb_check_shape("nann_hnsw_build_device", n_items, d, emb_dtype, M, ef)) return rc0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -744,17 +805,25 @@ int nann_hnsw_build_device_ex(const void* item_embs, int64_t n_items, int32_t d,
   g.emb = item_embs; g.adj0 = adj0; g.cnt0 = s.cnt0; g.up_row = up_row; g.adj_up = adj_up; g.cnt_up = s.cnt_up;
   g.n_items = N; g.d = d; g.M = M; g.keep_pruned = keep_pruned ? 1 : 0;
   // order[0] is the entry point: inserted with no links
-  return hb_insert("nann_hnsw_build_device", g, emb_dtype, levels, order, 1, 0, order[0], levels[order[0]], 0x7fffffff, ef, s, st);
+  return hb_insert("nann_hnsw_build_device", g, emb_dtype, metric, levels, order, 1, 0, order[0], levels[order[0]], 0x7fffffff, ef, s, st);
 }
 
 int nann_hnsw_append_device(const void* item_embs, int64_t n_old, int64_t n_new, int32_t d, int32_t emb_dtype, int32_t M,
                             int32_t ef_construction, int32_t keep_pruned, const int32_t* levels, int32_t* adj0,
                             int32_t* up_row, int32_t* adj_up, nann_stream_t stream) {
+  return nann_hnsw_append_device_metric(item_embs, n_old, n_new, d, emb_dtype, M, ef_construction, keep_pruned, NANN_SCORER_L2, levels, adj0, up_row, adj_up, stream);
+}
+
+int nann_hnsw_append_device_metric(const void* item_embs, int64_t n_old, int64_t n_new, int32_t d, int32_t emb_dtype, int32_t M,
+                                   int32_t ef_construction, int32_t keep_pruned, int32_t metric, const int32_t* levels,
+                                   int32_t* adj0, int32_t* up_row, int32_t* adj_up, nann_stream_t stream) {
   const char* who = "nann_hnsw_append_device";
   if (!item_embs || !levels || !adj0 || !up_row || n_old < 1 || n_new < 0)
     return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument, n_old < 1 or n_new < 0");
+  int rc = hb_check_metric(who, metric);
+  if (rc) return rc;
   const int ef = ef_construction > 0 ? ef_construction : 40;
-  int rc = hb_check_shape(who, n_old > 0x7fffffffll - n_new ? 0x80000000ll : n_old + n_new, d, emb_dtype, M, ef);
+  rc = hb_check_shape(who, n_old > 0x7fffffffll - n_new ? 0x80000000ll : n_old + n_new, d, emb_dtype, M, ef);
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N0 = (int)n_old, N1 = (int)n_new, N = N0 + N1;
@@ -816,7 +885,7 @@ int nann_hnsw_append_device(const void* item_embs, int64_t n_old, int64_t n_new,
   g.emb = item_embs; g.adj0 = adj0; g.cnt0 = s.cnt0; g.up_row = up_row; g.adj_up = adj_up; g.cnt_up = s.cnt_up;
   g.n_items = N; g.d = d; g.M = M; g.keep_pruned = keep_pruned ? 1 : 0;
   const int batch_cap = std::max(1, (N1 + kHbAppendDiv - 1) / kHbAppendDiv);
-  return hb_insert(who, g, emb_dtype, levels, order, 0, n_old, entry, levels[entry], batch_cap, ef, s, st);
+  return hb_insert(who, g, emb_dtype, metric, levels, order, 0, n_old, entry, levels[entry], batch_cap, ef, s, st);
 }
 
 namespace {

@@ -48,9 +48,20 @@ def _lib():
     return _LIB
 
 
-def build_hnsw(embeddings, num_neighbors=32, ef_construction=40, seed=0, n_threads=None):
+_METRICS = {"l2": 0, "ip": 2}  # nann_scorer_kind (include/nann_hip.h): the scorer the index is searched with
+
+
+def _metric_kind(metric):
+    if not isinstance(metric, str) or metric not in _METRICS:
+        raise ValueError(f"metric must be 'l2' or 'ip', not {metric!r}")
+    return _METRICS[metric]
+
+
+def build_hnsw(embeddings, num_neighbors=32, ef_construction=40, seed=0, n_threads=None, metric="l2"):
     """-> dict(levels i32[N], offsets i64[N+1], neighbors i32[slots], cum_nneighbor_per_level),
-    the arrays build_hnsw_index.py:36-39 reads from faiss' `index.hnsw`."""
+    the arrays build_hnsw_index.py:36-39 reads from faiss' `index.hnsw`.  metric: "l2", or "ip" for an index that is searched
+    with the inner-product scorer -- rows are linked by dist(a, b) = -<a, b> (Faiss' METRIC_INNER_PRODUCT)."""
+    kind = _metric_kind(metric)
     x = np.ascontiguousarray(embeddings, dtype=np.float32)
     n, d = x.shape
     if n_threads is None:
@@ -61,12 +72,12 @@ def build_hnsw(embeddings, num_neighbors=32, ef_construction=40, seed=0, n_threa
     n_slots, max_levels = C.c_int64(0), C.c_int32(0)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
     args = [p(x), C.c_int64(n), C.c_int32(d), C.c_int32(num_neighbors), C.c_int32(ef_construction),
-            C.c_uint64(seed), C.c_int32(n_threads), p(levels), p(offsets)]
-    rc = _lib().nann_hnsw_build(*args, None, C.byref(n_slots), p(cum), C.byref(max_levels))
+            C.c_uint64(seed), C.c_int32(n_threads), C.c_int32(kind), p(levels), p(offsets)]
+    rc = _lib().nann_hnsw_build_metric(*args, None, C.byref(n_slots), p(cum), C.byref(max_levels))
     if rc:
         raise ValueError(f"nann_hnsw_build: bad argument ({rc})")
     neighbors = np.empty(n_slots.value, np.int32)
-    rc = _lib().nann_hnsw_build(*args, p(neighbors), C.byref(n_slots), p(cum), C.byref(max_levels))
+    rc = _lib().nann_hnsw_build_metric(*args, p(neighbors), C.byref(n_slots), p(cum), C.byref(max_levels))
     if rc:
         raise ValueError(f"nann_hnsw_build: bad argument ({rc})")
     return {"levels": levels, "offsets": offsets, "neighbors": neighbors,
@@ -95,9 +106,9 @@ def export_levels(raw, start_level=2):
     return {"enter_points": enter_points, "nb_values": nb_values, "nb_row_splits": nb_row_splits}
 
 
-def build_and_save_index(embeddings, start_level, num_neighbors, output_dir, seed=0, n_threads=None):
-    """Same name and arguments as the reference's function (build_hnsw_index.py:33)."""
-    raw = build_hnsw(embeddings, num_neighbors=num_neighbors, seed=seed, n_threads=n_threads)
+def build_and_save_index(embeddings, start_level, num_neighbors, output_dir, seed=0, n_threads=None, metric="l2"):
+    """Same name and arguments as the reference's function (build_hnsw_index.py:33); metric as build_hnsw's."""
+    raw = build_hnsw(embeddings, num_neighbors=num_neighbors, seed=seed, n_threads=n_threads, metric=metric)
     ex = export_levels(raw, start_level)
     os.makedirs(output_dir, exist_ok=True)
     np.save(os.path.join(output_dir, "enter_points.npy"), ex["enter_points"])
@@ -131,15 +142,18 @@ def _export_torch(levels, adj0, up_row, adj_up, m, start_level):
 
 
 def build_hnsw_gpu(item_embs, num_neighbors=32, ef_construction=40, seed=0, start_level=2, want_raw=False,
-                   keep_pruned=False, want_state=False):
+                   keep_pruned=False, want_state=False, metric="l2"):
     """HNSW(M) over the rows of `item_embs` (CUDA tensor f16 | bf16 [N, d], or a numpy f16 array) built ON THE GPU
-    (nann_hnsw_build_device).  Returns the export of build_hnsw_index.py:41-66 -- {"enter_points", "nb_values"
+    (nann_hnsw_build_device_metric).  Returns the export of build_hnsw_index.py:41-66 -- {"enter_points", "nb_values"
     [start_level], "nb_row_splits"[start_level], "levels"} as numpy arrays (values int64 on disk) -- assembled with
     torch on the device; with want_raw also the Faiss-shaped raw arrays of build_hnsw().  keep_pruned: the selection
     heuristic's keepPrunedConnections switch (off in Faiss, hence in the reference's graphs): rows fill up to their cap --
     the dense-graph family (mean level-0 degree ~55 of 64 instead of ~17).  want_state: also "state", the builder's own
-    arrays on the device (item_embs, adj0, up_row, adj_up) with levels, M, ef_construction and keep_pruned -- what
-    append_hnsw_gpu() grows and export_hnsw_gpu() turns into an Index without leaving the device."""
+    arrays on the device (item_embs, adj0, up_row, adj_up) with levels, M, ef_construction, keep_pruned and metric -- what
+    append_hnsw_gpu() grows and export_hnsw_gpu() turns into an Index without leaving the device.  metric: "l2", or "ip" for an
+    index that is searched with the inner-product scorer: rows are linked by dist(a, b) = -<a, b>.  Under "ip" the default
+    heuristic leaves sparse rows (mean level-0 degree 2-3 where L2 on the same rows gives 3-4); keep_pruned fills them."""
+    kind = _metric_kind(metric)
     import torch
     from . import _lib
     from .ops import _check, _ptr, _stream, _DT
@@ -156,14 +170,13 @@ def build_hnsw_gpu(item_embs, num_neighbors=32, ef_construction=40, seed=0, star
     up_row = torch.empty(n, dtype=torch.int32, device=x.device)
     adj_up = torch.empty((max(n_up.value, 1), m), dtype=torch.int32, device=x.device)
     torch.cuda.synchronize()
-    _check(L.nann_hnsw_build_device_ex(_ptr(x), C.c_int64(n), C.c_int32(d), C.c_int32(_DT[x.dtype]), C.c_int32(m),
-                                       C.c_int32(ef_construction), C.c_int32(1 if keep_pruned else 0),
-                                       levels.ctypes.data_as(C.c_void_p), _ptr(adj0), _ptr(up_row), _ptr(adj_up), _stream()),
+    _check(L.nann_hnsw_build_device_metric(_ptr(x), n, d, _DT[x.dtype], m, int(ef_construction), 1 if keep_pruned else 0, kind,
+                                           levels.ctypes.data_as(C.c_void_p), _ptr(adj0), _ptr(up_row), _ptr(adj_up), _stream()),
            "hnsw build")
     out = _export_torch(levels, adj0, up_row, adj_up, m, start_level)
     if want_state:
         out["state"] = {"item_embs": x, "adj0": adj0, "up_row": up_row, "adj_up": adj_up, "levels": levels, "M": m,
-                        "ef_construction": int(ef_construction), "keep_pruned": bool(keep_pruned)}
+                        "ef_construction": int(ef_construction), "keep_pruned": bool(keep_pruned), "metric": metric}
     if want_raw:
         cum = np.concatenate([[0], 2 * m + m * np.arange(int(levels.max()))]).astype(np.int32)
         offsets = np.zeros(n + 1, np.int64)
@@ -180,7 +193,7 @@ def build_hnsw_gpu(item_embs, num_neighbors=32, ef_construction=40, seed=0, star
 
 def append_hnsw_gpu(state, new_rows, seed, start_level=2, want_export=True):
     """Append `new_rows` ([n_new, d], the dtype of the state's rows) to the graph of `state` (build_hnsw_gpu(want_state=True)
-    or an earlier append) ON THE GPU (nann_hnsw_append_device).  The rows are concatenated and the three arrays grown into NEW
+    or an earlier append) ON THE GPU (nann_hnsw_append_device_metric, with the state's "metric"; a state without one is "l2").  The rows are concatenated and the three arrays grown into NEW
     tensors: the input state is left as it is, so an index still serving from it is safe (back-links rewrite old rows).  The
     new nodes' levels are drawn with `seed`.  Returns what build_hnsw_gpu(want_state=True) returns, over the grown corpus;
     want_export=False: {"levels", "state"} only, without the torch export and its copy to the host -- the live path, which goes
@@ -189,6 +202,8 @@ def append_hnsw_gpu(state, new_rows, seed, start_level=2, want_export=True):
     from . import _lib
     from .ops import _check, _ptr, _stream, _DT
     L = _lib.lib()
+    metric = state.get("metric", "l2")
+    kind = _metric_kind(metric)
     x0, m = state["item_embs"], int(state["M"])
     n_old, d = x0.shape
     new = new_rows if isinstance(new_rows, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(new_rows))
@@ -211,12 +226,12 @@ def append_hnsw_gpu(state, new_rows, seed, start_level=2, want_export=True):
     adj_up = torch.full((max(n_up, 1), m), -1, dtype=torch.int32, device=x.device)
     adj_up[:n_up_old] = state["adj_up"][:n_up_old]
     torch.cuda.synchronize()
-    _check(L.nann_hnsw_append_device(_ptr(x), n_old, n_new, d, _DT[x.dtype], m, int(state["ef_construction"]),
-                                     1 if state["keep_pruned"] else 0, levels.ctypes.data_as(C.c_void_p), _ptr(adj0),
-                                     _ptr(up_row), _ptr(adj_up), _stream()), "hnsw append")
+    _check(L.nann_hnsw_append_device_metric(_ptr(x), n_old, n_new, d, _DT[x.dtype], m, int(state["ef_construction"]),
+                                            1 if state["keep_pruned"] else 0, kind, levels.ctypes.data_as(C.c_void_p), _ptr(adj0),
+                                            _ptr(up_row), _ptr(adj_up), _stream()), "hnsw append")
     out = _export_torch(levels, adj0, up_row, adj_up, m, start_level) if want_export else {"levels": levels}
     out["state"] = {"item_embs": x, "adj0": adj0, "up_row": up_row, "adj_up": adj_up, "levels": levels, "M": m,
-                    "ef_construction": int(state["ef_construction"]), "keep_pruned": bool(state["keep_pruned"])}
+                    "ef_construction": int(state["ef_construction"]), "keep_pruned": bool(state["keep_pruned"]), "metric": metric}
     return out
 
 

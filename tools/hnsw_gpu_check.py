@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """GPU HNSW builder vs the CPU builder on the bench corpus: build time, degree statistics, structural invariants, and
-recall@200 of the serving traversal (L2) against brute force on each graph.  usage: tools/hnsw_gpu_check.py [items] [dim] [ef] [dtype]"""
+recall@200 of the serving traversal (L2) against brute force on each graph.
+usage: tools/hnsw_gpu_check.py [items] [dim] [ef] [dtype] [nocpu] [ip]
+With `ip`: the device builder with metric="ip" next to metric="l2" on the same rows -- the bench corpus with its rows scaled by
+per-row factors in [0.25, 4], so that norms carry information --: build seconds, mean degrees, and recall@200 of the
+inner-product traversal against search_all with the same scorer on the IP-linked and on the L2-linked graph
+(profiles/hnsw_ip_build.txt)."""
 import os
 import sys
 import time
@@ -46,12 +51,44 @@ def recall(g, dim, ef, items, nq=64):
     return round(hits / max(tot, 1), 4), float((st == 0).mean()), float(r.counters[st == 0][:, 2, :].sum(1).float().mean())
 
 
+def ip_check(items, dim, ef, dtype, nq=256):
+    """the device builder under both metrics on rows whose norms vary by 16x, searched by inner product"""
+    ncl = bench.n_clusters_for(items, ef)
+    embs, _ = synth.make_corpus(items, dim, n_clusters=ncl, noise=1.0, seed=1234, item_seed=1334)
+    factors = np.exp2(np.random.default_rng(7).uniform(-2.0, 2.0, items)).astype(np.float32)
+    x = embs.astype(np.float32) * factors[:, None]
+    rows = torch.as_tensor(x).cuda().to(torch.bfloat16 if dtype == "bf16" else torch.float16)
+    q = ops.user_seq_mean(bench.make_query_batches(dim, nq, 1, 1.0, torch.device("cuda"), n_clusters=ncl)[0])
+    sc = ops.Scorer("ip", dim, rows.dtype)
+    print(f"{items} x {dim} {dtype}, rows scaled by factors in [0.25, 4], M 32, ef_construction 40; IP traversal at ef {ef}, {nq} queries", flush=True)
+    for metric in ("l2", "ip"):
+        for it in range(2):
+            torch.cuda.synchronize()
+            t = time.time()
+            ex = index_build.build_hnsw_gpu(rows, 32, 40, seed=1236, metric=metric)
+            torch.cuda.synchronize()
+            t_gpu = time.time() - t
+        inv = invariants(ex, items, 32)
+        dix = retrieval.Index(rows, synth.make_item_ids(items, seed=1235), ex["nb_values"], ex["nb_row_splits"], ex["enter_points"])
+        topn = [min(ef, len(ex["enter_points"]))] + [ef] * 4 + [200]
+        r = retrieval.search(dix, sc, q, topn)
+        truth = retrieval.search_all(dix, sc, q, 200)
+        torch.cuda.synchronize()
+        st, got, want = r.status.cpu().numpy(), r.index.cpu().numpy(), truth.index.cpu().numpy()
+        hits = sum(len(set(got[b].tolist()) & set(want[b].tolist())) for b in range(nq) if st[b] == 0)
+        print(f"metric {metric}: build {t_gpu:.3f} s (second run, incl. export); mean degree L0 {inv['deg0']:.2f}, L1 over members "
+              f"{inv['deg1_over_members']:.2f}, max L0 {inv['max0']}, enter points {inv['E']}; IP recall@200 {hits / want.size:.4f} "
+              f"(failed queries count as zero hits), valid {float((st == 0).mean()):.3f}", flush=True)
+
+
 def main():
     items = int(sys.argv[1]) if len(sys.argv) > 1 else 200_000
     dim = int(sys.argv[2]) if len(sys.argv) > 2 else 128
     ef = int(sys.argv[3]) if len(sys.argv) > 3 else 128
     dtype = sys.argv[4] if len(sys.argv) > 4 else "f16"
-    skip_cpu = len(sys.argv) > 5 and sys.argv[5] == "nocpu"
+    skip_cpu = "nocpu" in sys.argv[5:]
+    if "ip" in sys.argv[5:]:
+        return ip_check(items, dim, ef, dtype)
     ncl = bench.n_clusters_for(items, ef)
     embs, _ = synth.make_corpus(items, dim, n_clusters=ncl, noise=1.0, seed=1234, item_seed=1334)
     ids = synth.make_item_ids(items, seed=1235)

@@ -922,6 +922,55 @@ int nann_hnsw_export_fill(const int32_t* adj0, const int32_t* up_row, const int3
                           const int32_t* levels /*[host] n*/, int64_t n, int32_t M, int32_t start_level,
                           const int64_t* row_splits0, const int64_t* row_splits1, const int64_t* nnz /*[host] 2*/,
                           int32_t* values0, int32_t* values1, int32_t* enter_points, nann_stream_t stream);
+/* Remove: rows leave a graph that a build or an append made; the result is a SMALLER, RENUMBERED graph over the survivors whose
+ * rows have been reconnected across the holes -- at the cost of the rows that lost a neighbour, not of a rebuild.  (A withdrawn
+ * row is hidden at once by a deny bit, nann_filter; it still costs its embedding, its place in every pre-projected table and a
+ * gather and a score in every traversal that meets it, and the unfiltered calls do not know the bitmap.  This call is what
+ * follows when the denied share has grown.)  The semantics are this library's own: the reference and Faiss' IndexHNSWFlat have
+ * no removal.
+ *   remove_bits  device u32[ceil(n / 32)], the deny bitmap's convention: row r is removed iff bit (r & 31) of word (r >> 5) is
+ *                set; bits at or beyond n are ignored.  A nann_filter's deny_bits goes in as it is.
+ *   the old graph (adj0, up_row, adj_up: device; levels: host; n nodes) and item_embs [n, d] are const and stay untouched, so an
+ *                index that still serves from them is safe; the outputs are NEW arrays, the caller's.
+ * Renumbering: the survivor with old id i gets new id = number of survivors below i (order kept); it keeps its levels;
+ * out_up_row follows the prefix rule over the survivors' levels.  The result is therefore valid input of
+ * nann_hnsw_append_device(_metric), of nann_hnsw_export_count / _fill and of this call again.
+ * A row none of whose entries is removed is copied, renumbered, slot for slot.  A row with at least one removed entry is
+ * REPAIRED (the delete consolidation of FreshDiskANN, alg. 4, with this builder's selection heuristic in the place of
+ * RobustPrune): the candidate pool of node p on level l is the SET (p itself left out) of the surviving entries of p's row and,
+ * for every removed entry r of the row, the surviving entries of r's row on level l -- one hop: removed entries of r's row are
+ * not followed.  The pool is cut to its 64 nearest members by the build's (distance to p, id) key in `metric` (L2, or -<a, b>),
+ * the heuristic runs over them in ascending order with the level's cap (2M on level 0, M above) and honours keep_pruned, and the
+ * row is written as a dense prefix in that order with -1 behind.
+ * WHAT IT DOES NOT DO: no back-links are added (no other row learns of a repaired row's new entries); a node may come out with
+ * an empty row or without in-links, which is counted in stats and not healed; and nothing guards the entry layer -- after a
+ * removal the serving enter points are the survivors with levels > 2, and when fewer remain than the first top-k asks for,
+ * requests fail k > n exactly as on any small index.  That is the caller's to watch (new_levels says how many are left).
+ *   nann_hnsw_remove_count  step 1, because the sizes depend on the data (as nann_hnsw_export_count).  kept_rows device i32[n]:
+ *                its head holds the n_keep surviving old ids ascending -- the `indices` nann_gather_rows takes to compact
+ *                item_embs and item_ids; new_levels [host] i32[n]: its head holds the survivors' levels; *n_keep, *n_up_rows
+ *                [host] (sum(levels - 1) over the survivors).  Tails are left as they were.  The graph is not read.  Synchronises.
+ *   nann_hnsw_remove_device step 2.  out_adj0 i32[n_keep, 2M], out_up_row i32[n_keep], out_adj_up i32[max(n_up_rows, 1), M]
+ *                (device).  stats [host] i64[4] or NULL: {rows repaired (all levels), level-0 rows that were non-empty and came
+ *                out empty, rows whose distinct pool exceeded 64, survivors}.  Synchronous.
+ * The old graph is INPUT, and malformed input never faults: the validation pass of the append runs first over all n nodes (the
+ * same four rules, the same words in nann_last_error, the lowest offending node); the old -> new map comes from the call's own
+ * scan of remove_bits, no caller array is trusted; an n_keep that is not the bitmap's survivor count is refused.  All of these
+ * give NANN_ERR_BAD_ARGUMENT with every output array untouched.  Argument checks come before any device call:
+ * NANN_ERR_BAD_ARGUMENT (a null pointer -- out_adj_up included, adj_up when a node has more than one level --, n < 1,
+ * levels[i] < 1, n_keep < 1: a graph keeps at least one node, n_keep > n, a metric that is no scorer kind);
+ * NANN_ERR_UNSUPPORTED (n > 2^31 - 1, d, dtype or M outside the build's limits, NANN_SCORER_MLP); NANN_ERR_HIP.
+ * Removing nothing is not an error: the outputs equal the inputs bit for bit, kept_rows = 0 .. n - 1, stats[0] = 0.
+ * Deterministic: a row's result depends on the inputs only, and the counters are totals. */
+int nann_hnsw_remove_count(const uint32_t* remove_bits, const int32_t* levels /*[host] n*/, int64_t n,
+                           int32_t* kept_rows, int32_t* new_levels /*[host]*/, int64_t* n_keep, int64_t* n_up_rows,
+                           nann_stream_t stream);
+int nann_hnsw_remove_device(const void* item_embs, int64_t n, int32_t d, int32_t emb_dtype, int32_t M,
+                            int32_t keep_pruned, int32_t metric, const int32_t* levels /*[host] n*/,
+                            const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up,
+                            const uint32_t* remove_bits, int64_t n_keep,
+                            int32_t* out_adj0, int32_t* out_up_row, int32_t* out_adj_up, int64_t* stats,
+                            nann_stream_t stream);
 
 /* ---- 8(f2): the reference's own scorer model behind the BlazeXlaOp contract -------------
  * NANN_impls/nann/model/model.py:189-233 + model_util.py:70-97: softmax attention of the candidate

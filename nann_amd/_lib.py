@@ -51,6 +51,7 @@ SYMBOLS = [
     "nann_sharded_topk", "nann_hnsw_draw_levels", "nann_hnsw_build_device", "nann_hnsw_build_device_ex",
     "nann_hnsw_append_device", "nann_hnsw_export_count", "nann_hnsw_export_fill",
     "nann_hnsw_build_device_metric", "nann_hnsw_append_device_metric",
+    "nann_hnsw_remove_count", "nann_hnsw_remove_device",
 ]
 
 
@@ -195,6 +196,15 @@ def lib():
         L.nann_hnsw_export_count.restype = C.c_int
         L.nann_hnsw_export_fill.argtypes = head + [C.POINTER(C.c_int64)] + [C.c_void_p] * 4
         L.nann_hnsw_export_fill.restype = C.c_int
+        # (remove_bits, levels, n, kept_rows, new_levels, *n_keep, *n_up_rows, stream)
+        L.nann_hnsw_remove_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64), C.c_void_p]
+        L.nann_hnsw_remove_count.restype = C.c_int
+        # (item_embs, n, d, emb_dtype, M, keep_pruned, metric, levels, adj0, up_row, adj_up, remove_bits, n_keep, out_adj0,
+        #  out_up_row, out_adj_up, stats, stream)
+        L.nann_hnsw_remove_device.argtypes = [C.c_void_p, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 5 + [C.c_int64] + \
+                                              [C.c_void_p] * 3 + [C.POINTER(C.c_int64), C.c_void_p]
+        L.nann_hnsw_remove_device.restype = C.c_int
         _LIB = L
     return _LIB
 

@@ -32,6 +32,10 @@
 // would; build and append share hb_insert.  EXPORT (nann_hnsw_export_count / _fill): the arrays -> the per-level CSR
 // and enter points nann_index_create takes, on the device (tests/test_index_append_gpu.py).
 //
+// REMOVE (nann_hnsw_remove_count / nann_hnsw_remove_device): the arrays and a bitmap of rows to drop -> NEW arrays over the
+// survivors, renumbered in order; a row that lost an entry is re-selected (wave_select) from its survivors and the surviving
+// entries of its removed entries' rows, one hop (k_hb_repair; tests/test_index_remove_gpu.py).
+//
 // METRIC (nann_hnsw_build_device_metric / nann_hnsw_append_device_metric): the same kernels with dist(a, b) = -<a, b>, for an
 // index that is searched with the inner-product scorer.  Algorithms 1-4 run on that distance unchanged; the beam's keys take
 // an order-preserving map of its bits (hb_key).  tests/test_index_build_ip_gpu.py.
@@ -91,7 +95,11 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
   return ((unsigned long long)hi << 32) | lo;
 }
 
-// ascending bitonic sort of one 64-bit key per lane over the wavefront
+// ascending bitonic sort of one 64-bit key per lane over the wavefront.  USER (here and on wave_select): a tag with no meaning
+// in the code.  The build's kernels use instance 0, k_hb_repair instance 1: a further user of ONE always-inlined instance changes
+// the order in which hipcc emits a few instructions of the kernels that already inline it (Remove), and the
+// build's kernels are to compile to what they did.
+template <int USER = 0>
 __device__ __forceinline__ unsigned long long wave_sort64(unsigned long long key, int lane) {
 #pragma unroll
   for (int size = 2; size <= 64; size <<= 1) {
@@ -187,7 +195,7 @@ struct HbWaveLds {
 // base: keep c iff it is closer to the base than to every candidate kept so far (dist(c, s) >= dist(c, base) for every kept
 // s, in the kernel's metric); at most `cap`.  cand_key: lane i = i-th nearest (kKeyInf beyond n).  Rows are staged into
 // `rows` (LDS, n x d halves).  Returns the keep mask (bit i = candidate i kept; wave-uniform).
-template <int LPR, int DT, int MT>
+template <int LPR, int DT, int MT, int USER = 0>
 __device__ __forceinline__ uint64_t wave_select(const HbGraph& g, unsigned long long cand_key, int n, int cap,
                                                 uint16_t* rows, int lane) {
   constexpr int GPW = 64 / LPR;
@@ -609,6 +617,177 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_export_fill(const int32_t*
   }
 }
 
+// ---- remove: a smaller, renumbered graph whose surviving rows are reconnected across the holes ----------------
+// The removal bitmap is the deny bitmap of nann_filter: row r is removed iff bit (r & 31) of word (r >> 5) is set.  Entries of
+// a checked graph lie in [0, n), so no word at or beyond ceil(n / 32) is ever read.
+__device__ __forceinline__ bool hb_removed(const uint32_t* bits, int r) { return (bits[(uint32_t)r >> 5] >> (r & 31)) & 1u; }
+
+// keep flags (for the scan that gives the old -> new map) ...
+__global__ void k_hb_keep_flags(const uint32_t* bits, int n, int32_t* flag) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (size_t)n) flag[i] = hb_removed(bits, (int)i) ? 0 : 1;
+}
+
+// ... and the compaction of the surviving ids through that map: kept_rows[map[i]] = i
+__global__ void k_hb_kept_rows(const uint32_t* bits, const int32_t* map, int n, int32_t* kept_rows) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (size_t)n && !hb_removed(bits, (int)i)) kept_rows[map[i]] = (int32_t)i;
+}
+
+// `sorted` ascending over the lanes and free of duplicates, `fresh` arbitrary -> the 64 smallest DISTINCT keys of the 128,
+// ascending (kKeyInf behind); returns how many distinct keys the 128 held.  wave_merge64 with both halves of the bitonic merge
+// kept: a key that is in both inputs (the same id reached twice has the same key) would otherwise take two of the 64 places
+// and push a pool member out before the duplicate is seen.  Equal keys are adjacent in the sorted 128; the first of each run
+// is compacted through `buf` (LDS, 64 keys).
+__device__ __forceinline__ unsigned long long wave_merge64_unique(unsigned long long sorted, unsigned long long fresh, int lane,
+                                                                  unsigned long long* buf, int* n_distinct) {
+  fresh = wave_sort64<1>(fresh, lane);
+  const unsigned long long rev = shfl_xor_u64(fresh, 63);  // descending
+  unsigned long long lo = sorted < rev ? sorted : rev, hi = sorted < rev ? rev : sorted;  // two bitonic halves, lo <= hi
+#pragma unroll
+  for (int stride = 32; stride > 0; stride >>= 1) {
+    const unsigned long long olo = shfl_xor_u64(lo, stride), ohi = shfl_xor_u64(hi, stride);
+    const bool lower = (lane & stride) == 0;
+    lo = lower ? (lo < olo ? lo : olo) : (lo > olo ? lo : olo);
+    hi = lower ? (hi < ohi ? hi : ohi) : (hi > ohi ? hi : ohi);
+  }
+  auto from_lane = [](unsigned long long v, int src) -> unsigned long long {
+    return ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src);
+  };
+  const int below = (lane + 63) & 63;  // the lane before this one; lane 0 of `hi` follows lane 63 of `lo`
+  const unsigned long long plo = from_lane(lo, below), phi = from_lane(hi, below);
+  const bool keep_lo = lo != kKeyInf && (lane == 0 || lo != plo);
+  const bool keep_hi = hi != kKeyInf && hi != (lane == 0 ? plo : phi);
+  const uint64_t mlo = __ballot(keep_lo), mhi = __ballot(keep_hi);
+  const int nlo = popc64(mlo);
+  buf[lane] = kKeyInf;
+  __builtin_amdgcn_wave_barrier();
+  if (keep_lo) buf[popc64(mlo & lanemask_lt(lane))] = lo;
+  const int at = nlo + popc64(mhi & lanemask_lt(lane));
+  if (keep_hi && at < kHbMaxCand) buf[at] = hi;
+  __builtin_amdgcn_wave_barrier();
+  const unsigned long long out = buf[lane];
+  __builtin_amdgcn_wave_barrier();
+  *n_distinct = nlo + popc64(mhi);
+  return out;
+}
+
+struct HbRepair {
+  const void* emb;            // [n, d] the old rows
+  const int32_t* adj0;        // the old graph, checked by k_hb_check
+  const int32_t* up_expect;   // [n] first upper row of a node by the prefix rule (what the check held up_row to)
+  const int32_t* adj_up;
+  const int32_t* up_owner;    // [up_rows] the node an upper row belongs to
+  const uint32_t* bits;       // the removal bitmap
+  const int32_t* map;         // [n] old -> new id of a survivor (exclusive scan of the keep flags)
+  const int32_t* out_up_row;  // [n_keep] the survivors' first upper rows, already written
+  int32_t* out_adj0;
+  int32_t* out_adj_up;
+  unsigned long long* stats;  // {rows repaired, level-0 rows that came out empty, rows whose distinct pool exceeded 64}
+  int n, d, M, keep_pruned;
+  long long n_work;           // n level-0 rows, then the upper rows
+};
+
+// One wavefront per (old node, level).  A removed node's rows are dropped.  A surviving row none of whose entries is removed is
+// copied through the map, slot for slot.  A row with a removed entry is repaired (FreshDiskANN alg. 4 with this builder's
+// heuristic): the pool is the SET of the row's surviving entries and of the surviving entries of every removed entry's row on
+// the same level (one hop; p itself left out), held as the beam of up to 64 nearest (distance to p, id) keys; wave_select
+// picks the new row from it in ascending order.  Every row read belongs to a node of a checked graph on a level it has.
+template <int LPR, int DT, int MT>
+__global__ __launch_bounds__(kHbWaves * 64) void k_hb_repair(HbRepair r) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int GPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long w = (long long)blockIdx.x * kHbWaves + wave;
+  if (w >= r.n_work) return;
+  int node, level;
+  if (w < r.n) { node = (int)w; level = 0; }
+  else { const long long u = w - r.n; node = r.up_owner[u]; level = (int)(u - r.up_expect[node]) + 1; }
+  if (hb_removed(r.bits, node)) return;
+  const int cap = level == 0 ? 2 * r.M : r.M;
+  auto old_row = [&](int v) -> const int32_t* {
+    return level == 0 ? r.adj0 + (size_t)v * 2 * r.M : r.adj_up + ((size_t)r.up_expect[v] + (size_t)(level - 1)) * r.M;
+  };
+  const int me = r.map[node];
+  int32_t* dst = level == 0 ? r.out_adj0 + (size_t)me * 2 * r.M : r.out_adj_up + ((size_t)r.out_up_row[me] + (size_t)(level - 1)) * r.M;
+  const int e = lane < cap ? old_row(node)[lane] : -1;
+  const bool gone = e >= 0 && hb_removed(r.bits, e);
+  const uint64_t holes = __ballot(gone);
+  if (!holes) {
+    if (lane < cap) dst[lane] = e >= 0 ? r.map[e] : -1;
+    return;
+  }
+  const int sub = lane % LPR, grp = lane / LPR;
+  const size_t row_bytes = (size_t)kHbMaxCand * r.d * 2;
+  unsigned char* mine_lds = smem + (size_t)wave * (row_bytes + 1024);
+  uint16_t* rows = reinterpret_cast<uint16_t*>(mine_lds);                   // wave_select's staging
+  float* dist = reinterpret_cast<float*>(mine_lds + row_bytes);             // [64]
+  int32_t* ids = reinterpret_cast<int32_t*>(mine_lds + row_bytes + 256);    // [64]
+  unsigned long long* buf = reinterpret_cast<unsigned long long*>(mine_lds + row_bytes + 512);  // [64]
+  float q[8];
+  hb_load8<DT>(r.emb, (size_t)node, r.d, sub, q);
+  unsigned long long beam = kKeyInf;
+  bool over = false;
+  // the surviving entries among one row's slots (one per lane) join the beam
+  auto pool_add = [&](int id, bool member) {
+    const uint64_t fm = __ballot(member);
+    if (!fm) return;
+    const int n_new = popc64(fm);
+    if (member) ids[popc64(fm & lanemask_lt(lane))] = id;
+    __builtin_amdgcn_wave_barrier();
+    for (int i0 = 0; i0 < n_new; i0 += GPW) {  // distances to p, GPW rows per step
+      const int i = i0 + grp;
+      float x[8];
+      hb_load8<DT>(r.emb, (size_t)ids[min(i, n_new - 1)], r.d, sub, x);
+      float acc = 0.0f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if constexpr (MT == kHbIp) acc = __fmaf_rn(q[k], x[k], acc);
+        else { const float t = q[k] - x[k]; acc = __fmaf_rn(t, t, acc); }
+      }
+      acc = hb_dist_of_sum<MT>(hb_group_sum<LPR>(acc));
+      if (i < n_new && sub == 0) dist[i] = acc;
+    }
+    __builtin_amdgcn_wave_barrier();
+    const unsigned long long fresh = lane < n_new ? hb_key<MT>(dist[lane], ids[lane]) : kKeyInf;
+    __builtin_amdgcn_wave_barrier();
+    int n_distinct;
+    beam = wave_merge64_unique(beam, fresh, lane, buf, &n_distinct);
+    over = over || n_distinct > kHbMaxCand;
+  };
+  pool_add(e, e >= 0 && !gone && e != node);
+  for (uint64_t todo = holes; todo; todo &= todo - 1) {  // uniform
+    const int v = __shfl(e, __ffsll((unsigned long long)todo) - 1);
+    const int f = lane < cap ? old_row(v)[lane] : -1;
+    pool_add(f, f >= 0 && f != node && !hb_removed(r.bits, f));
+  }
+  const int n_cand = popc64(__ballot(beam != kKeyInf));
+  HbGraph g;
+  g.emb = r.emb; g.adj0 = nullptr; g.cnt0 = nullptr; g.up_row = nullptr; g.adj_up = nullptr; g.cnt_up = nullptr;
+  g.n_items = r.n; g.d = r.d; g.M = r.M; g.keep_pruned = r.keep_pruned;
+  const uint64_t kept = wave_select<LPR, DT, MT, 1>(g, beam, n_cand, cap, rows, lane);
+  const int n_kept = popc64(kept);
+  if ((kept >> lane) & 1ull) dst[popc64(kept & lanemask_lt(lane))] = r.map[(int)(uint32_t)beam];
+  if (lane >= n_kept && lane < cap) dst[lane] = -1;
+  if (lane == 0) {
+    atomicAdd(&r.stats[0], 1ull);
+    if (level == 0 && n_kept == 0) atomicAdd(&r.stats[1], 1ull);
+    if (over) atomicAdd(&r.stats[2], 1ull);
+  }
+}
+
+template <int LPR, int DT, int MT>
+int run_repair(const HbRepair& r, hipStream_t st) {
+  const size_t lds = ((size_t)kHbMaxCand * r.d * 2 + 1024) * kHbWaves;  // k_hb_backlink's budget
+  auto kern = k_hb_repair<LPR, DT, MT>;
+  if (lds > 48 * 1024)
+    HB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const unsigned blocks = (unsigned)((r.n_work + kHbWaves - 1) / kHbWaves);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(kHbWaves * 64), lds, st, r);
+  HB_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
 // ---- what build and append share: the scratch of a run and the batch loop ------------------------------------
 struct HbScratch {
   std::vector<void*> owned;
@@ -989,6 +1168,154 @@ int nann_hnsw_export_fill(const int32_t* adj0, const int32_t* up_row, const int3
       (rc = hb_hip_rc(hipStreamSynchronize(st), who)))
     return cleanup(rc);
   if (h_bad) return cleanup(fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": row_splits are not this graph's (call nann_hnsw_export_count first)"));
+  return cleanup(NANN_OK);
+}
+
+namespace {
+// the old -> new map of a removal on the stream: keep flags, their exclusive scan into `map`; the bitmap also comes to the
+// host (h_bits, ceil(n / 32) words), where the survivors' levels are walked.  The caller synchronises.
+int hb_remove_map(const char* who, const uint32_t* remove_bits, int N, int32_t** map, std::vector<uint32_t>* h_bits,
+                  std::vector<void*>* owned, hipStream_t st) {
+  int32_t* flag;
+  int rc;
+  if ((rc = dev_alloc(&flag, (size_t)N, owned)) || (rc = dev_alloc(map, (size_t)N, owned))) return rc;
+  size_t scan_bytes = 0;
+  hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, flag, *map, N, st);
+  unsigned char* d_scan;
+  if ((rc = dev_alloc(&d_scan, scan_bytes, owned))) return rc;
+  hipLaunchKernelGGL(k_hb_keep_flags, dim3((unsigned)(((size_t)N + 255) / 256)), dim3(256), 0, st, remove_bits, N, flag);
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_keep_flags"))) return rc;
+  if (hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, flag, *map, N, st) != hipSuccess)
+    return fail(NANN_ERR_HIP, std::string(who) + ": scan failed");
+  h_bits->resize(((size_t)N + 31) / 32);
+  return hb_hip_rc(hipMemcpyAsync(h_bits->data(), remove_bits, h_bits->size() * 4, hipMemcpyDeviceToHost, st), "remove_bits");
+}
+
+inline bool hb_bit(const std::vector<uint32_t>& bits, int i) { return (bits[(size_t)i >> 5] >> (i & 31)) & 1u; }
+}  // namespace
+
+int nann_hnsw_remove_count(const uint32_t* remove_bits, const int32_t* levels, int64_t n, int32_t* kept_rows,
+                           int32_t* new_levels, int64_t* n_keep, int64_t* n_up_rows, nann_stream_t stream) {
+  const char* who = "nann_hnsw_remove_count";
+  if (!remove_bits || !levels || !kept_rows || !new_levels || !n_keep || !n_up_rows || n < 1)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument or n < 1");
+  if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 items");
+  const int N = (int)n;
+  for (int i = 0; i < N; ++i)
+    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  std::vector<void*> owned;
+  auto cleanup = [&](int r) { for (void* p : owned) (void)hipFree(p); return r; };
+  int32_t* map;
+  std::vector<uint32_t> h_bits;
+  int rc = hb_remove_map(who, remove_bits, N, &map, &h_bits, &owned, st);
+  if (rc) return cleanup(rc);
+  hipLaunchKernelGGL(k_hb_kept_rows, dim3((unsigned)(((size_t)N + 255) / 256)), dim3(256), 0, st, remove_bits, map, N, kept_rows);
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_kept_rows")) || (rc = hb_hip_rc(hipStreamSynchronize(st), who))) return cleanup(rc);
+  int64_t keep = 0, up = 0;
+  for (int i = 0; i < N; ++i) {
+    if (hb_bit(h_bits, i)) continue;
+    new_levels[keep++] = levels[i];
+    up += levels[i] - 1;
+  }
+  *n_keep = keep;
+  *n_up_rows = up;
+  return cleanup(NANN_OK);
+}
+
+int nann_hnsw_remove_device(const void* item_embs, int64_t n, int32_t d, int32_t emb_dtype, int32_t M, int32_t keep_pruned,
+                            int32_t metric, const int32_t* levels, const int32_t* adj0, const int32_t* up_row,
+                            const int32_t* adj_up, const uint32_t* remove_bits, int64_t n_keep, int32_t* out_adj0,
+                            int32_t* out_up_row, int32_t* out_adj_up, int64_t* stats, nann_stream_t stream) {
+  const char* who = "nann_hnsw_remove_device";
+  if (!item_embs || !levels || !adj0 || !up_row || !remove_bits || !out_adj0 || !out_up_row || !out_adj_up || n < 1)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument or n < 1");
+  if (n_keep < 1 || n_keep > n)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_keep must lie in [1, n] (a graph keeps at least one node)");
+  int rc = hb_check_metric(who, metric);
+  if (rc) return rc;
+  if ((rc = hb_check_shape(who, n, d, emb_dtype, M, 0))) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int N = (int)n;
+  // ---- from `levels`: every old node's first upper row and the owner of every upper row
+  std::vector<int32_t> h_up((size_t)N), h_owner;
+  int64_t up_rows = 0;
+  for (int i = 0; i < N; ++i) {
+    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
+    h_up[(size_t)i] = levels[i] > 1 ? (int32_t)up_rows : -1;
+    up_rows += levels[i] - 1;
+    if (up_rows > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 upper rows");
+    h_owner.insert(h_owner.end(), (size_t)(levels[i] - 1), i);
+  }
+  if (up_rows > 0 && !adj_up) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": adj_up is null");
+
+  std::vector<void*> owned;
+  auto cleanup = [&](int r) { for (void* p : owned) (void)hipFree(p); return r; };
+  // ---- the old graph is checked, and the bitmap scanned, before anything is written
+  int32_t *d_levels, *d_up, *d_owner, *d_bad, *cnt0, *cnt_up, *map;
+  unsigned long long* d_stats;
+  if ((rc = dev_alloc(&d_levels, (size_t)N, &owned)) || (rc = dev_alloc(&d_up, (size_t)N, &owned)) ||
+      (rc = dev_alloc(&d_owner, (size_t)std::max<int64_t>(up_rows, 1), &owned)) || (rc = dev_alloc(&d_bad, (size_t)kHbRules, &owned)) ||
+      (rc = dev_alloc(&cnt0, (size_t)N, &owned)) || (rc = dev_alloc(&cnt_up, (size_t)std::max<int64_t>(up_rows, 1), &owned)) ||
+      (rc = dev_alloc(&d_stats, 3, &owned)))
+    return cleanup(rc);
+  int32_t h_bad[kHbRules] = {kHbNone, kHbNone, kHbNone, kHbNone};
+  if ((rc = hb_hip_rc(hipMemcpyAsync(d_levels, levels, (size_t)N * 4, hipMemcpyHostToDevice, st), "levels")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(d_up, h_up.data(), (size_t)N * 4, hipMemcpyHostToDevice, st), "up_row")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(d_bad, h_bad, sizeof(h_bad), hipMemcpyHostToDevice, st), "flag")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(d_stats, 0, 3 * sizeof(unsigned long long), st), "stats")))
+    return cleanup(rc);
+  if (up_rows > 0 && (rc = hb_hip_rc(hipMemcpyAsync(d_owner, h_owner.data(), (size_t)up_rows * 4, hipMemcpyHostToDevice, st), "owner")))
+    return cleanup(rc);
+  hipLaunchKernelGGL(k_hb_check, dim3((unsigned)((N + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, adj0, up_row, adj_up,
+                     d_levels, d_up, N, M, cnt0, cnt_up, d_bad);
+  std::vector<uint32_t> h_bits;
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_check")) || (rc = hb_remove_map(who, remove_bits, N, &map, &h_bits, &owned, st)) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, st), "flag")) ||
+      (rc = hb_hip_rc(hipStreamSynchronize(st), "k_hb_check")))
+    return cleanup(rc);
+  static const char* const kRule[kHbRules] = {
+      "up_row differs from what levels implies (-1 for one level, else the running sum of levels - 1)",
+      "a row entry lies outside [-1, n_old)", "a row entry follows a -1 (rows are dense prefixes)",
+      "a row entry names a node that has no row on that level"};
+  for (int r = 0; r < kHbRules; ++r)
+    if (h_bad[r] != kHbNone)
+      return cleanup(fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": malformed graph, node " + std::to_string(h_bad[r]) + ": " + kRule[r]));
+  // ---- the survivors: their count against n_keep, their first upper rows by the prefix rule
+  std::vector<int32_t> h_new_up;
+  h_new_up.reserve((size_t)n_keep);
+  int64_t keep = 0, new_up_rows = 0;
+  for (int i = 0; i < N; ++i) {
+    if (hb_bit(h_bits, i)) continue;
+    if (++keep <= n_keep) h_new_up.push_back(levels[i] > 1 ? (int32_t)new_up_rows : -1);
+    new_up_rows += levels[i] - 1;
+  }
+  if (keep != n_keep)
+    return cleanup(fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_keep is " + std::to_string(n_keep) + ", the bitmap leaves " +
+                                                   std::to_string(keep) + " rows (call nann_hnsw_remove_count first)"));
+  if ((rc = hb_hip_rc(hipMemcpyAsync(out_up_row, h_new_up.data(), (size_t)n_keep * 4, hipMemcpyHostToDevice, st), "out_up_row")))
+    return cleanup(rc);
+  HbRepair r;
+  r.emb = item_embs; r.adj0 = adj0; r.up_expect = d_up; r.adj_up = adj_up; r.up_owner = d_owner; r.bits = remove_bits; r.map = map;
+  r.out_up_row = out_up_row; r.out_adj0 = out_adj0; r.out_adj_up = out_adj_up; r.stats = d_stats;
+  r.n = N; r.d = d; r.M = M; r.keep_pruned = keep_pruned ? 1 : 0; r.n_work = (long long)N + up_rows;
+  auto repair = [&]() -> int {
+#define HB_CASE(LPR_)                                                                                            \
+  if (metric == NANN_SCORER_IP) return emb_dtype == NANN_F16 ? run_repair<LPR_, 0, kHbIp>(r, st) : run_repair<LPR_, 1, kHbIp>(r, st); \
+  return emb_dtype == NANN_F16 ? run_repair<LPR_, 0, kHbL2>(r, st) : run_repair<LPR_, 1, kHbL2>(r, st)
+    if (d == 64) { HB_CASE(8); }
+    if (d == 128) { HB_CASE(16); }
+    HB_CASE(32);
+#undef HB_CASE
+  };
+  unsigned long long h_stats[3] = {0, 0, 0};
+  if ((rc = repair()) || (rc = hb_hip_rc(hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st), "stats")) ||
+      (rc = hb_hip_rc(hipStreamSynchronize(st), who)))
+    return cleanup(rc);
+  if (stats) {
+    for (int i = 0; i < 3; ++i) stats[i] = (int64_t)h_stats[i];
+    stats[3] = n_keep;
+  }
   return cleanup(NANN_OK);
 }
 

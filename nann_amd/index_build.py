@@ -235,6 +235,78 @@ def append_hnsw_gpu(state, new_rows, seed, start_level=2, want_export=True):
     return out
 
 
+def _remove_bits(n, remove_rows, deny_bits, dev):
+    """the removal bitmap of remove_hnsw_gpu: i32[ceil(n / 32)] on `dev`, bit (r & 31) of word (r >> 5) = row r is removed"""
+    import torch
+    if (remove_rows is None) == (deny_bits is None):
+        raise ValueError("remove_hnsw_gpu: give exactly one of remove_rows and deny_bits")
+    words = (n + 31) // 32
+    if deny_bits is not None:
+        b = deny_bits if isinstance(deny_bits, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(deny_bits))
+        if b.dtype != torch.bool:  # packed words, as retrieval.make_filter(...).deny_bits
+            if b.dtype not in (torch.int32, torch.uint32) or b.numel() != words:
+                raise ValueError(f"remove_hnsw_gpu: deny_bits is a bool mask [n] or {words} packed 32-bit words")
+            return b.view(torch.int32).to(dev).contiguous()
+        if b.numel() != n:
+            raise ValueError(f"remove_hnsw_gpu: the mask has {b.numel()} entries, the graph {n} rows")
+        flags = torch.zeros(words * 32, dtype=torch.bool, device=dev)
+        flags[:n] = b.reshape(-1).to(dev)
+    else:
+        r = remove_rows if isinstance(remove_rows, torch.Tensor) else torch.as_tensor(np.asarray(remove_rows, dtype=np.int64))
+        r = r.reshape(-1).to(device=dev, dtype=torch.int64)
+        flags = torch.zeros(words * 32, dtype=torch.bool, device=dev)
+        flags[r[(r >= 0) & (r < n)]] = True  # rows outside the graph remove nothing; a row named twice is removed once
+    w = (flags.view(words, 32).to(torch.int64) << torch.arange(32, dtype=torch.int64, device=dev)).sum(1)
+    return torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32).contiguous()
+
+
+def remove_hnsw_gpu(state, remove_rows=None, deny_bits=None, start_level=2, want_export=True):
+    """Remove rows from the graph of `state` (build_hnsw_gpu(want_state=True), an append or an earlier removal) ON THE GPU
+    (nann_hnsw_remove_count / nann_hnsw_remove_device, with the state's "metric"; a state without one is "l2").  Exactly one of
+    remove_rows (an integer array or tensor of internal rows; rows outside the graph are dropped, duplicates allowed) and
+    deny_bits (a bool mask [n], or the packed words of retrieval.make_filter(...).deny_bits as they are).  The survivors are
+    renumbered in order, rows that lost an entry are repaired from their removed neighbours' rows (one hop; include/nann_hip.h),
+    and everything goes into NEW tensors: the input state is left as it is.  Returns what append_hnsw_gpu returns, over the
+    survivors ("state" holds item_embs gathered by kept_rows), and "kept_rows" (device i32[n_keep]: the old row of every new
+    row, for the caller's item_ids) and "stats" (i64[4]: rows repaired, level-0 rows that came out empty, rows whose pool
+    exceeded 64, survivors).  No back-links are added, isolated nodes are counted and not healed, and the entry layer (survivors
+    with levels > start_level) is the caller's to watch.  want_export=False skips the torch export, as in the append."""
+    import torch
+    from . import _lib
+    from .ops import _check, _ptr, _stream, _DT
+    L = _lib.lib()
+    metric = state.get("metric", "l2")
+    kind = _metric_kind(metric)
+    x0, m = state["item_embs"], int(state["M"])
+    n, d = x0.shape
+    dev = x0.device
+    old_levels = np.ascontiguousarray(state["levels"], dtype=np.int32)
+    bits = _remove_bits(n, remove_rows, deny_bits, dev)
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    new_levels = np.zeros(n, np.int32)
+    n_keep, n_up = C.c_int64(0), C.c_int64(0)
+    torch.cuda.synchronize()
+    _check(L.nann_hnsw_remove_count(_ptr(bits), old_levels.ctypes.data_as(C.c_void_p), n, _ptr(kept),
+                                    new_levels.ctypes.data_as(C.c_void_p), C.byref(n_keep), C.byref(n_up), _stream()), "hnsw remove count")
+    nk = n_keep.value
+    adj0 = torch.empty((max(nk, 1), 2 * m), dtype=torch.int32, device=dev)[:nk]
+    up_row = torch.empty(max(nk, 1), dtype=torch.int32, device=dev)[:nk]
+    adj_up = torch.empty((max(n_up.value, 1), m), dtype=torch.int32, device=dev)
+    stats = (C.c_int64 * 4)()
+    _check(L.nann_hnsw_remove_device(_ptr(x0), n, d, _DT[x0.dtype], m, 1 if state["keep_pruned"] else 0, kind,
+                                     old_levels.ctypes.data_as(C.c_void_p), _ptr(state["adj0"]), _ptr(state["up_row"]),
+                                     _ptr(state["adj_up"]), _ptr(bits), nk, _ptr(adj0), _ptr(up_row), _ptr(adj_up), stats, _stream()),
+           "hnsw remove")
+    kept, levels = kept[:nk].contiguous(), np.ascontiguousarray(new_levels[:nk])
+    x = x0[kept.long()].contiguous()
+    out = _export_torch(levels, adj0, up_row, adj_up, m, start_level) if want_export else {"levels": levels}
+    out["state"] = {"item_embs": x, "adj0": adj0, "up_row": up_row, "adj_up": adj_up, "levels": levels, "M": m,
+                    "ef_construction": int(state["ef_construction"]), "keep_pruned": bool(state["keep_pruned"]), "metric": metric}
+    out["kept_rows"] = kept
+    out["stats"] = np.array(list(stats), np.int64)
+    return out
+
+
 def export_hnsw_gpu(state, start_level=2):
     """The export of build_hnsw_index.py:41-66 ON THE DEVICE (nann_hnsw_export_count / _fill): {"enter_points" i32,
     "nb_values" [i32 l0, l1], "nb_row_splits" [i64 l0, l1]} as device tensors -- what retrieval.Index(...) takes as they are,

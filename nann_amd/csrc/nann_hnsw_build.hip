@@ -29,8 +29,13 @@
 //
 // APPEND (nann_hnsw_append_device): the same batch loop started from a graph that exists -- the old rows are checked
 // once (k_hb_check: the rules the kernels rely on, and the rows' fill counts), then the new nodes go in as a build's
-// would; build and append share hb_insert.  EXPORT (nann_hnsw_export_count / _fill): the arrays -> the per-level CSR
-// and enter points nann_index_create takes, on the device (tests/test_index_append_gpu.py).
+// would.  EXPORT (nann_hnsw_export_count / _fill): the arrays -> the per-level CSR and enter points nann_index_create
+// takes, on the device (tests/test_index_append_gpu.py).
+//
+// HOST SIDE, what the calls share: build and append the scratch of a run and the batch loop (HbScratch, hb_insert); every
+// call the walk over `levels` (hb_levels: first upper rows, their total, the refusals) and the owner of its device memory
+// (HbOwned, filled by dev_alloc, freed on every return); append and remove the check of the graph they are given
+// (hb_check_enqueue, hb_check_result); search, back-link and repair the map (d, dtype, metric) -> <LPR, DT, MT> (hb_dispatch).
 //
 // REMOVE (nann_hnsw_remove_count / nann_hnsw_remove_device): the arrays and a bitmap of rows to drop -> NEW arrays over the
 // survivors, renumbered in order; a row that lost an entry is re-selected (wave_select) from its survivors and the surviving
@@ -48,6 +53,7 @@
 #include <cstring>
 #include <random>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nann_hip.h"
@@ -495,11 +501,20 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_backlink(HbGraph g, int le
   if (lane == 0) *cnt = c;
 }
 
+// the device allocations of one call: freed when it returns, by whichever return
+struct HbOwned {
+  std::vector<void*> ptrs;
+  HbOwned() = default;
+  HbOwned(const HbOwned&) = delete;
+  HbOwned& operator=(const HbOwned&) = delete;
+  ~HbOwned() { for (void* p : ptrs) (void)hipFree(p); }
+};
+
 template <typename T>
-int dev_alloc(T** p, size_t n, std::vector<void*>* owned) {
+int dev_alloc(T** p, size_t n, HbOwned* owned) {
   void* q = nullptr;
   HB_TRY(hipMalloc(&q, std::max<size_t>(n * sizeof(T), 16)));
-  owned->push_back(q);
+  owned->ptrs.push_back(q);
   *p = static_cast<T*>(q);
   return NANN_OK;
 }
@@ -788,34 +803,28 @@ int run_repair(const HbRepair& r, hipStream_t st) {
   return NANN_OK;
 }
 
-// ---- what build and append share: the scratch of a run and the batch loop ------------------------------------
+// ---- the host side (the header's HOST SIDE paragraph): first what build and append share, the scratch of a run -----------
 struct HbScratch {
-  std::vector<void*> owned;
   int32_t *order = nullptr, *cnt0 = nullptr, *cnt_up = nullptr, *entry = nullptr, *run_first = nullptr, *run_len = nullptr;
   uint32_t *pair_dst = nullptr, *pair_src = nullptr, *pair_dst2 = nullptr, *pair_src2 = nullptr;
   int* n_runs = nullptr;
   void* sort = nullptr;
   size_t sort_bytes = 0;
   int max_batch = 16384, pair_cap = 0;
-  ~HbScratch() { for (void* p : owned) (void)hipFree(p); }
   // n_order: nodes this run inserts (+ the entry point of a build); n_nodes / up_rows: the whole graph's
-  int alloc(size_t n_order, size_t n_nodes, int64_t up_rows, int M, hipStream_t st) {
+  int alloc(size_t n_order, size_t n_nodes, int64_t up_rows, int M, HbOwned* own, hipStream_t st) {
     pair_cap = 2 * M;
-    int rc = dev_alloc(&order, n_order, &owned);
-    if (!rc) rc = dev_alloc(&cnt0, n_nodes, &owned);
-    if (!rc) rc = dev_alloc(&cnt_up, (size_t)std::max<int64_t>(up_rows, 1), &owned);
-    if (!rc) rc = dev_alloc(&entry, (size_t)max_batch, &owned);
-    if (!rc) rc = dev_alloc(&pair_dst, (size_t)max_batch * pair_cap, &owned);
-    if (!rc) rc = dev_alloc(&pair_src, (size_t)max_batch * pair_cap, &owned);
-    if (!rc) rc = dev_alloc(&pair_dst2, (size_t)max_batch * pair_cap, &owned);
-    if (!rc) rc = dev_alloc(&pair_src2, (size_t)max_batch * pair_cap, &owned);
-    if (!rc) rc = dev_alloc(&run_first, (size_t)max_batch * pair_cap, &owned);
-    if (!rc) rc = dev_alloc(&run_len, (size_t)max_batch * pair_cap, &owned);
-    if (!rc) rc = dev_alloc(&n_runs, 1, &owned);
-    if (rc) return rc;
+    const size_t pairs = (size_t)max_batch * pair_cap;
+    int rc;
+    if ((rc = dev_alloc(&order, n_order, own)) || (rc = dev_alloc(&cnt0, n_nodes, own)) ||
+        (rc = dev_alloc(&cnt_up, (size_t)std::max<int64_t>(up_rows, 1), own)) || (rc = dev_alloc(&entry, (size_t)max_batch, own)) ||
+        (rc = dev_alloc(&pair_dst, pairs, own)) || (rc = dev_alloc(&pair_src, pairs, own)) || (rc = dev_alloc(&pair_dst2, pairs, own)) ||
+        (rc = dev_alloc(&pair_src2, pairs, own)) || (rc = dev_alloc(&run_first, pairs, own)) || (rc = dev_alloc(&run_len, pairs, own)) ||
+        (rc = dev_alloc(&n_runs, 1, own)))
+      return rc;
     hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, pair_dst, pair_dst2, pair_src, pair_src2, max_batch * pair_cap, 0, 32, st);
     unsigned char* p;
-    if ((rc = dev_alloc(&p, sort_bytes, &owned))) return rc;
+    if ((rc = dev_alloc(&p, sort_bytes, own))) return rc;
     sort = p;
     return NANN_OK;
   }
@@ -823,6 +832,74 @@ struct HbScratch {
 
 int hb_hip_rc(hipError_t e, const char* what) {
   return e == hipSuccess ? NANN_OK : fail(NANN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The one walk over `levels`: *up_rows = the number of upper rows (the sum of levels - 1) and, where asked for, up_first[i] =
+// node i's first upper row by the prefix rule (-1: one level).  Refused: a level < 1; with up_first (int32 rows) a total beyond
+// 2^31 - 1, at the node that crosses it, before a caller sizes anything by it; with adj_up (the address of the caller's
+// pointer) upper rows and no adj_up.
+int hb_levels(const char* who, const int32_t* levels, int n, const int32_t* const* adj_up, std::vector<int32_t>* up_first,
+              int64_t* up_rows) {
+  if (up_first) up_first->resize((size_t)n);
+  int64_t up = 0;
+  for (int i = 0; i < n; ++i) {
+    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
+    if (up_first) (*up_first)[(size_t)i] = levels[i] > 1 ? (int32_t)up : -1;
+    up += levels[i] - 1;
+    if (up_first && up > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 upper rows");
+  }
+  if (adj_up && up > 0 && !*adj_up) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": adj_up is null");
+  *up_rows = up;
+  return NANN_OK;
+}
+
+// The check of a graph that is input (append, remove), before anything is written.  hb_check_enqueue puts on the stream: levels
+// and the first upper rows the host derived go up, k_hb_check runs over the n nodes (fill counts -> cnt0 / cnt_up), the flags
+// come back into c->h_bad.  The caller synchronises, once, with whatever else it has on the stream; hb_check_result then turns
+// the flags into the refusal.
+struct HbCheck {
+  int32_t *levels = nullptr, *up_expect = nullptr, *bad = nullptr;  // on the device
+  int32_t h_bad[kHbRules] = {kHbNone, kHbNone, kHbNone, kHbNone};
+};
+
+int hb_check_enqueue(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up, const int32_t* levels,
+                     const std::vector<int32_t>& h_up, int n, int M, int32_t* cnt0, int32_t* cnt_up, HbCheck* c, HbOwned* own,
+                     hipStream_t st) {
+  int rc;
+  if ((rc = dev_alloc(&c->levels, (size_t)n, own)) || (rc = dev_alloc(&c->up_expect, (size_t)n, own)) ||
+      (rc = dev_alloc(&c->bad, (size_t)kHbRules, own)) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(c->levels, levels, (size_t)n * 4, hipMemcpyHostToDevice, st), "levels")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(c->up_expect, h_up.data(), (size_t)n * 4, hipMemcpyHostToDevice, st), "up_row")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(c->bad, c->h_bad, sizeof(c->h_bad), hipMemcpyHostToDevice, st), "flag")))
+    return rc;
+  hipLaunchKernelGGL(k_hb_check, dim3((unsigned)((n + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, adj0, up_row, adj_up,
+                     c->levels, c->up_expect, n, M, cnt0, cnt_up, c->bad);
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_check"))) return rc;
+  return hb_hip_rc(hipMemcpyAsync(c->h_bad, c->bad, sizeof(c->h_bad), hipMemcpyDeviceToHost, st), "flag");
+}
+
+int hb_check_result(const char* who, const HbCheck& c) {
+  static const char* const kRule[kHbRules] = {
+      "up_row differs from what levels implies (-1 for one level, else the running sum of levels - 1)",
+      "a row entry lies outside [-1, n_old)", "a row entry follows a -1 (rows are dense prefixes)",
+      "a row entry names a node that has no row on that level"};
+  for (int r = 0; r < kHbRules; ++r)
+    if (c.h_bad[r] != kHbNone)
+      return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": malformed graph, node " + std::to_string(c.h_bad[r]) + ": " + kRule[r]);
+  return NANN_OK;
+}
+
+// (d, emb_dtype, metric), all checked by then -> the kernels' <LPR, DT, MT>: f(lpr, dt, mt) gets them as integral constants
+template <int V>
+using HbInt = std::integral_constant<int, V>;
+
+template <typename F>
+int hb_dispatch(int d, int emb_dtype, int metric, F&& f) {
+  auto with_lpr = [&](auto lpr) -> int {
+    auto with_dt = [&](auto dt) -> int { return metric == NANN_SCORER_IP ? f(lpr, dt, HbInt<kHbIp>{}) : f(lpr, dt, HbInt<kHbL2>{}); };
+    return emb_dtype == NANN_F16 ? with_dt(HbInt<0>{}) : with_dt(HbInt<1>{});
+  };
+  return d == 64 ? with_lpr(HbInt<8>{}) : d == 128 ? with_lpr(HbInt<16>{}) : with_lpr(HbInt<32>{});
 }
 
 // The batch loop.  order[pos0 .. n_order) (also on the device, s.order) go into the graph `g`, which holds `base` nodes
@@ -835,28 +912,6 @@ int hb_insert(const char* who, const HbGraph& g, int emb_dtype, int metric, cons
               int entry, int T, int batch_cap, int ef, HbScratch& s, hipStream_t st) {
   const int n_order = (int)order.size(), d = g.d, pair_cap = s.pair_cap;
   std::vector<int32_t> h_entry((size_t)s.max_batch, entry);
-  auto search = [&](const HbBatch& b) -> int {
-#define HB_CASE(LPR_)                                                                                      \
-  if (metric == NANN_SCORER_IP)                                                                            \
-    return emb_dtype == NANN_F16 ? run_batch_level<LPR_, 0, kHbIp>(g, b, st) : run_batch_level<LPR_, 1, kHbIp>(g, b, st); \
-  return emb_dtype == NANN_F16 ? run_batch_level<LPR_, 0, kHbL2>(g, b, st) : run_batch_level<LPR_, 1, kHbL2>(g, b, st)
-    if (d == 64) { HB_CASE(8); }
-    if (d == 128) { HB_CASE(16); }
-    HB_CASE(32);
-#undef HB_CASE
-  };
-  auto backlink = [&](int level, int n_pairs) -> int {
-#define HB_CASE(LPR_)                                                                                                        \
-  if (metric == NANN_SCORER_IP)                                                                                              \
-    return emb_dtype == NANN_F16 ? run_backlink<LPR_, 0, kHbIp>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st) \
-                                 : run_backlink<LPR_, 1, kHbIp>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st); \
-  return emb_dtype == NANN_F16 ? run_backlink<LPR_, 0, kHbL2>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st) \
-                               : run_backlink<LPR_, 1, kHbL2>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st)
-    if (d == 64) { HB_CASE(8); }
-    if (d == 128) { HB_CASE(16); }
-    HB_CASE(32);
-#undef HB_CASE
-  };
   int rc;
   int pos = pos0;
   while (pos < n_order) {
@@ -873,14 +928,18 @@ int hb_insert(const char* who, const HbGraph& g, int emb_dtype, int metric, cons
       b.link = level <= lv - 1;
       b.ef = b.link ? ef : 1;
       b.entry = s.entry; b.pair_dst = s.pair_dst; b.pair_src = s.pair_src; b.pair_cap = pair_cap;
-      if ((rc = search(b))) return rc;
+      if ((rc = hb_dispatch(d, emb_dtype, metric, [&](auto lpr, auto dt, auto mt) { return run_batch_level<lpr(), dt(), mt()>(g, b, st); })))
+        return rc;
       if (!b.link) continue;
       const int n_pairs = n * pair_cap;
       if (hipcub::DeviceRadixSort::SortPairs(s.sort, s.sort_bytes, s.pair_dst, s.pair_dst2, s.pair_src, s.pair_src2, n_pairs, 0, 32, st) != hipSuccess)
         return fail(NANN_ERR_HIP, std::string(who) + ": radix sort failed");
       if ((rc = hb_hip_rc(hipMemsetAsync(s.n_runs, 0, 4, st), "n_runs"))) return rc;
       hipLaunchKernelGGL(k_hb_runs, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, s.pair_dst2, n_pairs, s.run_first, s.run_len, s.n_runs);
-      if ((rc = backlink(level, n_pairs))) return rc;
+      if ((rc = hb_dispatch(d, emb_dtype, metric, [&](auto lpr, auto dt, auto mt) {
+             return run_backlink<lpr(), dt(), mt()>(g, level, s.pair_dst2, s.pair_src2, s.run_first, s.run_len, s.n_runs, n_pairs, st);
+           })))
+        return rc;
     }
     if (lv > T) {
       if ((rc = hb_hip_rc(hipStreamSynchronize(st), "entry"))) return rc;  // the enqueued copies of h_entry have been read
@@ -892,9 +951,30 @@ int hb_insert(const char* who, const HbGraph& g, int emb_dtype, int metric, cons
   return hb_hip_rc(hipStreamSynchronize(st), who);
 }
 
-// the argument limits build and append share
-int hb_check_shape(const char* who, int64_t n_total, int32_t d, int32_t emb_dtype, int32_t M, int ef) {
+// The nodes [n0, n) go in (a build: n0 = 0): their order goes up, and the tails of the arrays, theirs, become empty rows with the
+// prefix rule continued -- up_row from h_up, upper rows [up0, up_rows).
+int hb_new_rows(const HbScratch& s, const std::vector<int32_t>& order, const std::vector<int32_t>& h_up, int n0, int n, int64_t up0,
+                int64_t up_rows, int M, int32_t* adj0, int32_t* up_row, int32_t* adj_up, hipStream_t st) {
+  const size_t n_new = (size_t)(n - n0), up_new = (size_t)(up_rows - up0);
+  int rc;
+  if ((rc = hb_hip_rc(hipMemcpyAsync(s.order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st), "order")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(up_row + n0, h_up.data() + n0, n_new * 4, hipMemcpyHostToDevice, st), "up_row")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(adj0 + (size_t)n0 * 2 * M, 0xff, n_new * 2 * M * 4, st), "adj0")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(s.cnt0 + n0, 0, n_new * 4, st), "cnt0")))
+    return rc;
+  if (up_new > 0 && ((rc = hb_hip_rc(hipMemsetAsync(adj_up + (size_t)up0 * M, 0xff, up_new * M * 4, st), "adj_up")) ||
+                     (rc = hb_hip_rc(hipMemsetAsync(s.cnt_up + up0, 0, up_new * 4, st), "cnt_up"))))
+    return rc;
+  return NANN_OK;
+}
+
+// the limits build, append and remove share, checked before anything is launched or written: the metric (a nann_scorer_kind),
+// then the shape
+int hb_check_args(const char* who, int32_t metric, int64_t n_total, int32_t d, int32_t emb_dtype, int32_t M, int ef) {
   const std::string w(who);
+  if (metric == NANN_SCORER_MLP) return fail(NANN_ERR_UNSUPPORTED, w + ": rows are linked by L2 or inner product, not by a model");
+  if (metric != NANN_SCORER_L2 && metric != NANN_SCORER_IP)
+    return fail(NANN_ERR_BAD_ARGUMENT, w + ": metric must be NANN_SCORER_L2 or NANN_SCORER_IP");
   if (n_total > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, w + ": more than 2^31 - 1 items");
   if (!(d == 64 || d == 128 || d == 256)) return fail(NANN_ERR_UNSUPPORTED, w + ": d must be 64, 128 or 256");
   if (emb_dtype != NANN_F16 && emb_dtype != NANN_BF16) return fail(NANN_ERR_UNSUPPORTED, w + ": f16 or bf16 rows");
@@ -903,14 +983,39 @@ int hb_check_shape(const char* who, int64_t n_total, int32_t d, int32_t emb_dtyp
   return NANN_OK;
 }
 
-// the metric of a build or an append: a nann_scorer_kind, checked before anything is launched or written
-int hb_check_metric(const char* who, int32_t metric) {
-  if (metric == NANN_SCORER_L2 || metric == NANN_SCORER_IP) return NANN_OK;
-  if (metric == NANN_SCORER_MLP) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": rows are linked by L2 or inner product, not by a model");
-  return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": metric must be NANN_SCORER_L2 or NANN_SCORER_IP");
+constexpr int kHbAppendDiv = 64;  // an append goes in in at least this many batches (DESIGN.md 4.6: 8 and 32 measured short)
+
+// the arguments the two export calls share
+int hb_export_args(const char* who, const void* adj0, const void* up_row, const int32_t* levels, int64_t n, int32_t M,
+                   int32_t start_level) {
+  const std::string w(who);
+  if (!adj0 || !up_row || !levels || n < 1) return fail(NANN_ERR_BAD_ARGUMENT, w + ": null argument or n < 1");
+  if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, w + ": more than 2^31 - 1 items");
+  if (M < 2 || 2 * M > kHbMaxCand) return fail(NANN_ERR_UNSUPPORTED, w + ": 2 <= M <= 32");
+  if (start_level != 2) return fail(NANN_ERR_UNSUPPORTED, w + ": start_level must be 2 (the levels serving walks)");
+  return NANN_OK;
 }
 
-constexpr int kHbAppendDiv = 64;  // an append goes in in at least this many batches (DESIGN.md 4.6: 8 and 32 measured short)
+// the old -> new map of a removal on the stream: keep flags, their exclusive scan into `map`; the bitmap also comes to the
+// host (h_bits, ceil(n / 32) words), where the survivors' levels are walked.  The caller synchronises.
+int hb_remove_map(const char* who, const uint32_t* remove_bits, int N, int32_t** map, std::vector<uint32_t>* h_bits, HbOwned* own,
+                  hipStream_t st) {
+  int32_t* flag;
+  int rc;
+  if ((rc = dev_alloc(&flag, (size_t)N, own)) || (rc = dev_alloc(map, (size_t)N, own))) return rc;
+  size_t scan_bytes = 0;
+  hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, flag, *map, N, st);
+  unsigned char* d_scan;
+  if ((rc = dev_alloc(&d_scan, scan_bytes, own))) return rc;
+  hipLaunchKernelGGL(k_hb_keep_flags, dim3((unsigned)(((size_t)N + 255) / 256)), dim3(256), 0, st, remove_bits, N, flag);
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_keep_flags"))) return rc;
+  if (hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, flag, *map, N, st) != hipSuccess)
+    return fail(NANN_ERR_HIP, std::string(who) + ": scan failed");
+  h_bits->resize(((size_t)N + 31) / 32);
+  return hb_hip_rc(hipMemcpyAsync(h_bits->data(), remove_bits, h_bits->size() * 4, hipMemcpyDeviceToHost, st), "remove_bits");
+}
+
+inline bool hb_bit(const std::vector<uint32_t>& bits, int i) { return (bits[(size_t)i >> 5] >> (i & 31)) & 1u; }
 
 }  // namespace
 
@@ -948,43 +1053,31 @@ int nann_hnsw_build_device_ex(const void* item_embs, int64_t n_items, int32_t d,
 int nann_hnsw_build_device_metric(const void* item_embs, int64_t n_items, int32_t d, int32_t emb_dtype, int32_t M,
                                   int32_t ef_construction, int32_t keep_pruned, int32_t metric, const int32_t* levels,
                                   int32_t* adj0, int32_t* up_row, int32_t* adj_up, nann_stream_t stream) {
-  if (!item_embs || !levels || !adj0 || !up_row || n_items <= 0)
-    return fail(NANN_ERR_BAD_ARGUMENT, "nann_hnsw_build_device: null argument");
-  if (int rcm = hb_check_metric("nann_hnsw_build_device", metric)) return rcm;
+  const char* who = "nann_hnsw_build_device";
+  if (!item_embs || !levels || !adj0 || !up_row || n_items <= 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
   const int ef = ef_construction > 0 ? ef_construction : 40;
-  if (int rc0 = hb_check_shape("nann_hnsw_build_device", n_items, d, emb_dtype, M, ef)) return rc0;
+  int rc = hb_check_args(who, metric, n_items, d, emb_dtype, M, ef);
+  if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = (int)n_items;
-  // ---- insertion order: top level first, ascending id inside a level (Faiss adds the highest levels first)
-  std::vector<int32_t> order((size_t)N), h_up((size_t)N);
-  int max_lv = 1;
+  std::vector<int32_t> h_up;
   int64_t up_rows = 0;
-  for (int i = 0; i < N; ++i) {
-    order[(size_t)i] = i;
-    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, "nann_hnsw_build_device: levels must be >= 1");
-    max_lv = std::max(max_lv, levels[i]);
-    h_up[(size_t)i] = levels[i] > 1 ? (int32_t)up_rows : -1;
-    up_rows += levels[i] - 1;
-  }
-  if (up_rows > 0 && !adj_up) return fail(NANN_ERR_BAD_ARGUMENT, "nann_hnsw_build_device: adj_up is null");
+  if ((rc = hb_levels(who, levels, N, &adj_up, &h_up, &up_rows))) return rc;
+  // ---- insertion order: top level first, ascending id inside a level (Faiss adds the highest levels first)
+  std::vector<int32_t> order((size_t)N);
+  for (int i = 0; i < N; ++i) order[(size_t)i] = i;
   std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return levels[a] > levels[b]; });
 
+  HbOwned own;
   HbScratch s;
-  int rc = s.alloc((size_t)N, (size_t)N, up_rows, M, st);
-  if (rc) return rc;
-  if ((rc = hb_hip_rc(hipMemcpyAsync(s.order, order.data(), (size_t)N * 4, hipMemcpyHostToDevice, st), "order")) ||
-      (rc = hb_hip_rc(hipMemcpyAsync(up_row, h_up.data(), (size_t)N * 4, hipMemcpyHostToDevice, st), "up_row")) ||
-      (rc = hb_hip_rc(hipMemsetAsync(adj0, 0xff, (size_t)N * 2 * M * 4, st), "adj0")) ||
-      (rc = hb_hip_rc(hipMemsetAsync(s.cnt0, 0, (size_t)N * 4, st), "cnt0")) ||
-      (rc = hb_hip_rc(hipMemsetAsync(s.cnt_up, 0, (size_t)std::max<int64_t>(up_rows, 1) * 4, st), "cnt_up")))
+  if ((rc = s.alloc((size_t)N, (size_t)N, up_rows, M, &own, st)) ||
+      (rc = hb_new_rows(s, order, h_up, 0, N, 0, up_rows, M, adj0, up_row, adj_up, st)))
     return rc;
-  if (up_rows > 0 && (rc = hb_hip_rc(hipMemsetAsync(adj_up, 0xff, (size_t)up_rows * M * 4, st), "adj_up"))) return rc;
-
   HbGraph g;
   g.emb = item_embs; g.adj0 = adj0; g.cnt0 = s.cnt0; g.up_row = up_row; g.adj_up = adj_up; g.cnt_up = s.cnt_up;
   g.n_items = N; g.d = d; g.M = M; g.keep_pruned = keep_pruned ? 1 : 0;
   // order[0] is the entry point: inserted with no links
-  return hb_insert("nann_hnsw_build_device", g, emb_dtype, metric, levels, order, 1, 0, order[0], levels[order[0]], 0x7fffffff, ef, s, st);
+  return hb_insert(who, g, emb_dtype, metric, levels, order, 1, 0, order[0], levels[order[0]], 0x7fffffff, ef, s, st);
 }
 
 int nann_hnsw_append_device(const void* item_embs, int64_t n_old, int64_t n_new, int32_t d, int32_t emb_dtype, int32_t M,
@@ -999,85 +1092,40 @@ int nann_hnsw_append_device_metric(const void* item_embs, int64_t n_old, int64_t
   const char* who = "nann_hnsw_append_device";
   if (!item_embs || !levels || !adj0 || !up_row || n_old < 1 || n_new < 0)
     return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument, n_old < 1 or n_new < 0");
-  int rc = hb_check_metric(who, metric);
-  if (rc) return rc;
   const int ef = ef_construction > 0 ? ef_construction : 40;
-  rc = hb_check_shape(who, n_old > 0x7fffffffll - n_new ? 0x80000000ll : n_old + n_new, d, emb_dtype, M, ef);
+  int rc = hb_check_args(who, metric, n_old > 0x7fffffffll - n_new ? 0x80000000ll : n_old + n_new, d, emb_dtype, M, ef);
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N0 = (int)n_old, N1 = (int)n_new, N = N0 + N1;
-  // ---- from `levels`: every node's first upper row, the old graph's entry point, the new nodes' order
-  std::vector<int32_t> h_up((size_t)N);
+  std::vector<int32_t> h_up;
   int64_t up_rows = 0, up_rows_old = 0;
+  if ((rc = hb_levels(who, levels, N, &adj_up, &h_up, &up_rows))) return rc;
+  // ---- the old graph's entry point and upper rows, the new nodes' order
   int entry = 0;
-  for (int i = 0; i < N; ++i) {
-    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
-    if (i < N0 && levels[i] > levels[entry]) entry = i;  // the lowest id among the nodes with the most levels
-    h_up[(size_t)i] = levels[i] > 1 ? (int32_t)up_rows : -1;
-    up_rows += levels[i] - 1;
-    if (i == N0 - 1) up_rows_old = up_rows;
+  for (int i = 0; i < N0; ++i) {
+    if (levels[i] > levels[entry]) entry = i;  // the lowest id among the nodes with the most levels
+    up_rows_old += levels[i] - 1;
   }
-  if (up_rows > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 upper rows");
-  if (up_rows > 0 && !adj_up) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": adj_up is null");
   std::vector<int32_t> order((size_t)N1);
   for (int i = 0; i < N1; ++i) order[(size_t)i] = N0 + i;
   std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return levels[a] > levels[b]; });
 
+  HbOwned own;
   HbScratch s;
-  if ((rc = s.alloc((size_t)std::max(N1, 1), (size_t)N, up_rows, M, st))) return rc;
-  // ---- the old graph is checked before anything is written: levels and the expected up_row go up, one pass, one flag back
-  int32_t *d_levels, *d_up, *d_bad;
-  if ((rc = dev_alloc(&d_levels, (size_t)N0, &s.owned)) || (rc = dev_alloc(&d_up, (size_t)N0, &s.owned)) ||
-      (rc = dev_alloc(&d_bad, (size_t)kHbRules, &s.owned)))
+  HbCheck check;
+  // ---- the old graph is checked before anything is written: one pass, one flag back
+  if ((rc = s.alloc((size_t)std::max(N1, 1), (size_t)N, up_rows, M, &own, st)) ||
+      (rc = hb_check_enqueue(adj0, up_row, adj_up, levels, h_up, N0, M, s.cnt0, s.cnt_up, &check, &own, st)) ||
+      (rc = hb_hip_rc(hipStreamSynchronize(st), "k_hb_check")) || (rc = hb_check_result(who, check)))
     return rc;
-  int32_t h_bad[kHbRules] = {kHbNone, kHbNone, kHbNone, kHbNone};
-  if ((rc = hb_hip_rc(hipMemcpyAsync(d_levels, levels, (size_t)N0 * 4, hipMemcpyHostToDevice, st), "levels")) ||
-      (rc = hb_hip_rc(hipMemcpyAsync(d_up, h_up.data(), (size_t)N0 * 4, hipMemcpyHostToDevice, st), "up_row")) ||
-      (rc = hb_hip_rc(hipMemcpyAsync(d_bad, h_bad, sizeof(h_bad), hipMemcpyHostToDevice, st), "flag")))
-    return rc;
-  hipLaunchKernelGGL(k_hb_check, dim3((unsigned)((N0 + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, adj0, up_row, adj_up,
-                     d_levels, d_up, N0, M, s.cnt0, s.cnt_up, d_bad);
-  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_check")) ||
-      (rc = hb_hip_rc(hipMemcpyAsync(h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, st), "flag")) ||
-      (rc = hb_hip_rc(hipStreamSynchronize(st), "k_hb_check")))
-    return rc;
-  static const char* const kRule[kHbRules] = {
-      "up_row differs from what levels implies (-1 for one level, else the running sum of levels - 1)",
-      "a row entry lies outside [-1, n_old)", "a row entry follows a -1 (rows are dense prefixes)",
-      "a row entry names a node that has no row on that level"};
-  for (int r = 0; r < kHbRules; ++r)
-    if (h_bad[r] != kHbNone)
-      return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": malformed graph, node " + std::to_string(h_bad[r]) + ": " + kRule[r]);
   if (N1 == 0) return NANN_OK;
-  // ---- the tails: empty rows, the prefix rule continued
-  const int64_t up_new = up_rows - up_rows_old;
-  if ((rc = hb_hip_rc(hipMemcpyAsync(s.order, order.data(), (size_t)N1 * 4, hipMemcpyHostToDevice, st), "order")) ||
-      (rc = hb_hip_rc(hipMemcpyAsync(up_row + N0, h_up.data() + N0, (size_t)N1 * 4, hipMemcpyHostToDevice, st), "up_row")) ||
-      (rc = hb_hip_rc(hipMemsetAsync(adj0 + (size_t)N0 * 2 * M, 0xff, (size_t)N1 * 2 * M * 4, st), "adj0")) ||
-      (rc = hb_hip_rc(hipMemsetAsync(s.cnt0 + N0, 0, (size_t)N1 * 4, st), "cnt0")))
-    return rc;
-  if (up_new > 0 &&
-      ((rc = hb_hip_rc(hipMemsetAsync(adj_up + (size_t)up_rows_old * M, 0xff, (size_t)up_new * M * 4, st), "adj_up")) ||
-       (rc = hb_hip_rc(hipMemsetAsync(s.cnt_up + up_rows_old, 0, (size_t)up_new * 4, st), "cnt_up"))))
-    return rc;
+  if ((rc = hb_new_rows(s, order, h_up, N0, N, up_rows_old, up_rows, M, adj0, up_row, adj_up, st))) return rc;
   HbGraph g;
   g.emb = item_embs; g.adj0 = adj0; g.cnt0 = s.cnt0; g.up_row = up_row; g.adj_up = adj_up; g.cnt_up = s.cnt_up;
   g.n_items = N; g.d = d; g.M = M; g.keep_pruned = keep_pruned ? 1 : 0;
   const int batch_cap = std::max(1, (N1 + kHbAppendDiv - 1) / kHbAppendDiv);
   return hb_insert(who, g, emb_dtype, metric, levels, order, 0, n_old, entry, levels[entry], batch_cap, ef, s, st);
 }
-
-namespace {
-int hb_export_args(const char* who, const void* adj0, const void* up_row, const int32_t* levels, int64_t n, int32_t M,
-                   int32_t start_level) {
-  const std::string w(who);
-  if (!adj0 || !up_row || !levels || n < 1) return fail(NANN_ERR_BAD_ARGUMENT, w + ": null argument or n < 1");
-  if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, w + ": more than 2^31 - 1 items");
-  if (M < 2 || 2 * M > kHbMaxCand) return fail(NANN_ERR_UNSUPPORTED, w + ": 2 <= M <= 32");
-  if (start_level != 2) return fail(NANN_ERR_UNSUPPORTED, w + ": start_level must be 2 (the levels serving walks)");
-  return NANN_OK;
-}
-}  // namespace
 
 int nann_hnsw_export_count(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up, const int32_t* levels, int64_t n,
                            int32_t M, int32_t start_level, int64_t* row_splits0, int64_t* row_splits1, int64_t* nnz,
@@ -1089,44 +1137,38 @@ int nann_hnsw_export_count(const int32_t* adj0, const int32_t* up_row, const int
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = (int)n;
   int64_t n_up = 0, enter = 0;
-  for (int i = 0; i < N; ++i) {
-    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
-    n_up += levels[i] - 1;
-    enter += levels[i] > start_level;
-  }
-  if (n_up > 0 && !adj_up) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": adj_up is null");
-  std::vector<void*> owned;
-  auto cleanup = [&](int r) { for (void* p : owned) (void)hipFree(p); return r; };
+  if ((rc = hb_levels(who, levels, N, &adj_up, nullptr, &n_up))) return rc;
+  for (int i = 0; i < N; ++i) enter += levels[i] > start_level;
+  HbOwned own;
   int32_t* d_levels;
   int64_t* d_len;
   int* d_bad;
-  if ((rc = dev_alloc(&d_levels, (size_t)N, &owned)) || (rc = dev_alloc(&d_len, (size_t)N * 2, &owned)) ||
-      (rc = dev_alloc(&d_bad, 1, &owned)))
-    return cleanup(rc);
+  if ((rc = dev_alloc(&d_levels, (size_t)N, &own)) || (rc = dev_alloc(&d_len, (size_t)N * 2, &own)) || (rc = dev_alloc(&d_bad, 1, &own)))
+    return rc;
   size_t scan_bytes = 0;
   hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, d_len, row_splits0 + 1, N, st);
   unsigned char* d_scan;
-  if ((rc = dev_alloc(&d_scan, scan_bytes, &owned))) return cleanup(rc);
-  if ((rc = hb_hip_rc(hipMemcpyAsync(d_levels, levels, (size_t)N * 4, hipMemcpyHostToDevice, st), "levels")) ||
+  if ((rc = dev_alloc(&d_scan, scan_bytes, &own)) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(d_levels, levels, (size_t)N * 4, hipMemcpyHostToDevice, st), "levels")) ||
       (rc = hb_hip_rc(hipMemsetAsync(d_bad, 0, 4, st), "flag")) ||
       (rc = hb_hip_rc(hipMemsetAsync(row_splits0, 0, 8, st), "row_splits")) ||
       (rc = hb_hip_rc(hipMemsetAsync(row_splits1, 0, 8, st), "row_splits")))
-    return cleanup(rc);
+    return rc;
   hipLaunchKernelGGL(k_hb_export_count, dim3((unsigned)((N + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, adj0, up_row,
                      adj_up, d_levels, N, n_up, M, d_len, d_len + N, d_bad);
-  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_export_count"))) return cleanup(rc);
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_export_count"))) return rc;
   if (hipcub::DeviceScan::InclusiveSum(d_scan, scan_bytes, d_len, row_splits0 + 1, N, st) != hipSuccess ||
       hipcub::DeviceScan::InclusiveSum(d_scan, scan_bytes, d_len + N, row_splits1 + 1, N, st) != hipSuccess)
-    return cleanup(fail(NANN_ERR_HIP, std::string(who) + ": scan failed"));
+    return fail(NANN_ERR_HIP, std::string(who) + ": scan failed");
   int h_bad = 0;
   if ((rc = hb_hip_rc(hipMemcpyAsync(&nnz[0], row_splits0 + N, 8, hipMemcpyDeviceToHost, st), "nnz")) ||
       (rc = hb_hip_rc(hipMemcpyAsync(&nnz[1], row_splits1 + N, 8, hipMemcpyDeviceToHost, st), "nnz")) ||
       (rc = hb_hip_rc(hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st), "flag")) ||
       (rc = hb_hip_rc(hipStreamSynchronize(st), who)))
-    return cleanup(rc);
-  if (h_bad) return cleanup(fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": an up_row entry lies outside adj_up"));
+    return rc;
+  if (h_bad) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": an up_row entry lies outside adj_up");
   *n_enter = enter;
-  return cleanup(NANN_OK);
+  return NANN_OK;
 }
 
 int nann_hnsw_export_fill(const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up, const int32_t* levels, int64_t n,
@@ -1141,58 +1183,32 @@ int nann_hnsw_export_fill(const int32_t* adj0, const int32_t* up_row, const int3
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = (int)n;
   int64_t n_up = 0;
+  if ((rc = hb_levels(who, levels, N, nullptr, nullptr, &n_up))) return rc;
   std::vector<int32_t> enter;
-  for (int i = 0; i < N; ++i) {
-    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
-    n_up += levels[i] - 1;
+  for (int i = 0; i < N; ++i)
     if (levels[i] > start_level) enter.push_back(i);
-  }
   if ((n_up > 0 && !adj_up) || (!enter.empty() && !enter_points))
     return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": adj_up or enter_points is null");
-  std::vector<void*> owned;
-  auto cleanup = [&](int r) { for (void* p : owned) (void)hipFree(p); return r; };
+  HbOwned own;
   int32_t* d_levels;
   int* d_bad;
-  if ((rc = dev_alloc(&d_levels, (size_t)N, &owned)) || (rc = dev_alloc(&d_bad, 1, &owned))) return cleanup(rc);
-  if ((rc = hb_hip_rc(hipMemcpyAsync(d_levels, levels, (size_t)N * 4, hipMemcpyHostToDevice, st), "levels")) ||
+  if ((rc = dev_alloc(&d_levels, (size_t)N, &own)) || (rc = dev_alloc(&d_bad, 1, &own)) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(d_levels, levels, (size_t)N * 4, hipMemcpyHostToDevice, st), "levels")) ||
       (rc = hb_hip_rc(hipMemsetAsync(d_bad, 0, 4, st), "flag")))
-    return cleanup(rc);
+    return rc;
   if (!enter.empty() &&
       (rc = hb_hip_rc(hipMemcpyAsync(enter_points, enter.data(), enter.size() * 4, hipMemcpyHostToDevice, st), "enter_points")))
-    return cleanup(rc);
+    return rc;
   hipLaunchKernelGGL(k_hb_export_fill, dim3((unsigned)((N + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, adj0, up_row,
                      adj_up, d_levels, N, n_up, M, row_splits0, row_splits1, nnz[0], nnz[1], values0, values1, d_bad);
   int h_bad = 0;
   if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_export_fill")) ||
       (rc = hb_hip_rc(hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st), "flag")) ||
       (rc = hb_hip_rc(hipStreamSynchronize(st), who)))
-    return cleanup(rc);
-  if (h_bad) return cleanup(fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": row_splits are not this graph's (call nann_hnsw_export_count first)"));
-  return cleanup(NANN_OK);
+    return rc;
+  if (h_bad) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": row_splits are not this graph's (call nann_hnsw_export_count first)");
+  return NANN_OK;
 }
-
-namespace {
-// the old -> new map of a removal on the stream: keep flags, their exclusive scan into `map`; the bitmap also comes to the
-// host (h_bits, ceil(n / 32) words), where the survivors' levels are walked.  The caller synchronises.
-int hb_remove_map(const char* who, const uint32_t* remove_bits, int N, int32_t** map, std::vector<uint32_t>* h_bits,
-                  std::vector<void*>* owned, hipStream_t st) {
-  int32_t* flag;
-  int rc;
-  if ((rc = dev_alloc(&flag, (size_t)N, owned)) || (rc = dev_alloc(map, (size_t)N, owned))) return rc;
-  size_t scan_bytes = 0;
-  hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, flag, *map, N, st);
-  unsigned char* d_scan;
-  if ((rc = dev_alloc(&d_scan, scan_bytes, owned))) return rc;
-  hipLaunchKernelGGL(k_hb_keep_flags, dim3((unsigned)(((size_t)N + 255) / 256)), dim3(256), 0, st, remove_bits, N, flag);
-  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_keep_flags"))) return rc;
-  if (hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, flag, *map, N, st) != hipSuccess)
-    return fail(NANN_ERR_HIP, std::string(who) + ": scan failed");
-  h_bits->resize(((size_t)N + 31) / 32);
-  return hb_hip_rc(hipMemcpyAsync(h_bits->data(), remove_bits, h_bits->size() * 4, hipMemcpyDeviceToHost, st), "remove_bits");
-}
-
-inline bool hb_bit(const std::vector<uint32_t>& bits, int i) { return (bits[(size_t)i >> 5] >> (i & 31)) & 1u; }
-}  // namespace
 
 int nann_hnsw_remove_count(const uint32_t* remove_bits, const int32_t* levels, int64_t n, int32_t* kept_rows,
                            int32_t* new_levels, int64_t* n_keep, int64_t* n_up_rows, nann_stream_t stream) {
@@ -1201,17 +1217,16 @@ int nann_hnsw_remove_count(const uint32_t* remove_bits, const int32_t* levels, i
     return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument or n < 1");
   if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 items");
   const int N = (int)n;
-  for (int i = 0; i < N; ++i)
-    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
+  int64_t up_old = 0;  // not asked for: the survivors' is
+  int rc = hb_levels(who, levels, N, nullptr, nullptr, &up_old);
+  if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  std::vector<void*> owned;
-  auto cleanup = [&](int r) { for (void* p : owned) (void)hipFree(p); return r; };
+  HbOwned own;
   int32_t* map;
   std::vector<uint32_t> h_bits;
-  int rc = hb_remove_map(who, remove_bits, N, &map, &h_bits, &owned, st);
-  if (rc) return cleanup(rc);
+  if ((rc = hb_remove_map(who, remove_bits, N, &map, &h_bits, &own, st))) return rc;
   hipLaunchKernelGGL(k_hb_kept_rows, dim3((unsigned)(((size_t)N + 255) / 256)), dim3(256), 0, st, remove_bits, map, N, kept_rows);
-  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_kept_rows")) || (rc = hb_hip_rc(hipStreamSynchronize(st), who))) return cleanup(rc);
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_kept_rows")) || (rc = hb_hip_rc(hipStreamSynchronize(st), who))) return rc;
   int64_t keep = 0, up = 0;
   for (int i = 0; i < N; ++i) {
     if (hb_bit(h_bits, i)) continue;
@@ -1220,7 +1235,7 @@ int nann_hnsw_remove_count(const uint32_t* remove_bits, const int32_t* levels, i
   }
   *n_keep = keep;
   *n_up_rows = up;
-  return cleanup(NANN_OK);
+  return NANN_OK;
 }
 
 int nann_hnsw_remove_device(const void* item_embs, int64_t n, int32_t d, int32_t emb_dtype, int32_t M, int32_t keep_pruned,
@@ -1232,55 +1247,33 @@ int nann_hnsw_remove_device(const void* item_embs, int64_t n, int32_t d, int32_t
     return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument or n < 1");
   if (n_keep < 1 || n_keep > n)
     return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_keep must lie in [1, n] (a graph keeps at least one node)");
-  int rc = hb_check_metric(who, metric);
+  int rc = hb_check_args(who, metric, n, d, emb_dtype, M, 0);
   if (rc) return rc;
-  if ((rc = hb_check_shape(who, n, d, emb_dtype, M, 0))) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = (int)n;
-  // ---- from `levels`: every old node's first upper row and the owner of every upper row
-  std::vector<int32_t> h_up((size_t)N), h_owner;
+  std::vector<int32_t> h_up, h_owner;
   int64_t up_rows = 0;
-  for (int i = 0; i < N; ++i) {
-    if (levels[i] < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": levels must be >= 1");
-    h_up[(size_t)i] = levels[i] > 1 ? (int32_t)up_rows : -1;
-    up_rows += levels[i] - 1;
-    if (up_rows > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 upper rows");
-    h_owner.insert(h_owner.end(), (size_t)(levels[i] - 1), i);
-  }
-  if (up_rows > 0 && !adj_up) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": adj_up is null");
+  if ((rc = hb_levels(who, levels, N, &adj_up, &h_up, &up_rows))) return rc;
+  // ---- the owner of every upper row: grown only now that their number is known to be in range
+  h_owner.reserve((size_t)up_rows);
+  for (int i = 0; i < N; ++i) h_owner.insert(h_owner.end(), (size_t)(levels[i] - 1), i);
 
-  std::vector<void*> owned;
-  auto cleanup = [&](int r) { for (void* p : owned) (void)hipFree(p); return r; };
+  HbOwned own;
+  HbCheck check;
   // ---- the old graph is checked, and the bitmap scanned, before anything is written
-  int32_t *d_levels, *d_up, *d_owner, *d_bad, *cnt0, *cnt_up, *map;
+  int32_t *d_owner, *cnt0, *cnt_up, *map;
   unsigned long long* d_stats;
-  if ((rc = dev_alloc(&d_levels, (size_t)N, &owned)) || (rc = dev_alloc(&d_up, (size_t)N, &owned)) ||
-      (rc = dev_alloc(&d_owner, (size_t)std::max<int64_t>(up_rows, 1), &owned)) || (rc = dev_alloc(&d_bad, (size_t)kHbRules, &owned)) ||
-      (rc = dev_alloc(&cnt0, (size_t)N, &owned)) || (rc = dev_alloc(&cnt_up, (size_t)std::max<int64_t>(up_rows, 1), &owned)) ||
-      (rc = dev_alloc(&d_stats, 3, &owned)))
-    return cleanup(rc);
-  int32_t h_bad[kHbRules] = {kHbNone, kHbNone, kHbNone, kHbNone};
-  if ((rc = hb_hip_rc(hipMemcpyAsync(d_levels, levels, (size_t)N * 4, hipMemcpyHostToDevice, st), "levels")) ||
-      (rc = hb_hip_rc(hipMemcpyAsync(d_up, h_up.data(), (size_t)N * 4, hipMemcpyHostToDevice, st), "up_row")) ||
-      (rc = hb_hip_rc(hipMemcpyAsync(d_bad, h_bad, sizeof(h_bad), hipMemcpyHostToDevice, st), "flag")) ||
+  if ((rc = dev_alloc(&d_owner, (size_t)std::max<int64_t>(up_rows, 1), &own)) || (rc = dev_alloc(&cnt0, (size_t)N, &own)) ||
+      (rc = dev_alloc(&cnt_up, (size_t)std::max<int64_t>(up_rows, 1), &own)) || (rc = dev_alloc(&d_stats, 3, &own)) ||
       (rc = hb_hip_rc(hipMemsetAsync(d_stats, 0, 3 * sizeof(unsigned long long), st), "stats")))
-    return cleanup(rc);
+    return rc;
   if (up_rows > 0 && (rc = hb_hip_rc(hipMemcpyAsync(d_owner, h_owner.data(), (size_t)up_rows * 4, hipMemcpyHostToDevice, st), "owner")))
-    return cleanup(rc);
-  hipLaunchKernelGGL(k_hb_check, dim3((unsigned)((N + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, adj0, up_row, adj_up,
-                     d_levels, d_up, N, M, cnt0, cnt_up, d_bad);
+    return rc;
   std::vector<uint32_t> h_bits;
-  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_check")) || (rc = hb_remove_map(who, remove_bits, N, &map, &h_bits, &owned, st)) ||
-      (rc = hb_hip_rc(hipMemcpyAsync(h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, st), "flag")) ||
-      (rc = hb_hip_rc(hipStreamSynchronize(st), "k_hb_check")))
-    return cleanup(rc);
-  static const char* const kRule[kHbRules] = {
-      "up_row differs from what levels implies (-1 for one level, else the running sum of levels - 1)",
-      "a row entry lies outside [-1, n_old)", "a row entry follows a -1 (rows are dense prefixes)",
-      "a row entry names a node that has no row on that level"};
-  for (int r = 0; r < kHbRules; ++r)
-    if (h_bad[r] != kHbNone)
-      return cleanup(fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": malformed graph, node " + std::to_string(h_bad[r]) + ": " + kRule[r]));
+  if ((rc = hb_check_enqueue(adj0, up_row, adj_up, levels, h_up, N, M, cnt0, cnt_up, &check, &own, st)) ||
+      (rc = hb_remove_map(who, remove_bits, N, &map, &h_bits, &own, st)) ||
+      (rc = hb_hip_rc(hipStreamSynchronize(st), "k_hb_check")) || (rc = hb_check_result(who, check)))
+    return rc;
   // ---- the survivors: their count against n_keep, their first upper rows by the prefix rule
   std::vector<int32_t> h_new_up;
   h_new_up.reserve((size_t)n_keep);
@@ -1291,32 +1284,24 @@ int nann_hnsw_remove_device(const void* item_embs, int64_t n, int32_t d, int32_t
     new_up_rows += levels[i] - 1;
   }
   if (keep != n_keep)
-    return cleanup(fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_keep is " + std::to_string(n_keep) + ", the bitmap leaves " +
-                                                   std::to_string(keep) + " rows (call nann_hnsw_remove_count first)"));
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_keep is " + std::to_string(n_keep) + ", the bitmap leaves " +
+                                           std::to_string(keep) + " rows (call nann_hnsw_remove_count first)");
   if ((rc = hb_hip_rc(hipMemcpyAsync(out_up_row, h_new_up.data(), (size_t)n_keep * 4, hipMemcpyHostToDevice, st), "out_up_row")))
-    return cleanup(rc);
+    return rc;
   HbRepair r;
-  r.emb = item_embs; r.adj0 = adj0; r.up_expect = d_up; r.adj_up = adj_up; r.up_owner = d_owner; r.bits = remove_bits; r.map = map;
+  r.emb = item_embs; r.adj0 = adj0; r.up_expect = check.up_expect; r.adj_up = adj_up; r.up_owner = d_owner; r.bits = remove_bits; r.map = map;
   r.out_up_row = out_up_row; r.out_adj0 = out_adj0; r.out_adj_up = out_adj_up; r.stats = d_stats;
   r.n = N; r.d = d; r.M = M; r.keep_pruned = keep_pruned ? 1 : 0; r.n_work = (long long)N + up_rows;
-  auto repair = [&]() -> int {
-#define HB_CASE(LPR_)                                                                                            \
-  if (metric == NANN_SCORER_IP) return emb_dtype == NANN_F16 ? run_repair<LPR_, 0, kHbIp>(r, st) : run_repair<LPR_, 1, kHbIp>(r, st); \
-  return emb_dtype == NANN_F16 ? run_repair<LPR_, 0, kHbL2>(r, st) : run_repair<LPR_, 1, kHbL2>(r, st)
-    if (d == 64) { HB_CASE(8); }
-    if (d == 128) { HB_CASE(16); }
-    HB_CASE(32);
-#undef HB_CASE
-  };
   unsigned long long h_stats[3] = {0, 0, 0};
-  if ((rc = repair()) || (rc = hb_hip_rc(hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st), "stats")) ||
+  if ((rc = hb_dispatch(d, emb_dtype, metric, [&](auto lpr, auto dt, auto mt) { return run_repair<lpr(), dt(), mt()>(r, st); })) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st), "stats")) ||
       (rc = hb_hip_rc(hipStreamSynchronize(st), who)))
-    return cleanup(rc);
+    return rc;
   if (stats) {
     for (int i = 0; i < 3; ++i) stats[i] = (int64_t)h_stats[i];
     stats[3] = n_keep;
   }
-  return cleanup(NANN_OK);
+  return NANN_OK;
 }
 
 }  // extern "C"

@@ -141,6 +141,44 @@ def _export_torch(levels, adj0, up_row, adj_up, m, start_level):
     return out
 
 
+def _device_api():
+    """what every device call below starts with: torch, the library, and ops' call helpers"""
+    import torch
+    from . import _lib
+    from .ops import _check, _ptr, _stream, _DT
+    return torch, _lib.lib(), _check, _ptr, _stream, _DT
+
+
+def _graph_arrays(n, n_up, m, device, fill=None):
+    """new i32 tensors adj0 [n, 2m], up_row [n], adj_up [max(n_up, 1), m] on `device`: uninitialised, or full of `fill`"""
+    import torch
+    new = lambda *shape: (torch.empty(shape, dtype=torch.int32, device=device) if fill is None else
+                          torch.full(shape, fill, dtype=torch.int32, device=device))
+    return new(max(n, 1), 2 * m)[:n], new(max(n, 1))[:n], new(max(n_up, 1), m)
+
+
+def _device_rows(rows, device=None):
+    """rows (a tensor, or what numpy takes) -> a contiguous tensor on `device` (None: the current CUDA device)"""
+    import torch
+    t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(rows))
+    return (t.cuda() if device is None else t.to(device=device)).contiguous()
+
+
+def _state(item_embs, adj0, up_row, adj_up, levels, m, ef_construction, keep_pruned, metric):
+    """the builder's own arrays on the device with what the next append, removal or export needs to know"""
+    return {"item_embs": item_embs, "adj0": adj0, "up_row": up_row, "adj_up": adj_up, "levels": levels, "M": m,
+            "ef_construction": int(ef_construction), "keep_pruned": bool(keep_pruned), "metric": metric}
+
+
+def _result(state, start_level, want_export=True, want_state=True):
+    """what the device calls return: the torch export of the arrays of `state` (or "levels" alone), and "state" itself"""
+    out = (_export_torch(state["levels"], state["adj0"], state["up_row"], state["adj_up"], state["M"], start_level)
+           if want_export else {"levels": state["levels"]})
+    if want_state:
+        out["state"] = state
+    return out
+
+
 def build_hnsw_gpu(item_embs, num_neighbors=32, ef_construction=40, seed=0, start_level=2, want_raw=False,
                    keep_pruned=False, want_state=False, metric="l2"):
     """HNSW(M) over the rows of `item_embs` (CUDA tensor f16 | bf16 [N, d], or a numpy f16 array) built ON THE GPU
@@ -154,29 +192,20 @@ def build_hnsw_gpu(item_embs, num_neighbors=32, ef_construction=40, seed=0, star
     index that is searched with the inner-product scorer: rows are linked by dist(a, b) = -<a, b>.  Under "ip" the default
     heuristic leaves sparse rows (mean level-0 degree 2-3 where L2 on the same rows gives 3-4); keep_pruned fills them."""
     kind = _metric_kind(metric)
-    import torch
-    from . import _lib
-    from .ops import _check, _ptr, _stream, _DT
-    L = _lib.lib()
-    x = item_embs if isinstance(item_embs, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(item_embs))
-    x = x.cuda().contiguous()
+    torch, L, _check, _ptr, _stream, _DT = _device_api()
+    x = _device_rows(item_embs)
     n, d = x.shape
     m = int(num_neighbors)
     levels = np.zeros(n, np.int32)
     n_up = C.c_int64(0)
     _check(L.nann_hnsw_draw_levels(C.c_int64(n), C.c_int32(m), C.c_uint64(seed), levels.ctypes.data_as(C.c_void_p),
                                    C.byref(n_up)), "hnsw levels")
-    adj0 = torch.empty((n, 2 * m), dtype=torch.int32, device=x.device)
-    up_row = torch.empty(n, dtype=torch.int32, device=x.device)
-    adj_up = torch.empty((max(n_up.value, 1), m), dtype=torch.int32, device=x.device)
+    adj0, up_row, adj_up = _graph_arrays(n, n_up.value, m, x.device)
     torch.cuda.synchronize()
     _check(L.nann_hnsw_build_device_metric(_ptr(x), n, d, _DT[x.dtype], m, int(ef_construction), 1 if keep_pruned else 0, kind,
                                            levels.ctypes.data_as(C.c_void_p), _ptr(adj0), _ptr(up_row), _ptr(adj_up), _stream()),
            "hnsw build")
-    out = _export_torch(levels, adj0, up_row, adj_up, m, start_level)
-    if want_state:
-        out["state"] = {"item_embs": x, "adj0": adj0, "up_row": up_row, "adj_up": adj_up, "levels": levels, "M": m,
-                        "ef_construction": int(ef_construction), "keep_pruned": bool(keep_pruned), "metric": metric}
+    out = _result(_state(x, adj0, up_row, adj_up, levels, m, ef_construction, keep_pruned, metric), start_level, want_state=want_state)
     if want_raw:
         cum = np.concatenate([[0], 2 * m + m * np.arange(int(levels.max()))]).astype(np.int32)
         offsets = np.zeros(n + 1, np.int64)
@@ -198,16 +227,12 @@ def append_hnsw_gpu(state, new_rows, seed, start_level=2, want_export=True):
     new nodes' levels are drawn with `seed`.  Returns what build_hnsw_gpu(want_state=True) returns, over the grown corpus;
     want_export=False: {"levels", "state"} only, without the torch export and its copy to the host -- the live path, which goes
     on with export_hnsw_gpu(state) on the device."""
-    import torch
-    from . import _lib
-    from .ops import _check, _ptr, _stream, _DT
-    L = _lib.lib()
+    torch, L, _check, _ptr, _stream, _DT = _device_api()
     metric = state.get("metric", "l2")
     kind = _metric_kind(metric)
     x0, m = state["item_embs"], int(state["M"])
     n_old, d = x0.shape
-    new = new_rows if isinstance(new_rows, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(new_rows))
-    new = new.to(device=x0.device).reshape(-1, d)
+    new = _device_rows(new_rows, x0.device).reshape(-1, d)
     if new.dtype != x0.dtype:
         raise ValueError(f"append_hnsw_gpu: rows are {new.dtype}, the graph's are {x0.dtype}")
     n_new = new.shape[0]
@@ -219,20 +244,13 @@ def append_hnsw_gpu(state, new_rows, seed, start_level=2, want_export=True):
     levels = np.ascontiguousarray(np.concatenate([np.asarray(state["levels"], np.int32), new_levels]))
     n = n_old + n_new
     n_up_old, n_up = int((levels[:n_old] - 1).sum()), int((levels.astype(np.int64) - 1).sum())
-    adj0 = torch.full((n, 2 * m), -1, dtype=torch.int32, device=x.device)
-    adj0[:n_old] = state["adj0"]
-    up_row = torch.full((n,), -1, dtype=torch.int32, device=x.device)
-    up_row[:n_old] = state["up_row"]
-    adj_up = torch.full((max(n_up, 1), m), -1, dtype=torch.int32, device=x.device)
-    adj_up[:n_up_old] = state["adj_up"][:n_up_old]
+    adj0, up_row, adj_up = _graph_arrays(n, n_up, m, x.device, fill=-1)
+    adj0[:n_old], up_row[:n_old], adj_up[:n_up_old] = state["adj0"], state["up_row"], state["adj_up"][:n_up_old]
     torch.cuda.synchronize()
     _check(L.nann_hnsw_append_device_metric(_ptr(x), n_old, n_new, d, _DT[x.dtype], m, int(state["ef_construction"]),
                                             1 if state["keep_pruned"] else 0, kind, levels.ctypes.data_as(C.c_void_p), _ptr(adj0),
                                             _ptr(up_row), _ptr(adj_up), _stream()), "hnsw append")
-    out = _export_torch(levels, adj0, up_row, adj_up, m, start_level) if want_export else {"levels": levels}
-    out["state"] = {"item_embs": x, "adj0": adj0, "up_row": up_row, "adj_up": adj_up, "levels": levels, "M": m,
-                    "ef_construction": int(state["ef_construction"]), "keep_pruned": bool(state["keep_pruned"]), "metric": metric}
-    return out
+    return _result(_state(x, adj0, up_row, adj_up, levels, m, state["ef_construction"], state["keep_pruned"], metric), start_level, want_export)
 
 
 def _remove_bits(n, remove_rows, deny_bits, dev):
@@ -271,10 +289,7 @@ def remove_hnsw_gpu(state, remove_rows=None, deny_bits=None, start_level=2, want
     row, for the caller's item_ids) and "stats" (i64[4]: rows repaired, level-0 rows that came out empty, rows whose pool
     exceeded 64, survivors).  No back-links are added, isolated nodes are counted and not healed, and the entry layer (survivors
     with levels > start_level) is the caller's to watch.  want_export=False skips the torch export, as in the append."""
-    import torch
-    from . import _lib
-    from .ops import _check, _ptr, _stream, _DT
-    L = _lib.lib()
+    torch, L, _check, _ptr, _stream, _DT = _device_api()
     metric = state.get("metric", "l2")
     kind = _metric_kind(metric)
     x0, m = state["item_embs"], int(state["M"])
@@ -289,9 +304,7 @@ def remove_hnsw_gpu(state, remove_rows=None, deny_bits=None, start_level=2, want
     _check(L.nann_hnsw_remove_count(_ptr(bits), old_levels.ctypes.data_as(C.c_void_p), n, _ptr(kept),
                                     new_levels.ctypes.data_as(C.c_void_p), C.byref(n_keep), C.byref(n_up), _stream()), "hnsw remove count")
     nk = n_keep.value
-    adj0 = torch.empty((max(nk, 1), 2 * m), dtype=torch.int32, device=dev)[:nk]
-    up_row = torch.empty(max(nk, 1), dtype=torch.int32, device=dev)[:nk]
-    adj_up = torch.empty((max(n_up.value, 1), m), dtype=torch.int32, device=dev)
+    adj0, up_row, adj_up = _graph_arrays(nk, n_up.value, m, dev)
     stats = (C.c_int64 * 4)()
     _check(L.nann_hnsw_remove_device(_ptr(x0), n, d, _DT[x0.dtype], m, 1 if state["keep_pruned"] else 0, kind,
                                      old_levels.ctypes.data_as(C.c_void_p), _ptr(state["adj0"]), _ptr(state["up_row"]),
@@ -299,9 +312,7 @@ def remove_hnsw_gpu(state, remove_rows=None, deny_bits=None, start_level=2, want
            "hnsw remove")
     kept, levels = kept[:nk].contiguous(), np.ascontiguousarray(new_levels[:nk])
     x = x0[kept.long()].contiguous()
-    out = _export_torch(levels, adj0, up_row, adj_up, m, start_level) if want_export else {"levels": levels}
-    out["state"] = {"item_embs": x, "adj0": adj0, "up_row": up_row, "adj_up": adj_up, "levels": levels, "M": m,
-                    "ef_construction": int(state["ef_construction"]), "keep_pruned": bool(state["keep_pruned"]), "metric": metric}
+    out = _result(_state(x, adj0, up_row, adj_up, levels, m, state["ef_construction"], state["keep_pruned"], metric), start_level, want_export)
     out["kept_rows"] = kept
     out["stats"] = np.array(list(stats), np.int64)
     return out
@@ -311,10 +322,7 @@ def export_hnsw_gpu(state, start_level=2):
     """The export of build_hnsw_index.py:41-66 ON THE DEVICE (nann_hnsw_export_count / _fill): {"enter_points" i32,
     "nb_values" [i32 l0, l1], "nb_row_splits" [i64 l0, l1]} as device tensors -- what retrieval.Index(...) takes as they are,
     so a grown graph reaches serving without a host round trip."""
-    import torch
-    from . import _lib
-    from .ops import _check, _ptr, _stream
-    L = _lib.lib()
+    torch, L, _check, _ptr, _stream, _ = _device_api()
     adj0, up_row, adj_up, levels, m = state["adj0"], state["up_row"], state["adj_up"], state["levels"], int(state["M"])
     levels = np.ascontiguousarray(levels, dtype=np.int32)
     n, dev = len(levels), adj0.device

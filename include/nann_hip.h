@@ -994,7 +994,21 @@ typedef struct {
   const float* alpha[3];
   int32_t precision;  /* enum nann_mlp_precision: NANN_MLP_SPLIT_F16 (every f32 operand as hi + lo f16 on the
                        * 16-bit MFMA, 3x fewer matrix cycles; logits within ~1e-6 of the exact form; the default),
-                       * NANN_MLP_EXACT_F32 (f32-input MFMA); NANN_MLP_CERTIFIED is rejected (MLP scorers only) */
+                       * NANN_MLP_EXACT_F32 (f32-input MFMA); NANN_MLP_CERTIFIED is rejected (MLP scorers only).
+                       * Both forms hold 1e-5 max(1, |s|) against the f32 chain at every seq_len in [1, 64] and with a
+                       * peaked softmax as with a flat one: attention logits spanning 15-21 per row, |att| up to ~25
+                       * (wq2 and wk2 x 32), measured <= 6.3e-7 split, <= 5.7e-7 exact (tests/test_attn_shapes_gpu.py).
+                       * Range of the split form: a user's projected keys are carried as f16 hi + lo of k x 2^7
+                       * (k_attn_prepare_split, round-to-nearest conversions), so every component of every key needs
+                       * |k| < 511.875 (|k| x 2^7 < 65520, where the conversion to f16 stays finite).  A position with
+                       * a key component at or beyond that gets hi = +-inf, lo = -+inf and a NaN attention logit, and
+                       * the softmax DROPS it: fmaxf skips the NaN in the row maximum and the exponential clamps its
+                       * argument from below, so the position gets weight 0 and the others are renormalised.  That
+                       * user's logits are FINITE AND WRONG -- the model's logits for the sequence without that
+                       * position -- with no status and no NaN to test for; they are NaN only when every one of the
+                       * user's L positions overflows.  Other users are not touched.  A caller that cannot bound its
+                       * keys must check them itself or use the exact form, which has no such limit.
+                       * (tests/attn_reference.py split_softmax restates those lines; test_attn_shapes_gpu.py runs it.) */
 } nann_attn_desc;
 int nann_attn_scorer_create(const nann_attn_desc* desc /*[host]*/, nann_attn_scorer** out);
 void nann_attn_scorer_destroy(nann_attn_scorer* s);

@@ -380,6 +380,14 @@ class AttnModel:
         self.s = s
 
 
+def attn_prepare(model, user_seq):
+    """user_seq f32[L, E] -> (status, kproj f32[L, 4E]): the per-user key projection (oracle_attn_prepare)"""
+    u = _c(user_seq, np.float32)
+    kproj = np.zeros((model.s.L, 4 * model.s.E), np.float32)
+    rc = lib().oracle_attn_prepare(C.byref(model.s), _p(u), _p(kproj))
+    return rc, kproj
+
+
 def attn_score_rows(model, user_seq, rows):
     """user_seq f32[L, E]; rows [n, d] in the model's emb dtype -> (status, logits f32[n])"""
     u = _c(user_seq, np.float32)

@@ -124,12 +124,26 @@ def emulate_wave(w, u, rows, L):
 
 @pytest.mark.parametrize("d", [64, 128])
 def test_lane_level_model_of_the_attention_kernel(oracle, d):
+    _lane_level_case(oracle, d, 50, 1)
+
+
+@pytest.mark.parametrize("L,g", [(1, 1), (1, 32), (33, 1), (33, 32), (64, 1), (64, 32), (50, 32)])
+@pytest.mark.parametrize("d", [64, 128])
+def test_lane_level_model_at_other_lengths_and_a_peaked_softmax(oracle, d, L, g):
+    """L = 1 (one live position, the whole second tile and 31 of the first masked), 33 (one position into the second tile)
+    and 64 (no layout padding: nothing masked); g = 32 peaks the softmax (attn_reference.py), so a wrong mask or a wrong
+    position-to-register map moves the logit by far more than the tolerance."""
+    _lane_level_case(oracle, d, L, g)
+
+
+def _lane_level_case(oracle, d, L, g):
+    from attn_reference import sharpen
     from nann_amd import synth
-    E, L = 64, 50
-    w = synth.make_attn_weights(d, E)
+    E = 64
+    w = sharpen(synth.make_attn_weights(d, E), g)
     rng = np.random.default_rng(7 + d)
     u = (rng.standard_normal((L, E)) / 8).astype(np.float16).astype(np.float32)
-    u[44:] = 0
+    u[L - L // 8:] = 0
     rows = (rng.standard_normal((32, d)) / 8).astype(np.float16)
     m = oracle.AttnModel(d, E, L, oracle.EMB_F16, w)
     rc, exp = oracle.attn_score_rows(m, u, rows)

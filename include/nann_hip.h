@@ -827,7 +827,10 @@ int nann_sharded_topk(nann_comm* c, const float* scores, const int64_t* ids, con
  * without keepPrunedConnections), batched -- nodes go in by descending level in batches of at most a quarter of
  * the graph built so far (<= 16384), every node of a batch searches the graph of the earlier batches with one
  * wavefront, back-links are applied per target in a deterministic order (csrc/nann_hnsw_build.hip).  Index
- * contents are not a parity target (Faiss' own are thread-schedule dependent); layout, invariants and recall are.
+ * contents are not a parity target against Faiss (its own are thread-schedule dependent); layout, invariants and recall are.
+ * They are a pure function of (rows, levels, M, ef_construction, keep_pruned, metric), pinned entry for entry to the model
+ * of tests/hnsw_build_model.py for the cases of its tests.  Everything is ordered by the key (distance with -0 taken as +0,
+ * then id), ascending: the beam of a search, the candidates of a selection, a full row and its new link, a repair's pool.
  *   nann_hnsw_draw_levels   [host] levels[i] = number of levels of node i (Faiss convention, P(levels > l) = M^-l),
  *                           same draw as the CPU builder's; *n_up_rows = sum(levels - 1) = rows of adj_up
  *   nann_hnsw_build_device  item_embs device [n, d] f16 | bf16 (d in 64 | 128 | 256), levels [host];

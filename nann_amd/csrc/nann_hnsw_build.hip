@@ -24,8 +24,9 @@
 // adj0 [N, 2M] (-1 = empty slot), and for nodes with more than one level their rows in adj_up [rows, M]
 // (row of node i on level l >= 1: up_row[i] + l - 1).  nann_amd/index_build.py turns them into
 // neighbors_level_{l}_{values,row_splits}.npy / enter_points.npy exactly as build_hnsw_index.py:41-66 does.
-// Index CONTENTS are not a parity target (Faiss' own insertion order is thread-schedule dependent);
-// the structural invariants and recall are (tests/test_index_build.py, -m gpu).
+// Index CONTENTS are not a parity target against Faiss (its own insertion order is thread-schedule dependent);
+// the structural invariants and recall are (tests/test_index_build.py, -m gpu).  They ARE pinned, entry for entry, to the plain
+// model of tests/hnsw_build_model.py for the cases of its tests (tests/test_index_build_exact_gpu.py).
 //
 // APPEND (nann_hnsw_append_device): the same batch loop started from a graph that exists -- the old rows are checked
 // once (k_hb_check: the rules the kernels rely on, and the rows' fill counts), then the new nodes go in as a build's
@@ -365,11 +366,16 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_search(HbGraph g, HbBatch 
     __builtin_amdgcn_wave_barrier();
     unsigned long long fresh_key = kKeyInf;
     if (lane < n_new) fresh_key = hb_key<MT>(L.dist[lane], L.list[lane]);
-    // merge; a lane's `expanded` flag travels with its key: carry it in the key's bit 31 (ids are < 2^31)
-    const unsigned long long tagged = beam == kKeyInf ? beam : (beam | (expanded ? 0x80000000ull : 0ull));
-    const unsigned long long merged = wave_merge64(tagged, fresh_key, lane);
-    expanded = merged != kKeyInf && (merged & 0x80000000ull) != 0ull;
-    beam = merged == kKeyInf ? merged : (merged & ~0x80000000ull);
+    // merge; a lane's `expanded` flag travels with its key BELOW the id: the id half becomes (id << 1) | flag (ids are < 2^31).
+    // Ids are unique in the beam, so the flag never decides an order: the beam is sorted by (distance, id) alone, and it stays
+    // sorted -- what wave_merge64 asks of its first argument -- when lane p's flag has just been set.  (In bit 31, above the id,
+    // the flag put lane p behind the unexpanded lanes of the SAME distance without moving it: an unsorted input on exact ties.)
+    auto tag = [](unsigned long long k, bool e) -> unsigned long long {
+      return k == kKeyInf ? k : ((k & 0xffffffff00000000ull) | ((k & 0x7fffffffull) << 1) | (e ? 1ull : 0ull));
+    };
+    const unsigned long long merged = wave_merge64(tag(beam, expanded), tag(fresh_key, false), lane);
+    expanded = merged != kKeyInf && (merged & 1ull) != 0ull;
+    beam = merged == kKeyInf ? merged : ((merged & 0xffffffff00000000ull) | ((merged & 0xffffffffull) >> 1));
     if (lane >= ef) { beam = kKeyInf; expanded = false; }  // the beam holds ef candidates
     __builtin_amdgcn_wave_barrier();
   }

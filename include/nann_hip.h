@@ -946,7 +946,8 @@ int nann_hnsw_export_fill(const int32_t* adj0, const int32_t* up_row, const int3
  * the heuristic runs over them in ascending order with the level's cap (2M on level 0, M above) and honours keep_pruned, and the
  * row is written as a dense prefix in that order with -1 behind.
  * WHAT IT DOES NOT DO: no back-links are added (no other row learns of a repaired row's new entries); a node may come out with
- * an empty row or without in-links, which is counted in stats and not healed; and nothing guards the entry layer -- after a
+ * an empty row or without in-links, which is counted in stats and not healed here (nann_hnsw_orphan_bits followed by
+ * nann_hnsw_update_device, below, re-inserts such nodes); and nothing guards the entry layer -- after a
  * removal the serving enter points are the survivors with levels > 2, and when fewer remain than the first top-k asks for,
  * requests fail k > n exactly as on any small index.  That is the caller's to watch (new_levels says how many are left).
  *   nann_hnsw_remove_count  step 1, because the sizes depend on the data (as nann_hnsw_export_count).  kept_rows device i32[n]:
@@ -974,6 +975,57 @@ int nann_hnsw_remove_device(const void* item_embs, int64_t n, int32_t d, int32_t
                             const uint32_t* remove_bits, int64_t n_keep,
                             int32_t* out_adj0, int32_t* out_up_row, int32_t* out_adj_up, int64_t* stats,
                             nann_stream_t stream);
+/* Update: rows of a graph are refreshed IN PLACE -- an item whose embedding has changed, or a node a removal left without
+ * links.  Row numbers and levels do not change, so everything that speaks in internal rows (a nann_filter's deny_bits and
+ * excl_rows, nann_candidates.rows, out_index, the caller's item_ids order) stays valid; remove + nann_gather_rows + append
+ * would move the row to the tail and renumber every survivor.  Overwriting the embedding alone leaves the row's links, and the
+ * links to it, where its OLD embedding put them.
+ *   item_embs    device [n, d]: already holds the NEW embeddings of the marked rows.  The old ones are not needed: no distance
+ *                the call computes involves a marked row before that row is re-inserted.
+ *   update_bits  device u32[ceil(n / 32)], the deny bitmap's convention (row r is marked iff bit (r & 31) of word (r >> 5) is
+ *                set); bits at or beyond n are ignored.
+ *   the old graph (adj0, up_row, adj_up: device; levels: host; n nodes) is const and stays untouched; the outputs are NEW
+ *                arrays of the same shapes, the caller's: out_adj0 i32[n, 2M], out_up_row i32[n] (the prefix rule, equal to
+ *                up_row), out_adj_up i32[max(sum(levels - 1), 1), M] (without upper rows it is not written).  The result is
+ *                valid input of nann_hnsw_append_device(_metric), of the export calls, of nann_hnsw_remove_* and of this call again.
+ * Two phases, on the path build, append and remove share.
+ * DETACH is the repair of nann_hnsw_remove_device without the renumbering: a marked node's rows come out empty on every level;
+ * a staying row with no marked entry is copied slot for slot; a staying row with a marked entry is re-selected from its pool --
+ * the staying entries of the row and, one hop out, the staying entries of each marked entry's old row on that level, the node
+ * itself left out --, cut to its 64 nearest members by the (distance, id) key, with the level's cap and keep_pruned.  After it
+ * no row names a marked node.  The fill counts of the new arrays come from a device pass over them.
+ * RE-INSERT is the append's insertion: the marked nodes by descending level, then ascending id, onto the staying ones; the
+ * entry point is the lowest id among the STAYING nodes with the most levels; a batch is at most min(16384, (staying + inserted
+ * so far) / 4, ceil(n_marked / 64)) nodes; a marked node with more levels than the entry point goes in alone, is linked on the
+ * levels the graph has (its rows above stay empty) and is the entry point from then on; back-links as in the build.
+ *   stats [host] i64[4] or NULL: {rows repaired by the detach phase (all levels), level-0 rows of staying nodes that were
+ *                non-empty and came out of the detach phase empty, rows whose distinct pool exceeded 64, rows updated}.
+ * The old graph is INPUT, and malformed input never faults: the validation pass of the append runs first over all n nodes (the
+ * same four rules, the same words in nann_last_error, the lowest offending node); a malformed graph gives
+ * NANN_ERR_BAD_ARGUMENT with every output (stats included) untouched.  Argument checks come before any device call:
+ * NANN_ERR_BAD_ARGUMENT (a null pointer -- out_adj_up included, adj_up when a node has more than one level --, n < 1,
+ * levels[i] < 1, a metric that is no scorer kind); NANN_ERR_UNSUPPORTED (n > 2^31 - 1, d, dtype, M or ef_construction outside
+ * the build's limits, NANN_SCORER_MLP).  Every row marked, so that nothing stays, is NANN_ERR_BAD_ARGUMENT with the outputs
+ * untouched: that is a build.  Nothing marked is not an error: the outputs equal the inputs bit for bit, stats all zero.
+ * Synchronous.  Deterministic: the same inputs give the same arrays.  Outputs that alias inputs are the caller's error.
+ * WHAT IT DOES NOT DO: it does not heal the in-links of STAYING nodes (mark them: nann_hnsw_orphan_bits), and it does not
+ * promise that a re-inserted node keeps an in-link -- a full row may re-select it away.  It does promise that every re-inserted
+ * node's own level-0 row is non-empty when at least one node stays.
+ *   nann_hnsw_orphan_bits  which rows to heal: out_bits device u32[ceil(n / 32)], bit r set iff level-0 row r is empty or no
+ *                level-0 row names r; entries outside [0, n) are skipped as if their slots were empty, so a malformed adj0 never
+ *                faults; bits at or beyond n in the last word are zero.  *n_orphans [host] = the bits set.  Synchronous; the
+ *                output is a set, hence deterministic.  NANN_ERR_BAD_ARGUMENT (a null pointer, n < 1); NANN_ERR_UNSUPPORTED
+ *                (n > 2^31 - 1, M outside [2, 32]).  The heal after a removal: nann_hnsw_orphan_bits on the removal's output,
+ *                then nann_hnsw_update_device with those bits and the embeddings as they are. */
+int nann_hnsw_update_device(const void* item_embs, int64_t n, int32_t d, int32_t emb_dtype, int32_t M,
+                            int32_t ef_construction, int32_t keep_pruned, int32_t metric,
+                            const int32_t* levels /*[host] n*/,
+                            const int32_t* adj0, const int32_t* up_row, const int32_t* adj_up,
+                            const uint32_t* update_bits /*device, the deny bitmap's convention*/,
+                            int32_t* out_adj0, int32_t* out_up_row, int32_t* out_adj_up,
+                            int64_t* stats /*[host] i64[4] or NULL*/, nann_stream_t stream);
+int nann_hnsw_orphan_bits(const int32_t* adj0, int64_t n, int32_t M, uint32_t* out_bits /*device, ceil(n/32) words*/,
+                          int64_t* n_orphans /*[host]*/, nann_stream_t stream);
 
 /* ---- 8(f2): the reference's own scorer model behind the BlazeXlaOp contract -------------
  * NANN_impls/nann/model/model.py:189-233 + model_util.py:70-97: softmax attention of the candidate

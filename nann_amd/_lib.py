@@ -52,6 +52,7 @@ SYMBOLS = [
     "nann_hnsw_append_device", "nann_hnsw_export_count", "nann_hnsw_export_fill",
     "nann_hnsw_build_device_metric", "nann_hnsw_append_device_metric",
     "nann_hnsw_remove_count", "nann_hnsw_remove_device",
+    "nann_hnsw_update_device", "nann_hnsw_orphan_bits",
 ]
 
 
@@ -205,6 +206,13 @@ def lib():
         L.nann_hnsw_remove_device.argtypes = [C.c_void_p, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 5 + [C.c_int64] + \
                                               [C.c_void_p] * 3 + [C.POINTER(C.c_int64), C.c_void_p]
         L.nann_hnsw_remove_device.restype = C.c_int
+        # (item_embs, n, d, emb_dtype, M, ef_construction, keep_pruned, metric, levels, adj0, up_row, adj_up, update_bits, out_adj0,
+        #  out_up_row, out_adj_up, stats, stream)
+        L.nann_hnsw_update_device.argtypes = [C.c_void_p, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 8 + [C.POINTER(C.c_int64), C.c_void_p]
+        L.nann_hnsw_update_device.restype = C.c_int
+        # (adj0, n, M, out_bits, *n_orphans, stream)
+        L.nann_hnsw_orphan_bits.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+        L.nann_hnsw_orphan_bits.restype = C.c_int
         _LIB = L
     return _LIB
 

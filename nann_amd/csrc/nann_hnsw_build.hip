@@ -33,14 +33,19 @@
 // would.  EXPORT (nann_hnsw_export_count / _fill): the arrays -> the per-level CSR and enter points nann_index_create
 // takes, on the device (tests/test_index_append_gpu.py).
 //
-// HOST SIDE, what the calls share: build and append the scratch of a run and the batch loop (HbScratch, hb_insert); every
+// HOST SIDE, what the calls share: build, append and update the scratch of a run and the batch loop (HbScratch, hb_insert); every
 // call the walk over `levels` (hb_levels: first upper rows, their total, the refusals) and the owner of its device memory
-// (HbOwned, filled by dev_alloc, freed on every return); append and remove the check of the graph they are given
+// (HbOwned, filled by dev_alloc, freed on every return); append, remove and update the check of the graph they are given
 // (hb_check_enqueue, hb_check_result); search, back-link and repair the map (d, dtype, metric) -> <LPR, DT, MT> (hb_dispatch).
 //
 // REMOVE (nann_hnsw_remove_count / nann_hnsw_remove_device): the arrays and a bitmap of rows to drop -> NEW arrays over the
 // survivors, renumbered in order; a row that lost an entry is re-selected (wave_select) from its survivors and the surviving
 // entries of its removed entries' rows, one hop (k_hb_repair; tests/test_index_remove_gpu.py).
+//
+// UPDATE (nann_hnsw_update_device): rows whose embedding changed, or that a removal left without links, are refreshed IN PLACE --
+// detach (k_hb_repair with the identity map: nobody is renumbered, the marked nodes' rows come out empty), the fill counts of
+// the new arrays from a device pass (k_hb_check over them), then hb_insert as the append calls it.  nann_hnsw_orphan_bits
+// (k_hb_orphan_mark / _bits) names the rows a heal would mark.  tests/test_index_update_gpu.py; DESIGN.md 4.6.
 //
 // METRIC (nann_hnsw_build_device_metric / nann_hnsw_append_device_metric): the same kernels with dist(a, b) = -<a, b>, for an
 // index that is searched with the inner-product scorer.  Algorithms 1-4 run on that distance unchanged; the beam's keys take
@@ -797,6 +802,31 @@ __global__ __launch_bounds__(kHbWaves * 64) void k_hb_repair(HbRepair r) {
   }
 }
 
+// ---- orphans: the level-0 rows that a removal (or anything else) left empty or unnamed ----------------------------------------
+// One wavefront per row, a slot per lane.  An entry outside [0, n) is skipped as if the slot were empty, so nothing is read or
+// written beyond the bitmaps.  named: bit e set iff some row holds e; empty_bits: bit r set iff row r holds no entry.  Both are
+// sets, so the order of the atomics does not show.
+__global__ __launch_bounds__(kHbWaves * 64) void k_hb_orphan_mark(const int32_t* adj0, int n, int M, uint32_t* named, uint32_t* empty_bits) {
+  const int lane = threadIdx.x & 63;
+  const size_t at = (size_t)blockIdx.x * kHbWaves + (threadIdx.x >> 6);
+  if (at >= (size_t)n) return;
+  const int e = lane < 2 * M ? adj0[at * 2 * M + lane] : -1;
+  const bool valid = e >= 0 && e < n;
+  if (valid) atomicOr(&named[(uint32_t)e >> 5], 1u << (e & 31));
+  if (__ballot(valid) == 0ull && lane == 0) atomicOr(&empty_bits[at >> 5], 1u << (at & 31));
+}
+
+// bits (in: the empty rows) |= the unnamed rows, bits at or beyond n cleared; *count += the rows set
+__global__ void k_hb_orphan_bits(const uint32_t* named, int n, uint32_t* bits, unsigned long long* count) {
+  const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t words = ((size_t)n + 31) / 32;
+  if (w >= words) return;
+  const uint32_t mask = (w == words - 1 && (n & 31)) ? (1u << (n & 31)) - 1u : 0xffffffffu;
+  const uint32_t v = (bits[w] | ~named[w]) & mask;
+  bits[w] = v;
+  if (v) atomicAdd(count, (unsigned long long)__popc(v));
+}
+
 template <int LPR, int DT, int MT>
 int run_repair(const HbRepair& r, hipStream_t st) {
   const size_t lds = ((size_t)kHbMaxCand * r.d * 2 + 1024) * kHbWaves;  // k_hb_backlink's budget
@@ -1307,6 +1337,121 @@ int nann_hnsw_remove_device(const void* item_embs, int64_t n, int32_t d, int32_t
     for (int i = 0; i < 3; ++i) stats[i] = (int64_t)h_stats[i];
     stats[3] = n_keep;
   }
+  return NANN_OK;
+}
+
+int nann_hnsw_update_device(const void* item_embs, int64_t n, int32_t d, int32_t emb_dtype, int32_t M, int32_t ef_construction,
+                            int32_t keep_pruned, int32_t metric, const int32_t* levels, const int32_t* adj0, const int32_t* up_row,
+                            const int32_t* adj_up, const uint32_t* update_bits, int32_t* out_adj0, int32_t* out_up_row,
+                            int32_t* out_adj_up, int64_t* stats, nann_stream_t stream) {
+  const char* who = "nann_hnsw_update_device";
+  if (!item_embs || !levels || !adj0 || !up_row || !update_bits || !out_adj0 || !out_up_row || !out_adj_up || n < 1)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument or n < 1");
+  const int ef = ef_construction > 0 ? ef_construction : 40;
+  int rc = hb_check_args(who, metric, n, d, emb_dtype, M, ef);
+  if (rc) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int N = (int)n;
+  std::vector<int32_t> h_up, h_owner;
+  int64_t up_rows = 0;
+  if ((rc = hb_levels(who, levels, N, &adj_up, &h_up, &up_rows))) return rc;
+  h_owner.reserve((size_t)up_rows);
+  for (int i = 0; i < N; ++i) h_owner.insert(h_owner.end(), (size_t)(levels[i] - 1), i);
+
+  HbOwned own;
+  HbScratch s;
+  HbCheck check;
+  // ---- the old graph is checked, and the bitmap brought to the host, before anything is written
+  int32_t *d_owner, *ident, *bad2;
+  unsigned long long* d_stats;
+  const size_t words = ((size_t)N + 31) / 32;
+  std::vector<uint32_t> h_bits(words);
+  if ((rc = s.alloc((size_t)N, (size_t)N, up_rows, M, &own, st)) || (rc = dev_alloc(&d_owner, (size_t)std::max<int64_t>(up_rows, 1), &own)) ||
+      (rc = dev_alloc(&ident, (size_t)N, &own)) || (rc = dev_alloc(&bad2, (size_t)kHbRules, &own)) || (rc = dev_alloc(&d_stats, 3, &own)) ||
+      (rc = hb_hip_rc(hipMemsetAsync(d_stats, 0, 3 * sizeof(unsigned long long), st), "stats")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(h_bits.data(), update_bits, words * 4, hipMemcpyDeviceToHost, st), "update_bits")) ||
+      (rc = hb_check_enqueue(adj0, up_row, adj_up, levels, h_up, N, M, s.cnt0, s.cnt_up, &check, &own, st)) ||
+      (rc = hb_hip_rc(hipStreamSynchronize(st), "k_hb_check")) || (rc = hb_check_result(who, check)))
+    return rc;
+  // ---- the marked nodes in the order they go back in, and the entry point among those that stay
+  std::vector<int32_t> order;
+  int entry = -1;
+  for (int i = 0; i < N; ++i) {
+    if (hb_bit(h_bits, i)) order.push_back(i);
+    else if (entry < 0 || levels[i] > levels[entry]) entry = i;  // the lowest id among the staying nodes with the most levels
+  }
+  const int n_marked = (int)order.size();
+  if (n_marked == N)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": every row is marked, nothing stays to link to (that is a build)");
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return levels[a] > levels[b]; });
+  // ---- detach: the removal's repair under the identity map; the marked nodes' rows stay the empty rows written here
+  std::vector<int32_t> h_ident((size_t)N);
+  for (int i = 0; i < N; ++i) h_ident[(size_t)i] = i;
+  if ((rc = hb_hip_rc(hipMemcpyAsync(ident, h_ident.data(), (size_t)N * 4, hipMemcpyHostToDevice, st), "map")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(out_up_row, h_up.data(), (size_t)N * 4, hipMemcpyHostToDevice, st), "out_up_row")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(out_adj0, 0xff, (size_t)N * 2 * M * 4, st), "out_adj0")))
+    return rc;
+  if (up_rows > 0 && ((rc = hb_hip_rc(hipMemcpyAsync(d_owner, h_owner.data(), (size_t)up_rows * 4, hipMemcpyHostToDevice, st), "owner")) ||
+                      (rc = hb_hip_rc(hipMemsetAsync(out_adj_up, 0xff, (size_t)up_rows * M * 4, st), "out_adj_up"))))
+    return rc;
+  HbRepair r;
+  r.emb = item_embs; r.adj0 = adj0; r.up_expect = check.up_expect; r.adj_up = adj_up; r.up_owner = d_owner; r.bits = update_bits; r.map = ident;
+  r.out_up_row = out_up_row; r.out_adj0 = out_adj0; r.out_adj_up = out_adj_up; r.stats = d_stats;
+  r.n = N; r.d = d; r.M = M; r.keep_pruned = keep_pruned ? 1 : 0; r.n_work = (long long)N + up_rows;
+  unsigned long long h_stats[3] = {0, 0, 0};
+  if ((rc = hb_dispatch(d, emb_dtype, metric, [&](auto lpr, auto dt, auto mt) { return run_repair<lpr(), dt(), mt()>(r, st); })) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st), "stats")))
+    return rc;
+  if (n_marked > 0) {
+    // ---- the fill counts of the new arrays: the check's pass over them (its flags go nowhere: these rows are the call's own)
+    hipLaunchKernelGGL(k_hb_check, dim3((unsigned)((N + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, out_adj0, out_up_row,
+                       out_adj_up, check.levels, check.up_expect, N, M, s.cnt0, s.cnt_up, bad2);
+    if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_check")) ||
+        (rc = hb_hip_rc(hipMemcpyAsync(s.order, order.data(), order.size() * 4, hipMemcpyHostToDevice, st), "order")))
+      return rc;
+    // ---- re-insert, as an append of the marked nodes onto the staying ones
+    HbGraph g;
+    g.emb = item_embs; g.adj0 = out_adj0; g.cnt0 = s.cnt0; g.up_row = out_up_row; g.adj_up = out_adj_up; g.cnt_up = s.cnt_up;
+    g.n_items = N; g.d = d; g.M = M; g.keep_pruned = keep_pruned ? 1 : 0;
+    const int batch_cap = std::max(1, (n_marked + kHbAppendDiv - 1) / kHbAppendDiv);
+    if ((rc = hb_insert(who, g, emb_dtype, metric, levels, order, 0, (int64_t)(N - n_marked), entry, levels[entry], batch_cap, ef, s, st)))
+      return rc;
+  } else if ((rc = hb_hip_rc(hipStreamSynchronize(st), who))) {
+    return rc;
+  }
+  if (stats) {
+    for (int i = 0; i < 3; ++i) stats[i] = (int64_t)h_stats[i];
+    stats[3] = n_marked;
+  }
+  return NANN_OK;
+}
+
+int nann_hnsw_orphan_bits(const int32_t* adj0, int64_t n, int32_t M, uint32_t* out_bits, int64_t* n_orphans, nann_stream_t stream) {
+  const char* who = "nann_hnsw_orphan_bits";
+  if (!adj0 || !out_bits || !n_orphans || n < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument or n < 1");
+  if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 items");
+  if (M < 2 || 2 * M > kHbMaxCand) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": 2 <= M <= 32");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int N = (int)n;
+  const size_t words = ((size_t)N + 31) / 32;
+  HbOwned own;
+  uint32_t* named;
+  unsigned long long* d_count;
+  unsigned long long h_count = 0;
+  int rc;
+  if ((rc = dev_alloc(&named, words, &own)) || (rc = dev_alloc(&d_count, 1, &own)) ||
+      (rc = hb_hip_rc(hipMemsetAsync(named, 0, words * 4, st), "named")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(out_bits, 0, words * 4, st), "out_bits")) ||
+      (rc = hb_hip_rc(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st), "count")))
+    return rc;
+  hipLaunchKernelGGL(k_hb_orphan_mark, dim3((unsigned)((N + kHbWaves - 1) / kHbWaves)), dim3(kHbWaves * 64), 0, st, adj0, N, M, named, out_bits);
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_orphan_mark"))) return rc;
+  hipLaunchKernelGGL(k_hb_orphan_bits, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, named, N, out_bits, d_count);
+  if ((rc = hb_hip_rc(hipGetLastError(), "k_hb_orphan_bits")) ||
+      (rc = hb_hip_rc(hipMemcpyAsync(&h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, st), "count")) ||
+      (rc = hb_hip_rc(hipStreamSynchronize(st), who)))
+    return rc;
+  *n_orphans = (int64_t)h_count;
   return NANN_OK;
 }
 

@@ -318,6 +318,72 @@ def remove_hnsw_gpu(state, remove_rows=None, deny_bits=None, start_level=2, want
     return out
 
 
+def update_hnsw_gpu(state, rows, new_rows=None, start_level=2, want_export=True):
+    """Refresh rows of the graph of `state` IN PLACE ON THE GPU (nann_hnsw_update_device, with the state's "metric"; a state
+    without one is "l2"): every row keeps its number and its levels, so filters, candidate lists and the caller's item_ids stay
+    valid.  rows: an integer array or tensor of internal rows.  new_rows ([len(rows), d], the dtype of the state's rows): their
+    new embeddings, row i of new_rows for rows[i]; a row outside the graph or named twice is a ValueError, so is another dtype.
+    new_rows=None relinks the rows with the embeddings as they are -- the heal of a removal: update_hnsw_gpu(state,
+    orphan_rows_gpu(state)) --; rows outside the graph are then dropped and duplicates allowed, as in remove_hnsw_gpu.  The marked
+    nodes are detached (rows that named them are repaired as a removal repairs them) and inserted again as an append inserts
+    (include/nann_hip.h).  Everything goes into NEW tensors: the input state is left as it is, "item_embs" of the result is a new
+    tensor with the rows replaced.  Returns what append_hnsw_gpu returns, and "stats" (i64[4]: rows repaired by the detach, level-0
+    rows of staying nodes that came out of it empty, rows whose pool exceeded 64, rows updated).  Marking every row is refused:
+    that is a build."""
+    torch, L, _check, _ptr, _stream, _DT = _device_api()
+    metric = state.get("metric", "l2")
+    kind = _metric_kind(metric)
+    x0, m = state["item_embs"], int(state["M"])
+    n, d = x0.shape
+    dev = x0.device
+    levels = np.ascontiguousarray(state["levels"], dtype=np.int32)
+    r = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows, dtype=np.int64))
+    r = r.reshape(-1).to(device=dev, dtype=torch.int64)
+    x = x0.clone()
+    if new_rows is not None:
+        new = _device_rows(new_rows, dev).reshape(-1, d)
+        if new.dtype != x0.dtype:
+            raise ValueError(f"update_hnsw_gpu: rows are {new.dtype}, the graph's are {x0.dtype}")
+        if new.shape[0] != r.numel():
+            raise ValueError(f"update_hnsw_gpu: {r.numel()} rows named, {new.shape[0]} new rows given")
+        if r.numel() and (int(r.min()) < 0 or int(r.max()) >= n):
+            raise ValueError("update_hnsw_gpu: a row outside the graph")
+        if torch.unique(r).numel() != r.numel():
+            raise ValueError("update_hnsw_gpu: a row named twice")
+        x[r] = new
+    bits = _remove_bits(n, r, None, dev)
+    n_up = int((levels.astype(np.int64) - 1).sum())
+    adj0, up_row, adj_up = _graph_arrays(n, n_up, m, dev)
+    if n_up == 0:
+        adj_up.fill_(-1)  # no upper rows: the call does not write the placeholder row
+    stats = (C.c_int64 * 4)()
+    torch.cuda.synchronize()
+    _check(L.nann_hnsw_update_device(_ptr(x), n, d, _DT[x.dtype], m, int(state["ef_construction"]), 1 if state["keep_pruned"] else 0,
+                                     kind, levels.ctypes.data_as(C.c_void_p), _ptr(state["adj0"]), _ptr(state["up_row"]),
+                                     _ptr(state["adj_up"]), _ptr(bits), _ptr(adj0), _ptr(up_row), _ptr(adj_up), stats, _stream()),
+           "hnsw update")
+    out = _result(_state(x, adj0, up_row, adj_up, levels, m, state["ef_construction"], state["keep_pruned"], metric), start_level, want_export)
+    out["stats"] = np.array(list(stats), np.int64)
+    return out
+
+
+def orphan_rows_gpu(state):
+    """The rows of the graph of `state` whose level-0 row is empty or that no level-0 row names (nann_hnsw_orphan_bits): a device
+    tensor i64 of row numbers, ascending -- what update_hnsw_gpu(state, rows) relinks after a removal."""
+    torch, L, _check, _ptr, _stream, _ = _device_api()
+    adj0, m = state["adj0"], int(state["M"])
+    n, dev = adj0.shape[0], adj0.device
+    words = (n + 31) // 32
+    bits = torch.empty(words, dtype=torch.int32, device=dev)
+    count = C.c_int64(0)
+    torch.cuda.synchronize()
+    _check(L.nann_hnsw_orphan_bits(_ptr(adj0), n, m, _ptr(bits), C.byref(count), _stream()), "hnsw orphans")
+    flags = ((bits.view(words, 1) >> torch.arange(32, dtype=torch.int32, device=dev)) & 1).reshape(-1)[:n]
+    out = torch.nonzero(flags).reshape(-1)
+    assert out.numel() == count.value
+    return out
+
+
 def export_hnsw_gpu(state, start_level=2):
     """The export of build_hnsw_index.py:41-66 ON THE DEVICE (nann_hnsw_export_count / _fill): {"enter_points" i32,
     "nb_values" [i32 l0, l1], "nb_row_splits" [i64 l0, l1]} as device tensors -- what retrieval.Index(...) takes as they are,

@@ -618,6 +618,54 @@ int nann_search_all_model_filtered(const nann_index* ix, const nann_model* m, co
                                    int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
                                    int32_t* n_out, nann_stream_t stream);
 
+/* ---- range search: every row scoring at or above a per-query cut ------------------------------------------------------
+ * "Which rows score at least t for this query?" -- every item whose logit clears a serving cut, every near-duplicate within
+ * an L2 radius (L2 scores are -dist^2, so a radius is a cut), the size of a recall set before k is chosen.  The reference has
+ * no such call -- its test_all job keeps a top k -- so nothing here restates a line of it; the semantics below are this
+ * library's own.  The scoring of nann_search_all / nann_search_all_model, chunk by chunk, with a second
+ * selection stage over each chunk's scores (csrc/nann_range.h) in the place of the top k.  There is no k: NANN_ERR_TOPK_K_GT_N
+ * and the k <= 1024 limit do not apply.
+ *   q / comm_seq_f16  f32[n_queries, d] / f16[n_users, seq_len, E], as nann_search_all / nann_search_all_model take them
+ *   thresholds        device f32[n_queries]: the cut of every query
+ *   capacity          entries of out_item_ids / out_scores / out_index
+ *   out_row_splits    device i64[n_queries + 1]
+ *   out_item_ids      device i64[capacity] = item_ids[out_index]; NULL only with capacity == 0
+ *   out_scores        device f32[capacity] or NULL;  out_index device i32[capacity] (internal row numbers) or NULL
+ *   workspace         device, 256-byte aligned (else NANN_ERR_BAD_ARGUMENT), nann_search_all_range[_model]_workspace_bytes(...)
+ *                     bytes; smaller -> NANN_ERR_CAPACITY.  The unfiltered workspace of nann_search_all without its k-wide lists,
+ *                     plus 4 B per (query of a chunk, block of 2048 rows)
+ *   options           NULL = defaults; only `preprojection` is read, as in nann_search_all
+ *   filter            NULL: none.  Else as in nann_search_all_filtered, a malformed one included
+ * Match rule: row r matches query i iff score(i, r) >= thresholds[i] and score(i, r) != -inf, compared as IEEE does: -0 >= +0
+ * holds, a NaN score or a NaN threshold matches nothing.  -inf is how a denied row is marked, so a row scoring -inf is never
+ * returned, whatever the threshold: denied and excluded rows are absent also at a threshold of -inf.
+ * Results: out_row_splits holds the TRUE counts, whatever the capacity -- out_row_splits[0] = 0, out_row_splits[i + 1] -
+ * out_row_splits[i] rows match query i, out_row_splits[n_queries] is the total.  Query i's entries are the positions
+ * [out_row_splits[i], out_row_splits[i + 1]) of the outputs, in ASCENDING ROW ORDER.  Capacity guard: a position at or beyond
+ * capacity is dropped, never written -- what is written is the head [0, min(total, capacity)) of the uncapped result, and
+ * positions [min(total, capacity), capacity) are left untouched.  capacity == 0 with the three entry outputs NULL is a valid
+ * count-only call; the caller sees truncation by out_row_splits[n_queries] > capacity and calls again.
+ * Scores: each returned score is bit-identical to what nann_search_all / nann_search_all_model return for the same (query,
+ * row) under the same handle and options -- L2, inner product, EXACT_F32 and CERTIFIED MLP bit-identical to the oracle,
+ * SPLIT_F16 MLP and the attention model within 1e-5 max(1, |s|) of it.
+ * Batch independence: a query's segment -- rows, order, score bits -- does not depend on the batch it is in.
+ * Errors, each in front of the first launch, so that a failing call launches nothing and writes nothing: a null handle,
+ * n_queries < 0, capacity < 0, handle and index disagree on d / dtype, a bad struct_bytes of options or filter, a workspace off
+ * the 256-byte grid -> NANN_ERR_BAD_ARGUMENT; with work to do (n_queries > 0) a null q / thresholds / out_row_splits, or
+ * capacity > 0 with a null out_item_ids -> NANN_ERR_BAD_ARGUMENT; workspace too small -> NANN_ERR_CAPACITY; n_queries >
+ * 2^31 - 1 -> NANN_ERR_UNSUPPORTED; no pre-projected table: as in nann_search_all.  n_queries == 0 -> NANN_OK, nothing
+ * written.  Asynchronous on `stream`, no host read-back, re-entrant on shared handles. */
+int nann_search_all_range_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int64_t* nbytes);
+int nann_search_all_range(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                          const float* thresholds, int64_t capacity, int64_t* out_row_splits, int64_t* out_item_ids,
+                          float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                          const nann_search_options* options, const nann_filter* filter, nann_stream_t stream);
+int nann_search_all_range_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int64_t* nbytes);
+int nann_search_all_range_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                const float* thresholds, int64_t capacity, int64_t* out_row_splits, int64_t* out_item_ids,
+                                float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                                const nann_search_options* options, const nann_filter* filter, nann_stream_t stream);
+
 /* The traversal, filtered at its final selection: nann_search_opt / nann_search_model_opt -- same arguments, checks and error
  * codes -- plus the filter, k and n_out (device i32[n_queries], or NULL).  level_topn_max[5] is the FETCH WIDTH F: the inner
  * search runs unchanged at F into a staging area of the workspace (16 B x F per query, counted by the _workspace_bytes

@@ -42,6 +42,8 @@ SYMBOLS = [
     "nann_search_all_filtered_workspace_bytes", "nann_search_all_filtered", "nann_search_all_model_filtered_workspace_bytes",
     "nann_search_all_model_filtered", "nann_search_filtered_workspace_bytes", "nann_search_filtered",
     "nann_search_model_filtered_workspace_bytes", "nann_search_model_filtered",
+    "nann_search_all_range_workspace_bytes", "nann_search_all_range",
+    "nann_search_all_range_model_workspace_bytes", "nann_search_all_range_model",
     "nann_search_candidates_workspace_bytes", "nann_search_candidates",
     "nann_search_candidates_model_workspace_bytes", "nann_search_candidates_model",
     "nann_merge_topk", "nann_merge_topk_host",
@@ -154,6 +156,16 @@ def lib():
             fn.restype = C.c_int
             wb = getattr(L, name + "_workspace_bytes")
             wb.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+            wb.restype = C.c_int
+        # the range forms: (ix, scorer | model, n, *nbytes) / (ix, scorer | model, q | comm_seq_f16, n, thresholds, capacity,
+        #  out_row_splits, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options, filter, stream)
+        for name in ("nann_search_all_range", "nann_search_all_range_model"):
+            fn = getattr(L, name)
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + \
+                          [C.c_int64, C.POINTER(SearchOptions), C.POINTER(Filter), C.c_void_p]
+            fn.restype = C.c_int
+            wb = getattr(L, name + "_workspace_bytes")
+            wb.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
             wb.restype = C.c_int
         # (ix, scorer | model, q, n_queries, level_topn_max, level_topn, workspace, workspace_bytes, out_item_ids, out_scores,
         #  out_index, status, counters, [phase_ticks,] options, plan, filter, k, n_out, stream)

@@ -1,5 +1,6 @@
 // nann_flat.hip -- the host side of the flat retrieval calls, the ones that do not walk the graph: the exhaustive search
-// (nann_search_all, nann_search_all_filtered, nann_search_all_model, nann_search_all_model_filtered; kernels in nann_scan.h)
+// (nann_search_all, nann_search_all_filtered, nann_search_all_model, nann_search_all_model_filtered; kernels in nann_scan.h),
+// its range form (nann_search_all_range, nann_search_all_range_model; selection kernels in nann_range.h)
 // and the candidate-list search (nann_search_candidates, nann_search_candidates_model; kernels in nann_cand.h), each with its
 // *_workspace_bytes.
 //
@@ -278,6 +279,90 @@ static int flat_all(const nann_index* ix, const nann_scorer* scorer, const nann_
   return rc;
 }
 
+// ---- range search (nann_range.h): every row at or above a per-query cut, under a scorer or a model ----------------------------
+// The third walk over the same steps.  There is no k: flat_check runs at k = 0, the workspace is the unfiltered ScanLayout at
+// k = 0 -- no candidate lists -- with the block counts of the range selection behind it, and launch_scan takes the range form.
+// Every check stands in front of the first launch, the mean of an l2 / mlp model included: a failing call writes nothing.
+static int flat_range_check(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, const char* who,
+                            FlatBy* by) {
+  const int rc = flat_check(ix, scorer, m, n, 0, false, 0, who, by);
+  if (rc) return rc;
+  if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many " + by->unit + " in one call");
+  return NANN_OK;
+}
+static size_t flat_range_bytes(const nann_index* ix, const FlatBy& by, int64_t n, ScanLayout* L) {
+  const size_t scan = flat_all_bytes(ix, by, n, 0, false, L);
+  return scan + range_counts_bytes(L->chunk, (long long)ix->desc.n_items);
+}
+
+static int flat_range_size(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, int64_t* nbytes,
+                           const char* who) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  const int rc = flat_range_check(ix, scorer, m, n, who, &by);
+  if (rc) return rc;
+  ScanLayout L;
+  *nbytes = n == 0 ? 0 : (int64_t)flat_range_bytes(ix, by, n, &L);
+  return NANN_OK;
+}
+
+static int flat_range(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, const void* x, int64_t n,
+                      const float* thresholds, int64_t capacity, int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores,
+                      int32_t* out_index, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                      const nann_filter* filter, nann_stream_t stream, const char* who) {
+  FlatBy by;
+  int rc = flat_range_check(ix, scorer, m, n, who, &by);
+  if (rc) return rc;
+  if (capacity < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": capacity < 0");
+  if (n == 0) return NANN_OK;
+  if (!x || !thresholds || !out_row_splits) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (capacity > 0 && !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": out_item_ids is null while capacity > 0");
+  rc = check_options(options);
+  if (rc) return rc;
+  ScanFilter sf = {};
+  rc = resolve_filter(filter, ix, &sf.f);
+  if (rc) return rc;
+  ScanLayout L;
+  const size_t need = flat_range_bytes(ix, by, n, &L);
+  rc = flat_workspace(workspace, workspace_bytes, need, who, "");
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  ScanArgs a = {};
+  std::shared_ptr<ProjTable> tab;
+  if (by.cache) {
+    rc = flat_table(by, ix, options, st, who, &tab);
+    if (rc) return rc;
+    DeviceInfo di;
+    rc = device_info(&di);
+    if (rc) return rc;
+    a.proj = tab->table;
+    a.mlp_workgroups = di.cus;
+  }
+  if (by.mean_of) {  // (behind every check: the mean is the first thing on the stream)
+    const float* q = nullptr;
+    rc = flat_stage_mean(by, x, n, &q, &workspace, &workspace_bytes, stream);
+    if (rc) return rc;
+    x = q;
+  }
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  ScanRange r = {};
+  r.thr = thresholds;
+  r.capacity = (long long)capacity;
+  r.row_splits = out_row_splits;
+  r.counts = reinterpret_cast<int32_t*>(ws + L.total);
+  r.n_blocks = range_n_blocks((long long)ix->desc.n_items);
+  a.range = &r;
+  if (sf.f.deny_bits || filter_has_lists(sf.f)) a.filter = &sf;  // (stage and n_out stay null: the range form reads `f` only)
+  flat_rows_of(ix, &a);
+  a.kind = by.kind;
+  a.exact = by.exact;
+  a.mlp = by.mlp;
+  a.attn = by.attn;
+  rc = launch_scan(a, L, static_cast<const float*>(x), (long long)n, 0, ws, out_item_ids, out_scores, out_index, st);
+  if (tab) projection_used(*by.cache, tab, st);
+  return rc;
+}
+
 // ---- candidate-list search (nann_cand.h): the top k of every query's own list of rows, under a scorer or a model -------------
 static int flat_cand_size(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, int64_t n_cand,
                           int32_t k, int64_t* nbytes, const char* who) {
@@ -384,6 +469,27 @@ int nann_search_all_model_filtered(const nann_index* ix, const nann_model* m, co
                                    int32_t* n_out, nann_stream_t stream) {
   return flat_all(ix, nullptr, m, comm_seq_f16, n_users, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes,
                   options, true, filter, n_out, stream, "nann_search_all_model");
+}
+
+int nann_search_all_range_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int64_t* nbytes) {
+  return flat_range_size(ix, scorer, nullptr, n_queries, nbytes, "nann_search_all_range_workspace_bytes");
+}
+int nann_search_all_range(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, const float* thresholds,
+                          int64_t capacity, int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                          void* workspace, int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                          nann_stream_t stream) {
+  return flat_range(ix, scorer, nullptr, q, n_queries, thresholds, capacity, out_row_splits, out_item_ids, out_scores, out_index,
+                    workspace, workspace_bytes, options, filter, stream, "nann_search_all_range");
+}
+int nann_search_all_range_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int64_t* nbytes) {
+  return flat_range_size(ix, nullptr, m, n_users, nbytes, "nann_search_all_range_model_workspace_bytes");
+}
+int nann_search_all_range_model(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                const float* thresholds, int64_t capacity, int64_t* out_row_splits, int64_t* out_item_ids,
+                                float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                                const nann_search_options* options, const nann_filter* filter, nann_stream_t stream) {
+  return flat_range(ix, nullptr, m, comm_seq_f16, n_users, thresholds, capacity, out_row_splits, out_item_ids, out_scores,
+                    out_index, workspace, workspace_bytes, options, filter, stream, "nann_search_all_range_model");
 }
 
 int nann_search_candidates_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int64_t n_cand,

@@ -29,6 +29,7 @@
 #include <cstddef>
 
 #include "nann_filter.h"
+#include "nann_range.h"
 #include "nann_search.h"
 
 namespace nann {
@@ -56,6 +57,8 @@ struct ScanArgs {
                             // f16[n_queries, attn.L, kAttnE], from which each chunk's kt / upad are prepared into the workspace
   const ScanFilter* filter; // null: the unfiltered call.  Else -inf over the denied scores of every chunk before the slab top-k
                             // (nann_filter.h), and k_filter_compact behind the merge writes the outputs
+  const ScanRange* range;   // null: the top k.  Else the range form (nann_range.h): every row at or above the query's cut, in the
+                            // place of the slab top-k and the merge; of a filter only `f` is read, and the call's k not at all
 };
 constexpr int kScanAttn = 100;  // ScanArgs::kind of the attention model (no nann_scorer_kind: it has a handle type of its own)
 constexpr size_t kScanAttnUserBytes = (size_t)(256 * kAttnLP + kAttnLP * kAttnE) * 4;  // kt 64 KB + upad 16 KB (nann_attn_prepare)

@@ -1,5 +1,6 @@
 // nann_scan_inst.hip -- the kernels of the exhaustive search (nann_scan.h): the L2 and inner-product scans for every (d, row dtype), the MLP scan
-// in both precisions, the slab top-k and the merge; workspace layout and the launch sequence of a call.
+// in both precisions, the slab top-k and the merge, and the range selection (nann_range.h); workspace layout and the launch
+// sequence of a call.
 #define NANN_SCAN_IMPL
 #include "nann_scan.h"
 
@@ -75,6 +76,24 @@ static int launch_scan_mlp_as(const ScanArgs& a, const float* u, int n_q, float*
   return NANN_OK;
 }
 
+int launch_range(const ScanRange& r, const float* scores, long long n_items, long long c0, int n_q, const int64_t* item_ids,
+                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, hipStream_t st) {
+  static_assert(kScanMaxChunk <= kRangeNT, "k_range_splits: one thread per query of a chunk");
+  int32_t* totals = r.counts + (size_t)n_q * r.n_blocks;
+  const dim3 grid((unsigned)r.n_blocks, (unsigned)n_q);
+  hipLaunchKernelGGL(k_range_count, grid, dim3(kRangeNT), 0, st, scores, n_items, r.thr, c0, r.counts);
+  NANN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_range_scan, dim3((unsigned)n_q), dim3(kRangeNT), 0, st, r.counts, r.n_blocks, totals);
+  NANN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_range_splits, dim3(1), dim3(kRangeNT), 0, st, totals, n_q, c0, r.row_splits);
+  NANN_HIP_TRY(hipGetLastError());
+  if (r.capacity <= 0) return NANN_OK;  // a count-only call: nothing to fill
+  hipLaunchKernelGGL(k_range_fill, grid, dim3(kRangeNT), 0, st, scores, n_items, r.thr, c0, r.counts, r.row_splits, r.capacity,
+                     item_ids, out_item_ids, out_scores, out_index);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
 int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, hipStream_t st) {
   float* scores = reinterpret_cast<float*>(ws + L.off_scores);
@@ -109,6 +128,11 @@ int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long lon
     if (a.filter) {  // the denied rows of this chunk leave the selection: exclusion lists go by the call's query number c0 + i
       rc = launch_filter_scatter(a.filter->f, scores, c0, n_q, st);
       if (rc) return rc;
+    }
+    if (a.range) {  // every row at or above the cut, not the best k: the ragged outputs are addressed by the call's row_splits
+      rc = launch_range(*a.range, scores, a.n_items, c0, n_q, a.item_ids, out_item_ids, out_scores, out_index, st);
+      if (rc) return rc;
+      continue;
     }
     hipLaunchKernelGGL(k_scan_slab_topk, dim3((unsigned)((long long)n_q * L.n_slabs)), dim3(kNT), 0, st, scores, a.n_items, L.n_slabs, k,
                        cand_scores, cand_rows);

@@ -13,6 +13,8 @@ per request.  Two equivalent executions of that schedule live here:
   * `make_filter()`   a deny bitmap for every query and an exclusion list per query; search(), search_model(),
                       and search_all() take it as `filter=`, search_all_model_filtered() as an argument
                       (the nann_*_filtered calls: the reference has no such feature);
+  * `search_all_range()` / `search_all_range_model()` every row scoring at or above a per-query cut instead of the best k,
+                      ragged outputs (nann_search_all_range[_model]: the reference has no such call);
   * `search_candidates()` / `search_candidates_model()` the exact top k of every query's own list of rows, under a
                       scorer / under any ops.Model, the attention model included (nann_search_candidates[_model]);
   * `search_per_op()` the same schedule spelled op by op with the drop-in ops
@@ -445,6 +447,95 @@ def _search_all_model(index, model, comm_seq, k, options, filter):
         raise TypeError("search_all_model: an ops.Model (an ops.Scorer goes through search_all)")
     seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
     return _flat_all(index, model.handle, seq, k, options, filter, "nann_search_all_model", "search_all_model")
+
+
+# positions of the score buffer per workgroup of the range selection (csrc/nann_range.h: kRangeBlockRows)
+RANGE_BLOCK_ROWS = 2048
+
+
+class RangeResult:
+    """Outputs of search_all_range (device tensors): ragged, query b owns the positions row_splits[b] .. row_splits[b + 1] of
+    item_ids / scores / index (internal rows), in ascending row order (sort=True: score descending, ties to the lower row).
+    row_splits i64[B + 1] holds the TRUE counts whatever the capacity; total = row_splits[B] (a host int); truncated: total >
+    capacity -- the entry tensors then hold the head [0, capacity) of the whole result."""
+    __slots__ = ("row_splits", "item_ids", "scores", "index", "total", "truncated", "_ws")
+
+    def __init__(self, row_splits, item_ids, scores, index, total, truncated, ws=None):
+        self.row_splits, self.item_ids, self.scores, self.index = row_splits, item_ids, scores, index
+        self.total, self.truncated, self._ws = total, truncated, ws
+
+
+def search_all_range(index, scorer, q, thresholds, capacity=None, filter=None, options=None, sort=False):
+    """Range search for a batch (nann_search_all_range; the reference has no such call): every item of `index` scored for
+    every query as search_all scores it -- the same score bits -- and every row with score >= thresholds[b] returned, denied
+    rows and rows scoring -inf never, a NaN threshold nothing -> RangeResult.  `scorer`: ops.Scorer with q f32[B, d], or an
+    ops.Model of kind l2 / mlp with q = comm_seq (its ops.user_seq_mean is the query; the attention model: search_all_range_model).
+    thresholds: a float for every query, or a tensor / array of B floats.  capacity: entries of the outputs; what does not fit
+    is dropped and result.truncated is set.  capacity=None runs a count-only call, reads the total on the host, then runs the
+    filling call at exactly that capacity: THE INDEX IS SCORED TWICE, and the call synchronises.  filter: make_filter.
+    sort=True reorders each segment by (score descending, row ascending) with torch on the device."""
+    dev = index.device
+    handle = scorer.handle
+    if isinstance(scorer, ops.Model):
+        if scorer.kind == "attention":
+            raise NotImplementedError("search_all_range: l2 / mlp scorers only; the attention model goes through search_all_range_model")
+        q = ops.user_seq_mean(q.to(dev))
+        handle = C.c_void_p(lib().nann_model_scorer(scorer.handle))  # (borrowed: the model owns it)
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    return _flat_range(index, handle, q, thresholds, capacity, filter, options, sort, "nann_search_all_range", "search_all_range")
+
+
+def search_all_range_model(index, model, comm_seq, thresholds, capacity=None, filter=None, options=None, sort=False):
+    """search_all_range under a model (nann_search_all_range_model): comm_seq f16[B, seq_len, E], `model` an ops.Model of any
+    kind, the attention model included -- the score bits of search_all_model.  Everything else as search_all_range."""
+    if not isinstance(model, ops.Model):
+        raise TypeError("search_all_range_model: an ops.Model (an ops.Scorer goes through search_all_range)")
+    seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
+    return _flat_range(index, model.handle, seq, thresholds, capacity, filter, options, sort, "nann_search_all_range_model",
+                       "search_all_range_model")
+
+
+def _flat_range(index, handle, x, thresholds, capacity, filter, options, sort, symbol, what):
+    dev, b = index.device, x.shape[0]
+    if isinstance(thresholds, (int, float)):
+        thr = torch.full((b,), float(thresholds), dtype=torch.float32, device=dev)
+    else:
+        thr = torch.as_tensor(thresholds).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert thr.numel() == b, "thresholds: one per query of the batch"
+    L = lib()
+    nbytes = C.c_int64(0)
+    _check(getattr(L, symbol + "_workspace_bytes")(index.handle, handle, b, C.byref(nbytes)), what)
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    splits = torch.zeros(b + 1, dtype=torch.int64, device=dev)
+
+    def call(cap, ids, scores, rows):
+        with torch.cuda.device(dev):
+            _check(getattr(L, symbol)(index.handle, handle, _ptr(x), b, _ptr(thr), cap, _ptr(splits), _ptr(ids), _ptr(scores),
+                                      _ptr(rows), _ptr(ws), ws.numel(), C.byref(options) if options is not None else None,
+                                      _filter_args(filter, b, index), _stream()), what)
+
+    counted = capacity is None
+    if counted:  # count, read the total, fill: the index is scored twice
+        call(0, None, None, None)
+        capacity = int(splits[b].item()) if b else 0
+    capacity = int(capacity)
+    assert capacity >= 0, "capacity >= 0"
+    ids = torch.zeros(capacity, dtype=torch.int64, device=dev)
+    scores = torch.zeros(capacity, dtype=torch.float32, device=dev)
+    rows = torch.zeros(capacity, dtype=torch.int32, device=dev)
+    if capacity > 0:
+        call(capacity, ids, scores, rows)
+    elif not counted:
+        call(0, None, None, None)
+    total = int(splits[b].item()) if b else 0
+    if sort and min(total, capacity) > 1:
+        n = min(total, capacity)
+        seg = torch.searchsorted(splits[1:].contiguous(), torch.arange(n, device=dev), right=True)  # the query of every entry
+        # stable sorts, last key first: row ascending (the entries already are, within a query), score descending, query ascending
+        order = torch.sort(scores[:n], descending=True, stable=True).indices
+        order = order[torch.sort(seg[order], stable=True).indices]
+        ids[:n], scores[:n], rows[:n] = ids[:n][order], scores[:n][order], rows[:n][order]
+    return RangeResult(splits, ids, scores, rows, total, total > capacity, ws)
 
 
 # candidates per work item of the scoring kernels of search_candidates (csrc/nann_cand.h: kCandRows, kCandMlpRows)

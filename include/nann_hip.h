@@ -773,6 +773,85 @@ int nann_search_candidates_model(const nann_index* ix, const nann_model* m, cons
                                  int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
                                  const nann_search_options* options, nann_stream_t stream);
 
+/* ---- multi-vector queries: union top-k over a user's interest vectors --------------------------------------------------
+ * A user tower that emits several interest vectors per user (MIND, ComiRec) wants the k best rows by the best score ANY of the
+ * user's vectors gives a row.  The reference has no such call; the semantics below are this library's own.
+ *
+ * nann_union_topk is the step on its own, for result lists from anywhere -- several traversals, a filtered search plus a
+ * candidate search, ...: a user brings n_lists lists of k_in (score, row) entries.
+ *   scores       f32[n_users, n_lists, k_in];  rows i32, the same shape (internal row numbers)
+ *   n_valid      i32[n_users, n_lists], or NULL = k_in everywhere: only the first clamp(n_valid[u][l], 0, k_in) entries of list
+ *                l count (a filtered call's n_out, a candidate call's n_out)
+ *   n_items      rows outside [0, n_items) are dropped;  item_ids device i64[n_items], or NULL
+ *   out_index    i32[n_users, k], required;  out_scores f32, out_item_ids i64 (= item_ids[out_index], needs item_ids), out_list
+ *                i32 (the list l the entry came from: "which interest retrieved this"), each [n_users, k], n_out i32[n_users]
+ *                -- each may be NULL
+ *   workspace    device, 256-byte aligned, nann_union_topk_workspace_bytes(...) bytes: 8 B per entry
+ * Entry p = l * k_in + j of a user is VALID iff j < clamp(n_valid[u][l], 0, k_in) and its row lies in [0, n_items); anything
+ * else is dropped, malformed input never faults.  Among the valid entries that share a row the REPRESENTATIVE is the one with
+ * the largest score (-0 and +0 tie), ties -> the lowest p; every other entry of the row is deleted.  The answer is TopKV2 over
+ * the representatives taken in ascending p: score descending, ties -> the lower p.  n_out[u] = min(k, distinct valid rows)
+ * entries at the head of row u of every output, zeros behind.  NaN scores stay outside the contract, as for nann_topk; -inf is
+ * a score like any other.  Limits: n_lists * k_in <= NANN_UNION_MAX_IN, k <= 1024.
+ * Nothing is launched for: a negative n_users, n_lists, k_in, n_items or k, k > n_lists * k_in, out_item_ids without item_ids,
+ * null scores / rows / out_index when there is work, a workspace off the 256-byte grid -> NANN_ERR_BAD_ARGUMENT; k > 1024,
+ * n_lists * k_in > NANN_UNION_MAX_IN, n_items or n_users > 2^31 - 1 -> NANN_ERR_UNSUPPORTED; a workspace smaller than
+ * nann_union_topk_workspace_bytes() -> NANN_ERR_CAPACITY; n_users == 0 or k == 0 -> NANN_OK, nothing written.  (Where
+ * several apply: the sizes and k first, their NANN_ERR_BAD_ARGUMENT before their NANN_ERR_UNSUPPORTED, then the early
+ * NANN_OK, then the null pointers, out_item_ids without item_ids, the workspace's size, its alignment.)  nann_union_topk_workspace_bytes leaves
+ * *nbytes untouched when it fails.  A user's answer does not depend on the batch it is in.  Asynchronous on `stream`, no host
+ * read-back. */
+#define NANN_UNION_MAX_IN 8192
+int nann_union_topk_workspace_bytes(int64_t n_users, int32_t n_lists, int32_t k_in, int64_t* nbytes);
+int nann_union_topk(const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_users, int32_t n_lists,
+                    int32_t k_in, int64_t n_items, const int64_t* item_ids, int32_t k, int32_t* out_index, float* out_scores,
+                    int64_t* out_item_ids, int32_t* out_list, int32_t* n_out, void* workspace, int64_t workspace_bytes,
+                    nann_stream_t stream);
+
+/* The traversal form: q is f32[n_users, n_vec, d], n_vec interest vectors per user.  The inner search is nann_search_opt,
+ * unchanged, over the n_users * n_vec vectors as queries at the fetch width F = level_topn_max[5], into a staging area of the
+ * workspace (16 B x F per vector, counted by nann_search_multi_workspace_bytes); level_topn, optional, is device
+ * i32[n_users * n_vec, 6], per VECTOR.  Then the union above with list l of user u = what vector (u, l) returned: its own
+ * level_topn[..][5] entries, or none when status[u][l] != 0.
+ *   status       i32[n_users, n_vec], required: what the inner search reports per vector.  A failed vector contributes nothing;
+ *                the user still gets the union of the vectors that succeeded
+ *   out_item_ids i64[n_users, k], required;  out_scores f32, out_index i32, out_vec i32 (the vector an entry came from), each
+ *                [n_users, k], n_out i32[n_users] -- each may be NULL
+ *   counters     i32[n_users * n_vec, 3, NANN_NUM_ROUNDS] or NULL, options, plan: the inner search's
+ *   workspace    device, 256-byte aligned (else NANN_ERR_BAD_ARGUMENT); smaller than ..._workspace_bytes -> NANN_ERR_CAPACITY
+ * Every scorer nann_search_opt accepts is accepted: L2, the inner product, the MLP in every precision; a returned score has the
+ * bits nann_search_opt returns for that (vector, row).  n_vec < 1, k outside [0, n_vec * F] -> NANN_ERR_BAD_ARGUMENT; n_vec * F >
+ * NANN_UNION_MAX_IN or k > 1024 -> NANN_ERR_UNSUPPORTED; these, the null pointers and the workspace are looked at before
+ * anything is launched.  n_users == 0 or k == 0 -> NANN_OK behind those shape checks, nothing launched and nothing written,
+ * status included, as in nann_union_topk.  A user with fewer than n_vec interests repeats one of them: duplicates collapse, the answer is that of
+ * the distinct vectors.  Filters compose from the parts: nann_search_filtered over the n_users * n_vec vectors, then
+ * nann_union_topk with n_valid = its n_out.  There is no _model form: a comm_seq is ONE user sequence, which a model turns into
+ * one query (l2 / mlp: its mean) or scores as a whole (attention); several interest vectors are the caller's user tower's. */
+int nann_search_multi_workspace_bytes(const nann_index* ix, const int32_t level_topn[6] /*[host]*/, int64_t n_users,
+                                      int32_t n_vec, int64_t* nbytes);
+int nann_search_multi(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,
+                      const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                      int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_vec, int32_t* n_out,
+                      int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan, int32_t k,
+                      nann_stream_t stream);
+
+/* The exhaustive form, the ground truth of multi-vector recall: nann_search_all over the n_users * n_vec vectors at k, then the
+ * union of each user's n_vec lists.  The union of per-vector top-k lists is EXACT: let b(r) = max_m s(q_m, r) be a row's best
+ * score and r a row whose b(r) is among the k largest; with m the vector that attains b(r), any row r' ahead of r in vector
+ * m's order has s(q_m, r') >= b(r), hence b(r') >= b(r), and fewer than k rows can be ahead of r under the total order -- so r
+ * stands in vector m's top k with its best score, and the returned score values are the k largest of max_m s(q_m, r).  (Among
+ * rows that tie at the k-th value, which ones are returned follows the union's position rule.)
+ * Checks: nann_search_all's -- k > n_items -> NANN_ERR_TOPK_K_GT_N, k > 1024 -> NANN_ERR_UNSUPPORTED, ... -- and n_vec < 1 ->
+ * NANN_ERR_BAD_ARGUMENT, n_vec * k > NANN_UNION_MAX_IN -> NANN_ERR_UNSUPPORTED; n_users == 0 or k == 0 -> NANN_OK, nothing
+ * written.  out_item_ids i64[n_users, k] is required; out_scores, out_index, out_vec, n_out (always min(k, n_items) = k) may be
+ * NULL.  No _model form, as above. */
+int nann_search_all_multi_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_users, int32_t n_vec,
+                                          int32_t k, int64_t* nbytes);
+int nann_search_all_multi(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,
+                          int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_vec,
+                          int32_t* n_out, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                          nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

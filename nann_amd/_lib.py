@@ -22,6 +22,7 @@ SCORER_L2, SCORER_MLP, SCORER_IP = 0, 1, 2
 MLP_DEFAULT, MLP_SPLIT_F16, MLP_EXACT_F32, MLP_CERTIFIED = 0, 1, 2, 3
 NUM_ROUNDS = 5
 NUM_PHASES = 19
+UNION_MAX_IN = 8192  # NANN_UNION_MAX_IN: most entries (n_lists * k_in) a user brings to nann_union_topk
 PHASE_NAMES = ("zero", "walk", "expand", "score", "topk", "other", "tk_load", "tk_search",
                "tk_collect", "tk_sort", "ex_pass1", "ex_loop", "ex_walkbusy",
                "ex_lookup", "ex_load", "ex_insert", "ex_bar_a", "ex_check", "ex_rank")
@@ -46,6 +47,8 @@ SYMBOLS = [
     "nann_search_all_range_model_workspace_bytes", "nann_search_all_range_model",
     "nann_search_candidates_workspace_bytes", "nann_search_candidates",
     "nann_search_candidates_model_workspace_bytes", "nann_search_candidates_model",
+    "nann_union_topk_workspace_bytes", "nann_union_topk", "nann_search_multi_workspace_bytes", "nann_search_multi",
+    "nann_search_all_multi_workspace_bytes", "nann_search_all_multi",
     "nann_merge_topk", "nann_merge_topk_host",
     "nann_attn_scorer_create", "nann_attn_scorer_destroy", "nann_attn_prepare", "nann_attn_score",
     "nann_blaze_options_parse", "nann_model_load", "nann_model_destroy", "nann_model_kind", "nann_model_scorer", "nann_model_workspace_bytes", "nann_model_forward",
@@ -194,6 +197,29 @@ def lib():
         L.nann_search_candidates_model_workspace_bytes.restype = C.c_int
         L.nann_search_candidates_model.argtypes = list(L.nann_search_candidates.argtypes)
         L.nann_search_candidates_model.restype = C.c_int
+        # (n_users, n_lists, k_in, *nbytes) / (scores, rows, n_valid, n_users, n_lists, k_in, n_items, item_ids, k, out_index,
+        #  out_scores, out_item_ids, out_list, n_out, workspace, workspace_bytes, stream)
+        L.nann_union_topk_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+        L.nann_union_topk_workspace_bytes.restype = C.c_int
+        L.nann_union_topk.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32] + \
+                                     [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]
+        L.nann_union_topk.restype = C.c_int
+        # (ix, level_topn, n_users, n_vec, *nbytes) / (ix, scorer, q, n_users, n_vec, level_topn_max, level_topn, workspace,
+        #  workspace_bytes, out_item_ids, out_scores, out_index, out_vec, n_out, status, counters, options, plan, k, stream)
+        L.nann_search_multi_workspace_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+        L.nann_search_multi_workspace_bytes.restype = C.c_int
+        L.nann_search_multi.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
+                                                           C.c_int64] + [C.c_void_p] * 7 + \
+                                       [C.POINTER(SearchOptions), C.POINTER(SearchPlan), C.c_int32, C.c_void_p]
+        L.nann_search_multi.restype = C.c_int
+        # (ix, scorer, n_users, n_vec, k, *nbytes) / (ix, scorer, q, n_users, n_vec, k, out_item_ids, out_scores, out_index,
+        #  out_vec, n_out, workspace, workspace_bytes, options, stream)
+        L.nann_search_all_multi_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                                            C.POINTER(C.c_int64)]
+        L.nann_search_all_multi_workspace_bytes.restype = C.c_int
+        L.nann_search_all_multi.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + \
+                                           [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
+        L.nann_search_all_multi.restype = C.c_int
         # (item_embs, n_old, n_new, d, emb_dtype, M, ef_construction, keep_pruned, levels, adj0, up_row, adj_up, stream)
         L.nann_hnsw_append_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 5
         L.nann_hnsw_append_device.restype = C.c_int

@@ -1,7 +1,10 @@
 // nann_cand_inst.hip -- the kernels of the candidate-list search (nann_cand.h): the plan, the L2 and inner-product scorers for every (d, row
-// dtype), the MLP scorer in both precisions and the per-query top-k; workspace layout and the launch sequence of a call.
+// dtype), the MLP scorer in both precisions and the per-query top-k; workspace layout and the launch sequence of a call.  Also
+// the union top-k (nann_union.h), a per-user selection over wg_topk like k_cand_topk, and its launch.
 #define NANN_CAND_IMPL
+#define NANN_UNION_IMPL
 #include "nann_cand.h"
+#include "nann_union.h"
 
 #include <algorithm>
 
@@ -107,6 +110,21 @@ int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long lon
   }
   return launch_cand_topk(s.plan, a.rows, s.scores, n_queries, k, a.item_ids, out_item_ids, out_scores, out_index, out_pos, n_out,
                           status, st);
+}
+
+// ---- the union top-k (nann_union.h) -----------------------------------------------------------------------------------
+size_t union_ws_bytes(long long n_users, long long n_in) { return up256((size_t)n_users * (size_t)n_in * 8); }
+
+int launch_union_topk(const UnionArgs& a, long long n_users, hipStream_t st) {
+  const int n_in = a.n_lists * a.k_in;
+  if (n_users <= 0) return NANN_OK;
+  const size_t lds = union_lds_bytes(n_in);
+  if (lds > 64 * 1024)  // (only the sizes beyond the default limit need the opt-in: n_in > 4096)
+    NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_union_topk), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)union_lds_bytes(NANN_UNION_MAX_IN)));
+  hipLaunchKernelGGL(k_union_topk, dim3((unsigned)n_users), dim3(kNT), lds, st, a, union_slots_log2(n_in));
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
 }
 
 }  // namespace nann

@@ -2,7 +2,8 @@
 // (nann_search_all, nann_search_all_filtered, nann_search_all_model, nann_search_all_model_filtered; kernels in nann_scan.h),
 // its range form (nann_search_all_range, nann_search_all_range_model; selection kernels in nann_range.h)
 // and the candidate-list search (nann_search_candidates, nann_search_candidates_model; kernels in nann_cand.h), each with its
-// *_workspace_bytes.
+// *_workspace_bytes; the union top-k on its own (nann_union_topk; kernel in nann_union.h) and behind the exhaustive search
+// over a user's interest vectors (nann_search_all_multi).
 //
 // Compiled into nann_core.o behind nann_hip.hip, as ONE translation unit with it (build.py writes the wrapper), on the terms
 // nann_comm.hip lives there: this file uses nann_hip.hip's file-scope types and helpers directly -- nann_index, nann_scorer,
@@ -26,6 +27,7 @@
 // where they branch for it (tests/test_flat_contract_gpu.py pins them).
 #include "nann_scan.h"
 #include "nann_cand.h"
+#include "nann_union.h"
 
 #include <memory>
 #include <string>
@@ -426,8 +428,142 @@ static int flat_cand(const nann_index* ix, const nann_scorer* scorer, const nann
   return rc;
 }
 
+// ---- union top-k (nann_union.h): a user's n_lists result lists -> the k best distinct rows -----------------------------------
+// the shape of a union: n_in = n_lists * k_in entries per user.  `who`: the entry point in a message.
+static int union_check(int64_t n_users, int64_t n_lists, int64_t k_in, int64_t k, const char* who) {
+  if (n_users < 0 || n_lists < 0 || k_in < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": negative size");
+  if (k < 0) return flat_bad_k((int32_t)k);
+  if (k > n_lists * k_in) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k exceeds the n_lists * k_in entries a user brings");
+  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
+  if (n_lists * k_in > NANN_UNION_MAX_IN)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": at most NANN_UNION_MAX_IN = 8192 entries per user");
+  if (n_users > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many users in one call");
+  return NANN_OK;
+}
+
+// ---- exhaustive multi-vector search: flat_all over the n_users * n_vec vectors at k into a staging area, then the union ------
+// workspace: [flat_all's, rounded up to 256 | item ids i64[n, k], scores f32[n, k], rows i32[n, k] of the n = n_users * n_vec
+// vectors, rounded up | the union's]
+struct FlatMultiBytes {
+  size_t inner, stage_off, union_off, total;
+};
+static size_t flat_multi_stage_bytes(int64_t n, int32_t k) { return ((size_t)n * (size_t)k * 16 + 255) & ~(size_t)255; }
+static int flat_all_multi_check(const nann_index* ix, const nann_scorer* scorer, int64_t n_users, int32_t n_vec, int32_t k,
+                                const char* who, FlatBy* by) {
+  if (n_vec < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_vec < 1");
+  if (n_users > 0x7fffffffll / n_vec) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many vectors in one call");
+  int rc = flat_check(ix, scorer, nullptr, n_users * n_vec, k, false, 0, who, by);
+  if (rc) return rc;
+  return union_check(n_users, n_vec, k, k, who);
+}
+static FlatMultiBytes flat_all_multi_bytes(const nann_index* ix, const FlatBy& by, int64_t n_users, int32_t n_vec, int32_t k) {
+  ScanLayout L;
+  FlatMultiBytes b;
+  b.inner = flat_all_bytes(ix, by, n_users * n_vec, k, false, &L);
+  b.stage_off = (b.inner + 255) & ~(size_t)255;
+  b.union_off = b.stage_off + flat_multi_stage_bytes(n_users * n_vec, k);
+  b.total = b.union_off + union_ws_bytes((long long)n_users, (long long)n_vec * k);
+  return b;
+}
+
+static int flat_all_multi(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec, int32_t k,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_vec, int32_t* n_out,
+                          void* workspace, int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream,
+                          const char* who) {
+  FlatBy by;
+  int rc = flat_all_multi_check(ix, scorer, n_users, n_vec, k, who, &by);
+  if (rc) return rc;
+  if (n_users == 0 || k == 0) return NANN_OK;
+  if (!q || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  const FlatMultiBytes b = flat_all_multi_bytes(ix, by, n_users, n_vec, k);
+  rc = flat_workspace(workspace, workspace_bytes, b.total, who, "");
+  if (rc) return rc;
+  const int64_t n = n_users * n_vec;
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  int64_t* s_ids = reinterpret_cast<int64_t*>(ws + b.stage_off);
+  float* s_scores = reinterpret_cast<float*>(ws + b.stage_off + (size_t)n * k * 8);
+  int32_t* s_rows = reinterpret_cast<int32_t*>(ws + b.stage_off + (size_t)n * k * 12);
+  rc = flat_all(ix, scorer, nullptr, q, n, k, s_ids, s_scores, s_rows, workspace, (int64_t)b.inner, options, false, nullptr, nullptr,
+                stream, "nann_search_all");
+  if (rc) return rc;
+  UnionArgs a = {};
+  a.scores = s_scores;
+  a.rows = s_rows;
+  a.n_lists = n_vec;
+  a.k_in = k;
+  a.k = k;
+  flat_ids_of(ix, &a);
+  a.best = reinterpret_cast<unsigned long long*>(ws + b.union_off);
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_item_ids = out_item_ids;
+  a.out_list = out_vec;
+  a.n_out = n_out;
+  return launch_union_topk(a, (long long)n_users, as_stream(stream));
+}
+
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
 extern "C" {
+
+int nann_union_topk_workspace_bytes(int64_t n_users, int32_t n_lists, int32_t k_in, int64_t* nbytes) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_union_topk_workspace_bytes: null argument");
+  const int rc = union_check(n_users, n_lists, k_in, 0, "nann_union_topk_workspace_bytes");
+  if (rc) return rc;
+  *nbytes = (int64_t)union_ws_bytes((long long)n_users, (long long)n_lists * k_in);
+  return NANN_OK;
+}
+int nann_union_topk(const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_users, int32_t n_lists,
+                    int32_t k_in, int64_t n_items, const int64_t* item_ids, int32_t k, int32_t* out_index, float* out_scores,
+                    int64_t* out_item_ids, int32_t* out_list, int32_t* n_out, void* workspace, int64_t workspace_bytes,
+                    nann_stream_t stream) {
+  const char* who = "nann_union_topk";
+  if (n_items < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": negative size");
+  const int rc = union_check(n_users, n_lists, k_in, k, who);
+  if (rc) return rc;
+  if (n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  if (n_users == 0 || k == 0) return NANN_OK;
+  if (!scores || !rows || !out_index) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (out_item_ids && !item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": out_item_ids without item_ids");
+  const int rw = flat_workspace(workspace, workspace_bytes, union_ws_bytes((long long)n_users, (long long)n_lists * k_in), who, "");
+  if (rw) return rw;
+  UnionArgs a = {};
+  a.scores = scores;
+  a.rows = rows;
+  a.n_valid = n_valid;
+  a.nv_stride = 1;
+  a.n_lists = n_lists;
+  a.k_in = k_in;
+  a.k = k;
+  a.n_items = (long long)n_items;
+  a.item_ids = item_ids;
+  a.best = static_cast<unsigned long long*>(workspace);
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_item_ids = out_item_ids;
+  a.out_list = out_list;
+  a.n_out = n_out;
+  return launch_union_topk(a, (long long)n_users, as_stream(stream));
+}
+
+int nann_search_all_multi_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_users, int32_t n_vec,
+                                          int32_t k, int64_t* nbytes) {
+  const char* who = "nann_search_all_multi_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  const int rc = flat_all_multi_check(ix, scorer, n_users, n_vec, k, who, &by);
+  if (rc) return rc;
+  *nbytes = n_users == 0 || k == 0 ? 0 : (int64_t)flat_all_multi_bytes(ix, by, n_users, n_vec, k).total;
+  return NANN_OK;
+}
+int nann_search_all_multi(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,
+                          int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_vec,
+                          int32_t* n_out, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                          nann_stream_t stream) {
+  return flat_all_multi(ix, scorer, q, n_users, n_vec, k, out_item_ids, out_scores, out_index, out_vec, n_out, workspace,
+                        workspace_bytes, options, stream, "nann_search_all_multi");
+}
 
 int nann_search_all_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k, int64_t* nbytes) {
   return flat_all_size(ix, scorer, nullptr, n_queries, k, false, nbytes, "nann_search_all_workspace_bytes");

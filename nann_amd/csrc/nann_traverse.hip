@@ -1,6 +1,6 @@
 // nann_traverse.hip -- the host side of the calls that walk the graph: the serving traversal (nann_search_opt,
-// nann_search_model_opt and their five deprecated spellings, nann_search_filtered, nann_search_model_filtered; kernels in
-// nann_search.h), the evaluation traversal (nann_search_eval, nann_search_eval_ex, nann_search_eval_model; nann_eval.h), each
+// nann_search_model_opt and their five deprecated spellings, nann_search_filtered, nann_search_model_filtered, nann_search_multi;
+// kernels in nann_search.h), the evaluation traversal (nann_search_eval, nann_search_eval_ex, nann_search_eval_model; nann_eval.h), each
 // with its *_workspace_bytes, and what nann_index_create measures for them: the probe and the pivots of the batch order.
 //
 // Compiled into nann_core.o behind nann_hip.hip and nann_flat.hip, as ONE translation unit with them (build.py writes the
@@ -25,6 +25,7 @@
 #include "nann_eval.h"
 #include "nann_order_kernels.h"
 #include "nann_filter.h"
+#include "nann_union.h"
 
 using namespace nann;
 
@@ -747,8 +748,97 @@ static int traverse_filtered(const nann_index* ix, const nann_scorer* scorer, co
                                out_scores, out_index, n_out, as_stream(stream));
 }
 
+// ---- the traversal over a user's interest vectors: the inner search over the n_users * n_vec vectors at the fetch width
+// F = level_topn_max[5] into the staging area a filtered call has behind its workspace, then the union top-k (nann_union.h)
+// of each user's n_vec lists, its workspace behind the staging area ---------------------------------------------------------
+static int traverse_multi_check(int64_t n_users, int32_t n_vec, const int32_t level_topn_max[6], int64_t k, const char* who) {
+  if (n_vec < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_vec < 1");
+  const int64_t f = level_topn_max[5];
+  if (k < 0 || k > (int64_t)n_vec * f) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k must lie in [0, n_vec * level_topn_max[5]]");
+  if (n_users > 0 && n_users > 0x7fffffffll / n_vec) return fail(NANN_ERR_UNSUPPORTED, "too many queries in one call");
+  return union_check(std::max<int64_t>(n_users, 0), n_vec, f, k, who);
+}
+// b->total: the filtered layout over the vectors (its end is where the union's workspace starts); *total: with the union's
+static int traverse_multi_bytes(const nann_index* ix, const int32_t level_topn_max[6], int64_t n_users, int32_t n_vec,
+                                TraverseBytes* b, int64_t* total) {
+  const int rc = traverse_bytes(ix, nullptr, level_topn_max, n_users * n_vec, true, b);
+  if (rc) return rc;
+  *total = up256_i64(b->total) + (int64_t)union_ws_bytes((long long)n_users, (long long)n_vec * level_topn_max[5]);
+  return NANN_OK;
+}
+
+static int traverse_multi(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,
+                          const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_vec, int32_t* n_out,
+                          int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan, int32_t k,
+                          nann_stream_t stream, const char* who) {
+  if (traverse_null(ix, scorer, nullptr, false, q, level_topn_max, out_item_ids, status, workspace))
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  int rc = traverse_multi_check(n_users, n_vec, level_topn_max, k, who);  // (also of an empty batch)
+  if (rc) return rc;
+  if (n_users <= 0 || k == 0) return NANN_OK;  // (nothing to return: no inner search either, as nann_union_topk)
+  if (!q) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  const int64_t n = n_users * n_vec;
+  const int f = level_topn_max[5];
+  TraverseBytes b;
+  int64_t total = 0;
+  rc = traverse_multi_bytes(ix, level_topn_max, n_users, n_vec, &b, &total);
+  if (rc) return rc;
+  // (the call's own workspace ahead of everything the inner search looks at, its options included)
+  if (!workspace || workspace_bytes < total) return short_workspace(who);
+  if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": workspace must be 256-byte aligned");
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  unsigned char* stage = ws + b.stage_off;
+  int64_t* s_ids = reinterpret_cast<int64_t*>(stage);
+  float* s_scores = reinterpret_cast<float*>(stage + (size_t)n * f * 8);
+  int32_t* s_rows = reinterpret_cast<int32_t*>(stage + (size_t)n * f * 12);
+  rc = traverse(ix, scorer, nullptr, false, q, n, level_topn_max, level_topn, workspace, b.inner, s_ids, s_scores, s_rows, status,
+                counters, nullptr, options, plan, stream, "nann_search_opt");
+  if (rc) return rc;
+  UnionArgs a = {};
+  a.scores = s_scores;
+  a.rows = s_rows;
+  a.n_valid = level_topn ? level_topn + 5 : nullptr;  // a vector's own level_topn[5]
+  a.nv_stride = 6;
+  a.status = status;
+  a.n_lists = n_vec;
+  a.k_in = f;
+  a.k = k;
+  a.n_items = (long long)ix->desc.n_items;
+  a.item_ids = ix->desc.item_ids;
+  a.best = reinterpret_cast<unsigned long long*>(ws + up256_i64(b.total));
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_item_ids = out_item_ids;
+  a.out_list = out_vec;
+  a.n_out = n_out;
+  return launch_union_topk(a, (long long)n_users, as_stream(stream));
+}
+
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
 extern "C" {
+
+int nann_search_multi_workspace_bytes(const nann_index* ix, const int32_t level_topn[6], int64_t n_users, int32_t n_vec,
+                                      int64_t* nbytes) {
+  const char* who = "nann_search_multi_workspace_bytes";
+  if (!ix || !level_topn || !nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  int rc = traverse_multi_check(n_users, n_vec, level_topn, 0, who);
+  if (rc) return rc;
+  TraverseBytes b;
+  int64_t total = 0;
+  rc = traverse_multi_bytes(ix, level_topn, std::max<int64_t>(n_users, 0), n_vec, &b, &total);
+  if (rc) return rc;
+  *nbytes = total;
+  return NANN_OK;
+}
+int nann_search_multi(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,
+                      const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                      int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_vec, int32_t* n_out,
+                      int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan, int32_t k,
+                      nann_stream_t stream) {
+  return traverse_multi(ix, scorer, q, n_users, n_vec, level_topn_max, level_topn, workspace, workspace_bytes, out_item_ids,
+                        out_scores, out_index, out_vec, n_out, status, counters, options, plan, k, stream, "nann_search_multi");
+}
 
 int nann_search_workspace_bytes(const nann_index* ix, const int32_t level_topn[6], int64_t n_queries, int64_t* nbytes) {
   return traverse_size(ix, nullptr, false, level_topn, n_queries, false, nbytes);

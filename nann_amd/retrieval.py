@@ -17,6 +17,9 @@ per request.  Two equivalent executions of that schedule live here:
                       ragged outputs (nann_search_all_range[_model]: the reference has no such call);
   * `search_candidates()` / `search_candidates_model()` the exact top k of every query's own list of rows, under a
                       scorer / under any ops.Model, the attention model included (nann_search_candidates[_model]);
+  * `search_multi()` / `search_all_multi()` / `union_topk()` several interest vectors per user: the k best distinct rows by
+                      the best score any vector gives a row, through the traversal / exhaustively, and the union step on its
+                      own for result lists from anywhere (nann_search_multi, nann_search_all_multi, nann_union_topk);
   * `search_per_op()` the same schedule spelled op by op with the drop-in ops
                       of nann_amd.ops, line for line against build_model(), so
                       that each op is exercised in the composition the
@@ -652,6 +655,105 @@ def search_candidates_model(index, model, comm_seq, candidates=None, candidate_i
     seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
     return _flat_candidates(index, model.handle, seq, candidates, candidate_item_ids, k, options, "nann_search_candidates_model",
                             "search_candidates_model", "user", (seq,))
+
+
+UNION_MAX_IN = _lib.UNION_MAX_IN  # most entries (n_lists * k_in, n_vec * F, n_vec * k) a user brings to a union
+
+
+class MultiResult:
+    """Outputs of union_topk / search_multi / search_all_multi, [n_users, k] device tensors: the k best DISTINCT rows of a user
+    by the best score any of its lists (interest vectors) gives a row, n_out[u] valid entries at the head of row u and zeros
+    behind.  vec: the list (vector) an entry came from.  status: i32[n_users, n_vec], what the inner search of search_multi
+    reported per vector (None elsewhere); plan: its planner's choice (None elsewhere).  item_ids is None for a union_topk
+    without an index."""
+    __slots__ = ("item_ids", "scores", "index", "vec", "n_out", "status", "plan", "_ws")
+
+    def __init__(self, item_ids, scores, index, vec, n_out, status=None, plan=None, ws=None):
+        self.item_ids, self.scores, self.index, self.vec, self.n_out = item_ids, scores, index, vec, n_out
+        self.status, self.plan, self._ws = status, plan, ws
+
+
+def _multi_outputs(n_users, k, dev, item_ids=True):
+    kk = max(int(k), 0)
+    return (torch.zeros((n_users, kk), dtype=torch.int64, device=dev) if item_ids else None,
+            torch.zeros((n_users, kk), dtype=torch.float32, device=dev), torch.zeros((n_users, kk), dtype=torch.int32, device=dev),
+            torch.zeros((n_users, kk), dtype=torch.int32, device=dev), torch.zeros(n_users, dtype=torch.int32, device=dev))
+
+
+def union_topk(scores, rows, k, n_valid=None, index=None):
+    """Union top-k (nann_union_topk): scores f32 / rows i32 [n_users, n_lists, k_in] CUDA tensors, a user's n_lists result
+    lists from anywhere; only the first n_valid[u][l] (i32[n_users, n_lists]; None: k_in) entries of a list count, and rows
+    outside [0, index.n_items) -- without an index: negative rows -- are dropped.  Per row the entry with the largest score
+    represents it (ties -> the lower position l * k_in + j), and the k best representatives are returned, descending, ties ->
+    the lower position -> MultiResult (item_ids only with an index).  n_lists * k_in <= UNION_MAX_IN, k <= 1024.
+    Asynchronous on torch's current stream."""
+    dev = scores.device
+    scores = scores.to(dtype=torch.float32).contiguous()
+    rows = rows.to(device=dev, dtype=torch.int32).contiguous()
+    assert scores.dim() == 3 and rows.shape == scores.shape, "scores, rows: [n_users, n_lists, k_in]"
+    n_users, n_lists, k_in = scores.shape
+    if n_valid is not None:
+        n_valid = n_valid.to(device=dev, dtype=torch.int32).contiguous()
+        assert n_valid.shape == (n_users, n_lists), "n_valid: [n_users, n_lists]"
+    k = int(k)
+    out_ids, out_scores, out_index, out_list, n_out = _multi_outputs(n_users, k, dev, index is not None)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_union_topk_workspace_bytes(n_users, n_lists, k_in, C.byref(nbytes)), "union_topk")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    n_items = int(index.n_items) if index is not None else (1 << 31) - 1
+    with torch.cuda.device(dev):
+        _check(lib().nann_union_topk(_ptr(scores), _ptr(rows), _ptr(n_valid), n_users, n_lists, k_in, n_items,
+                                     _ptr(index.item_ids) if index is not None else None, k, _ptr(out_index), _ptr(out_scores),
+                                     _ptr(out_ids), _ptr(out_list), _ptr(n_out), _ptr(ws), ws.numel(), _stream()), "union_topk")
+    return MultiResult(out_ids, out_scores, out_index, out_list, n_out, ws=ws)
+
+
+def search_multi(index, scorer, q, level_topn, k=None, options=None):
+    """Multi-vector traversal (nann_search_multi): q f32[n_users, n_vec, d], n_vec interest vectors per user.  search() runs
+    unchanged over the n_users * n_vec vectors at the fetch width F = level_topn[5] (level_topn: i32[6], or [n_users * n_vec,
+    6] per vector), then each user's n_vec lists are united: the k (default F) best distinct rows by the best score any vector
+    gives a row -> MultiResult; result.vec names the vector, result.status [n_users, n_vec] what the inner search reported -- a
+    failed vector contributes nothing.  A user with fewer interests repeats one of them.  `scorer`: an ops.Scorer of any kind
+    search() takes.  n_vec * F <= UNION_MAX_IN, k <= 1024.  Asynchronous on torch's current stream."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    assert q.dim() == 3, "q: [n_users, n_vec, d]"
+    n_users, n_vec = int(q.shape[0]), int(q.shape[1])
+    t, tq, k_fetch = _level_topn_args(level_topn, n_users * n_vec, dev)
+    k = int(k) if k is not None else k_fetch
+    out_ids, out_scores, out_index, out_vec, n_out = _multi_outputs(n_users, k, dev)
+    status = torch.zeros((n_users, n_vec), dtype=torch.int32, device=dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_multi_workspace_bytes(index.handle, t, n_users, n_vec, C.byref(nbytes)), "search_multi")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    plan = _lib.SearchPlan()
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_multi(index.handle, scorer.handle, _ptr(q), n_users, n_vec, t, _ptr(tq), _ptr(ws), ws.numel(),
+                                       _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(out_vec), _ptr(n_out), _ptr(status),
+                                       None, C.byref(options) if options is not None else None, C.byref(plan), k, _stream()),
+               "search_multi")
+    return MultiResult(out_ids, out_scores, out_index, out_vec, n_out, status, _plan_dict(plan), ws)
+
+
+def search_all_multi(index, scorer, q, k, options=None):
+    """Exhaustive multi-vector search (nann_search_all_multi), the ground truth of search_multi: search_all over the n_users *
+    n_vec vectors of q f32[n_users, n_vec, d] at k, then the union per user -> MultiResult.  Its scores are exactly the k
+    largest of max over the user's vectors of a row's score.  `scorer`: an ops.Scorer.  n_vec * k <= UNION_MAX_IN.
+    Asynchronous on torch's current stream."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    assert q.dim() == 3, "q: [n_users, n_vec, d]"
+    n_users, n_vec, k = int(q.shape[0]), int(q.shape[1]), int(k)
+    out_ids, out_scores, out_index, out_vec, n_out = _multi_outputs(n_users, k, dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_all_multi_workspace_bytes(index.handle, scorer.handle, n_users, n_vec, k, C.byref(nbytes)),
+           "search_all_multi")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_all_multi(index.handle, scorer.handle, _ptr(q), n_users, n_vec, k, _ptr(out_ids), _ptr(out_scores),
+                                           _ptr(out_index), _ptr(out_vec), _ptr(n_out), _ptr(ws), ws.numel(),
+                                           C.byref(options) if options is not None else None, _stream()), "search_all_multi")
+    return MultiResult(out_ids, out_scores, out_index, out_vec, n_out, ws=ws)
 
 
 def prepare(index, scorer):

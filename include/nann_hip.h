@@ -852,6 +852,104 @@ int nann_search_all_multi(const nann_index* ix, const nann_scorer* scorer, const
                           int32_t* n_out, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
                           nann_stream_t stream);
 
+/* ---- group caps: at most m rows per group in every top-k ----------------------------------------------------------------
+ * "At most 2 items of one seller", "at most 3 of one category", "one per brand" among the k rows a query returns.  The
+ * reference has no such call; the semantics below are this library's own.
+ *
+ * A GROUPING is group_of_row, device i32[n_items]: the group id of every internal row.  An id >= 0 can be any value and there
+ * can be any number of distinct ids; a negative id means UNGROUPED: the row is never capped and never counts against anything.
+ * A CAP m >= 1 applies to every query, or caps, device i32[n_queries], gives one cap per query; caps[i] <= 0: query i is
+ * uncapped.
+ *
+ * The input per query is a RANKED list of k_in (row, score) entries.  Entry j is VALID iff j < clamp(n_valid[i], 0, k_in), its
+ * row lies in [0, n_items) and it is not denied by the nann_filter where one is given; anything else is dropped, malformed
+ * input never faults.  Walking the valid entries in ascending j, an entry is KEPT iff its group g is negative, or fewer than m
+ * valid entries before it have group g -- equivalently, its rank among the valid entries of its group is < m.  Denied and
+ * invalid entries use no quota ("filter first, then cap").  A row that appears twice counts twice: there is no dedup, that is
+ * nann_union_topk's job.  The answer is the first k kept entries with their order unchanged: n_out[i] entries at the head of
+ * row i of every output, zeros behind.  Scores are carried through, never recomputed and never compared: NaN and -inf are
+ * scores like any other here.
+ *
+ * PREFIX PROPERTY: for any F' >= F, the capped list over the first F entries is a prefix of the capped list over the first
+ * F'.  Proof: whether entry j is valid and kept depends only on entries 0 .. j, so both walks decide every j < F alike; the
+ * walk over F' only appends entries j >= F behind them.  Two consequences: a query with n_out == k has the exact answer over
+ * the full ranking; a query with n_out < k was cut short by F, unless the list held every valid row -- the host sees this from
+ * n_out and widens F.  A query's answer does not depend on the batch it is in. */
+typedef struct {
+  int32_t struct_bytes;          /* 0 or sizeof(nann_groups) */
+  const int32_t* group_of_row;   /* device i32[n_items]; < 0 = ungrouped */
+  int32_t cap;                   /* >= 1 when caps is NULL */
+  const int32_t* caps;           /* device i32[n_queries] or NULL; caps[i] <= 0: query i uncapped */
+} nann_groups;
+
+/* The step on its own, for ranked lists from anywhere: a union's output, a candidate search's, another shard's.
+ *   scores       f32[n_queries, k_in], or NULL (out_scores then holds zeros);  rows i32[n_queries, k_in] (internal row numbers)
+ *   n_valid      i32[n_queries], or NULL = k_in everywhere (a filtered / union / candidate call's n_out)
+ *   n_items      rows outside [0, n_items) are dropped;  item_ids device i64[n_items], or NULL
+ *   groups       required;  filter optional (its exclusion lists are by the query number of THIS call)
+ *   out_index    i32[n_queries, k], required;  out_scores f32, out_item_ids i64 (= item_ids[out_index], needs item_ids),
+ *                out_group i32 (the group id of each returned row), out_pos i32 (the position j in the input list), each
+ *                [n_queries, k], n_out i32[n_queries] -- each may be NULL
+ * No workspace.  Limits: k_in <= 1024, 0 <= k <= k_in.
+ * Nothing is launched and nothing written for: a negative n_queries, k_in, n_items or k, k > k_in, a null groups, a bad
+ * groups->struct_bytes, a null group_of_row, cap < 1 with caps == NULL, a malformed filter, out_item_ids without item_ids, null
+ * rows / out_index when there is work -> NANN_ERR_BAD_ARGUMENT; k_in > 1024, n_items or n_queries > 2^31 - 1 ->
+ * NANN_ERR_UNSUPPORTED; n_queries == 0 or k == 0 -> NANN_OK, nothing written.  (Where several apply: the sizes and k first,
+ * their NANN_ERR_BAD_ARGUMENT before their NANN_ERR_UNSUPPORTED, then the groups, then the early NANN_OK, then the null
+ * pointers, out_item_ids without item_ids, the filter.)  None of these checks touches the device.  Asynchronous on `stream`,
+ * no host read-back. */
+int nann_group_cap_topk(const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_queries, int32_t k_in,
+                        int64_t n_items, const int64_t* item_ids, const nann_groups* groups, const nann_filter* filter, int32_t k,
+                        int32_t* out_index, float* out_scores, int64_t* out_item_ids, int32_t* out_group, int32_t* out_pos,
+                        int32_t* n_out, nann_stream_t stream);
+
+/* The traversal forms: the arguments of nann_search_filtered / nann_search_model_filtered plus the groups and out_group
+ * (i32[n_queries, k] or NULL); the filter may be NULL.  The inner search is nann_search_opt / nann_search_model_opt,
+ * unchanged, at the fetch width F = level_topn_max[5] into the staging area a filtered call has -- the workspace is that of
+ * the filtered call -- and the cap runs over what it returned: a query's own level_topn[5] entries, none when status[i] != 0.
+ * status, counters, plan, nann_search_reruns and nann_search_refined are the inner search's.  A failed query gets n_out = 0
+ * and zeros.  k outside [0, F], a null groups / group_of_row, a bad struct_bytes, cap < 1 with caps == NULL ->
+ * NANN_ERR_BAD_ARGUMENT, in front of the first launch; a short workspace -> NANN_ERR_CAPACITY.  n_queries == 0 -> NANN_OK.  By
+ * the prefix property a query with n_out == k has the capped answer over the traversal's whole ranking. */
+int nann_search_grouped_workspace_bytes(const nann_index* ix, const int32_t level_topn[6] /*[host]*/, int64_t n_queries,
+                                        int64_t* nbytes);
+int nann_search_grouped(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                        const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                        int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status, int32_t* counters,
+                        int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
+                        const nann_filter* filter, const nann_groups* groups, int32_t k, int32_t* out_group, int32_t* n_out,
+                        nann_stream_t stream);
+int nann_search_model_grouped_workspace_bytes(const nann_index* ix, const nann_model* m, const int32_t level_topn[6],
+                                              int64_t n_queries, int64_t* nbytes);
+int nann_search_model_grouped(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_queries,
+                              const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                              int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                              int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan,
+                              const nann_filter* filter, const nann_groups* groups, int32_t k, int32_t* out_group,
+                              int32_t* n_out, nann_stream_t stream);
+
+/* The exhaustive forms: the arguments of nann_search_all_filtered / nann_search_all_model_filtered plus the fetch width and the
+ * groups; the filter may be NULL.  F = fetch, 0 <= k <= fetch (else NANN_ERR_BAD_ARGUMENT).  The inner call is the existing
+ * filtered exhaustive search at k = F, with nann_search_all's checks applied to F: fetch > 1024 -> NANN_ERR_UNSUPPORTED, fetch >
+ * n_items -> NANN_ERR_TOPK_K_GT_N.  It writes into a staging list in the workspace (16 B x F per query, plus its n_out), and
+ * the cap runs over that list's n_out entries.  By the prefix property this is the ground truth of the traversal form
+ * wherever n_out == k; with fetch = n_items it is the capped answer over the whole ranking of the allowed rows.  A workspace
+ * smaller than ..._workspace_bytes -> NANN_ERR_CAPACITY, off the 256-byte grid -> NANN_ERR_BAD_ARGUMENT; n_queries == 0 or k == 0
+ * -> NANN_OK, nothing written. */
+int nann_search_all_grouped_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t fetch,
+                                            int64_t* nbytes);
+int nann_search_all_grouped(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t fetch,
+                            int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_group,
+                            void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                            const nann_filter* filter, const nann_groups* groups, int32_t* n_out, nann_stream_t stream);
+int nann_search_all_model_grouped_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t fetch,
+                                                  int64_t* nbytes);
+int nann_search_all_model_grouped(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                  int32_t fetch, int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                  int32_t* out_group, void* workspace, int64_t workspace_bytes,
+                                  const nann_search_options* options, const nann_filter* filter, const nann_groups* groups,
+                                  int32_t* n_out, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

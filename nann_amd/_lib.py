@@ -49,6 +49,10 @@ SYMBOLS = [
     "nann_search_candidates_model_workspace_bytes", "nann_search_candidates_model",
     "nann_union_topk_workspace_bytes", "nann_union_topk", "nann_search_multi_workspace_bytes", "nann_search_multi",
     "nann_search_all_multi_workspace_bytes", "nann_search_all_multi",
+    "nann_group_cap_topk", "nann_search_grouped_workspace_bytes", "nann_search_grouped",
+    "nann_search_model_grouped_workspace_bytes", "nann_search_model_grouped",
+    "nann_search_all_grouped_workspace_bytes", "nann_search_all_grouped",
+    "nann_search_all_model_grouped_workspace_bytes", "nann_search_all_model_grouped",
     "nann_merge_topk", "nann_merge_topk_host",
     "nann_attn_scorer_create", "nann_attn_scorer_destroy", "nann_attn_prepare", "nann_attn_score",
     "nann_blaze_options_parse", "nann_model_load", "nann_model_destroy", "nann_model_kind", "nann_model_scorer", "nann_model_workspace_bytes", "nann_model_forward",
@@ -78,6 +82,11 @@ class Filter(C.Structure):
     """nann_filter: a deny bitmap for every query and an exclusion list per query (device pointers, borrowed per call)"""
     _fields_ = [("struct_bytes", C.c_int32), ("deny_bits", C.c_void_p), ("excl_row_splits", C.c_void_p),
                 ("excl_rows", C.c_void_p), ("n_excl", C.c_int64)]
+
+
+class Groups(C.Structure):
+    """nann_groups: the group of every row and the cap -- one for the call, or one per query (device pointers, borrowed per call)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("group_of_row", C.c_void_p), ("cap", C.c_int32), ("caps", C.c_void_p)]
 
 
 class Candidates(C.Structure):
@@ -184,6 +193,32 @@ def lib():
         L.nann_search_model_filtered_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int64,
                                                                  C.POINTER(C.c_int64)]
         L.nann_search_model_filtered_workspace_bytes.restype = C.c_int
+        # the grouped forms: (scores, rows, n_valid, n_queries, k_in, n_items, item_ids, groups, filter, k, out_index, out_scores,
+        #  out_item_ids, out_group, out_pos, n_out, stream)
+        L.nann_group_cap_topk.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(Groups),
+                                                             C.POINTER(Filter), C.c_int32] + [C.c_void_p] * 7
+        L.nann_group_cap_topk.restype = C.c_int
+        # the filtered traversal's list with (filter, groups, k, out_group, n_out, stream) in the place of (filter, k, n_out, stream)
+        gtail = [C.POINTER(SearchOptions), C.POINTER(SearchPlan), C.POINTER(Filter), C.POINTER(Groups), C.c_int32, C.c_void_p,
+                 C.c_void_p, C.c_void_p]
+        L.nann_search_grouped.argtypes = head + [C.c_void_p] + gtail
+        L.nann_search_grouped.restype = C.c_int
+        L.nann_search_model_grouped.argtypes = head + gtail
+        L.nann_search_model_grouped.restype = C.c_int
+        L.nann_search_grouped_workspace_bytes.argtypes = list(L.nann_search_filtered_workspace_bytes.argtypes)
+        L.nann_search_grouped_workspace_bytes.restype = C.c_int
+        L.nann_search_model_grouped_workspace_bytes.argtypes = list(L.nann_search_model_filtered_workspace_bytes.argtypes)
+        L.nann_search_model_grouped_workspace_bytes.restype = C.c_int
+        # (ix, scorer | model, n, fetch, *nbytes) / (ix, scorer | model, q | comm_seq_f16, n, fetch, k, out_item_ids, out_scores,
+        #  out_index, out_group, workspace, workspace_bytes, options, filter, groups, n_out, stream)
+        for name in ("nann_search_all_grouped", "nann_search_all_model_grouped"):
+            fn = getattr(L, name)
+            fn.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
+                          [C.c_int64, C.POINTER(SearchOptions), C.POINTER(Filter), C.POINTER(Groups), C.c_void_p, C.c_void_p]
+            fn.restype = C.c_int
+            wb = getattr(L, name + "_workspace_bytes")
+            wb.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+            wb.restype = C.c_int
         # (ix, scorer, n_queries, n_cand, k, *nbytes) / (ix, scorer, q, n_queries, k, cand, out_item_ids, out_scores, out_index,
         #  out_pos, n_out, status, workspace, workspace_bytes, options, stream)
         L.nann_search_candidates_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,

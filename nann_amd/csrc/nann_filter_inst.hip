@@ -1,6 +1,9 @@
-// nann_filter_inst.hip -- the kernels of filtered retrieval (nann_filter.h) and their launchers.
+// nann_filter_inst.hip -- the kernels of filtered retrieval (nann_filter.h) and their launchers.  Also the group cap
+// (nann_groupcap.h), a per-query pass over a ranked list of the shape of k_filter_compact, and its launch.
 #define NANN_FILTER_IMPL
+#define NANN_GROUPCAP_IMPL
 #include "nann_filter.h"
+#include "nann_groupcap.h"
 
 namespace nann {
 
@@ -27,6 +30,15 @@ int launch_filter_compact(const FilterArgs& f, const int32_t* in_rows, const flo
   if (k < 0 || in_stride < 0 || in_stride > kMaxK) return fail(NANN_ERR_BAD_ARGUMENT, "filter: a ranked list holds at most 1024 entries");
   hipLaunchKernelGGL(k_filter_compact, dim3((unsigned)n_q), dim3(kFilterNT), 0, st, f, in_rows, in_scores, in_stride, n_in, tq, status,
                      q0, k, item_ids, out_item_ids, out_scores, out_index, n_out);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+int launch_group_cap(const GroupCapArgs& a, long long n_queries, hipStream_t st) {
+  if (n_queries <= 0) return NANN_OK;
+  if (n_queries > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, "too many queries in one call");
+  if (a.k < 0 || a.k_in < 0 || a.k_in > kMaxK) return fail(NANN_ERR_BAD_ARGUMENT, "group cap: a ranked list holds at most 1024 entries");
+  hipLaunchKernelGGL(k_group_cap, dim3((unsigned)n_queries), dim3(kFilterNT), 0, st, a);
   NANN_HIP_TRY(hipGetLastError());
   return NANN_OK;
 }

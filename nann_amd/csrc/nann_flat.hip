@@ -3,7 +3,8 @@
 // its range form (nann_search_all_range, nann_search_all_range_model; selection kernels in nann_range.h)
 // and the candidate-list search (nann_search_candidates, nann_search_candidates_model; kernels in nann_cand.h), each with its
 // *_workspace_bytes; the union top-k on its own (nann_union_topk; kernel in nann_union.h) and behind the exhaustive search
-// over a user's interest vectors (nann_search_all_multi).
+// over a user's interest vectors (nann_search_all_multi); the group cap on its own (nann_group_cap_topk; kernel in
+// nann_groupcap.h) and behind the filtered exhaustive search at a fetch width (nann_search_all_grouped, nann_search_all_model_grouped).
 //
 // Compiled into nann_core.o behind nann_hip.hip, as ONE translation unit with it (build.py writes the wrapper), on the terms
 // nann_comm.hip lives there: this file uses nann_hip.hip's file-scope types and helpers directly -- nann_index, nann_scorer,
@@ -28,6 +29,7 @@
 #include "nann_scan.h"
 #include "nann_cand.h"
 #include "nann_union.h"
+#include "nann_groupcap.h"
 
 #include <memory>
 #include <string>
@@ -116,10 +118,10 @@ static int flat_cand_check(const nann_index* ix, const nann_scorer* scorer, cons
   return NANN_OK;
 }
 
-// the caller's nann_filter as the kernels take it; NULL denies nothing
-static int resolve_filter(const nann_filter* f, const nann_index* ix, FilterArgs* out) {
+// the caller's nann_filter as the kernels take it, over n_items rows; NULL denies nothing
+static int resolve_filter_rows(const nann_filter* f, long long n_items, FilterArgs* out) {
   *out = FilterArgs{};
-  out->n_items = (long long)ix->desc.n_items;
+  out->n_items = n_items;
   if (!f) return NANN_OK;
   if (f->struct_bytes != 0 && f->struct_bytes != (int32_t)sizeof(nann_filter)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: struct_bytes");
   if (f->n_excl < 0) return fail(NANN_ERR_BAD_ARGUMENT, "nann_filter: n_excl < 0");
@@ -130,6 +132,21 @@ static int resolve_filter(const nann_filter* f, const nann_index* ix, FilterArgs
     out->rows = f->excl_rows;
     out->n_excl = (long long)f->n_excl;
   }
+  return NANN_OK;
+}
+static int resolve_filter(const nann_filter* f, const nann_index* ix, FilterArgs* out) {
+  return resolve_filter_rows(f, (long long)ix->desc.n_items, out);
+}
+
+// the caller's nann_groups into the launch arguments of the cap (nann_groupcap.h).  `who`: the entry point in a message.
+static int resolve_groups(const nann_groups* g, const char* who, GroupCapArgs* a) {
+  if (!g) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null nann_groups");
+  if (g->struct_bytes != 0 && g->struct_bytes != (int32_t)sizeof(nann_groups)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_groups: struct_bytes");
+  if (!g->group_of_row) return fail(NANN_ERR_BAD_ARGUMENT, "nann_groups: group_of_row is null");
+  if (!g->caps && g->cap < 1) return fail(NANN_ERR_BAD_ARGUMENT, "nann_groups: cap < 1 without caps");
+  a->group_of_row = g->group_of_row;
+  a->cap = g->cap;
+  a->caps = g->caps;
   return NANN_OK;
 }
 
@@ -504,8 +521,146 @@ static int flat_all_multi(const nann_index* ix, const nann_scorer* scorer, const
   return launch_union_topk(a, (long long)n_users, as_stream(stream));
 }
 
+// ---- exhaustive search under a group cap: flat_all, filtered, at k = the fetch width F into a staging list, then the cap ------
+// workspace: [flat_all's filtered workspace at k = F, rounded up to 256 | item ids i64[n, F], scores f32[n, F], rows i32[n, F],
+// n_out i32[n], rounded up]
+struct FlatGroupedBytes {
+  size_t inner, stage_off, total;
+};
+static int flat_all_grouped_check(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, int32_t fetch,
+                                  const char* who, FlatBy* by) {
+  const int rc = flat_check(ix, scorer, m, n, fetch, false, 0, who, by);  // (nann_search_all's checks, held against F)
+  if (rc) return rc;
+  if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many " + by->unit + " in one call");
+  return NANN_OK;
+}
+static FlatGroupedBytes flat_all_grouped_bytes(const nann_index* ix, const FlatBy& by, int64_t n, int32_t fetch) {
+  ScanLayout L;
+  FlatGroupedBytes b;
+  b.inner = flat_all_bytes(ix, by, n, fetch, true, &L);
+  b.stage_off = (b.inner + 255) & ~(size_t)255;
+  b.total = b.stage_off + (((size_t)n * (size_t)fetch * 16 + (size_t)n * 4 + 255) & ~(size_t)255);
+  return b;
+}
+static int flat_all_grouped_size(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, int32_t fetch,
+                                 int64_t* nbytes, const char* who) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  const int rc = flat_all_grouped_check(ix, scorer, m, n, fetch, who, &by);
+  if (rc) return rc;
+  *nbytes = n == 0 || fetch == 0 ? 0 : (int64_t)flat_all_grouped_bytes(ix, by, n, fetch).total;
+  return NANN_OK;
+}
+
+static int flat_all_grouped(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, const void* x, int64_t n,
+                            int32_t fetch, int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                            int32_t* out_group, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                            const nann_filter* filter, const nann_groups* groups, int32_t* n_out, nann_stream_t stream,
+                            const char* who, const char* inner_who) {
+  FlatBy by;
+  int rc = flat_all_grouped_check(ix, scorer, m, n, fetch, who, &by);
+  if (rc) return rc;
+  if (k < 0 || k > fetch) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k must lie in [0, fetch]");
+  GroupCapArgs a = {};
+  rc = resolve_groups(groups, who, &a);
+  if (rc) return rc;
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!x || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  rc = resolve_filter(filter, ix, &a.f);  // (a malformed filter fails the call here; the inner search resolves it for itself)
+  if (rc) return rc;
+  const FlatGroupedBytes b = flat_all_grouped_bytes(ix, by, n, fetch);
+  rc = flat_workspace(workspace, workspace_bytes, b.total, who, "");
+  if (rc) return rc;
+  unsigned char* stage = static_cast<unsigned char*>(workspace) + b.stage_off;
+  int64_t* s_ids = reinterpret_cast<int64_t*>(stage);
+  float* s_scores = reinterpret_cast<float*>(stage + (size_t)n * fetch * 8);
+  int32_t* s_rows = reinterpret_cast<int32_t*>(stage + (size_t)n * fetch * 12);
+  int32_t* s_n = reinterpret_cast<int32_t*>(stage + (size_t)n * fetch * 16);
+  rc = flat_all(ix, scorer, m, x, n, fetch, s_ids, s_scores, s_rows, workspace, (int64_t)b.inner, options, true, filter, s_n, stream,
+                inner_who);
+  if (rc) return rc;
+  a.f = FilterArgs{};  // (the staged list holds allowed rows only: filter first, then cap)
+  a.f.n_items = (long long)ix->desc.n_items;
+  a.item_ids = ix->desc.item_ids;
+  a.in_rows = s_rows;
+  a.in_scores = s_scores;
+  a.k_in = fetch;
+  a.n_valid = s_n;
+  a.nv_stride = 1;
+  a.k = k;
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_item_ids = out_item_ids;
+  a.out_group = out_group;
+  a.n_out = n_out;
+  return launch_group_cap(a, (long long)n, as_stream(stream));
+}
+
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
 extern "C" {
+
+int nann_group_cap_topk(const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_queries, int32_t k_in,
+                        int64_t n_items, const int64_t* item_ids, const nann_groups* groups, const nann_filter* filter, int32_t k,
+                        int32_t* out_index, float* out_scores, int64_t* out_item_ids, int32_t* out_group, int32_t* out_pos,
+                        int32_t* n_out, nann_stream_t stream) {
+  const char* who = "nann_group_cap_topk";
+  if (n_queries < 0 || k_in < 0 || n_items < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": negative size");
+  if (k < 0) return flat_bad_k(k);
+  if (k > k_in) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k exceeds the k_in entries a query brings");
+  if (k_in > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k_in <= 1024");
+  if (n_queries > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many queries in one call");
+  if (n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  GroupCapArgs a = {};
+  int rc = resolve_groups(groups, who, &a);
+  if (rc) return rc;
+  if (n_queries == 0 || k == 0) return NANN_OK;
+  if (!rows || !out_index) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (out_item_ids && !item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": out_item_ids without item_ids");
+  rc = resolve_filter_rows(filter, (long long)n_items, &a.f);
+  if (rc) return rc;
+  a.in_rows = rows;
+  a.in_scores = scores;
+  a.k_in = k_in;
+  a.n_valid = n_valid;
+  a.nv_stride = 1;
+  a.k = k;
+  a.item_ids = item_ids;
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_item_ids = out_item_ids;
+  a.out_group = out_group;
+  a.out_pos = out_pos;
+  a.n_out = n_out;
+  return launch_group_cap(a, (long long)n_queries, as_stream(stream));
+}
+
+int nann_search_all_grouped_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t fetch,
+                                            int64_t* nbytes) {
+  return flat_all_grouped_size(ix, scorer, nullptr, n_queries, fetch, nbytes, "nann_search_all_grouped_workspace_bytes");
+}
+int nann_search_all_grouped(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t fetch,
+                            int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_group,
+                            void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                            const nann_filter* filter, const nann_groups* groups, int32_t* n_out, nann_stream_t stream) {
+  return flat_all_grouped(ix, scorer, nullptr, q, n_queries, fetch, k, out_item_ids, out_scores, out_index, out_group, workspace,
+                          workspace_bytes, options, filter, groups, n_out, stream, "nann_search_all_grouped", "nann_search_all");
+}
+int nann_search_all_model_grouped_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t fetch,
+                                                  int64_t* nbytes) {
+  return flat_all_grouped_size(ix, nullptr, m, n_users, fetch, nbytes, "nann_search_all_model_grouped_workspace_bytes");
+}
+int nann_search_all_model_grouped(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                  int32_t fetch, int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                  int32_t* out_group, void* workspace, int64_t workspace_bytes,
+                                  const nann_search_options* options, const nann_filter* filter, const nann_groups* groups,
+                                  int32_t* n_out, nann_stream_t stream) {
+  if (!m) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_model_grouped: null argument");
+  return flat_all_grouped(ix, nullptr, m, comm_seq_f16, n_users, fetch, k, out_item_ids, out_scores, out_index, out_group, workspace,
+                          workspace_bytes, options, filter, groups, n_out, stream, "nann_search_all_model_grouped",
+                          "nann_search_all_model");
+}
 
 int nann_union_topk_workspace_bytes(int64_t n_users, int32_t n_lists, int32_t k_in, int64_t* nbytes) {
   if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_union_topk_workspace_bytes: null argument");

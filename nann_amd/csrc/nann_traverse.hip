@@ -1,5 +1,6 @@
 // nann_traverse.hip -- the host side of the calls that walk the graph: the serving traversal (nann_search_opt,
-// nann_search_model_opt and their five deprecated spellings, nann_search_filtered, nann_search_model_filtered, nann_search_multi;
+// nann_search_model_opt and their five deprecated spellings, nann_search_filtered, nann_search_model_filtered, nann_search_multi,
+// nann_search_grouped, nann_search_model_grouped;
 // kernels in nann_search.h), the evaluation traversal (nann_search_eval, nann_search_eval_ex, nann_search_eval_model; nann_eval.h), each
 // with its *_workspace_bytes, and what nann_index_create measures for them: the probe and the pivots of the batch order.
 //
@@ -26,6 +27,7 @@
 #include "nann_order_kernels.h"
 #include "nann_filter.h"
 #include "nann_union.h"
+#include "nann_groupcap.h"
 
 using namespace nann;
 
@@ -748,6 +750,52 @@ static int traverse_filtered(const nann_index* ix, const nann_scorer* scorer, co
                                out_scores, out_index, n_out, as_stream(stream));
 }
 
+// ---- the traversal under a group cap: traverse_filtered's walk -- the same checks in the same order, the same workspace and
+// staging layout, the same inner search at the fetch width F = level_topn_max[5] -- with k_group_cap (nann_groupcap.h), which
+// applies the filter and then the cap, in the place of k_filter_compact -----------------------------------------------------
+static int traverse_grouped(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, bool model, const void* x,
+                            int64_t n_queries, const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                            int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status,
+                            int32_t* counters, int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
+                            const nann_filter* filter, const nann_groups* groups, int32_t k, int32_t* out_group, int32_t* n_out,
+                            nann_stream_t stream, const char* who, const char* inner_who) {
+  if (traverse_null(ix, scorer, m, model, x, level_topn_max, out_item_ids, status, workspace))
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  const int f = level_topn_max[5];
+  if (k < 0 || k > f) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k must lie in [0, level_topn_max[5]]");  // (also of an empty batch)
+  GroupCapArgs a = {};
+  int rc = resolve_groups(groups, who, &a);
+  if (rc) return rc;
+  if (n_queries <= 0) return NANN_OK;
+  rc = resolve_filter(filter, ix, &a.f);  // (a malformed filter fails the call before anything is launched)
+  if (rc) return rc;
+  TraverseBytes b;
+  rc = traverse_bytes(ix, m, level_topn_max, n_queries, true, &b);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < b.total) return short_workspace(who);
+  unsigned char* stage = static_cast<unsigned char*>(workspace) + b.stage_off;
+  int64_t* s_ids = reinterpret_cast<int64_t*>(stage);
+  float* s_scores = reinterpret_cast<float*>(stage + (size_t)n_queries * f * 8);
+  int32_t* s_rows = reinterpret_cast<int32_t*>(stage + (size_t)n_queries * f * 12);
+  rc = traverse(ix, scorer, m, model, x, n_queries, level_topn_max, level_topn, workspace, b.inner, s_ids, s_scores, s_rows, status,
+                counters, phase_ticks, options, plan, stream, inner_who);
+  if (rc) return rc;
+  a.in_rows = s_rows;
+  a.in_scores = s_scores;
+  a.k_in = f;
+  a.n_valid = level_topn ? level_topn + 5 : nullptr;  // a query's own level_topn[5]
+  a.nv_stride = 6;
+  a.status = status;
+  a.k = k;
+  a.item_ids = ix->desc.item_ids;
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_item_ids = out_item_ids;
+  a.out_group = out_group;
+  a.n_out = n_out;
+  return launch_group_cap(a, (long long)n_queries, as_stream(stream));
+}
+
 // ---- the traversal over a user's interest vectors: the inner search over the n_users * n_vec vectors at the fetch width
 // F = level_topn_max[5] into the staging area a filtered call has behind its workspace, then the union top-k (nann_union.h)
 // of each user's n_vec lists, its workspace behind the staging area ---------------------------------------------------------
@@ -817,6 +865,34 @@ static int traverse_multi(const nann_index* ix, const nann_scorer* scorer, const
 
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
 extern "C" {
+
+int nann_search_grouped_workspace_bytes(const nann_index* ix, const int32_t level_topn[6], int64_t n_queries, int64_t* nbytes) {
+  return traverse_size(ix, nullptr, false, level_topn, n_queries, true, nbytes);
+}
+int nann_search_grouped(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                        const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                        int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status, int32_t* counters,
+                        int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
+                        const nann_filter* filter, const nann_groups* groups, int32_t k, int32_t* out_group, int32_t* n_out,
+                        nann_stream_t stream) {
+  return traverse_grouped(ix, scorer, nullptr, false, q, n_queries, level_topn_max, level_topn, workspace, workspace_bytes,
+                          out_item_ids, out_scores, out_index, status, counters, phase_ticks, options, plan, filter, groups, k,
+                          out_group, n_out, stream, "nann_search_grouped", "nann_search_opt");
+}
+int nann_search_model_grouped_workspace_bytes(const nann_index* ix, const nann_model* m, const int32_t level_topn[6],
+                                              int64_t n_queries, int64_t* nbytes) {
+  return traverse_size(ix, m, true, level_topn, n_queries, true, nbytes);
+}
+int nann_search_model_grouped(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_queries,
+                              const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                              int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                              int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan,
+                              const nann_filter* filter, const nann_groups* groups, int32_t k, int32_t* out_group,
+                              int32_t* n_out, nann_stream_t stream) {
+  return traverse_grouped(ix, nullptr, m, true, comm_seq_f16, n_queries, level_topn_max, level_topn, workspace, workspace_bytes,
+                          out_item_ids, out_scores, out_index, status, counters, nullptr, options, plan, filter, groups, k,
+                          out_group, n_out, stream, "nann_search_model_grouped", "nann_search_model");
+}
 
 int nann_search_multi_workspace_bytes(const nann_index* ix, const int32_t level_topn[6], int64_t n_users, int32_t n_vec,
                                       int64_t* nbytes) {

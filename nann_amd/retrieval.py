@@ -20,6 +20,10 @@ per request.  Two equivalent executions of that schedule live here:
   * `search_multi()` / `search_all_multi()` / `union_topk()` several interest vectors per user: the k best distinct rows by
                       the best score any vector gives a row, through the traversal / exhaustively, and the union step on its
                       own for result lists from anywhere (nann_search_multi, nann_search_all_multi, nann_union_topk);
+  * `search_grouped()` / `search_model_grouped()` / `search_all_grouped()` / `search_all_model_grouped()` / `cap_groups()`
+                      at most m rows of one group (seller, category, brand: make_groups) among the k a query returns,
+                      through the traversal / exhaustively, and the cap on its own for ranked lists from anywhere
+                      (nann_search_grouped, nann_search_all_grouped, their _model forms, nann_group_cap_topk);
   * `search_per_op()` the same schedule spelled op by op with the drop-in ops
                       of nann_amd.ops, line for line against build_model(), so
                       that each op is exercised in the composition the
@@ -754,6 +758,192 @@ def search_all_multi(index, scorer, q, k, options=None):
                                            _ptr(out_index), _ptr(out_vec), _ptr(n_out), _ptr(ws), ws.numel(),
                                            C.byref(options) if options is not None else None, _stream()), "search_all_multi")
     return MultiResult(out_ids, out_scores, out_index, out_vec, n_out, ws=ws)
+
+
+class Groups:
+    """What make_groups returns: the tensors of a nann_groups (they may live on the CPU: testable without a GPU) and its
+    ctypes struct, which borrows their memory.
+      group_of_row  i32[n_items]: the group id of every internal row; < 0 = ungrouped (never capped, counts against nothing)
+      cap           at most this many rows of one group among a query's answer (>= 1), for every query when caps is None
+      caps          i32[n_queries] or None: one cap per query; <= 0: the query is uncapped"""
+    __slots__ = ("group_of_row", "cap", "caps", "n_queries", "n_items", "device", "struct")
+
+    def __init__(self, group_of_row, cap, caps, n_items, device):
+        self.group_of_row, self.cap, self.caps, self.n_items, self.device = group_of_row, int(cap), caps, n_items, device
+        self.n_queries = None if caps is None else int(caps.numel())
+        st = _lib.Groups()
+        st.struct_bytes = C.sizeof(_lib.Groups)
+        st.group_of_row = group_of_row.data_ptr()
+        st.cap = int(cap)
+        st.caps = caps.data_ptr() if caps is not None else None
+        self.struct = st
+
+
+def make_groups(index, group_of_row=None, group_of_item_id=None, cap=1, caps=None, device=None):
+    """A nann_groups for capped searches on `index`: at most `cap` rows of one group in a query's answer.  group_of_row: the
+    group id of every internal row, [n_items] (negative: ungrouped); or group_of_item_id = (item_ids, groups), two 1-D arrays
+    of one length, mapped through index.item_ids -- an unknown id names nothing, an item that is not named is ungrouped.
+    caps: one cap per query of the batch the groups will be used with (<= 0: that query is uncapped) in the place of `cap`.
+    device: where the tensors live (default: the index's; "cpu" builds them without a GPU).  -> Groups."""
+    dev = torch.device(device if device is not None else index.device)
+    n = int(index.n_items)
+    assert (group_of_row is None) != (group_of_item_id is None), "one of group_of_row and group_of_item_id"
+    if group_of_row is not None:
+        g = _i64(group_of_row)
+        assert g.numel() == n, "group_of_row: one group id per row of the index"
+    else:
+        ids, grp = _i64(group_of_item_id[0]), _i64(group_of_item_id[1])
+        assert ids.numel() == grp.numel(), "group_of_item_id: (item_ids, groups) of one length"
+        g = torch.full((n,), -1, dtype=torch.int64)
+        vals, perm = _sorted_item_ids(index)
+        if vals.numel() and ids.numel():
+            pos = torch.searchsorted(vals, ids.to(vals.device)).clamp_(max=vals.numel() - 1)
+            found = (vals[pos] == ids.to(vals.device)).cpu()
+            g[perm[pos].cpu()[found]] = grp[found]
+    assert g.numel() == 0 or (int(g.min()) >= -(1 << 31) and int(g.max()) < (1 << 31)), "group ids are 32-bit"
+    assert caps is not None or int(cap) >= 1, "cap >= 1"
+    if caps is not None:
+        caps = _i64(caps).clamp(min=-(1 << 31), max=(1 << 31) - 1).to(torch.int32).to(dev).contiguous()
+    return Groups(g.to(torch.int32).to(dev).contiguous(), cap, caps, n, dev)
+
+
+class GroupedResult:
+    """Outputs of cap_groups / search_grouped / search_model_grouped / search_all_grouped / search_all_model_grouped, [B, k]
+    device tensors: the first k entries of a ranked list that keep to the cap, n_out[b] of them at the head of row b and zeros
+    behind.  group: the group id of each returned row.  pos (cap_groups only): the entry's position in the input list.  status,
+    counters, plan: the inner search's (the traversal forms; None elsewhere).  item_ids is None for a cap_groups without an
+    index.  A row with n_out == k holds the capped answer over the full ranking; n_out < k: the fetch width cut it short."""
+    __slots__ = ("item_ids", "scores", "index", "group", "n_out", "pos", "status", "counters", "plan", "_ws")
+
+    def __init__(self, item_ids, scores, index, group, n_out, pos=None, status=None, counters=None, plan=None, ws=None):
+        self.item_ids, self.scores, self.index, self.group, self.n_out = item_ids, scores, index, group, n_out
+        self.pos, self.status, self.counters, self.plan, self._ws = pos, status, counters, plan, ws
+
+
+def _groups_args(groups, b, n_items, dev):
+    """POINTER(nann_groups) for a batch of b queries over n_items rows"""
+    assert isinstance(groups, Groups), "groups: what make_groups returns"
+    assert n_items is None or groups.n_items == n_items, "the groups were made for another index"
+    assert groups.group_of_row.device == torch.empty(0, device=dev).device, "the groups' tensors must live on the device of the call"
+    assert groups.n_queries is None or groups.n_queries == b, "the groups' caps: one per query of the batch"
+    return C.byref(groups.struct)
+
+
+def _grouped_outputs(b, k, dev, item_ids=True):
+    """(item ids, scores, rows, groups) [b, k] and n_out [b]: the cap kernel writes every element of a row, zeros behind n_out"""
+    kk = max(int(k), 0)
+    return (torch.empty((b, kk), dtype=torch.int64, device=dev) if item_ids else None,
+            torch.empty((b, kk), dtype=torch.float32, device=dev), torch.empty((b, kk), dtype=torch.int32, device=dev),
+            torch.empty((b, kk), dtype=torch.int32, device=dev), torch.zeros(b, dtype=torch.int32, device=dev))
+
+
+def cap_groups(scores, rows, groups, k, n_valid=None, index=None, filter=None):
+    """The group cap on its own (nann_group_cap_topk): scores f32 / rows i32 [B, k_in] CUDA tensors, a RANKED list per query
+    from anywhere -- union_topk's, search_candidates' output -- of which the first n_valid[b] (i32[B]; None: k_in) entries
+    count.  Walking a list in order, an entry is kept while fewer than the cap of valid entries of its group stand before it;
+    the first k kept entries are returned, order unchanged -> GroupedResult (item_ids only with an index; pos: each entry's
+    position in its list).  filter (make_filter): denied rows are dropped first and use no quota.  Rows outside [0, n_items)
+    are dropped.  k_in <= 1024, k <= k_in.  Asynchronous on torch's current stream."""
+    dev = rows.device
+    rows = rows.to(dtype=torch.int32).contiguous()
+    assert rows.dim() == 2, "rows: [n_queries, k_in]"
+    b, k_in = rows.shape
+    if scores is not None:
+        scores = scores.to(device=dev, dtype=torch.float32).contiguous()
+        assert scores.shape == rows.shape, "scores: the shape of rows"
+    if n_valid is not None:
+        n_valid = n_valid.to(device=dev, dtype=torch.int32).contiguous()
+        assert n_valid.shape == (b,), "n_valid: [n_queries]"
+    k = int(k)
+    n_items = groups.n_items
+    out_ids, out_scores, out_index, out_group, n_out = _grouped_outputs(b, k, dev, index is not None)
+    out_pos = torch.empty_like(out_index)
+    with torch.cuda.device(dev):
+        _check(lib().nann_group_cap_topk(_ptr(scores), _ptr(rows), _ptr(n_valid), b, k_in, n_items,
+                                         _ptr(index.item_ids) if index is not None else None,
+                                         _groups_args(groups, b, int(index.n_items) if index is not None else None, dev),
+                                         _filter_args(filter, b, index) if index is not None else
+                                         (C.byref(filter.struct) if filter is not None else None), k, _ptr(out_index),
+                                         _ptr(out_scores), _ptr(out_ids), _ptr(out_group), _ptr(out_pos), _ptr(n_out), _stream()),
+               "cap_groups")
+    return GroupedResult(out_ids, out_scores, out_index, out_group, n_out, pos=out_pos)
+
+
+def search_grouped(index, scorer, q, level_topn, groups, k=None, filter=None, want_counters=True, options=None):
+    """search() under a group cap (nann_search_grouped): the unchanged traversal at the fetch width F = level_topn[5]
+    (level_topn: i32[6], or [B, 6] per query), then the first k (default F) entries of its ranked answer that keep to the cap
+    of `groups` (make_groups) -- after `filter` (make_filter), where one is given, has dropped its rows -> GroupedResult with
+    the inner search's status / counters / plan.  A failed query gets n_out = 0.  Asynchronous on torch's current stream."""
+    q = q.to(device=index.device, dtype=torch.float32).contiguous()
+    return _traverse_grouped(index, scorer, q, False, level_topn, groups, k, filter, want_counters, options)
+
+
+def search_model_grouped(index, model, comm_seq, level_topn, groups, k=None, filter=None, want_counters=True, options=None):
+    """search_model() under a group cap (nann_search_model_grouped): comm_seq f16[B, seq_len, E], scored by `model`; the rest
+    as search_grouped."""
+    seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
+    return _traverse_grouped(index, model, seq, True, level_topn, groups, k, filter, want_counters, options)
+
+
+def _traverse_grouped(index, by, x, model, level_topn, groups, k, filter, want_counters, options):
+    dev, b = index.device, x.shape[0]
+    t, tq, k_fetch = _level_topn_args(level_topn, b, dev)
+    k = int(k) if k is not None else k_fetch
+    out_ids, out_scores, out_index, out_group, n_out = _grouped_outputs(b, k, dev)
+    status = torch.zeros(b, dtype=torch.int32, device=dev)
+    counters = torch.zeros((b, 3, _lib.NUM_ROUNDS), dtype=torch.int32, device=dev) if want_counters else None
+    L = lib()
+    nbytes = C.c_int64(0)
+    if model:
+        _check(L.nann_search_model_grouped_workspace_bytes(index.handle, by.handle, t, C.c_int64(b), C.byref(nbytes)), "search_grouped")
+    else:
+        _check(L.nann_search_grouped_workspace_bytes(index.handle, t, C.c_int64(b), C.byref(nbytes)), "search_grouped")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    plan = _lib.SearchPlan()
+    ticks_arg = () if model else (None,)  # the model form has no phase ticks
+    call = L.nann_search_model_grouped if model else L.nann_search_grouped
+    with torch.cuda.device(dev):
+        _check(call(index.handle, by.handle, _ptr(x), C.c_int64(b), t, _ptr(tq), _ptr(ws), C.c_int64(ws.numel()), _ptr(out_ids),
+                    _ptr(out_scores), _ptr(out_index), _ptr(status), _ptr(counters), *ticks_arg,
+                    C.byref(options) if options is not None else None, C.byref(plan), _filter_args(filter, b, index),
+                    _groups_args(groups, b, int(index.n_items), dev), k, _ptr(out_group), _ptr(n_out), _stream()), "search_grouped")
+    return GroupedResult(out_ids, out_scores, out_index, out_group, n_out, status=status, counters=counters,
+                         plan=_plan_dict(plan), ws=ws)
+
+
+def search_all_grouped(index, scorer, q, k, groups, fetch=None, filter=None, options=None):
+    """Exhaustive search under a group cap (nann_search_all_grouped): search_all over the allowed rows at k = fetch (default:
+    min(n_items, 1024)), then the first k entries of that ranking that keep to the cap -> GroupedResult.  With fetch =
+    n_items it is the capped answer over the whole ranking: the ground truth of search_grouped wherever n_out == k.
+    `scorer`: an ops.Scorer with q f32[B, d].  0 <= k <= fetch <= min(n_items, 1024).  Asynchronous on torch's current stream."""
+    q = q.to(device=index.device, dtype=torch.float32).contiguous()
+    return _flat_all_grouped(index, scorer.handle, q, k, groups, fetch, filter, options, "nann_search_all_grouped",
+                             "search_all_grouped")
+
+
+def search_all_model_grouped(index, model, comm_seq, k, groups, fetch=None, filter=None, options=None):
+    """search_all_grouped under a model (nann_search_all_model_grouped): comm_seq f16[B, seq_len, E], an ops.Model of any kind."""
+    if not isinstance(model, ops.Model):
+        raise TypeError("search_all_model_grouped: an ops.Model (an ops.Scorer goes through search_all_grouped)")
+    seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
+    return _flat_all_grouped(index, model.handle, seq, k, groups, fetch, filter, options, "nann_search_all_model_grouped",
+                             "search_all_model_grouped")
+
+
+def _flat_all_grouped(index, handle, x, k, groups, fetch, filter, options, symbol, what):
+    dev = index.device
+    b, k = x.shape[0], int(k)
+    fetch = int(fetch) if fetch is not None else min(int(index.n_items), 1024)
+    out_ids, out_scores, out_index, out_group, n_out = _grouped_outputs(b, k, dev)
+    nbytes = C.c_int64(0)
+    _check(getattr(lib(), symbol + "_workspace_bytes")(index.handle, handle, b, fetch, C.byref(nbytes)), what)
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(getattr(lib(), symbol)(index.handle, handle, _ptr(x), b, fetch, k, _ptr(out_ids), _ptr(out_scores), _ptr(out_index),
+                                      _ptr(out_group), _ptr(ws), ws.numel(), C.byref(options) if options is not None else None,
+                                      _filter_args(filter, b, index), _groups_args(groups, b, int(index.n_items), dev),
+                                      _ptr(n_out), _stream()), what)
+    return GroupedResult(out_ids, out_scores, out_index, out_group, n_out, ws=ws)
 
 
 def prepare(index, scorer):

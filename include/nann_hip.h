@@ -950,6 +950,108 @@ int nann_search_all_model_grouped(const nann_index* ix, const nann_model* m, con
                                   const nann_search_options* options, const nann_filter* filter, const nann_groups* groups,
                                   int32_t* n_out, nann_stream_t stream);
 
+/* ---- diversified results: MMR re-ranking of a fetched top-F ---------------------------------------------------------------
+ * "Do not return 200 near-copies of the best hit": group caps give diversity by label, this gives it by embedding.  MMR
+ * (maximal marginal relevance, Carbonell & Goldstein) picks k of F fetched entries one at a time, each time the entry whose
+ * score, weighted by lambda, least resembles what was picked before it.  The reference has no such call; the semantics below
+ * are this library's own.
+ *
+ * The input per query i is a list of k_in (row, score) entries.  Entry j is VALID iff j < clamp(n_valid[i], 0, k_in), its row
+ * lies in [0, n_items), its score is finite and -- in the search forms -- the nann_filter does not deny the row; anything else
+ * is dropped, malformed input never faults.  A row that appears twice gives two candidates: there is no dedup, that is
+ * nann_union_topk's job.
+ *
+ * PARAMETERS: lambda in [0, 1] for every query (NaN or out of range: NANN_ERR_BAD_ARGUMENT), or lambdas, device
+ * f32[n_queries], one per query, a value x read as !(x >= 0) ? 0 : (x > 1 ? 1 : x).  sim: NANN_SCORER_L2 or NANN_SCORER_IP
+ * (NANN_SCORER_MLP: NANN_ERR_UNSUPPORTED; any other value: NANN_ERR_BAD_ARGUMENT).  Let a be the query's lambda and
+ * b = 1.0f - a.
+ *
+ * SIMILARITY: sim(j, t) is the canonical score of the chosen metric (L2: -||q - x||^2, IP: <q, x>) with row rows[t] widened
+ * exactly to f32 as the query and row rows[j] as the item: the lane sums and the xor butterfly of nann_score, so it is bit for
+ * bit what nann_score returns for that pair.
+ *
+ * SELECTION, all arithmetic f32 and uncontracted: r_j = a * s_j, computed once.  Step 0 picks the valid j with the greatest
+ * r_j.  After pick t the penalty updates: p_j = sim(j, t) after the first pick, afterwards p_j = (sim(j, t) > p_j) ?
+ * sim(j, t) : p_j.  Step n >= 1 picks, among the valid unpicked j, the greatest v_j = r_j - (b * p_j).  "Greatest" is by the
+ * key of TopKV2's order here: x + 0.0f, then the monotone u32 map of the bits; ties go to the lower j.  Selection stops after
+ * n_out = min(k, #valid) picks.  Every output is filled in pick order, zeros behind.
+ *
+ * CONSEQUENCES: with lambda == 1 the answer is the valid entries in (score descending, position ascending) order -- on a
+ * ranked list, the input's prefix.  A query's answer does not depend on the batch it is in.  The answer is MMR over the F
+ * entries given, not over the whole table, and there is NO PREFIX PROPERTY: the picks over the first F entries need not begin
+ * the picks over the first F' > F, and n_out == k says nothing about a wider fetch. */
+typedef struct {
+  int32_t struct_bytes;   /* 0 or sizeof(nann_diversity) */
+  float lambda;           /* in [0, 1]: 1 = relevance only, 0 = the first entry, then the farthest rows */
+  const float* lambdas;   /* device f32[n_queries] or NULL; clamped per query as above */
+  int32_t sim;            /* NANN_SCORER_L2 | NANN_SCORER_IP */
+} nann_diversity;
+
+/* The step on its own, for lists from anywhere.  From ix it reads the table, d, the row dtype, n_items and item_ids.
+ *   scores       f32[n_queries, k_in];  rows i32[n_queries, k_in] (internal row numbers)
+ *   n_valid      i32[n_queries], or NULL = k_in everywhere (a filtered / union / candidate call's n_out)
+ *   out_index    i32[n_queries, k], required;  out_scores f32 (the ORIGINAL s_j, carried through), out_mmr f32 (r_j at step
+ *                0, v_j after), out_pos i32 (the picked j), out_item_ids i64 (= item_ids[out_index]), each [n_queries, k],
+ *                n_out i32[n_queries] -- each may be NULL
+ * No workspace.  Limits: k_in <= 1024, 0 <= k <= k_in.
+ * Nothing is launched and nothing written for: a negative n_queries, k_in or k, k > k_in, a null diversity, a bad
+ * diversity->struct_bytes, a sim that is no scorer kind, a lambda outside [0, 1] or NaN, null ix / scores / rows / out_index
+ * when there is work -> NANN_ERR_BAD_ARGUMENT; k_in > 1024, n_queries > 2^31 - 1, sim == NANN_SCORER_MLP, an index whose d is
+ * not 64 / 128 / 256 / 512 -> NANN_ERR_UNSUPPORTED; n_queries == 0 or k == 0 -> NANN_OK, nothing written.  (Where several
+ * apply: the sizes and k first, their NANN_ERR_BAD_ARGUMENT before their NANN_ERR_UNSUPPORTED, then the diversity -- null,
+ * struct_bytes, sim, lambda --, then the early NANN_OK, then the null pointers, and last the index, which nothing before it
+ * reads.)  None of these checks touches the device.  Asynchronous on `stream`, no host read-back. */
+int nann_mmr_topk(const nann_index* ix, const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_queries,
+                  int32_t k_in, const nann_diversity* diversity, int32_t k, int32_t* out_index, float* out_scores,
+                  float* out_mmr, int32_t* out_pos, int64_t* out_item_ids, int32_t* n_out, nann_stream_t stream);
+
+/* The traversal forms: the arguments of nann_search_filtered / nann_search_model_filtered plus the diversity and out_mmr /
+ * out_pos (f32 / i32 [n_queries, k] or NULL); the filter may be NULL.  The inner search is nann_search_opt /
+ * nann_search_model_opt, unchanged, at the fetch width F = level_topn_max[5] into the staging area a filtered call has -- the
+ * workspace is that of the filtered call -- and MMR runs over what it returned: a query's own level_topn[5] entries without
+ * the rows the filter denies, none when status[i] != 0.  out_pos is the position in that fetched list.  status, counters,
+ * plan, nann_search_reruns and nann_search_refined are the inner search's.  A failed query gets n_out = 0 and zeros.  k
+ * outside [0, F], a null diversity, a bad struct_bytes, sim or lambda -> as above, in front of the first launch; a short
+ * workspace -> NANN_ERR_CAPACITY.  n_queries == 0 -> NANN_OK.  The similarity is over the index's rows whatever scored them:
+ * under an MLP scorer or an attention model choose the metric the embeddings were trained for. */
+int nann_search_diverse_workspace_bytes(const nann_index* ix, const int32_t level_topn[6] /*[host]*/, int64_t n_queries,
+                                        int64_t* nbytes);
+int nann_search_diverse(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                        const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                        int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status, int32_t* counters,
+                        int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
+                        const nann_filter* filter, const nann_diversity* diversity, int32_t k, float* out_mmr, int32_t* out_pos,
+                        int32_t* n_out, nann_stream_t stream);
+int nann_search_model_diverse_workspace_bytes(const nann_index* ix, const nann_model* m, const int32_t level_topn[6],
+                                              int64_t n_queries, int64_t* nbytes);
+int nann_search_model_diverse(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_queries,
+                              const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                              int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                              int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan,
+                              const nann_filter* filter, const nann_diversity* diversity, int32_t k, float* out_mmr,
+                              int32_t* out_pos, int32_t* n_out, nann_stream_t stream);
+
+/* The exhaustive forms: the arguments of nann_search_all_filtered / nann_search_all_model_filtered plus the fetch width and the
+ * diversity; the filter may be NULL.  F = fetch, 0 <= k <= fetch (else NANN_ERR_BAD_ARGUMENT).  The inner call is the existing
+ * filtered exhaustive search at k = F, with nann_search_all's checks applied to F as in nann_search_all_grouped: fetch > 1024
+ * -> NANN_ERR_UNSUPPORTED, fetch > n_items -> NANN_ERR_TOPK_K_GT_N.  It writes into a staging list in the workspace (16 B x F
+ * per query, plus its n_out), and MMR runs over that list's n_out entries: the exact top F of the allowed rows, re-ranked.  A
+ * workspace smaller than ..._workspace_bytes -> NANN_ERR_CAPACITY, off the 256-byte grid -> NANN_ERR_BAD_ARGUMENT;
+ * n_queries == 0 or k == 0 -> NANN_OK, nothing written. */
+int nann_search_all_diverse_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t fetch,
+                                            int64_t* nbytes);
+int nann_search_all_diverse(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t fetch,
+                            int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, float* out_mmr,
+                            int32_t* out_pos, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                            const nann_filter* filter, const nann_diversity* diversity, int32_t* n_out, nann_stream_t stream);
+int nann_search_all_model_diverse_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t fetch,
+                                                  int64_t* nbytes);
+int nann_search_all_model_diverse(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                  int32_t fetch, int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                  float* out_mmr, int32_t* out_pos, void* workspace, int64_t workspace_bytes,
+                                  const nann_search_options* options, const nann_filter* filter,
+                                  const nann_diversity* diversity, int32_t* n_out, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

@@ -53,6 +53,10 @@ SYMBOLS = [
     "nann_search_model_grouped_workspace_bytes", "nann_search_model_grouped",
     "nann_search_all_grouped_workspace_bytes", "nann_search_all_grouped",
     "nann_search_all_model_grouped_workspace_bytes", "nann_search_all_model_grouped",
+    "nann_mmr_topk", "nann_search_diverse_workspace_bytes", "nann_search_diverse",
+    "nann_search_model_diverse_workspace_bytes", "nann_search_model_diverse",
+    "nann_search_all_diverse_workspace_bytes", "nann_search_all_diverse",
+    "nann_search_all_model_diverse_workspace_bytes", "nann_search_all_model_diverse",
     "nann_merge_topk", "nann_merge_topk_host",
     "nann_attn_scorer_create", "nann_attn_scorer_destroy", "nann_attn_prepare", "nann_attn_score",
     "nann_blaze_options_parse", "nann_model_load", "nann_model_destroy", "nann_model_kind", "nann_model_scorer", "nann_model_workspace_bytes", "nann_model_forward",
@@ -87,6 +91,11 @@ class Filter(C.Structure):
 class Groups(C.Structure):
     """nann_groups: the group of every row and the cap -- one for the call, or one per query (device pointers, borrowed per call)"""
     _fields_ = [("struct_bytes", C.c_int32), ("group_of_row", C.c_void_p), ("cap", C.c_int32), ("caps", C.c_void_p)]
+
+
+class Diversity(C.Structure):
+    """nann_diversity: lambda -- one for the call, or one per query (a device pointer, borrowed per call) -- and the similarity"""
+    _fields_ = [("struct_bytes", C.c_int32), ("lam", C.c_float), ("lambdas", C.c_void_p), ("sim", C.c_int32)]
 
 
 class Candidates(C.Structure):
@@ -215,6 +224,31 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
                           [C.c_int64, C.POINTER(SearchOptions), C.POINTER(Filter), C.POINTER(Groups), C.c_void_p, C.c_void_p]
+            fn.restype = C.c_int
+            wb = getattr(L, name + "_workspace_bytes")
+            wb.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+            wb.restype = C.c_int
+        # the diverse forms: (ix, scores, rows, n_valid, n_queries, k_in, diversity, k, out_index, out_scores, out_mmr, out_pos,
+        #  out_item_ids, n_out, stream)
+        L.nann_mmr_topk.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.POINTER(Diversity), C.c_int32] + [C.c_void_p] * 7
+        L.nann_mmr_topk.restype = C.c_int
+        # the filtered traversal's list with (filter, diversity, k, out_mmr, out_pos, n_out, stream) in the place of its tail
+        dtail = [C.POINTER(SearchOptions), C.POINTER(SearchPlan), C.POINTER(Filter), C.POINTER(Diversity), C.c_int32, C.c_void_p,
+                 C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nann_search_diverse.argtypes = head + [C.c_void_p] + dtail
+        L.nann_search_diverse.restype = C.c_int
+        L.nann_search_model_diverse.argtypes = head + dtail
+        L.nann_search_model_diverse.restype = C.c_int
+        L.nann_search_diverse_workspace_bytes.argtypes = list(L.nann_search_filtered_workspace_bytes.argtypes)
+        L.nann_search_diverse_workspace_bytes.restype = C.c_int
+        L.nann_search_model_diverse_workspace_bytes.argtypes = list(L.nann_search_model_filtered_workspace_bytes.argtypes)
+        L.nann_search_model_diverse_workspace_bytes.restype = C.c_int
+        # (ix, scorer | model, n, fetch, *nbytes) / (ix, scorer | model, q | comm_seq_f16, n, fetch, k, out_item_ids, out_scores,
+        #  out_index, out_mmr, out_pos, workspace, workspace_bytes, options, filter, diversity, n_out, stream)
+        for name in ("nann_search_all_diverse", "nann_search_all_model_diverse"):
+            fn = getattr(L, name)
+            fn.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + \
+                          [C.c_int64, C.POINTER(SearchOptions), C.POINTER(Filter), C.POINTER(Diversity), C.c_void_p, C.c_void_p]
             fn.restype = C.c_int
             wb = getattr(L, name + "_workspace_bytes")
             wb.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]

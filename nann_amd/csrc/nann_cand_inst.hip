@@ -1,10 +1,13 @@
 // nann_cand_inst.hip -- the kernels of the candidate-list search (nann_cand.h): the plan, the L2 and inner-product scorers for every (d, row
 // dtype), the MLP scorer in both precisions and the per-query top-k; workspace layout and the launch sequence of a call.  Also
-// the union top-k (nann_union.h), a per-user selection over wg_topk like k_cand_topk, and its launch.
+// the union top-k (nann_union.h), a per-user selection over wg_topk like k_cand_topk, and its launch; and the MMR re-ranking
+// (nann_mmr.h), a per-query selection over the L2 / inner-product scorer for the (d, row dtype) set of k_cand_score_l2, and its launch.
 #define NANN_CAND_IMPL
 #define NANN_UNION_IMPL
+#define NANN_MMR_IMPL
 #include "nann_cand.h"
 #include "nann_union.h"
+#include "nann_mmr.h"
 
 #include <algorithm>
 
@@ -125,6 +128,46 @@ int launch_union_topk(const UnionArgs& a, long long n_users, hipStream_t st) {
   hipLaunchKernelGGL(k_union_topk, dim3((unsigned)n_users), dim3(kNT), lds, st, a, union_slots_log2(n_in));
   NANN_HIP_TRY(hipGetLastError());
   return NANN_OK;
+}
+
+// ---- the MMR re-ranking (nann_mmr.h) ----------------------------------------------------------------------------------
+template <int LPR, int DT>
+static int launch_mmr_as(const MmrArgs& a, unsigned grid, size_t lds, hipStream_t st) {
+  auto run = [&](auto kern) -> int {
+    if (lds > 48 * 1024)
+      NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kMmrNT), lds, st, a);
+    NANN_HIP_TRY(hipGetLastError());
+    return NANN_OK;
+  };
+  return a.metric == MT_IP ? run(k_mmr<LPR, DT, MT_IP>) : run(k_mmr<LPR, DT, MT_L2>);
+}
+
+template <int LPR>
+static int launch_mmr_dt(const MmrArgs& a, unsigned grid, size_t lds, hipStream_t st) {
+  if (a.dt == NANN_F16) return launch_mmr_as<LPR, DT_F16>(a, grid, lds, st);
+  if (a.dt == NANN_BF16) return launch_mmr_as<LPR, DT_BF16>(a, grid, lds, st);
+  if (a.dt == NANN_F32) return launch_mmr_as<LPR, DT_F32>(a, grid, lds, st);
+  return fail(NANN_ERR_UNSUPPORTED, "mmr: rows must be f16, bf16 or f32");
+}
+
+int launch_mmr(const MmrArgs& a0, long long n_queries, hipStream_t st) {
+  if (n_queries <= 0 || a0.k == 0) return NANN_OK;
+  if (n_queries > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, "too many queries in one call");
+  if (a0.k < 0 || a0.k_in < 0 || a0.k_in > kMaxK) return fail(NANN_ERR_BAD_ARGUMENT, "mmr: a list holds at most 1024 entries");
+  if (a0.metric != MT_L2 && a0.metric != MT_IP) return fail(NANN_ERR_BAD_ARGUMENT, "mmr: the similarity is L2 or the inner product");
+  MmrArgs a = a0;
+  const int row_bytes = a.d * (a.dt == NANN_F32 ? 4 : 2);
+  a.lds_rows = mmr_rows_in_lds(a.k_in, row_bytes) ? 1 : 0;
+  const size_t lds = (size_t)kMmrStateBytes + (a.lds_rows ? (size_t)a.k_in * (size_t)(row_bytes + kMmrRowPad) : 0);
+  const unsigned grid = (unsigned)n_queries;
+  switch (a.d) {
+    case 64: return launch_mmr_dt<8>(a, grid, lds, st);
+    case 128: return launch_mmr_dt<16>(a, grid, lds, st);
+    case 256: return launch_mmr_dt<32>(a, grid, lds, st);
+    case 512: return launch_mmr_dt<64>(a, grid, lds, st);
+    default: return fail(NANN_ERR_UNSUPPORTED, "mmr: d must be 64, 128, 256 or 512");
+  }
 }
 
 }  // namespace nann

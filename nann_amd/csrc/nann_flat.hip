@@ -4,7 +4,9 @@
 // and the candidate-list search (nann_search_candidates, nann_search_candidates_model; kernels in nann_cand.h), each with its
 // *_workspace_bytes; the union top-k on its own (nann_union_topk; kernel in nann_union.h) and behind the exhaustive search
 // over a user's interest vectors (nann_search_all_multi); the group cap on its own (nann_group_cap_topk; kernel in
-// nann_groupcap.h) and behind the filtered exhaustive search at a fetch width (nann_search_all_grouped, nann_search_all_model_grouped).
+// nann_groupcap.h) and behind the filtered exhaustive search at a fetch width (nann_search_all_grouped, nann_search_all_model_grouped);
+// the MMR re-ranking on its own (nann_mmr_topk; kernel in nann_mmr.h) and behind the same search (nann_search_all_diverse,
+// nann_search_all_model_diverse).
 //
 // Compiled into nann_core.o behind nann_hip.hip, as ONE translation unit with it (build.py writes the wrapper), on the terms
 // nann_comm.hip lives there: this file uses nann_hip.hip's file-scope types and helpers directly -- nann_index, nann_scorer,
@@ -30,6 +32,7 @@
 #include "nann_cand.h"
 #include "nann_union.h"
 #include "nann_groupcap.h"
+#include "nann_mmr.h"
 
 #include <memory>
 #include <string>
@@ -598,8 +601,142 @@ static int flat_all_grouped(const nann_index* ix, const nann_scorer* scorer, con
   return launch_group_cap(a, (long long)n, as_stream(stream));
 }
 
+// ---- MMR re-ranking (nann_mmr.h) ---------------------------------------------------------------------------------------------
+// the caller's nann_diversity into the launch arguments: null, struct_bytes, sim, lambda, in this order.  `who`: the entry point
+// in a message.  Touches nothing but the struct.
+static int resolve_diversity(const nann_diversity* dv, const char* who, MmrArgs* a) {
+  if (!dv) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null nann_diversity");
+  if (dv->struct_bytes != 0 && dv->struct_bytes != (int32_t)sizeof(nann_diversity)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_diversity: struct_bytes");
+  if (dv->sim == NANN_SCORER_MLP) return fail(NANN_ERR_UNSUPPORTED, "nann_diversity: the similarity is NANN_SCORER_L2 or NANN_SCORER_IP, not a learned scorer");
+  if (dv->sim != NANN_SCORER_L2 && dv->sim != NANN_SCORER_IP) return fail(NANN_ERR_BAD_ARGUMENT, "nann_diversity: unknown sim");
+  if (!(dv->lambda >= 0.0f && dv->lambda <= 1.0f)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_diversity: lambda must lie in [0, 1]");
+  a->metric = dv->sim == NANN_SCORER_IP ? MT_IP : MT_L2;
+  a->lambda = dv->lambda;
+  a->lambdas = dv->lambdas;
+  return NANN_OK;
+}
+// the index's fields the step reads; its d against the kernel's instances
+static int mmr_index(const nann_index* ix, const char* who, MmrArgs* a) {
+  const int d = ix->desc.d;
+  if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
+  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  a->emb = ix->desc.item_embs;
+  a->d = d;
+  a->dt = ix->desc.emb_dtype;
+  a->item_ids = ix->desc.item_ids;
+  a->f.n_items = (long long)ix->desc.n_items;
+  return NANN_OK;
+}
+
+// ---- exhaustive search, diversified: flat_all_grouped's walk -- the same checks, workspace and staging list, the filtered
+// exhaustive search at k = F -- with k_mmr in the place of the cap ------------------------------------------------------------
+static int flat_all_diverse(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, const void* x, int64_t n,
+                            int32_t fetch, int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, float* out_mmr,
+                            int32_t* out_pos, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                            const nann_filter* filter, const nann_diversity* diversity, int32_t* n_out, nann_stream_t stream,
+                            const char* who, const char* inner_who) {
+  FlatBy by;
+  int rc = flat_all_grouped_check(ix, scorer, m, n, fetch, who, &by);
+  if (rc) return rc;
+  if (k < 0 || k > fetch) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k must lie in [0, fetch]");
+  MmrArgs a = {};
+  rc = resolve_diversity(diversity, who, &a);
+  if (rc) return rc;
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!x || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  FilterArgs f;
+  rc = resolve_filter(filter, ix, &f);  // (a malformed filter fails the call here; the inner search resolves it for itself)
+  if (rc) return rc;
+  rc = mmr_index(ix, who, &a);  // (the staged list holds allowed rows only: a.f stays empty but for n_items)
+  if (rc) return rc;
+  const FlatGroupedBytes b = flat_all_grouped_bytes(ix, by, n, fetch);
+  rc = flat_workspace(workspace, workspace_bytes, b.total, who, "");
+  if (rc) return rc;
+  unsigned char* stage = static_cast<unsigned char*>(workspace) + b.stage_off;
+  int64_t* s_ids = reinterpret_cast<int64_t*>(stage);
+  float* s_scores = reinterpret_cast<float*>(stage + (size_t)n * fetch * 8);
+  int32_t* s_rows = reinterpret_cast<int32_t*>(stage + (size_t)n * fetch * 12);
+  int32_t* s_n = reinterpret_cast<int32_t*>(stage + (size_t)n * fetch * 16);
+  rc = flat_all(ix, scorer, m, x, n, fetch, s_ids, s_scores, s_rows, workspace, (int64_t)b.inner, options, true, filter, s_n, stream,
+                inner_who);
+  if (rc) return rc;
+  a.in_rows = s_rows;
+  a.in_scores = s_scores;
+  a.k_in = fetch;
+  a.n_valid = s_n;
+  a.nv_stride = 1;
+  a.k = k;
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_mmr = out_mmr;
+  a.out_pos = out_pos;
+  a.out_item_ids = out_item_ids;
+  a.n_out = n_out;
+  return launch_mmr(a, (long long)n, as_stream(stream));
+}
+
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
 extern "C" {
+
+int nann_mmr_topk(const nann_index* ix, const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_queries,
+                  int32_t k_in, const nann_diversity* diversity, int32_t k, int32_t* out_index, float* out_scores,
+                  float* out_mmr, int32_t* out_pos, int64_t* out_item_ids, int32_t* n_out, nann_stream_t stream) {
+  const char* who = "nann_mmr_topk";
+  if (n_queries < 0 || k_in < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": negative size");
+  if (k < 0) return flat_bad_k(k);
+  if (k > k_in) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k exceeds the k_in entries a query brings");
+  if (k_in > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k_in <= 1024");
+  if (n_queries > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many queries in one call");
+  MmrArgs a = {};
+  int rc = resolve_diversity(diversity, who, &a);
+  if (rc) return rc;
+  if (n_queries == 0 || k == 0) return NANN_OK;
+  if (!ix || !scores || !rows || !out_index) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  rc = mmr_index(ix, who, &a);  // (the first read of the index)
+  if (rc) return rc;
+  a.in_rows = rows;
+  a.in_scores = scores;
+  a.k_in = k_in;
+  a.n_valid = n_valid;
+  a.nv_stride = 1;
+  a.k = k;
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_mmr = out_mmr;
+  a.out_pos = out_pos;
+  a.out_item_ids = out_item_ids;
+  a.n_out = n_out;
+  return launch_mmr(a, (long long)n_queries, as_stream(stream));
+}
+
+int nann_search_all_diverse_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t fetch,
+                                            int64_t* nbytes) {
+  return flat_all_grouped_size(ix, scorer, nullptr, n_queries, fetch, nbytes, "nann_search_all_diverse_workspace_bytes");
+}
+int nann_search_all_diverse(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t fetch,
+                            int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, float* out_mmr,
+                            int32_t* out_pos, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                            const nann_filter* filter, const nann_diversity* diversity, int32_t* n_out, nann_stream_t stream) {
+  return flat_all_diverse(ix, scorer, nullptr, q, n_queries, fetch, k, out_item_ids, out_scores, out_index, out_mmr, out_pos,
+                          workspace, workspace_bytes, options, filter, diversity, n_out, stream, "nann_search_all_diverse",
+                          "nann_search_all");
+}
+int nann_search_all_model_diverse_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t fetch,
+                                                  int64_t* nbytes) {
+  return flat_all_grouped_size(ix, nullptr, m, n_users, fetch, nbytes, "nann_search_all_model_diverse_workspace_bytes");
+}
+int nann_search_all_model_diverse(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                  int32_t fetch, int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                  float* out_mmr, int32_t* out_pos, void* workspace, int64_t workspace_bytes,
+                                  const nann_search_options* options, const nann_filter* filter,
+                                  const nann_diversity* diversity, int32_t* n_out, nann_stream_t stream) {
+  if (!m) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_model_diverse: null argument");
+  return flat_all_diverse(ix, nullptr, m, comm_seq_f16, n_users, fetch, k, out_item_ids, out_scores, out_index, out_mmr, out_pos,
+                          workspace, workspace_bytes, options, filter, diversity, n_out, stream, "nann_search_all_model_diverse",
+                          "nann_search_all_model");
+}
 
 int nann_group_cap_topk(const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_queries, int32_t k_in,
                         int64_t n_items, const int64_t* item_ids, const nann_groups* groups, const nann_filter* filter, int32_t k,

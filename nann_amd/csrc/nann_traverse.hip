@@ -1,6 +1,6 @@
 // nann_traverse.hip -- the host side of the calls that walk the graph: the serving traversal (nann_search_opt,
 // nann_search_model_opt and their five deprecated spellings, nann_search_filtered, nann_search_model_filtered, nann_search_multi,
-// nann_search_grouped, nann_search_model_grouped;
+// nann_search_grouped, nann_search_model_grouped, nann_search_diverse, nann_search_model_diverse;
 // kernels in nann_search.h), the evaluation traversal (nann_search_eval, nann_search_eval_ex, nann_search_eval_model; nann_eval.h), each
 // with its *_workspace_bytes, and what nann_index_create measures for them: the probe and the pivots of the batch order.
 //
@@ -28,6 +28,7 @@
 #include "nann_filter.h"
 #include "nann_union.h"
 #include "nann_groupcap.h"
+#include "nann_mmr.h"
 
 using namespace nann;
 
@@ -796,6 +797,56 @@ static int traverse_grouped(const nann_index* ix, const nann_scorer* scorer, con
   return launch_group_cap(a, (long long)n_queries, as_stream(stream));
 }
 
+// ---- the traversal, diversified: traverse_grouped's walk -- the same checks in the same order, the same workspace and staging
+// layout, the same inner search at the fetch width F = level_topn_max[5] -- with k_mmr (nann_mmr.h), which applies the filter
+// and then re-ranks, in the place of the cap ----------------------------------------------------------------------------------
+static int traverse_diverse(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, bool model, const void* x,
+                            int64_t n_queries, const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                            int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status,
+                            int32_t* counters, int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
+                            const nann_filter* filter, const nann_diversity* diversity, int32_t k, float* out_mmr,
+                            int32_t* out_pos, int32_t* n_out, nann_stream_t stream, const char* who, const char* inner_who) {
+  if (traverse_null(ix, scorer, m, model, x, level_topn_max, out_item_ids, status, workspace))
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  const int f = level_topn_max[5];
+  if (k < 0 || k > f) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k must lie in [0, level_topn_max[5]]");  // (also of an empty batch)
+  MmrArgs a = {};
+  int rc = resolve_diversity(diversity, who, &a);
+  if (rc) return rc;
+  if (n_queries <= 0) return NANN_OK;
+  FilterArgs fa;
+  rc = resolve_filter(filter, ix, &fa);  // (a malformed filter fails the call before anything is launched)
+  if (rc) return rc;
+  rc = mmr_index(ix, who, &a);
+  if (rc) return rc;
+  a.f = fa;
+  TraverseBytes b;
+  rc = traverse_bytes(ix, m, level_topn_max, n_queries, true, &b);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < b.total) return short_workspace(who);
+  unsigned char* stage = static_cast<unsigned char*>(workspace) + b.stage_off;
+  int64_t* s_ids = reinterpret_cast<int64_t*>(stage);
+  float* s_scores = reinterpret_cast<float*>(stage + (size_t)n_queries * f * 8);
+  int32_t* s_rows = reinterpret_cast<int32_t*>(stage + (size_t)n_queries * f * 12);
+  rc = traverse(ix, scorer, m, model, x, n_queries, level_topn_max, level_topn, workspace, b.inner, s_ids, s_scores, s_rows, status,
+                counters, phase_ticks, options, plan, stream, inner_who);
+  if (rc) return rc;
+  a.in_rows = s_rows;
+  a.in_scores = s_scores;
+  a.k_in = f;
+  a.n_valid = level_topn ? level_topn + 5 : nullptr;  // a query's own level_topn[5]
+  a.nv_stride = 6;
+  a.status = status;
+  a.k = k;
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_mmr = out_mmr;
+  a.out_pos = out_pos;
+  a.out_item_ids = out_item_ids;
+  a.n_out = n_out;
+  return launch_mmr(a, (long long)n_queries, as_stream(stream));
+}
+
 // ---- the traversal over a user's interest vectors: the inner search over the n_users * n_vec vectors at the fetch width
 // F = level_topn_max[5] into the staging area a filtered call has behind its workspace, then the union top-k (nann_union.h)
 // of each user's n_vec lists, its workspace behind the staging area ---------------------------------------------------------
@@ -865,6 +916,34 @@ static int traverse_multi(const nann_index* ix, const nann_scorer* scorer, const
 
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
 extern "C" {
+
+int nann_search_diverse_workspace_bytes(const nann_index* ix, const int32_t level_topn[6], int64_t n_queries, int64_t* nbytes) {
+  return traverse_size(ix, nullptr, false, level_topn, n_queries, true, nbytes);
+}
+int nann_search_diverse(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                        const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                        int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status, int32_t* counters,
+                        int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
+                        const nann_filter* filter, const nann_diversity* diversity, int32_t k, float* out_mmr, int32_t* out_pos,
+                        int32_t* n_out, nann_stream_t stream) {
+  return traverse_diverse(ix, scorer, nullptr, false, q, n_queries, level_topn_max, level_topn, workspace, workspace_bytes,
+                          out_item_ids, out_scores, out_index, status, counters, phase_ticks, options, plan, filter, diversity, k,
+                          out_mmr, out_pos, n_out, stream, "nann_search_diverse", "nann_search_opt");
+}
+int nann_search_model_diverse_workspace_bytes(const nann_index* ix, const nann_model* m, const int32_t level_topn[6],
+                                              int64_t n_queries, int64_t* nbytes) {
+  return traverse_size(ix, m, true, level_topn, n_queries, true, nbytes);
+}
+int nann_search_model_diverse(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_queries,
+                              const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                              int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                              int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan,
+                              const nann_filter* filter, const nann_diversity* diversity, int32_t k, float* out_mmr,
+                              int32_t* out_pos, int32_t* n_out, nann_stream_t stream) {
+  return traverse_diverse(ix, nullptr, m, true, comm_seq_f16, n_queries, level_topn_max, level_topn, workspace, workspace_bytes,
+                          out_item_ids, out_scores, out_index, status, counters, nullptr, options, plan, filter, diversity, k,
+                          out_mmr, out_pos, n_out, stream, "nann_search_model_diverse", "nann_search_model");
+}
 
 int nann_search_grouped_workspace_bytes(const nann_index* ix, const int32_t level_topn[6], int64_t n_queries, int64_t* nbytes) {
   return traverse_size(ix, nullptr, false, level_topn, n_queries, true, nbytes);

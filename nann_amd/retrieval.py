@@ -24,6 +24,10 @@ per request.  Two equivalent executions of that schedule live here:
                       at most m rows of one group (seller, category, brand: make_groups) among the k a query returns,
                       through the traversal / exhaustively, and the cap on its own for ranked lists from anywhere
                       (nann_search_grouped, nann_search_all_grouped, their _model forms, nann_group_cap_topk);
+  * `search_diverse()` / `search_model_diverse()` / `search_all_diverse()` / `search_all_model_diverse()` / `mmr()`
+                      diversified results: MMR re-ranking (make_diversity) of the fetched top-F into k picks, through the
+                      traversal / exhaustively, and the step on its own for lists from anywhere
+                      (nann_search_diverse, nann_search_all_diverse, their _model forms, nann_mmr_topk);
   * `search_per_op()` the same schedule spelled op by op with the drop-in ops
                       of nann_amd.ops, line for line against build_model(), so
                       that each op is exercised in the composition the
@@ -944,6 +948,169 @@ def _flat_all_grouped(index, handle, x, k, groups, fetch, filter, options, symbo
                                       _filter_args(filter, b, index), _groups_args(groups, b, int(index.n_items), dev),
                                       _ptr(n_out), _stream()), what)
     return GroupedResult(out_ids, out_scores, out_index, out_group, n_out, ws=ws)
+
+
+class Diversity:
+    """What make_diversity returns: the parameters of an MMR re-ranking (nann_diversity).
+      lam   lambda in [0, 1] for every query when lams is None: 1 = relevance only, 0 = the first entry, then the farthest rows
+      lams  f32[n_queries] or None: one lambda per query, read as 0 below 0 or NaN and as 1 above 1
+      sim   "l2" | "ip" | None: the similarity between rows; None: "ip" under an inner-product scorer or model, else "l2" """
+    __slots__ = ("lam", "lams", "sim", "n_queries")
+
+    def __init__(self, lam, lams, sim):
+        self.lam, self.lams, self.sim = float(lam), lams, sim
+        self.n_queries = None if lams is None else int(lams.numel())
+
+
+def make_diversity(lam=0.5, lams=None, sim=None):
+    """The parameters of an MMR re-ranking: the k picks out of a fetched list maximise, one at a time, lam * score -
+    (1 - lam) * (the greatest similarity to a row picked before).  lams: one lambda per query of the batch in the place of `lam`.
+    sim: "l2" (-||a - b||^2) or "ip" (<a, b>) over the index's rows; None takes the scorer's metric where it has one of these
+    -> Diversity."""
+    assert sim in (None, "l2", "ip"), 'sim: "l2", "ip" or None'
+    lam = float(lam)
+    assert 0.0 <= lam <= 1.0, "lam must lie in [0, 1]"
+    if lams is not None:
+        lams = torch.as_tensor(lams).to(torch.float32).reshape(-1).contiguous()
+    return Diversity(lam, lams, sim)
+
+
+class DiverseResult:
+    """Outputs of mmr / search_diverse / search_model_diverse / search_all_diverse / search_all_model_diverse, [B, k] device
+    tensors in PICK order, n_out[b] = min(k, valid entries) of them at the head of row b and zeros behind.  scores: the
+    original score of each pick, carried through; mmr: the value it was picked at (lam * score at the first pick, lam * score
+    - (1 - lam) * penalty after); pos: its position in the list that was re-ranked.  status, counters, plan: the inner search's
+    (the traversal forms; None elsewhere).  The answer is MMR over the fetched list, not over the table: a wider fetch may
+    change every pick behind the first."""
+    __slots__ = ("item_ids", "scores", "index", "mmr", "pos", "n_out", "status", "counters", "plan", "_ws")
+
+    def __init__(self, item_ids, scores, index, mmr, pos, n_out, status=None, counters=None, plan=None, ws=None):
+        self.item_ids, self.scores, self.index, self.mmr, self.pos, self.n_out = item_ids, scores, index, mmr, pos, n_out
+        self.status, self.counters, self.plan, self._ws = status, counters, plan, ws
+
+
+def _diversity_args(diversity, b, dev, by=None):
+    """(POINTER(nann_diversity), what it borrows) for a batch of b queries scored by `by` (an ops.Scorer / ops.Model or None)"""
+    assert isinstance(diversity, Diversity), "diversity: what make_diversity returns"
+    assert diversity.n_queries is None or diversity.n_queries == b, "the diversity's lams: one per query of the batch"
+    sim = diversity.sim if diversity.sim is not None else ("ip" if getattr(by, "kind", None) == "ip" else "l2")
+    lams = diversity.lams.to(dev) if diversity.lams is not None else None
+    st = _lib.Diversity()
+    st.struct_bytes = C.sizeof(_lib.Diversity)
+    st.lam = diversity.lam
+    st.lambdas = lams.data_ptr() if lams is not None else None
+    st.sim = _lib.SCORER_IP if sim == "ip" else _lib.SCORER_L2
+    return C.byref(st), (st, lams)
+
+
+def _diverse_outputs(b, k, dev):
+    """(item ids, scores, rows, mmr values, positions) [b, k] and n_out [b]: the kernel writes every element of a row"""
+    kk = max(int(k), 0)
+    return (torch.empty((b, kk), dtype=torch.int64, device=dev), torch.empty((b, kk), dtype=torch.float32, device=dev),
+            torch.empty((b, kk), dtype=torch.int32, device=dev), torch.empty((b, kk), dtype=torch.float32, device=dev),
+            torch.empty((b, kk), dtype=torch.int32, device=dev), torch.zeros(b, dtype=torch.int32, device=dev))
+
+
+def mmr(index, scores, rows, diversity, k, n_valid=None):
+    """The MMR re-ranking on its own (nann_mmr_topk): scores f32 / rows i32 [B, k_in] CUDA tensors, a list of rows of `index`
+    per query from anywhere -- search's, union_topk's, search_candidates' output -- of which the first n_valid[b] (i32[B]; None:
+    k_in) entries count.  Entries whose row lies outside the index or whose score is not finite are dropped; a repeated row
+    is two candidates.  -> DiverseResult, the picks in pick order.  k_in <= 1024, k <= k_in.  Asynchronous on torch's current
+    stream."""
+    dev = index.device
+    rows = rows.to(device=dev, dtype=torch.int32).contiguous()
+    assert rows.dim() == 2, "rows: [n_queries, k_in]"
+    b, k_in = rows.shape
+    scores = scores.to(device=dev, dtype=torch.float32).contiguous()
+    assert scores.shape == rows.shape, "scores: the shape of rows"
+    if n_valid is not None:
+        n_valid = n_valid.to(device=dev, dtype=torch.int32).contiguous()
+        assert n_valid.shape == (b,), "n_valid: [n_queries]"
+    k = int(k)
+    out_ids, out_scores, out_index, out_mmr, out_pos, n_out = _diverse_outputs(b, k, dev)
+    dv, keep = _diversity_args(diversity, b, dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_mmr_topk(index.handle, _ptr(scores), _ptr(rows), _ptr(n_valid), b, k_in, dv, k, _ptr(out_index),
+                                   _ptr(out_scores), _ptr(out_mmr), _ptr(out_pos), _ptr(out_ids), _ptr(n_out), _stream()), "mmr")
+    return DiverseResult(out_ids, out_scores, out_index, out_mmr, out_pos, n_out, ws=keep)
+
+
+def search_diverse(index, scorer, q, level_topn, diversity, k=None, filter=None, want_counters=True, options=None):
+    """search() with diversified results (nann_search_diverse): the unchanged traversal at the fetch width F = level_topn[5]
+    (level_topn: i32[6], or [B, 6] per query), then k (default F) MMR picks out of its answer -- without the rows `filter`
+    (make_filter) denies, where one is given -> DiverseResult with the inner search's status / counters / plan.  A failed query
+    gets n_out = 0.  Asynchronous on torch's current stream."""
+    q = q.to(device=index.device, dtype=torch.float32).contiguous()
+    return _traverse_diverse(index, scorer, q, False, level_topn, diversity, k, filter, want_counters, options)
+
+
+def search_model_diverse(index, model, comm_seq, level_topn, diversity, k=None, filter=None, want_counters=True, options=None):
+    """search_model() with diversified results (nann_search_model_diverse): comm_seq f16[B, seq_len, E], scored by `model`;
+    the rest as search_diverse."""
+    seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
+    return _traverse_diverse(index, model, seq, True, level_topn, diversity, k, filter, want_counters, options)
+
+
+def _traverse_diverse(index, by, x, model, level_topn, diversity, k, filter, want_counters, options):
+    dev, b = index.device, x.shape[0]
+    t, tq, k_fetch = _level_topn_args(level_topn, b, dev)
+    k = int(k) if k is not None else k_fetch
+    out_ids, out_scores, out_index, out_mmr, out_pos, n_out = _diverse_outputs(b, k, dev)
+    status = torch.zeros(b, dtype=torch.int32, device=dev)
+    counters = torch.zeros((b, 3, _lib.NUM_ROUNDS), dtype=torch.int32, device=dev) if want_counters else None
+    L = lib()
+    nbytes = C.c_int64(0)
+    if model:
+        _check(L.nann_search_model_diverse_workspace_bytes(index.handle, by.handle, t, C.c_int64(b), C.byref(nbytes)), "search_diverse")
+    else:
+        _check(L.nann_search_diverse_workspace_bytes(index.handle, t, C.c_int64(b), C.byref(nbytes)), "search_diverse")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    plan = _lib.SearchPlan()
+    ticks_arg = () if model else (None,)  # the model form has no phase ticks
+    call = L.nann_search_model_diverse if model else L.nann_search_diverse
+    dv, keep = _diversity_args(diversity, b, dev, by)
+    with torch.cuda.device(dev):
+        _check(call(index.handle, by.handle, _ptr(x), C.c_int64(b), t, _ptr(tq), _ptr(ws), C.c_int64(ws.numel()), _ptr(out_ids),
+                    _ptr(out_scores), _ptr(out_index), _ptr(status), _ptr(counters), *ticks_arg,
+                    C.byref(options) if options is not None else None, C.byref(plan), _filter_args(filter, b, index),
+                    dv, k, _ptr(out_mmr), _ptr(out_pos), _ptr(n_out), _stream()), "search_diverse")
+    return DiverseResult(out_ids, out_scores, out_index, out_mmr, out_pos, n_out, status=status, counters=counters,
+                         plan=_plan_dict(plan), ws=(ws, keep))
+
+
+def search_all_diverse(index, scorer, q, k, diversity, fetch=None, filter=None, options=None):
+    """Exhaustive search with diversified results (nann_search_all_diverse): search_all over the allowed rows at k = fetch
+    (default: min(n_items, 1024)), then k MMR picks out of that exact top-fetch -> DiverseResult.  `scorer`: an ops.Scorer
+    with q f32[B, d].  0 <= k <= fetch <= min(n_items, 1024).  Asynchronous on torch's current stream."""
+    q = q.to(device=index.device, dtype=torch.float32).contiguous()
+    return _flat_all_diverse(index, scorer, scorer.handle, q, k, diversity, fetch, filter, options, "nann_search_all_diverse",
+                             "search_all_diverse")
+
+
+def search_all_model_diverse(index, model, comm_seq, k, diversity, fetch=None, filter=None, options=None):
+    """search_all_diverse under a model (nann_search_all_model_diverse): comm_seq f16[B, seq_len, E], an ops.Model of any kind."""
+    if not isinstance(model, ops.Model):
+        raise TypeError("search_all_model_diverse: an ops.Model (an ops.Scorer goes through search_all_diverse)")
+    seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
+    return _flat_all_diverse(index, model, model.handle, seq, k, diversity, fetch, filter, options,
+                             "nann_search_all_model_diverse", "search_all_model_diverse")
+
+
+def _flat_all_diverse(index, by, handle, x, k, diversity, fetch, filter, options, symbol, what):
+    dev = index.device
+    b, k = x.shape[0], int(k)
+    fetch = int(fetch) if fetch is not None else min(int(index.n_items), 1024)
+    out_ids, out_scores, out_index, out_mmr, out_pos, n_out = _diverse_outputs(b, k, dev)
+    nbytes = C.c_int64(0)
+    _check(getattr(lib(), symbol + "_workspace_bytes")(index.handle, handle, b, fetch, C.byref(nbytes)), what)
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    dv, keep = _diversity_args(diversity, b, dev, by)
+    with torch.cuda.device(dev):
+        _check(getattr(lib(), symbol)(index.handle, handle, _ptr(x), b, fetch, k, _ptr(out_ids), _ptr(out_scores), _ptr(out_index),
+                                      _ptr(out_mmr), _ptr(out_pos), _ptr(ws), ws.numel(),
+                                      C.byref(options) if options is not None else None, _filter_args(filter, b, index), dv,
+                                      _ptr(n_out), _stream()), what)
+    return DiverseResult(out_ids, out_scores, out_index, out_mmr, out_pos, n_out, ws=(ws, keep))
 
 
 def prepare(index, scorer):

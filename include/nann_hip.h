@@ -1052,6 +1052,104 @@ int nann_search_all_model_diverse(const nann_index* ix, const nann_model* m, con
                                   const nann_search_options* options, const nann_filter* filter,
                                   const nann_diversity* diversity, int32_t* n_out, nann_stream_t stream);
 
+/* ---- attribute predicates: per-query label, range and tag conditions -------------------------------------------------------
+ * "Only rows of category 7 or 12 for this user", "price between this user's bounds", "in stock in this user's region, and not
+ * adult": a condition on ROW ATTRIBUTES that differs from query to query.  The deny bitmap of a nann_filter is one for the whole
+ * batch, and an exclusion list would have to name every row that fails.  The reference has no such feature; the semantics below
+ * are this library's own.
+ *
+ * A nann_predicates is a plain struct, passed per call and BORROWED for the call, as nann_filter and nann_groups are.  Row
+ * attributes, each a device array of n_items entries or NULL: label_of_row (i32), value_of_row (f32), tags_of_row (u64: a set of
+ * up to 64 tags).  Per-query conditions, each by the query number of the call:
+ *   labels  query i allows the labels labels[label_splits[i] .. label_splits[i + 1]): any order, duplicates allowed, any number.
+ *           The range is clamped to [0, n_labels]; an empty or inverted range means NO label test for that query
+ *   value   the row passes iff value_lo[i] <= value_of_row[r] <= value_hi[i], compared as IEEE does: a NaN row value or a NaN
+ *           bound passes nothing; a NULL side is unbounded; lo > hi is how a caller says "match nothing"
+ *   tags    with t = tags_of_row[r] the row passes iff (t & all) == all, any == 0 || (t & any) != 0, and (t & none) == 0; a
+ *           NULL array reads as zeros
+ * A row PASSES query i iff every test that is present passes: the tests are ANDed with each other and with the nann_filter
+ * where one is given.  NULL, or a struct without any per-query condition, passes every row.
+ * Argument errors, all NANN_ERR_BAD_ARGUMENT: struct_bytes other than 0 or sizeof(nann_predicates); a per-query condition
+ * without its attribute column (label_splits without label_of_row, value_lo / value_hi without value_of_row, tags_all /
+ * tags_any / tags_none without tags_of_row); n_labels < 0; label_splits without labels while n_labels > 0.  All checks run in
+ * front of the first launch and none touches the device; the four search calls below look at the struct before any other
+ * argument, so a malformed one is refused whatever the handles and also for an empty batch.  Malformed device contents never fault. */
+typedef struct {
+  int32_t struct_bytes;             /* 0 or sizeof(nann_predicates) */
+  const int32_t* label_of_row;      /* device i32[n_items], or NULL */
+  const float* value_of_row;        /* device f32[n_items], or NULL */
+  const uint64_t* tags_of_row;      /* device u64[n_items], or NULL */
+  const int64_t* label_splits;      /* device i64[n_queries + 1], or NULL */
+  const int32_t* labels;            /* device i32[n_labels] */
+  int64_t n_labels;
+  const float* value_lo;            /* device f32[n_queries] each, or NULL */
+  const float* value_hi;
+  const uint64_t* tags_all;         /* device u64[n_queries] each, or NULL */
+  const uint64_t* tags_any;
+  const uint64_t* tags_none;
+} nann_predicates;
+
+/* The step on its own, for ranked lists from anywhere: the arguments of nann_group_cap_topk without the groups.  Entry j of
+ * query i is VALID iff j < clamp(n_valid[i], 0, k_in) and its row lies in [0, n_items); the answer is the first k valid entries
+ * that pass the predicates and the filter, order kept: n_out[i] of them at the head of row i of every output, zeros behind.
+ * Scores are carried through, never compared; a row that stands twice is judged twice.  Usage: a union's output filtered by
+ * predicate and handed on to nann_group_cap_topk through n_valid = this call's n_out.
+ *   out_index i32[n_queries, k] is required; out_scores f32, out_item_ids i64 (needs item_ids), out_pos i32 (the position j in
+ *   the input list), n_out i32[n_queries] may be NULL.  No workspace.  Limits: k_in <= 1024, 0 <= k <= k_in.
+ * Checks as nann_group_cap_topk's, with the predicates in the place of the groups (NULL: none), in front of the first launch. */
+int nann_predicate_topk(const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_queries, int32_t k_in,
+                        int64_t n_items, const int64_t* item_ids, const nann_predicates* predicates, const nann_filter* filter,
+                        int32_t k, int32_t* out_index, float* out_scores, int64_t* out_item_ids, int32_t* out_pos, int32_t* n_out,
+                        nann_stream_t stream);
+
+/* The SELECTIVITY: out_counts[i] (device i64[n_queries]) = rows of [0, n_items) that pass query i's predicates and the filter.
+ * It tells a caller whether a traversal at fetch width F can fill k -- about F x count / n_items of the fetched rows pass -- or
+ * the exhaustive form is the one to call.  A row an exclusion list names twice counts once.  Negative sizes, a malformed
+ * struct, a null out_counts while n_queries > 0 -> NANN_ERR_BAD_ARGUMENT; n_items > 2^31 - 1 -> NANN_ERR_UNSUPPORTED.
+ * Asynchronous on `stream`, no host read-back. */
+int nann_predicate_count(int64_t n_items, const nann_predicates* predicates, const nann_filter* filter, int64_t n_queries,
+                         int64_t* out_counts, nann_stream_t stream);
+
+/* The traversal forms: nann_search_filtered / nann_search_model_filtered plus the predicates, with the same fetch-width
+ * contract: the inner search is nann_search_opt / nann_search_model_opt, unchanged, at F = level_topn_max[5]; the answer is the
+ * first k passing entries of what the unchanged traversal returns at F, order kept.  The workspace is that of the filtered
+ * call.  n_out[i] < k means the list was cut short: widen F, or take the exhaustive form.  A failed query (status[i] != 0)
+ * gets n_out = 0 and zeros.  Rows that fail still guide the walk. */
+int nann_search_where_workspace_bytes(const nann_index* ix, const int32_t level_topn[6] /*[host]*/, int64_t n_queries,
+                                      int64_t* nbytes);
+int nann_search_where(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                      const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                      int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status, int32_t* counters,
+                      int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
+                      const nann_filter* filter, const nann_predicates* predicates, int32_t k, int32_t* n_out,
+                      nann_stream_t stream);
+int nann_search_model_where_workspace_bytes(const nann_index* ix, const nann_model* m, const int32_t level_topn[6],
+                                            int64_t n_queries, int64_t* nbytes);
+int nann_search_model_where(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_queries,
+                            const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                            int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                            int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan,
+                            const nann_filter* filter, const nann_predicates* predicates, int32_t k, int32_t* n_out,
+                            nann_stream_t stream);
+
+/* The exhaustive forms: nann_search_all_filtered / nann_search_all_model_filtered plus the predicates -- the same arguments,
+ * checks, error codes and workspace.  The top k over the PASSING rows is exact, in TopKV2 order (descending, ties -> lower row):
+ * n_out[i] = min(k, passing rows of query i) wherever the passing rows score above -inf -- the -inf caveat of the filtered call:
+ * failing rows are taken out by writing -inf over their scores between scoring and selection.  Scores are bit-identical to
+ * nann_search_all for the same (query, row), and a query's answer does not depend on its batch. */
+int nann_search_all_where_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k,
+                                          int64_t* nbytes);
+int nann_search_all_where(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
+                          int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                          const nann_predicates* predicates, int32_t* n_out, nann_stream_t stream);
+int nann_search_all_model_where_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k,
+                                                int64_t* nbytes);
+int nann_search_all_model_where(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
+                                int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                                const nann_predicates* predicates, int32_t* n_out, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

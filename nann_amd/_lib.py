@@ -57,6 +57,10 @@ SYMBOLS = [
     "nann_search_model_diverse_workspace_bytes", "nann_search_model_diverse",
     "nann_search_all_diverse_workspace_bytes", "nann_search_all_diverse",
     "nann_search_all_model_diverse_workspace_bytes", "nann_search_all_model_diverse",
+    "nann_predicate_topk", "nann_predicate_count", "nann_search_where_workspace_bytes", "nann_search_where",
+    "nann_search_model_where_workspace_bytes", "nann_search_model_where",
+    "nann_search_all_where_workspace_bytes", "nann_search_all_where",
+    "nann_search_all_model_where_workspace_bytes", "nann_search_all_model_where",
     "nann_merge_topk", "nann_merge_topk_host",
     "nann_attn_scorer_create", "nann_attn_scorer_destroy", "nann_attn_prepare", "nann_attn_score",
     "nann_blaze_options_parse", "nann_model_load", "nann_model_destroy", "nann_model_kind", "nann_model_scorer", "nann_model_workspace_bytes", "nann_model_forward",
@@ -91,6 +95,15 @@ class Filter(C.Structure):
 class Groups(C.Structure):
     """nann_groups: the group of every row and the cap -- one for the call, or one per query (device pointers, borrowed per call)"""
     _fields_ = [("struct_bytes", C.c_int32), ("group_of_row", C.c_void_p), ("cap", C.c_int32), ("caps", C.c_void_p)]
+
+
+class Predicates(C.Structure):
+    """nann_predicates: the attribute columns of the rows and the per-query label / range / tag conditions (device pointers,
+    borrowed per call)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("label_of_row", C.c_void_p), ("value_of_row", C.c_void_p),
+                ("tags_of_row", C.c_void_p), ("label_splits", C.c_void_p), ("labels", C.c_void_p), ("n_labels", C.c_int64),
+                ("value_lo", C.c_void_p), ("value_hi", C.c_void_p), ("tags_all", C.c_void_p), ("tags_any", C.c_void_p),
+                ("tags_none", C.c_void_p)]
 
 
 class Diversity(C.Structure):
@@ -249,6 +262,32 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + \
                           [C.c_int64, C.POINTER(SearchOptions), C.POINTER(Filter), C.POINTER(Diversity), C.c_void_p, C.c_void_p]
+            fn.restype = C.c_int
+            wb = getattr(L, name + "_workspace_bytes")
+            wb.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+            wb.restype = C.c_int
+        # the predicate forms: (scores, rows, n_valid, n_queries, k_in, n_items, item_ids, predicates, filter, k, out_index,
+        #  out_scores, out_item_ids, out_pos, n_out, stream) / (n_items, predicates, filter, n_queries, out_counts, stream)
+        L.nann_predicate_topk.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(Predicates),
+                                                             C.POINTER(Filter), C.c_int32] + [C.c_void_p] * 6
+        L.nann_predicate_topk.restype = C.c_int
+        L.nann_predicate_count.argtypes = [C.c_int64, C.POINTER(Predicates), C.POINTER(Filter), C.c_int64, C.c_void_p, C.c_void_p]
+        L.nann_predicate_count.restype = C.c_int
+        # the filtered traversal's list with (filter, predicates, k, n_out, stream) in the place of (filter, k, n_out, stream)
+        wtail = [C.POINTER(SearchOptions), C.POINTER(SearchPlan), C.POINTER(Filter), C.POINTER(Predicates), C.c_int32, C.c_void_p,
+                 C.c_void_p]
+        L.nann_search_where.argtypes = head + [C.c_void_p] + wtail
+        L.nann_search_where.restype = C.c_int
+        L.nann_search_model_where.argtypes = head + wtail
+        L.nann_search_model_where.restype = C.c_int
+        L.nann_search_where_workspace_bytes.argtypes = list(L.nann_search_filtered_workspace_bytes.argtypes)
+        L.nann_search_where_workspace_bytes.restype = C.c_int
+        L.nann_search_model_where_workspace_bytes.argtypes = list(L.nann_search_model_filtered_workspace_bytes.argtypes)
+        L.nann_search_model_where_workspace_bytes.restype = C.c_int
+        # the filtered exhaustive search's list with (filter, predicates, n_out, stream) in the place of (filter, n_out, stream)
+        for name, twin in (("nann_search_all_where", L.nann_search_all), ("nann_search_all_model_where", L.nann_search_all_model)):
+            fn = getattr(L, name)
+            fn.argtypes = twin.argtypes[:-1] + [C.POINTER(Filter), C.POINTER(Predicates), C.c_void_p, C.c_void_p]
             fn.restype = C.c_int
             wb = getattr(L, name + "_workspace_bytes")
             wb.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]

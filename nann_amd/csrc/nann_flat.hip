@@ -6,7 +6,9 @@
 // over a user's interest vectors (nann_search_all_multi); the group cap on its own (nann_group_cap_topk; kernel in
 // nann_groupcap.h) and behind the filtered exhaustive search at a fetch width (nann_search_all_grouped, nann_search_all_model_grouped);
 // the MMR re-ranking on its own (nann_mmr_topk; kernel in nann_mmr.h) and behind the same search (nann_search_all_diverse,
-// nann_search_all_model_diverse).
+// nann_search_all_model_diverse); the attribute predicates on their own (nann_predicate_topk, nann_predicate_count; kernels in
+// nann_predicate.h) and inside the filtered exhaustive search (nann_search_all_where, nann_search_all_model_where).
+// resolve_predicates is defined here; the traversal's _where forms (nann_traverse.hip) use it too.
 //
 // Compiled into nann_core.o behind nann_hip.hip, as ONE translation unit with it (build.py writes the wrapper), on the terms
 // nann_comm.hip lives there: this file uses nann_hip.hip's file-scope types and helpers directly -- nann_index, nann_scorer,
@@ -141,6 +143,33 @@ static int resolve_filter(const nann_filter* f, const nann_index* ix, FilterArgs
   return resolve_filter_rows(f, (long long)ix->desc.n_items, out);
 }
 
+// the caller's nann_predicates as the kernels take it (nann_predicate.h); NULL holds no condition.  Touches nothing but the struct.
+static int resolve_predicates(const nann_predicates* p, PredArgs* out) {
+  *out = PredArgs{};
+  if (!p) return NANN_OK;
+  if (p->struct_bytes != 0 && p->struct_bytes != (int32_t)sizeof(nann_predicates)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_predicates: struct_bytes");
+  if (p->n_labels < 0) return fail(NANN_ERR_BAD_ARGUMENT, "nann_predicates: n_labels < 0");
+  if (p->label_splits && p->n_labels > 0 && !p->labels) return fail(NANN_ERR_BAD_ARGUMENT, "nann_predicates: label_splits without labels");
+  if (p->label_splits && !p->label_of_row) return fail(NANN_ERR_BAD_ARGUMENT, "nann_predicates: label_splits without label_of_row");
+  if ((p->value_lo || p->value_hi) && !p->value_of_row) return fail(NANN_ERR_BAD_ARGUMENT, "nann_predicates: value bounds without value_of_row");
+  if ((p->tags_all || p->tags_any || p->tags_none) && !p->tags_of_row)
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_predicates: tag conditions without tags_of_row");
+  out->label_of_row = p->label_of_row;
+  out->value_of_row = p->value_of_row;
+  out->tags_of_row = reinterpret_cast<const unsigned long long*>(p->tags_of_row);
+  if (p->label_splits && p->n_labels > 0) {
+    out->label_splits = p->label_splits;
+    out->labels = p->labels;
+    out->n_labels = (long long)p->n_labels;
+  }
+  out->value_lo = p->value_lo;
+  out->value_hi = p->value_hi;
+  out->tags_all = reinterpret_cast<const unsigned long long*>(p->tags_all);
+  out->tags_any = reinterpret_cast<const unsigned long long*>(p->tags_any);
+  out->tags_none = reinterpret_cast<const unsigned long long*>(p->tags_none);
+  return NANN_OK;
+}
+
 // the caller's nann_groups into the launch arguments of the cap (nann_groupcap.h).  `who`: the entry point in a message.
 static int resolve_groups(const nann_groups* g, const char* who, GroupCapArgs* a) {
   if (!g) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null nann_groups");
@@ -241,7 +270,7 @@ static int flat_all_size(const nann_index* ix, const nann_scorer* scorer, const 
 static int flat_all(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, const void* x, int64_t n, int32_t k,
                     int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace, int64_t workspace_bytes,
                     const nann_search_options* options, bool filtered, const nann_filter* filter, int32_t* n_out,
-                    nann_stream_t stream, const char* who) {
+                    nann_stream_t stream, const char* who, const PredArgs* pred = nullptr) {  // pred: a filtered call's predicates
   FlatBy by;
   int rc = flat_check(ix, scorer, m, n, k, false, 0, who, &by);
   if (rc) return rc;
@@ -249,7 +278,7 @@ static int flat_all(const nann_index* ix, const nann_scorer* scorer, const nann_
   if (!x || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
   ScanLayout L;
   const size_t need = flat_all_bytes(ix, by, n, k, filtered, &L);
-  const char* form = filtered ? "_filtered" : "";
+  const char* form = pred ? "_where" : filtered ? "_filtered" : "";
   // a model form looks at its workspace before its options, a scorer form at its options and its filter first
   if (m) {
     rc = flat_workspace(workspace, workspace_bytes, need, who, form);
@@ -259,7 +288,7 @@ static int flat_all(const nann_index* ix, const nann_scorer* scorer, const nann_
       rc = flat_stage_mean(by, x, n, &q, &workspace, &workspace_bytes, stream);
       if (rc) return rc;
       return flat_all(ix, by.scorer, nullptr, q, n, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
-                      filtered, filter, n_out, stream, "nann_search_all");
+                      filtered, filter, n_out, stream, "nann_search_all", pred);
     }
   }
   rc = check_options(options);
@@ -288,6 +317,7 @@ static int flat_all(const nann_index* ix, const nann_scorer* scorer, const nann_
   if (filtered) {  // the staging area of the final selection lies behind the unfiltered workspace
     sf.stage = static_cast<unsigned char*>(workspace) + L.total;
     sf.n_out = n_out;
+    sf.pred = pred;
     a.filter = &sf;
   }
   flat_rows_of(ix, &a);
@@ -876,6 +906,87 @@ int nann_search_all_filtered(const nann_index* ix, const nann_scorer* scorer, co
                              int32_t* n_out, nann_stream_t stream) {
   return flat_all(ix, scorer, nullptr, q, n_queries, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
                   true, filter, n_out, stream, "nann_search_all");
+}
+
+// ---- attribute predicates (nann_predicate.h): the filtered forms with the predicates resolved in front of everything else
+int nann_search_all_where_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k,
+                                          int64_t* nbytes) {
+  return flat_all_size(ix, scorer, nullptr, n_queries, k, true, nbytes, "nann_search_all_workspace_bytes");
+}
+int nann_search_all_where(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
+                          int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                          const nann_predicates* predicates, int32_t* n_out, nann_stream_t stream) {
+  PredArgs pa;
+  const int rc = resolve_predicates(predicates, &pa);
+  if (rc) return rc;
+  return flat_all(ix, scorer, nullptr, q, n_queries, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes, options,
+                  true, filter, n_out, stream, "nann_search_all", &pa);
+}
+int nann_search_all_model_where_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k,
+                                                int64_t* nbytes) {
+  return flat_all_size(ix, nullptr, m, n_users, k, true, nbytes, "nann_search_all_model_workspace_bytes");
+}
+int nann_search_all_model_where(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users,
+                                int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, void* workspace,
+                                int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                                const nann_predicates* predicates, int32_t* n_out, nann_stream_t stream) {
+  PredArgs pa;
+  const int rc = resolve_predicates(predicates, &pa);
+  if (rc) return rc;
+  return flat_all(ix, nullptr, m, comm_seq_f16, n_users, k, out_item_ids, out_scores, out_index, workspace, workspace_bytes,
+                  options, true, filter, n_out, stream, "nann_search_all_model", &pa);
+}
+
+int nann_predicate_topk(const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_queries, int32_t k_in,
+                        int64_t n_items, const int64_t* item_ids, const nann_predicates* predicates, const nann_filter* filter,
+                        int32_t k, int32_t* out_index, float* out_scores, int64_t* out_item_ids, int32_t* out_pos, int32_t* n_out,
+                        nann_stream_t stream) {
+  const char* who = "nann_predicate_topk";
+  if (n_queries < 0 || k_in < 0 || n_items < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": negative size");
+  if (k < 0) return flat_bad_k(k);
+  if (k > k_in) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k exceeds the k_in entries a query brings");
+  if (k_in > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k_in <= 1024");
+  if (n_queries > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many queries in one call");
+  if (n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  PredCompactArgs a = {};
+  int rc = resolve_predicates(predicates, &a.p);
+  if (rc) return rc;
+  if (n_queries == 0 || k == 0) return NANN_OK;
+  if (!rows || !out_index) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (out_item_ids && !item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": out_item_ids without item_ids");
+  rc = resolve_filter_rows(filter, (long long)n_items, &a.f);
+  if (rc) return rc;
+  a.in_rows = rows;
+  a.in_scores = scores;
+  a.in_stride = a.n_in = k_in;
+  a.n_valid = n_valid;
+  a.nv_stride = 1;
+  a.k = k;
+  a.item_ids = item_ids;
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_item_ids = out_item_ids;
+  a.out_pos = out_pos;
+  a.n_out = n_out;
+  return launch_pred_compact(a, (long long)n_queries, as_stream(stream));
+}
+
+int nann_predicate_count(int64_t n_items, const nann_predicates* predicates, const nann_filter* filter, int64_t n_queries,
+                         int64_t* out_counts, nann_stream_t stream) {
+  const char* who = "nann_predicate_count";
+  if (n_queries < 0 || n_items < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": negative size");
+  if (n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  PredArgs pa;
+  int rc = resolve_predicates(predicates, &pa);
+  if (rc) return rc;
+  FilterArgs fa;
+  rc = resolve_filter_rows(filter, (long long)n_items, &fa);
+  if (rc) return rc;
+  if (n_queries == 0) return NANN_OK;
+  if (!out_counts) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  static_assert(sizeof(long long) == sizeof(int64_t), "the counts are 64-bit");
+  return launch_pred_count(fa, pa, (long long)n_queries, reinterpret_cast<long long*>(out_counts), as_stream(stream));
 }
 
 int nann_search_all_model_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, int64_t* nbytes) {

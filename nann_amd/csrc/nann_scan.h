@@ -29,6 +29,7 @@
 #include <cstddef>
 
 #include "nann_filter.h"
+#include "nann_predicate.h"
 #include "nann_range.h"
 #include "nann_search.h"
 
@@ -40,6 +41,8 @@ struct ScanFilter {
   FilterArgs f;
   unsigned char* stage;
   int32_t* n_out;  // i32[n_queries] or null
+  const PredArgs* pred;  // null: none.  Else the attribute predicates of the call (nann_predicate.h): k_pred_scatter behind the
+                         // filter's scatters, and k_pred_compact in the place of k_filter_compact
 };
 inline size_t scan_filter_stage_bytes(int chunk, int k) { return ((size_t)chunk * k * 16 + 255) & ~(size_t)255; }
 

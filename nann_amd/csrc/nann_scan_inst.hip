@@ -128,6 +128,8 @@ int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long lon
     if (a.filter) {  // the denied rows of this chunk leave the selection: exclusion lists go by the call's query number c0 + i
       rc = launch_filter_scatter(a.filter->f, scores, c0, n_q, st);
       if (rc) return rc;
+      if (a.filter->pred) rc = launch_pred_scatter(*a.filter->pred, scores, a.n_items, c0, n_q, st);  // ... and the rows that fail its predicates
+      if (rc) return rc;
     }
     if (a.range) {  // every row at or above the cut, not the best k: the ragged outputs are addressed by the call's row_splits
       rc = launch_range(*a.range, scores, a.n_items, c0, n_q, a.item_ids, out_item_ids, out_scores, out_index, st);
@@ -146,6 +148,25 @@ int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long lon
       hipLaunchKernelGGL(k_scan_merge, dim3((unsigned)n_q), dim3(kNT), 0, st, cand_scores, cand_rows, L.n_slabs * k, k, a.item_ids,
                          s_ids, s_scores, s_rows);
       NANN_HIP_TRY(hipGetLastError());
+      // (the shape both compactions hold their launch to, 0 <= k <= kMaxK, is flat_check's: it stood before the first chunk was scored)
+      if (a.filter->pred) {  // (a query with fewer than k passing rows has failing ones, at -inf, in its list as well)
+        PredCompactArgs pc = {};
+        pc.f = a.filter->f;
+        pc.p = *a.filter->pred;
+        pc.in_rows = s_rows;
+        pc.in_scores = s_scores;
+        pc.in_stride = pc.n_in = k;
+        pc.q0 = c0;
+        pc.k = k;
+        pc.item_ids = a.item_ids;
+        pc.out_item_ids = out_item_ids + (size_t)c0 * k;
+        pc.out_scores = out_scores ? out_scores + (size_t)c0 * k : nullptr;
+        pc.out_index = out_index ? out_index + (size_t)c0 * k : nullptr;
+        pc.n_out = a.filter->n_out ? a.filter->n_out + c0 : nullptr;
+        rc = launch_pred_compact(pc, n_q, st);
+        if (rc) return rc;
+        continue;
+      }
       rc = launch_filter_compact(a.filter->f, s_rows, s_scores, k, k, nullptr, nullptr, c0, n_q, k, a.item_ids,
                                  out_item_ids + (size_t)c0 * k, out_scores ? out_scores + (size_t)c0 * k : nullptr,
                                  out_index ? out_index + (size_t)c0 * k : nullptr, a.filter->n_out ? a.filter->n_out + c0 : nullptr, st);

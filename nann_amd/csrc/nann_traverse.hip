@@ -1,12 +1,13 @@
 // nann_traverse.hip -- the host side of the calls that walk the graph: the serving traversal (nann_search_opt,
 // nann_search_model_opt and their five deprecated spellings, nann_search_filtered, nann_search_model_filtered, nann_search_multi,
-// nann_search_grouped, nann_search_model_grouped, nann_search_diverse, nann_search_model_diverse;
+// nann_search_grouped, nann_search_model_grouped, nann_search_diverse, nann_search_model_diverse, nann_search_where,
+// nann_search_model_where;
 // kernels in nann_search.h), the evaluation traversal (nann_search_eval, nann_search_eval_ex, nann_search_eval_model; nann_eval.h), each
 // with its *_workspace_bytes, and what nann_index_create measures for them: the probe and the pivots of the batch order.
 //
 // Compiled into nann_core.o behind nann_hip.hip and nann_flat.hip, as ONE translation unit with them (build.py writes the
 // wrapper), on the terms nann_flat.hip lives there: this file uses nann_hip.hip's file-scope types and helpers directly and
-// nann_flat.hip's resolve_filter, and no header stands between them.  nann_index_create calls probe_index and choose_pivots
+// nann_flat.hip's resolve_filter and resolve_predicates, and no header stands between them.  nann_index_create calls probe_index and choose_pivots
 // through declarations.
 //
 // Every entry point is one walk -- traverse, traverse_filtered around it, evaluate -- over the steps below, each written once:
@@ -26,6 +27,7 @@
 #include "nann_eval.h"
 #include "nann_order_kernels.h"
 #include "nann_filter.h"
+#include "nann_predicate.h"
 #include "nann_union.h"
 #include "nann_groupcap.h"
 #include "nann_mmr.h"
@@ -726,7 +728,7 @@ static int traverse_filtered(const nann_index* ix, const nann_scorer* scorer, co
                              int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status,
                              int32_t* counters, int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
                              const nann_filter* filter, int32_t k, int32_t* n_out, nann_stream_t stream, const char* who,
-                             const char* inner_who) {
+                             const char* inner_who, const PredArgs* pred = nullptr) {  // pred: a _where form's predicates, resolved
   if (traverse_null(ix, scorer, m, model, x, level_topn_max, out_item_ids, status, workspace))
     return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
   const int f = level_topn_max[5];
@@ -747,6 +749,26 @@ static int traverse_filtered(const nann_index* ix, const nann_scorer* scorer, co
   rc = traverse(ix, scorer, m, model, x, n_queries, level_topn_max, level_topn, workspace, b.inner, s_ids, s_scores, s_rows, status,
                 counters, phase_ticks, options, plan, stream, inner_who);
   if (rc) return rc;
+  // (the shape both compactions hold their launch to stands since before the inner search: 0 <= k <= f above, and plan_search
+  // refuses a level_topn entry beyond kMaxK before the inner search launches anything)
+  if (pred) {  // k_pred_compact in the place of k_filter_compact: a query's own level_topn[5] entries, none when it failed
+    PredCompactArgs pc = {};
+    pc.f = fa;
+    pc.p = *pred;
+    pc.in_rows = s_rows;
+    pc.in_scores = s_scores;
+    pc.in_stride = pc.n_in = f;
+    pc.n_valid = level_topn ? level_topn + 5 : nullptr;
+    pc.nv_stride = 6;
+    pc.status = status;
+    pc.k = k;
+    pc.item_ids = ix->desc.item_ids;
+    pc.out_item_ids = out_item_ids;
+    pc.out_scores = out_scores;
+    pc.out_index = out_index;
+    pc.n_out = n_out;
+    return launch_pred_compact(pc, (long long)n_queries, as_stream(stream));
+  }
   return launch_filter_compact(fa, s_rows, s_scores, f, f, level_topn, status, 0, n_queries, k, ix->desc.item_ids, out_item_ids,
                                out_scores, out_index, n_out, as_stream(stream));
 }
@@ -1098,6 +1120,42 @@ int nann_search_model_filtered(const nann_index* ix, const nann_model* m, const 
   return traverse_filtered(ix, nullptr, m, true, comm_seq_f16, n_queries, level_topn_max, level_topn, workspace, workspace_bytes,
                            out_item_ids, out_scores, out_index, status, counters, nullptr, options, plan, filter, k, n_out, stream,
                            "nann_search_model_filtered", "nann_search_model");
+}
+
+
+// the filtered traversal plus the attribute predicates (nann_predicate.h): the workspace is the filtered call's
+int nann_search_where_workspace_bytes(const nann_index* ix, const int32_t level_topn[6], int64_t n_queries, int64_t* nbytes) {
+  return traverse_size(ix, nullptr, false, level_topn, n_queries, true, nbytes);
+}
+int nann_search_where(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                      const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
+                      int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* status, int32_t* counters,
+                      int64_t* phase_ticks, const nann_search_options* options, nann_search_plan* plan,
+                      const nann_filter* filter, const nann_predicates* predicates, int32_t k, int32_t* n_out,
+                      nann_stream_t stream) {
+  PredArgs pa;  // (the predicates in front of everything else of the call, its handles and an empty batch included)
+  const int rc = resolve_predicates(predicates, &pa);
+  if (rc) return rc;
+  return traverse_filtered(ix, scorer, nullptr, false, q, n_queries, level_topn_max, level_topn, workspace, workspace_bytes,
+                           out_item_ids, out_scores, out_index, status, counters, phase_ticks, options, plan, filter, k, n_out, stream,
+                           "nann_search_where", "nann_search_opt", &pa);
+}
+int nann_search_model_where_workspace_bytes(const nann_index* ix, const nann_model* m, const int32_t level_topn[6],
+                                            int64_t n_queries, int64_t* nbytes) {
+  return traverse_size(ix, m, true, level_topn, n_queries, true, nbytes);
+}
+int nann_search_model_where(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_queries,
+                            const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                            int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                            int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan,
+                            const nann_filter* filter, const nann_predicates* predicates, int32_t k, int32_t* n_out,
+                            nann_stream_t stream) {
+  PredArgs pa;
+  const int rc = resolve_predicates(predicates, &pa);
+  if (rc) return rc;
+  return traverse_filtered(ix, nullptr, m, true, comm_seq_f16, n_queries, level_topn_max, level_topn, workspace, workspace_bytes,
+                           out_item_ids, out_scores, out_index, status, counters, nullptr, options, plan, filter, k, n_out, stream,
+                           "nann_search_model_where", "nann_search_model", &pa);
 }
 
 }  // extern "C"

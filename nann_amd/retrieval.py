@@ -337,12 +337,13 @@ _TRAVERSE_CALLS = {(False, False): (None, "nann_search_opt"), (True, False): ("n
                    (True, True): ("nann_search_model_filtered_workspace_bytes", "nann_search_model_filtered")}
 
 
-def _traverse(index, by, x, model, level_topn, want_counters, want_phase_ticks, options, filter, k):
+def _traverse(index, by, x, model, level_topn, want_counters, want_phase_ticks, options, filter, k, predicates=None):
     """The traversal family's call (_TRAVERSE_CALLS) for the b rows of x -- queries of a scorer `by`, sequences of a model one; with
-    a filter or a k the _filtered twin -- into fresh outputs and a workspace of the size its _workspace_bytes twin gives."""
+    a filter or a k the _filtered twin, with predicates the _where one -- into fresh outputs and a workspace of the size its
+    _workspace_bytes twin gives."""
     dev, b = index.device, x.shape[0]
     t, tq, k_fetch = _level_topn_args(level_topn, b, dev)
-    filtered = filter is not None or k is not None
+    filtered = filter is not None or k is not None or predicates is not None
     k = int(k) if filtered and k is not None else k_fetch
     kk = max(k, 0) if filtered else k
     out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
@@ -354,6 +355,8 @@ def _traverse(index, by, x, model, level_topn, want_counters, want_phase_ticks, 
     ticks = torch.zeros((b, _lib.NUM_PHASES), dtype=torch.int64, device=dev) if want_phase_ticks else None
     assert not (want_phase_ticks and tq is not None), "phase ticks: uniform level_topn only"
     L, (size_call, search_call) = lib(), _TRAVERSE_CALLS[model, filtered]
+    if predicates is not None:
+        size_call, search_call = size_call.replace("_filtered", "_where"), search_call.replace("_filtered", "_where")
     if size_call is None:
         ws = index.workspace(list(t), b)
     else:
@@ -364,6 +367,8 @@ def _traverse(index, by, x, model, level_topn, want_counters, want_phase_ticks, 
     plan = _lib.SearchPlan()
     ticks_arg = () if model else (_ptr(ticks),)  # the model forms have no phase ticks
     filter_args = (_filter_args(filter, b, index), k, _ptr(n_out)) if filtered else ()  # what the filtered forms end on
+    if predicates is not None:
+        filter_args = (filter_args[0], _predicates_args(predicates, b, int(index.n_items), dev)) + filter_args[1:]
     with torch.cuda.device(dev):
         _check(getattr(L, search_call)(index.handle, by.handle, _ptr(x), C.c_int64(b), t, _ptr(tq), _ptr(ws), C.c_int64(ws.numel()),
                                        _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(status), _ptr(counters), *ticks_arg,
@@ -410,9 +415,10 @@ def search_all(index, scorer, q, k, options=None, filter=None):
     return _flat_all(index, handle, q, k, options, filter, "nann_search_all", "search_all")
 
 
-def _flat_all(index, handle, x, k, options, filter, symbol, what):
-    """The exhaustive family's call: `symbol` (with _filtered under a filter) for the b rows of x -- the queries of a scorer
-    `handle`, the sequences of a model one -- into fresh outputs and a workspace of the size its _workspace_bytes twin gives."""
+def _flat_all(index, handle, x, k, options, filter, symbol, what, predicates=None):
+    """The exhaustive family's call: `symbol` (with _filtered under a filter, _where under predicates) for the b rows of x -- the
+    queries of a scorer `handle`, the sequences of a model one -- into fresh outputs and a workspace of the size its
+    _workspace_bytes twin gives."""
     dev = index.device
     b, k = x.shape[0], int(k)
     kk = max(k, 0)
@@ -420,7 +426,10 @@ def _flat_all(index, handle, x, k, options, filter, symbol, what):
     out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
     out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
     n_out = None
-    if filter is not None:
+    if predicates is not None:
+        symbol += "_where"
+        n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+    elif filter is not None:
         symbol += "_filtered"
         n_out = torch.zeros(b, dtype=torch.int32, device=dev)
     nbytes = C.c_int64(0)
@@ -428,6 +437,8 @@ def _flat_all(index, handle, x, k, options, filter, symbol, what):
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         tail = (_filter_args(filter, b, index), _ptr(n_out)) if filter is not None else ()
+        if predicates is not None:
+            tail = (_filter_args(filter, b, index), _predicates_args(predicates, b, int(index.n_items), dev), _ptr(n_out))
         _check(getattr(lib(), symbol)(index.handle, handle, _ptr(x), b, k, _ptr(out_ids), _ptr(out_scores), _ptr(out_index),
                                       _ptr(ws), ws.numel(), C.byref(options) if options is not None else None, *tail, _stream()),
                what)
@@ -1111,6 +1122,238 @@ def _flat_all_diverse(index, by, handle, x, k, diversity, fetch, filter, options
                                       C.byref(options) if options is not None else None, _filter_args(filter, b, index), dv,
                                       _ptr(n_out), _stream()), what)
     return DiverseResult(out_ids, out_scores, out_index, out_mmr, out_pos, n_out, ws=(ws, keep))
+
+
+class Attributes:
+    """What make_attributes returns: the attribute columns of an index's rows, each [n_items] or None (they may live on the CPU).
+      label_of_row  i32: one label per row (a category, a region)
+      value_of_row  f32: one number per row (a price); NaN passes no range
+      tags_of_row   i64, read as u64: a set of up to 64 tags, bit t = tag t"""
+    __slots__ = ("label_of_row", "value_of_row", "tags_of_row", "n_items", "device")
+
+    def __init__(self, label_of_row, value_of_row, tags_of_row, n_items, device):
+        self.label_of_row, self.value_of_row, self.tags_of_row = label_of_row, value_of_row, tags_of_row
+        self.n_items, self.device = n_items, device
+
+
+def _u64_as_i64(a):
+    """tag words (ints, numpy uint64 / int64, an int64 tensor) as an int64 tensor of the same bits"""
+    if isinstance(a, torch.Tensor):
+        return a.cpu().to(torch.int64).reshape(-1)
+    if not (isinstance(a, np.ndarray) and a.dtype == np.uint64):  # (python ints one by one: numpy would read 2^64 - 1 next to 0 as a float)
+        flat = a.reshape(-1).tolist() if isinstance(a, np.ndarray) else list(np.asarray(a, dtype=object).reshape(-1))
+        a = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in flat], dtype=np.uint64)
+    return torch.from_numpy(np.ascontiguousarray(a.reshape(-1)).view(np.int64).copy())
+
+
+def make_attributes(index, label_of_row=None, value_of_row=None, tags_of_row=None, label_of_item_id=None, value_of_item_id=None,
+                    tags_of_item_id=None, device=None):
+    """The attribute columns of `index` for predicate searches, built once per index.  *_of_row: one entry per internal row,
+    [n_items]; or *_of_item_id = (item_ids, values), two 1-D arrays of one length, mapped through index.item_ids -- an unknown id
+    names nothing, and an item that is not named gets label -1, value NaN (which passes no range) and no tag.  Tags are int64
+    tensors (or uint64 arrays) read as 64 bits.  device: where the tensors live (default: the index's; "cpu" builds them
+    without a GPU).  -> Attributes."""
+    dev = torch.device(device if device is not None else index.device)
+    n = int(index.n_items)
+
+    def column(of_row, of_item_id, conv, dtype, missing, name):
+        assert of_row is None or of_item_id is None, "%s: one of %s_of_row and %s_of_item_id" % (name, name, name)
+        if of_row is not None:
+            c = conv(of_row)
+            assert c.numel() == n, "%s_of_row: one entry per row of the index" % name
+            return c.to(dtype).to(dev).contiguous()
+        if of_item_id is None:
+            return None
+        ids, vals = _i64(of_item_id[0]), conv(of_item_id[1])
+        assert ids.numel() == vals.numel(), "%s_of_item_id: (item_ids, values) of one length" % name
+        c = torch.full((n,), missing, dtype=dtype)
+        sv, perm = _sorted_item_ids(index)
+        if sv.numel() and ids.numel():
+            pos = torch.searchsorted(sv, ids.to(sv.device)).clamp_(max=sv.numel() - 1)
+            found = (sv[pos] == ids.to(sv.device)).cpu()
+            c[perm[pos].cpu()[found]] = vals.to(dtype)[found]
+        return c.to(dev).contiguous()
+
+    def f32(a):
+        return torch.as_tensor(np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float32)).reshape(-1)
+
+    def i32(a):
+        a = _i64(a)
+        assert a.numel() == 0 or (int(a.min()) >= -(1 << 31) and int(a.max()) < (1 << 31)), "labels are 32-bit"
+        return a
+
+    return Attributes(column(label_of_row, label_of_item_id, i32, torch.int32, -1, "label"),
+                      column(value_of_row, value_of_item_id, f32, torch.float32, float("nan"), "value"),
+                      column(tags_of_row, tags_of_item_id, _u64_as_i64, torch.int64, 0, "tags"), n, dev)
+
+
+class Predicates:
+    """What make_predicates returns: the per-query conditions of one batch over an Attributes (tensors on its device) and the
+    ctypes nann_predicates, which borrows their memory and the attribute columns'.
+      label_splits i64[n_queries + 1], labels i32[n_labels]: query i allows labels[label_splits[i] : label_splits[i + 1]]
+      value_lo, value_hi f32[n_queries];  tags_all, tags_any, tags_none i64[n_queries] read as u64 -- each or None"""
+    __slots__ = ("attributes", "label_splits", "labels", "value_lo", "value_hi", "tags_all", "tags_any", "tags_none", "n_queries",
+                 "n_items", "device", "struct")
+
+    def __init__(self, attributes, n_queries, label_splits, labels, value_lo, value_hi, tags_all, tags_any, tags_none):
+        self.attributes, self.n_queries, self.n_items, self.device = attributes, int(n_queries), attributes.n_items, attributes.device
+        self.label_splits, self.labels, self.value_lo, self.value_hi = label_splits, labels, value_lo, value_hi
+        self.tags_all, self.tags_any, self.tags_none = tags_all, tags_any, tags_none
+        st = _lib.Predicates()
+        st.struct_bytes = C.sizeof(_lib.Predicates)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None and t.numel() else None
+        st.label_of_row, st.value_of_row, st.tags_of_row = (ptr(attributes.label_of_row), ptr(attributes.value_of_row),
+                                                             ptr(attributes.tags_of_row))
+        st.label_splits = label_splits.data_ptr() if label_splits is not None else None
+        st.labels = ptr(labels)
+        st.n_labels = int(labels.numel()) if labels is not None else 0
+        st.value_lo, st.value_hi = ptr(value_lo), ptr(value_hi)
+        st.tags_all, st.tags_any, st.tags_none = ptr(tags_all), ptr(tags_any), ptr(tags_none)
+        self.struct = st
+
+
+def make_predicates(attributes, n_queries, label_in=None, value_range=None, tags_all=None, tags_any=None, tags_none=None):
+    """The per-query conditions of a batch of n_queries over `attributes` (make_attributes), ragged and built per batch.
+      label_in     one 1-D array of allowed labels per query (any order, duplicates, any number); None or an empty array: no
+                   label test for that query
+      value_range  (lo, hi): each None (unbounded), a number for every query, or an array [n_queries]; a row passes iff
+                   lo <= value <= hi, so lo > hi matches nothing and a NaN bound passes nothing
+      tags_all / tags_any / tags_none   a 64-bit word for every query or an array [n_queries]: the row's tags hold every bit of
+                   `all`, at least one of `any` (when it is not 0) and none of `none`
+    A row passes a query iff every test that is given passes.  -> Predicates."""
+    assert isinstance(attributes, Attributes), "attributes: what make_attributes returns"
+    dev, nq = attributes.device, int(n_queries)
+    splits = labels = None
+    if label_in is not None:
+        assert attributes.label_of_row is not None, "label_in needs the attributes' label_of_row"
+        assert len(label_in) == nq, "label_in: one list per query of the batch"
+        per = [_i64(l) if l is not None else torch.zeros(0, dtype=torch.int64) for l in label_in]
+        lens = torch.tensor([0] + [int(p.numel()) for p in per], dtype=torch.int64)
+        splits = torch.cumsum(lens, 0).to(dev).contiguous()
+        flat = torch.cat(per) if per else torch.zeros(0, dtype=torch.int64)
+        assert flat.numel() == 0 or (int(flat.min()) >= -(1 << 31) and int(flat.max()) < (1 << 31)), "labels are 32-bit"
+        labels = flat.to(torch.int32).to(dev).contiguous()
+
+    def per_query(v, conv, dtype):
+        if v is None:
+            return None
+        if isinstance(v, (int, float)):
+            v = [v] * nq
+        t = conv(v).to(dtype)
+        assert t.numel() == nq, "a per-query condition: one entry per query of the batch"
+        return t.to(dev).contiguous()
+
+    def f32(a):
+        return torch.as_tensor(np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float32)).reshape(-1)
+
+    lo = hi = None
+    if value_range is not None:
+        assert attributes.value_of_row is not None, "value_range needs the attributes' value_of_row"
+        lo, hi = per_query(value_range[0], f32, torch.float32), per_query(value_range[1], f32, torch.float32)
+    tags = [per_query(t, _u64_as_i64, torch.int64) for t in (tags_all, tags_any, tags_none)]
+    assert all(t is None for t in tags) or attributes.tags_of_row is not None, "tag conditions need the attributes' tags_of_row"
+    return Predicates(attributes, nq, splits, labels, lo, hi, *tags)
+
+
+def _predicates_args(predicates, b, n_items, dev):
+    """POINTER(nann_predicates) for a batch of b queries over n_items rows on `dev`"""
+    assert isinstance(predicates, Predicates), "predicates: what make_predicates returns"
+    assert n_items is None or predicates.n_items == n_items, "the predicates' attributes were made for another index"
+    assert torch.empty(0, device=predicates.device).device == torch.empty(0, device=dev).device, \
+        "the predicates' tensors must live on the device of the call"
+    assert predicates.n_queries == b, "the predicates: one set of conditions per query of the batch"
+    return C.byref(predicates.struct)
+
+
+class PredicateResult:
+    """Outputs of predicate_topk, [B, k] device tensors: the first k entries of a ranked list that pass, n_out[b] of them at the
+    head of row b and zeros behind.  pos: each entry's position in its input list.  item_ids is None without an index."""
+    __slots__ = ("item_ids", "scores", "index", "pos", "n_out")
+
+    def __init__(self, item_ids, scores, index, pos, n_out):
+        self.item_ids, self.scores, self.index, self.pos, self.n_out = item_ids, scores, index, pos, n_out
+
+
+def predicate_topk(scores, rows, predicates, k, n_valid=None, index=None, filter=None):
+    """The predicate step on its own (nann_predicate_topk): scores f32 / rows i32 [B, k_in] CUDA tensors, a RANKED list per query
+    from anywhere -- union_topk's, search_candidates' output -- of which the first n_valid[b] (i32[B]; None: k_in) entries count.
+    The first k entries whose row passes `predicates` (make_predicates) and `filter` (make_filter) are returned, order unchanged
+    -> PredicateResult (item_ids only with an index).  Its n_out is the n_valid of a cap_groups or mmr behind it.  k_in <= 1024,
+    k <= k_in.  Asynchronous on torch's current stream."""
+    dev = rows.device
+    rows = rows.to(dtype=torch.int32).contiguous()
+    assert rows.dim() == 2, "rows: [n_queries, k_in]"
+    b, k_in = rows.shape
+    if scores is not None:
+        scores = scores.to(device=dev, dtype=torch.float32).contiguous()
+        assert scores.shape == rows.shape, "scores: the shape of rows"
+    if n_valid is not None:
+        n_valid = n_valid.to(device=dev, dtype=torch.int32).contiguous()
+        assert n_valid.shape == (b,), "n_valid: [n_queries]"
+    k = int(k)
+    kk = max(k, 0)
+    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev) if index is not None else None
+    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
+    out_pos = torch.empty((b, kk), dtype=torch.int32, device=dev)
+    n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_predicate_topk(_ptr(scores), _ptr(rows), _ptr(n_valid), b, k_in, predicates.n_items,
+                                         _ptr(index.item_ids) if index is not None else None,
+                                         _predicates_args(predicates, b, int(index.n_items) if index is not None else None, dev),
+                                         _filter_args(filter, b, index) if index is not None else
+                                         (C.byref(filter.struct) if filter is not None else None), k, _ptr(out_index),
+                                         _ptr(out_scores), _ptr(out_ids), _ptr(out_pos), _ptr(n_out), _stream()), "predicate_topk")
+    return PredicateResult(out_ids, out_scores, out_index, out_pos, n_out)
+
+
+def predicate_count(predicates, filter=None):
+    """The selectivity (nann_predicate_count): i64[n_queries] on the device, the rows of the index that pass each query's
+    conditions and `filter`.  With count / n_items = s, a traversal at fetch width F finds about s * F passing rows: where that is
+    well above k, search_where is the call; where it is not, search_all_where.  Asynchronous on torch's current stream."""
+    dev, b = predicates.device, predicates.n_queries
+    out = torch.zeros(b, dtype=torch.int64, device=dev)
+    if filter is not None:
+        assert filter.n_items == predicates.n_items and filter.device == dev, "the filter was made for another index or device"
+        assert filter.n_queries is None or filter.n_queries == b, "the filter's exclusion lists: one per query of the batch"
+    with torch.cuda.device(dev):
+        _check(lib().nann_predicate_count(predicates.n_items, C.byref(predicates.struct),
+                                          C.byref(filter.struct) if filter is not None else None, b, _ptr(out), _stream()),
+               "predicate_count")
+    return out
+
+
+def search_where(index, scorer, q, level_topn, predicates, k=None, filter=None, want_counters=True, options=None):
+    """search() under attribute predicates (nann_search_where): the unchanged traversal at the fetch width F = level_topn[5]
+    (i32[6], or [B, 6] per query), then the first k (default F) entries of its ranked answer whose row passes `predicates`
+    (make_predicates) and `filter` -> SearchResult, n_out[b] entries at the head of row b and zeros behind.  n_out < k: the list
+    was cut short -- widen F, or call search_all_where (predicate_count tells in advance).  A failed query gets n_out = 0."""
+    q = q.to(device=index.device, dtype=torch.float32).contiguous()
+    return _traverse(index, scorer, q, False, level_topn, want_counters, False, options, filter, k, predicates)
+
+
+def search_model_where(index, model, comm_seq, level_topn, predicates, k=None, filter=None, want_counters=True, options=None):
+    """search_model() under attribute predicates (nann_search_model_where): comm_seq f16[B, seq_len, E]; the rest as search_where."""
+    seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
+    return _traverse(index, model, seq, True, level_topn, want_counters, False, options, filter, k, predicates)
+
+
+def search_all_where(index, scorer, q, k, predicates, filter=None, options=None):
+    """Exhaustive search over the rows that PASS (nann_search_all_where): the exact top k of every query's passing rows, TopKV2
+    order -> SearchAllResult with n_out[b] = min(k, passing rows) valid entries at the head of row b and zeros behind; scores
+    have the bits of search_all's.  The ground truth of search_where.  `scorer`: an ops.Scorer with q f32[B, d]."""
+    q = q.to(device=index.device, dtype=torch.float32).contiguous()
+    return _flat_all(index, scorer.handle, q, k, options, filter, "nann_search_all", "search_all_where", predicates)
+
+
+def search_all_model_where(index, model, comm_seq, k, predicates, filter=None, options=None):
+    """search_all_where under a model (nann_search_all_model_where): comm_seq f16[B, seq_len, E], an ops.Model of any kind."""
+    if not isinstance(model, ops.Model):
+        raise TypeError("search_all_model_where: an ops.Model (an ops.Scorer goes through search_all_where)")
+    seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
+    return _flat_all(index, model.handle, seq, k, options, filter, "nann_search_all_model", "search_all_model_where", predicates)
 
 
 def prepare(index, scorer):

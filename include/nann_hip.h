@@ -1150,6 +1150,104 @@ int nann_search_all_model_where(const nann_index* ix, const nann_model* m, const
                                 int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
                                 const nann_predicates* predicates, int32_t* n_out, nann_stream_t stream);
 
+/* ---- fused result lists: reciprocal rank fusion and weighted score fusion ----------------------------------------------------
+ * nann_union_topk keeps each row's BEST score: "any of my interests likes this row".  Hybrid retrieval -- a list from the L2
+ * traversal, one from the attention model, a lexical one from outside, each on its own scale -- and consensus over interest
+ * vectors want a score ACCUMULATED over the lists that contain a row instead.  The reference has no such call; the semantics
+ * below are this library's own.
+ *
+ * nann_fuse_topk is the step on its own: a user brings n_lists lists of k_in (score, row) entries, as for nann_union_topk, whose
+ * arguments these are, plus the fusion and with out_lists in the place of out_list.
+ *   scores       f32[n_users, n_lists, k_in];  rows i32, the same shape (internal row numbers)
+ *   n_valid      i32[n_users, n_lists], or NULL = k_in everywhere
+ *   n_items      rows outside [0, n_items) are dropped;  item_ids device i64[n_items], or NULL
+ *   fusion       required: the mode, the RRF constant and the weights -- device f32[n_lists] for a per-call weight
+ *                (weights_per_user == 0, w = weights[l]) or f32[n_users, n_lists] for a per-user weight (w = weights[u *
+ *                n_lists + l]); NULL means 1.0f.  Weights are used as given: negative and zero weights included, no host read-back
+ *   out_index    i32[n_users, k], required;  out_scores f32 (the fused score), out_item_ids i64 (= item_ids[out_index], needs
+ *                item_ids), out_lists u64 (bit l is set iff list l contains the row: "which retrievers found this"; this is
+ *                why n_lists <= NANN_FUSE_MAX_LISTS = 64), each [n_users, k], n_out i32[n_users] -- each may be NULL
+ *   workspace    device, 256-byte aligned, nann_fuse_topk_workspace_bytes(...) bytes: 24 B per entry
+ * VALIDITY.  Entry p = l * k_in + j of a user is VALID iff j < clamp(n_valid[u][l], 0, k_in) and its row lies in [0, n_items);
+ * no n_valid means k_in; in the search forms a list whose status word is non-zero counts as 0 entries.  Anything else is
+ * dropped; malformed input never faults.
+ * OCCURRENCES AND RANK.  Within one list a row COUNTS ONCE, at its lowest valid j; later entries of the same row in that list
+ * are ignored.  The rank of a counting entry is its position j, whether or not the entries before it are valid.
+ * THE TERM of list l for a row it contains, with s the counting entry's score and w the list's weight.  Every step is a single
+ * f32 operation; there is no FMA contraction:
+ *   NANN_FUSE_SUM        w * s
+ *   NANN_FUSE_SUM_FLOOR  w * (s - lo_l)
+ *   NANN_FUSE_MINMAX     w * ((s - lo_l) / (hi_l - lo_l)); where hi_l == lo_l the quotient is read as 1.0f
+ *   NANN_FUSE_RRF        w / (rrf_c + (float)(j + 1)): one add, one IEEE division
+ * lo_l and hi_l are the least and greatest valid score of list l for this user (every valid entry, counting or not), compared
+ * as TopKV2 compares scores, with -0 read as +0.  In NANN_FUSE_SUM_FLOOR every list is shifted so that its floor is 0, and a
+ * list that does not hold a row then rightly adds nothing: this is what makes a sum of L2 scores usable -- they are negative,
+ * and a missing list must not look better than a present one.  The score returned in that mode is the margin over the floors,
+ * not a sum of the scores.
+ * THE FUSED SCORE starts from +0.0f and takes the terms of the lists that contain the row in ascending l, one f32 add each; a
+ * list that does not contain the row adds nothing.  The order of the additions is fixed, so the result is reproducible bit for bit.
+ * THE ANSWER is TopKV2 over the distinct valid rows, taken in ascending order of each row's lowest valid p: fused score
+ * descending (-0 and +0 tie), ties -> the lower first p.  n_out[u] = min(k, distinct valid rows) entries at the head of row u
+ * of every output, zeros behind.  A user's answer does not depend on the batch it is in.
+ * OUTSIDE THE CONTRACT: NaN scores or weights; +-inf scores under NANN_FUSE_SUM_FLOOR and NANN_FUSE_MINMAX; a sum that meets
+ * +inf and -inf.  Under NANN_FUSE_SUM and NANN_FUSE_RRF -inf is a score like any other.
+ * Limits: n_lists <= NANN_FUSE_MAX_LISTS, n_lists * k_in <= NANN_UNION_MAX_IN, k <= 1024.
+ * Nothing is launched and nothing is written by a refused call.  The refusals are nann_union_topk's, in its order (the sizes
+ * and k, their NANN_ERR_BAD_ARGUMENT before their NANN_ERR_UNSUPPORTED); then n_lists > 64 -> NANN_ERR_UNSUPPORTED; then the
+ * fusion -> NANN_ERR_BAD_ARGUMENT: NULL, a struct_bytes that is neither 0 nor sizeof(nann_fusion), an unknown mode, under
+ * NANN_FUSE_RRF an rrf_c that is not a finite value >= 0, weights_per_user outside {0, 1}; then the early NANN_OK for n_users
+ * == 0 or k == 0; then the null pointers, out_item_ids without item_ids, the workspace's size (NANN_ERR_CAPACITY), its
+ * alignment.  nann_fuse_topk_workspace_bytes leaves *nbytes untouched when it fails.  Asynchronous on `stream`, no host
+ * read-back. */
+#define NANN_FUSE_MAX_LISTS 64
+enum { NANN_FUSE_SUM = 0, NANN_FUSE_SUM_FLOOR = 1, NANN_FUSE_MINMAX = 2, NANN_FUSE_RRF = 3 };
+typedef struct nann_fusion {            /* borrowed for the call, like nann_filter */
+  int32_t struct_bytes;                 /* 0 or sizeof(nann_fusion) */
+  int32_t mode;                         /* NANN_FUSE_SUM | _SUM_FLOOR | _MINMAX | _RRF */
+  float   rrf_c;                        /* RRF only; !(rrf_c >= 0) or inf -> NANN_ERR_BAD_ARGUMENT */
+  int32_t weights_per_user;             /* 0: weights f32[n_lists]; 1: f32[n_users, n_lists] */
+  const float* weights;                 /* device, or NULL = 1.0f */
+} nann_fusion;
+int nann_fuse_topk_workspace_bytes(int64_t n_users, int32_t n_lists, int32_t k_in, int64_t* nbytes);
+int nann_fuse_topk(const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_users, int32_t n_lists,
+                   int32_t k_in, int64_t n_items, const int64_t* item_ids, int32_t k, const nann_fusion* fusion,
+                   int32_t* out_index, float* out_scores, int64_t* out_item_ids, uint64_t* out_lists, int32_t* n_out,
+                   void* workspace, int64_t workspace_bytes, nann_stream_t stream);
+
+/* The traversal form: nann_search_multi with the fuse in the place of the union and out_lists (u64[n_users, k], bit m = vector
+ * m's list holds the row) in the place of out_vec.  The inner search is nann_search_opt, unchanged, over the n_users * n_vec
+ * vectors at the fetch width F = level_topn_max[5]; list l of user u is what vector (u, l) returned, its own level_topn[..][5]
+ * entries.  status is per vector, i32[n_users, n_vec]: a failed vector contributes nothing.  Every scorer nann_search_opt
+ * takes is accepted.  n_vec < 1, k outside [0, n_vec * F], a malformed fusion -> NANN_ERR_BAD_ARGUMENT; n_vec > 64, n_vec * F
+ * > NANN_UNION_MAX_IN or k > 1024 -> NANN_ERR_UNSUPPORTED; these, the null pointers and the workspace are looked at before
+ * anything is launched; n_users == 0 or k == 0 -> NANN_OK behind them, nothing launched and nothing written.
+ * Unlike the union, fusion over truncated lists has no exactness property: a row beyond depth F (here) or `fetch` (below) in a
+ * list loses that list's term, so the depth is the caller's trade-off between cost and how far down a list agreement is still
+ * seen.  A weighted NANN_FUSE_SUM of inner-product scores of several vectors equals ONE query with the weighted sum of the
+ * vectors; the multi forms are for NANN_FUSE_RRF, NANN_FUSE_MINMAX and the MLP scorer.  There are no _model forms, for the
+ * reason the union section gives: a comm_seq is one user sequence. */
+int nann_search_multi_fused_workspace_bytes(const nann_index* ix, const int32_t level_topn[6] /*[host]*/, int64_t n_users,
+                                            int32_t n_vec, int64_t* nbytes);
+int nann_search_multi_fused(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,
+                            const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                            int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                            uint64_t* out_lists, int32_t* n_out, int32_t* status, int32_t* counters,
+                            const nann_search_options* options, nann_search_plan* plan, int32_t k, const nann_fusion* fusion,
+                            nann_stream_t stream);
+
+/* The exhaustive form: nann_search_all over the n_users * n_vec vectors at k = fetch, the per-vector depth, then the fuse of each
+ * user's n_vec lists at k.  k outside [0, n_vec * fetch] -> NANN_ERR_BAD_ARGUMENT; the other checks are nann_search_all's, held
+ * against fetch (fetch > n_items -> NANN_ERR_TOPK_K_GT_N, fetch > 1024 -> NANN_ERR_UNSUPPORTED, ...), and n_vec < 1 or a
+ * malformed fusion -> NANN_ERR_BAD_ARGUMENT, n_vec > 64 or n_vec * fetch > NANN_UNION_MAX_IN -> NANN_ERR_UNSUPPORTED; n_users
+ * == 0 or k == 0 -> NANN_OK, nothing written.  out_item_ids i64[n_users, k] is required; out_scores, out_index, out_lists,
+ * n_out may be NULL.  `fetch` is the caller's trade-off, as above. */
+int nann_search_all_multi_fused_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_users, int32_t n_vec,
+                                                int32_t fetch, int64_t* nbytes);
+int nann_search_all_multi_fused(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,
+                                int32_t fetch, int32_t k, const nann_fusion* fusion, int64_t* out_item_ids, float* out_scores,
+                                int32_t* out_index, uint64_t* out_lists, int32_t* n_out, void* workspace,
+                                int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

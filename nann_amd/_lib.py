@@ -23,6 +23,8 @@ MLP_DEFAULT, MLP_SPLIT_F16, MLP_EXACT_F32, MLP_CERTIFIED = 0, 1, 2, 3
 NUM_ROUNDS = 5
 NUM_PHASES = 19
 UNION_MAX_IN = 8192  # NANN_UNION_MAX_IN: most entries (n_lists * k_in) a user brings to nann_union_topk
+FUSE_MAX_LISTS = 64  # NANN_FUSE_MAX_LISTS: most lists a user brings to nann_fuse_topk (out_lists is one u64 per entry)
+FUSE_SUM, FUSE_SUM_FLOOR, FUSE_MINMAX, FUSE_RRF = 0, 1, 2, 3
 PHASE_NAMES = ("zero", "walk", "expand", "score", "topk", "other", "tk_load", "tk_search",
                "tk_collect", "tk_sort", "ex_pass1", "ex_loop", "ex_walkbusy",
                "ex_lookup", "ex_load", "ex_insert", "ex_bar_a", "ex_check", "ex_rank")
@@ -49,6 +51,8 @@ SYMBOLS = [
     "nann_search_candidates_model_workspace_bytes", "nann_search_candidates_model",
     "nann_union_topk_workspace_bytes", "nann_union_topk", "nann_search_multi_workspace_bytes", "nann_search_multi",
     "nann_search_all_multi_workspace_bytes", "nann_search_all_multi",
+    "nann_fuse_topk_workspace_bytes", "nann_fuse_topk", "nann_search_multi_fused_workspace_bytes", "nann_search_multi_fused",
+    "nann_search_all_multi_fused_workspace_bytes", "nann_search_all_multi_fused",
     "nann_group_cap_topk", "nann_search_grouped_workspace_bytes", "nann_search_grouped",
     "nann_search_model_grouped_workspace_bytes", "nann_search_model_grouped",
     "nann_search_all_grouped_workspace_bytes", "nann_search_all_grouped",
@@ -77,6 +81,12 @@ class SearchOptions(C.Structure):
     """nann_search_options (include/nann_hip.h): -1 = the process default of the field"""
     _fields_ = [("struct_bytes", C.c_int32), ("traversal_mode", C.c_int32), ("slot_reserve", C.c_int32),
                 ("preprojection", C.c_int32), ("mlp_form", C.c_int32)]
+
+
+class Fusion(C.Structure):
+    """nann_fusion: how nann_fuse_topk and the _fused searches turn a row's entries in several lists into one score"""
+    _fields_ = [("struct_bytes", C.c_int32), ("mode", C.c_int32), ("rrf_c", C.c_float), ("weights_per_user", C.c_int32),
+                ("weights", C.c_void_p)]
 
 
 class SearchPlan(C.Structure):
@@ -328,6 +338,28 @@ def lib():
         L.nann_search_all_multi.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + \
                                            [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
         L.nann_search_all_multi.restype = C.c_int
+        # the union's arguments with (fusion) behind k and out_lists u64 in the place of out_list
+        L.nann_fuse_topk_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+        L.nann_fuse_topk_workspace_bytes.restype = C.c_int
+        L.nann_fuse_topk.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
+                                                        C.POINTER(Fusion)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]
+        L.nann_fuse_topk.restype = C.c_int
+        # nann_search_multi's with out_lists in the place of out_vec and (fusion) behind k
+        L.nann_search_multi_fused_workspace_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
+                                                              C.POINTER(C.c_int64)]
+        L.nann_search_multi_fused_workspace_bytes.restype = C.c_int
+        L.nann_search_multi_fused.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
+                                                                 C.c_int64] + [C.c_void_p] * 7 + \
+                                             [C.POINTER(SearchOptions), C.POINTER(SearchPlan), C.c_int32, C.POINTER(Fusion), C.c_void_p]
+        L.nann_search_multi_fused.restype = C.c_int
+        # (ix, scorer, n_users, n_vec, fetch, *nbytes) / (ix, scorer, q, n_users, n_vec, fetch, k, fusion, out_item_ids,
+        #  out_scores, out_index, out_lists, n_out, workspace, workspace_bytes, options, stream)
+        L.nann_search_all_multi_fused_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                                                  C.POINTER(C.c_int64)]
+        L.nann_search_all_multi_fused_workspace_bytes.restype = C.c_int
+        L.nann_search_all_multi_fused.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Fusion)] + \
+                                                 [C.c_void_p] * 6 + [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
+        L.nann_search_all_multi_fused.restype = C.c_int
         # (item_embs, n_old, n_new, d, emb_dtype, M, ef_construction, keep_pruned, levels, adj0, up_row, adj_up, stream)
         L.nann_hnsw_append_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 5
         L.nann_hnsw_append_device.restype = C.c_int

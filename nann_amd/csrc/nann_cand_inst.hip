@@ -2,12 +2,15 @@
 // dtype), the MLP scorer in both precisions and the per-query top-k; workspace layout and the launch sequence of a call.  Also
 // the union top-k (nann_union.h), a per-user selection over wg_topk like k_cand_topk, and its launch; and the MMR re-ranking
 // (nann_mmr.h), a per-query selection over the L2 / inner-product scorer for the (d, row dtype) set of k_cand_score_l2, and its launch.
+// And the fused top-k (nann_fuse.h), the union's sibling with an accumulator per row, and its launch.
 #define NANN_CAND_IMPL
 #define NANN_UNION_IMPL
 #define NANN_MMR_IMPL
+#define NANN_FUSE_IMPL
 #include "nann_cand.h"
 #include "nann_union.h"
 #include "nann_mmr.h"
+#include "nann_fuse.h"
 
 #include <algorithm>
 
@@ -126,6 +129,21 @@ int launch_union_topk(const UnionArgs& a, long long n_users, hipStream_t st) {
     NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_union_topk), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)union_lds_bytes(NANN_UNION_MAX_IN)));
   hipLaunchKernelGGL(k_union_topk, dim3((unsigned)n_users), dim3(kNT), lds, st, a, union_slots_log2(n_in));
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+// ---- the fused top-k (nann_fuse.h) --------------------------------------------------------------------------------------
+size_t fuse_ws_bytes(long long n_users, long long n_in) { return up256((size_t)n_users * (size_t)n_in * kFuseEntryBytes); }
+
+int launch_fuse_topk(const FuseArgs& a, long long n_users, hipStream_t st) {
+  const int n_in = a.n_lists * a.k_in;
+  if (n_users <= 0) return NANN_OK;
+  const size_t lds = fuse_lds_bytes(n_in);
+  if (lds > 64 * 1024)  // (only the sizes beyond the default limit need the opt-in: n_in > 4096)
+    NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fuse_topk), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)fuse_lds_bytes(NANN_UNION_MAX_IN)));
+  hipLaunchKernelGGL(k_fuse_topk, dim3((unsigned)n_users), dim3(kNT), lds, st, a, union_slots_log2(n_in));
   NANN_HIP_TRY(hipGetLastError());
   return NANN_OK;
 }

@@ -3,7 +3,8 @@
 // its range form (nann_search_all_range, nann_search_all_range_model; selection kernels in nann_range.h)
 // and the candidate-list search (nann_search_candidates, nann_search_candidates_model; kernels in nann_cand.h), each with its
 // *_workspace_bytes; the union top-k on its own (nann_union_topk; kernel in nann_union.h) and behind the exhaustive search
-// over a user's interest vectors (nann_search_all_multi); the group cap on its own (nann_group_cap_topk; kernel in
+// over a user's interest vectors (nann_search_all_multi); the fused top-k in the same two places (nann_fuse_topk,
+// nann_search_all_multi_fused; kernel in nann_fuse.h); the group cap on its own (nann_group_cap_topk; kernel in
 // nann_groupcap.h) and behind the filtered exhaustive search at a fetch width (nann_search_all_grouped, nann_search_all_model_grouped);
 // the MMR re-ranking on its own (nann_mmr_topk; kernel in nann_mmr.h) and behind the same search (nann_search_all_diverse,
 // nann_search_all_model_diverse); the attribute predicates on their own (nann_predicate_topk, nann_predicate_count; kernels in
@@ -33,8 +34,11 @@
 #include "nann_scan.h"
 #include "nann_cand.h"
 #include "nann_union.h"
+#include "nann_fuse.h"
 #include "nann_groupcap.h"
 #include "nann_mmr.h"
+
+#include <cfloat>
 
 #include <memory>
 #include <string>
@@ -554,6 +558,93 @@ static int flat_all_multi(const nann_index* ix, const nann_scorer* scorer, const
   return launch_union_topk(a, (long long)n_users, as_stream(stream));
 }
 
+// ---- fused top-k (nann_fuse.h): a user's n_lists result lists -> the k best distinct rows by an accumulated score -------------
+// the shape of a fuse: the union's refusals in their order, then the width of out_lists
+static int fuse_shape_check(int64_t n_users, int64_t n_lists, int64_t k_in, int64_t k, const char* who) {
+  const int rc = union_check(n_users, n_lists, k_in, k, who);
+  if (rc) return rc;
+  if (n_lists > NANN_FUSE_MAX_LISTS) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": at most NANN_FUSE_MAX_LISTS = 64 lists per user");
+  return NANN_OK;
+}
+// the caller's nann_fusion: null, struct_bytes, mode, rrf_c, weights_per_user, in this order.  Nothing of it is dereferenced.
+static int fusion_check(const nann_fusion* f, const char* who) {
+  if (!f) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null fusion");
+  if (f->struct_bytes != 0 && f->struct_bytes != (int32_t)sizeof(nann_fusion)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_fusion: struct_bytes");
+  if (f->mode < NANN_FUSE_SUM || f->mode > NANN_FUSE_RRF) return fail(NANN_ERR_BAD_ARGUMENT, "nann_fusion: unknown mode");
+  if (f->mode == NANN_FUSE_RRF && !(f->rrf_c >= 0.0f && f->rrf_c <= FLT_MAX))
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_fusion: rrf_c must be a finite value >= 0");
+  if (f->weights_per_user != 0 && f->weights_per_user != 1) return fail(NANN_ERR_BAD_ARGUMENT, "nann_fusion: weights_per_user must be 0 or 1");
+  return NANN_OK;
+}
+static void fusion_into(const nann_fusion* f, FuseArgs* a) {
+  a->mode = f->mode;
+  a->rrf_c = f->rrf_c;
+  a->weights = f->weights;
+  a->weights_per_user = f->weights_per_user;
+}
+
+// ---- exhaustive multi-vector search, fused: flat_all over the n_users * n_vec vectors at k = fetch into the staging area of
+// flat_all_multi, then the fuse at k.  workspace: [flat_all's at fetch, rounded up to 256 | the staging area | the fuse's]
+static int flat_all_multi_fused_check(const nann_index* ix, const nann_scorer* scorer, int64_t n_users, int32_t n_vec, int32_t fetch,
+                                      int64_t k, const char* who, FlatBy* by) {
+  if (n_vec < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_vec < 1");
+  if (n_users > 0x7fffffffll / n_vec) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many vectors in one call");
+  int rc = flat_check(ix, scorer, nullptr, n_users * n_vec, fetch, false, 0, who, by);
+  if (rc) return rc;
+  if (k < 0 || k > (int64_t)n_vec * fetch) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k must lie in [0, n_vec * fetch]");
+  return fuse_shape_check(n_users, n_vec, fetch, k, who);
+}
+static FlatMultiBytes flat_all_multi_fused_bytes(const nann_index* ix, const FlatBy& by, int64_t n_users, int32_t n_vec, int32_t fetch) {
+  ScanLayout L;
+  FlatMultiBytes b;
+  b.inner = flat_all_bytes(ix, by, n_users * n_vec, fetch, false, &L);
+  b.stage_off = (b.inner + 255) & ~(size_t)255;
+  b.union_off = b.stage_off + flat_multi_stage_bytes(n_users * n_vec, fetch);
+  b.total = b.union_off + fuse_ws_bytes((long long)n_users, (long long)n_vec * fetch);
+  return b;
+}
+
+static int flat_all_multi_fused(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,
+                                int32_t fetch, int32_t k, const nann_fusion* fusion, int64_t* out_item_ids, float* out_scores,
+                                int32_t* out_index, uint64_t* out_lists, int32_t* n_out, void* workspace, int64_t workspace_bytes,
+                                const nann_search_options* options, nann_stream_t stream, const char* who) {
+  FlatBy by;
+  int rc = flat_all_multi_fused_check(ix, scorer, n_users, n_vec, fetch, k, who, &by);
+  if (rc) return rc;
+  rc = fusion_check(fusion, who);
+  if (rc) return rc;
+  if (n_users == 0 || k == 0) return NANN_OK;
+  if (!q || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  const FlatMultiBytes b = flat_all_multi_fused_bytes(ix, by, n_users, n_vec, fetch);
+  rc = flat_workspace(workspace, workspace_bytes, b.total, who, "");
+  if (rc) return rc;
+  const int64_t n = n_users * n_vec;
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  int64_t* s_ids = reinterpret_cast<int64_t*>(ws + b.stage_off);
+  float* s_scores = reinterpret_cast<float*>(ws + b.stage_off + (size_t)n * fetch * 8);
+  int32_t* s_rows = reinterpret_cast<int32_t*>(ws + b.stage_off + (size_t)n * fetch * 12);
+  rc = flat_all(ix, scorer, nullptr, q, n, fetch, s_ids, s_scores, s_rows, workspace, (int64_t)b.inner, options, false, nullptr, nullptr,
+                stream, "nann_search_all");
+  if (rc) return rc;
+  FuseArgs a = {};
+  a.scores = s_scores;
+  a.rows = s_rows;
+  a.n_lists = n_vec;
+  a.k_in = fetch;
+  a.k = k;
+  flat_ids_of(ix, &a);
+  fusion_into(fusion, &a);
+  a.ws = ws + b.union_off;
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_item_ids = out_item_ids;
+  a.out_lists = reinterpret_cast<unsigned long long*>(out_lists);
+  a.n_out = n_out;
+  return launch_fuse_topk(a, (long long)n_users, as_stream(stream));
+}
+
 // ---- exhaustive search under a group cap: flat_all, filtered, at k = the fetch width F into a staging list, then the cap ------
 // workspace: [flat_all's filtered workspace at k = F, rounded up to 256 | item ids i64[n, F], scores f32[n, F], rows i32[n, F],
 // n_out i32[n], rounded up]
@@ -885,6 +976,68 @@ int nann_search_all_multi(const nann_index* ix, const nann_scorer* scorer, const
                           nann_stream_t stream) {
   return flat_all_multi(ix, scorer, q, n_users, n_vec, k, out_item_ids, out_scores, out_index, out_vec, n_out, workspace,
                         workspace_bytes, options, stream, "nann_search_all_multi");
+}
+
+int nann_fuse_topk_workspace_bytes(int64_t n_users, int32_t n_lists, int32_t k_in, int64_t* nbytes) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, "nann_fuse_topk_workspace_bytes: null argument");
+  const int rc = fuse_shape_check(n_users, n_lists, k_in, 0, "nann_fuse_topk_workspace_bytes");
+  if (rc) return rc;
+  *nbytes = (int64_t)fuse_ws_bytes((long long)n_users, (long long)n_lists * k_in);
+  return NANN_OK;
+}
+int nann_fuse_topk(const float* scores, const int32_t* rows, const int32_t* n_valid, int64_t n_users, int32_t n_lists,
+                   int32_t k_in, int64_t n_items, const int64_t* item_ids, int32_t k, const nann_fusion* fusion,
+                   int32_t* out_index, float* out_scores, int64_t* out_item_ids, uint64_t* out_lists, int32_t* n_out,
+                   void* workspace, int64_t workspace_bytes, nann_stream_t stream) {
+  const char* who = "nann_fuse_topk";
+  if (n_items < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": negative size");
+  int rc = union_check(n_users, n_lists, k_in, k, who);
+  if (rc) return rc;
+  if (n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  if (n_lists > NANN_FUSE_MAX_LISTS) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": at most NANN_FUSE_MAX_LISTS = 64 lists per user");
+  rc = fusion_check(fusion, who);
+  if (rc) return rc;
+  if (n_users == 0 || k == 0) return NANN_OK;
+  if (!scores || !rows || !out_index) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (out_item_ids && !item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": out_item_ids without item_ids");
+  rc = flat_workspace(workspace, workspace_bytes, fuse_ws_bytes((long long)n_users, (long long)n_lists * k_in), who, "");
+  if (rc) return rc;
+  FuseArgs a = {};
+  a.scores = scores;
+  a.rows = rows;
+  a.n_valid = n_valid;
+  a.nv_stride = 1;
+  a.n_lists = n_lists;
+  a.k_in = k_in;
+  a.k = k;
+  a.n_items = (long long)n_items;
+  a.item_ids = item_ids;
+  fusion_into(fusion, &a);
+  a.ws = static_cast<unsigned char*>(workspace);
+  a.out_index = out_index;
+  a.out_scores = out_scores;
+  a.out_item_ids = out_item_ids;
+  a.out_lists = reinterpret_cast<unsigned long long*>(out_lists);
+  a.n_out = n_out;
+  return launch_fuse_topk(a, (long long)n_users, as_stream(stream));
+}
+
+int nann_search_all_multi_fused_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_users, int32_t n_vec,
+                                                int32_t fetch, int64_t* nbytes) {
+  const char* who = "nann_search_all_multi_fused_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  const int rc = flat_all_multi_fused_check(ix, scorer, n_users, n_vec, fetch, 0, who, &by);
+  if (rc) return rc;
+  *nbytes = n_users == 0 || fetch == 0 ? 0 : (int64_t)flat_all_multi_fused_bytes(ix, by, n_users, n_vec, fetch).total;
+  return NANN_OK;
+}
+int nann_search_all_multi_fused(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,
+                                int32_t fetch, int32_t k, const nann_fusion* fusion, int64_t* out_item_ids, float* out_scores,
+                                int32_t* out_index, uint64_t* out_lists, int32_t* n_out, void* workspace,
+                                int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream) {
+  return flat_all_multi_fused(ix, scorer, q, n_users, n_vec, fetch, k, fusion, out_item_ids, out_scores, out_index, out_lists, n_out,
+                              workspace, workspace_bytes, options, stream, "nann_search_all_multi_fused");
 }
 
 int nann_search_all_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k, int64_t* nbytes) {

@@ -1,6 +1,6 @@
 // nann_traverse.hip -- the host side of the calls that walk the graph: the serving traversal (nann_search_opt,
 // nann_search_model_opt and their five deprecated spellings, nann_search_filtered, nann_search_model_filtered, nann_search_multi,
-// nann_search_grouped, nann_search_model_grouped, nann_search_diverse, nann_search_model_diverse, nann_search_where,
+// nann_search_multi_fused, nann_search_grouped, nann_search_model_grouped, nann_search_diverse, nann_search_model_diverse, nann_search_where,
 // nann_search_model_where;
 // kernels in nann_search.h), the evaluation traversal (nann_search_eval, nann_search_eval_ex, nann_search_eval_model; nann_eval.h), each
 // with its *_workspace_bytes, and what nann_index_create measures for them: the probe and the pivots of the batch order.
@@ -29,6 +29,7 @@
 #include "nann_filter.h"
 #include "nann_predicate.h"
 #include "nann_union.h"
+#include "nann_fuse.h"
 #include "nann_groupcap.h"
 #include "nann_mmr.h"
 
@@ -872,19 +873,23 @@ static int traverse_diverse(const nann_index* ix, const nann_scorer* scorer, con
 // ---- the traversal over a user's interest vectors: the inner search over the n_users * n_vec vectors at the fetch width
 // F = level_topn_max[5] into the staging area a filtered call has behind its workspace, then the union top-k (nann_union.h)
 // of each user's n_vec lists, its workspace behind the staging area ---------------------------------------------------------
-static int traverse_multi_check(int64_t n_users, int32_t n_vec, const int32_t level_topn_max[6], int64_t k, const char* who) {
+// fused: the nann_search_multi_fused form -- the fuse (nann_fuse.h) stands where the union does, with its own limit and workspace
+static int traverse_multi_check(int64_t n_users, int32_t n_vec, const int32_t level_topn_max[6], int64_t k, const char* who,
+                                bool fused = false) {
   if (n_vec < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_vec < 1");
   const int64_t f = level_topn_max[5];
   if (k < 0 || k > (int64_t)n_vec * f) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k must lie in [0, n_vec * level_topn_max[5]]");
   if (n_users > 0 && n_users > 0x7fffffffll / n_vec) return fail(NANN_ERR_UNSUPPORTED, "too many queries in one call");
+  if (fused) return fuse_shape_check(std::max<int64_t>(n_users, 0), n_vec, f, k, who);
   return union_check(std::max<int64_t>(n_users, 0), n_vec, f, k, who);
 }
 // b->total: the filtered layout over the vectors (its end is where the union's workspace starts); *total: with the union's
 static int traverse_multi_bytes(const nann_index* ix, const int32_t level_topn_max[6], int64_t n_users, int32_t n_vec,
-                                TraverseBytes* b, int64_t* total) {
+                                TraverseBytes* b, int64_t* total, bool fused = false) {
   const int rc = traverse_bytes(ix, nullptr, level_topn_max, n_users * n_vec, true, b);
   if (rc) return rc;
-  *total = up256_i64(b->total) + (int64_t)union_ws_bytes((long long)n_users, (long long)n_vec * level_topn_max[5]);
+  const long long n_in = (long long)n_vec * level_topn_max[5];
+  *total = up256_i64(b->total) + (int64_t)(fused ? fuse_ws_bytes((long long)n_users, n_in) : union_ws_bytes((long long)n_users, n_in));
   return NANN_OK;
 }
 
@@ -892,10 +897,13 @@ static int traverse_multi(const nann_index* ix, const nann_scorer* scorer, const
                           const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace, int64_t workspace_bytes,
                           int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_vec, int32_t* n_out,
                           int32_t* status, int32_t* counters, const nann_search_options* options, nann_search_plan* plan, int32_t k,
-                          nann_stream_t stream, const char* who) {
+                          nann_stream_t stream, const char* who, bool fused = false, const nann_fusion* fusion = nullptr,
+                          uint64_t* out_lists = nullptr) {
   if (traverse_null(ix, scorer, nullptr, false, q, level_topn_max, out_item_ids, status, workspace))
     return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  int rc = traverse_multi_check(n_users, n_vec, level_topn_max, k, who);  // (also of an empty batch)
+  int rc = traverse_multi_check(n_users, n_vec, level_topn_max, k, who, fused);  // (also of an empty batch)
+  if (rc) return rc;
+  if (fused) rc = fusion_check(fusion, who);
   if (rc) return rc;
   if (n_users <= 0 || k == 0) return NANN_OK;  // (nothing to return: no inner search either, as nann_union_topk)
   if (!q) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
@@ -903,7 +911,7 @@ static int traverse_multi(const nann_index* ix, const nann_scorer* scorer, const
   const int f = level_topn_max[5];
   TraverseBytes b;
   int64_t total = 0;
-  rc = traverse_multi_bytes(ix, level_topn_max, n_users, n_vec, &b, &total);
+  rc = traverse_multi_bytes(ix, level_topn_max, n_users, n_vec, &b, &total, fused);
   if (rc) return rc;
   // (the call's own workspace ahead of everything the inner search looks at, its options included)
   if (!workspace || workspace_bytes < total) return short_workspace(who);
@@ -916,6 +924,27 @@ static int traverse_multi(const nann_index* ix, const nann_scorer* scorer, const
   rc = traverse(ix, scorer, nullptr, false, q, n, level_topn_max, level_topn, workspace, b.inner, s_ids, s_scores, s_rows, status,
                 counters, nullptr, options, plan, stream, "nann_search_opt");
   if (rc) return rc;
+  if (fused) {  // the fuse (nann_fuse.h) in the place of the union, over the same lists
+    FuseArgs a = {};
+    a.scores = s_scores;
+    a.rows = s_rows;
+    a.n_valid = level_topn ? level_topn + 5 : nullptr;
+    a.nv_stride = 6;
+    a.status = status;
+    a.n_lists = n_vec;
+    a.k_in = f;
+    a.k = k;
+    a.n_items = (long long)ix->desc.n_items;
+    a.item_ids = ix->desc.item_ids;
+    fusion_into(fusion, &a);
+    a.ws = ws + up256_i64(b.total);
+    a.out_index = out_index;
+    a.out_scores = out_scores;
+    a.out_item_ids = out_item_ids;
+    a.out_lists = reinterpret_cast<unsigned long long*>(out_lists);
+    a.n_out = n_out;
+    return launch_fuse_topk(a, (long long)n_users, as_stream(stream));
+  }
   UnionArgs a = {};
   a.scores = s_scores;
   a.rows = s_rows;
@@ -1015,6 +1044,30 @@ int nann_search_multi(const nann_index* ix, const nann_scorer* scorer, const flo
                       nann_stream_t stream) {
   return traverse_multi(ix, scorer, q, n_users, n_vec, level_topn_max, level_topn, workspace, workspace_bytes, out_item_ids,
                         out_scores, out_index, out_vec, n_out, status, counters, options, plan, k, stream, "nann_search_multi");
+}
+
+int nann_search_multi_fused_workspace_bytes(const nann_index* ix, const int32_t level_topn[6], int64_t n_users, int32_t n_vec,
+                                            int64_t* nbytes) {
+  const char* who = "nann_search_multi_fused_workspace_bytes";
+  if (!ix || !level_topn || !nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  int rc = traverse_multi_check(n_users, n_vec, level_topn, 0, who, true);
+  if (rc) return rc;
+  TraverseBytes b;
+  int64_t total = 0;
+  rc = traverse_multi_bytes(ix, level_topn, std::max<int64_t>(n_users, 0), n_vec, &b, &total, true);
+  if (rc) return rc;
+  *nbytes = total;
+  return NANN_OK;
+}
+int nann_search_multi_fused(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,
+                            const int32_t level_topn_max[6], const int32_t* level_topn, void* workspace,
+                            int64_t workspace_bytes, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                            uint64_t* out_lists, int32_t* n_out, int32_t* status, int32_t* counters,
+                            const nann_search_options* options, nann_search_plan* plan, int32_t k, const nann_fusion* fusion,
+                            nann_stream_t stream) {
+  return traverse_multi(ix, scorer, q, n_users, n_vec, level_topn_max, level_topn, workspace, workspace_bytes, out_item_ids,
+                        out_scores, out_index, nullptr, n_out, status, counters, options, plan, k, stream, "nann_search_multi_fused",
+                        true, fusion, out_lists);
 }
 
 int nann_search_workspace_bytes(const nann_index* ix, const int32_t level_topn[6], int64_t n_queries, int64_t* nbytes) {

@@ -28,6 +28,11 @@ per request.  Two equivalent executions of that schedule live here:
                       diversified results: MMR re-ranking (make_diversity) of the fetched top-F into k picks, through the
                       traversal / exhaustively, and the step on its own for lists from anywhere
                       (nann_search_diverse, nann_search_all_diverse, their _model forms, nann_mmr_topk);
+  * `fuse_topk()` / `fuse_results()` / `search_multi_fused()` / `search_all_multi_fused()` fused result lists: reciprocal rank
+                      fusion or a weighted sum of raw, floor-shifted or min-max-normalised scores (make_fusion) over a user's
+                      lists -- the step on its own, over the results of several searches (hybrid retrieval), and behind the
+                      multi-vector traversal / exhaustive search (nann_fuse_topk, nann_search_multi_fused,
+                      nann_search_all_multi_fused);
   * `search_per_op()` the same schedule spelled op by op with the drop-in ops
                       of nann_amd.ops, line for line against build_model(), so
                       that each op is exercised in the composition the
@@ -773,6 +778,177 @@ def search_all_multi(index, scorer, q, k, options=None):
                                            _ptr(out_index), _ptr(out_vec), _ptr(n_out), _ptr(ws), ws.numel(),
                                            C.byref(options) if options is not None else None, _stream()), "search_all_multi")
     return MultiResult(out_ids, out_scores, out_index, out_vec, n_out, ws=ws)
+
+
+FUSE_MAX_LISTS = _lib.FUSE_MAX_LISTS  # most lists (vectors) a user brings to a fuse
+FUSION_MODES = {"sum": _lib.FUSE_SUM, "sum_floor": _lib.FUSE_SUM_FLOOR, "minmax": _lib.FUSE_MINMAX, "rrf": _lib.FUSE_RRF}
+
+
+class Fusion:
+    """How fuse_topk and the _fused searches turn a row's entries in several lists into one score (make_fusion).  mode: a
+    key of FUSION_MODES; weights: None, f32[n_lists] (per call) or f32[n_users, n_lists] (per user), moved to the device of
+    the call when it is made; rrf_c: the constant of reciprocal rank fusion."""
+    __slots__ = ("mode", "weights", "rrf_c")
+
+    def __init__(self, mode, weights, rrf_c):
+        self.mode, self.weights, self.rrf_c = mode, weights, rrf_c
+
+
+def make_fusion(mode="rrf", weights=None, rrf_c=60.0):
+    """A Fusion.  mode: "rrf" (a list adds w / (rrf_c + rank), rank from 1), "sum" (w * score), "sum_floor" (w * (score - the
+    list's least score): what makes negative L2 scores addable) or "minmax" (w * the score's place between the list's least
+    and greatest score, in [0, 1]).  weights: None (1.0), 1-D [n_lists] for a per-call weight or 2-D [n_users, n_lists] for a
+    per-user weight -- a tensor, an array or a sequence; used as given, negative and zero weights included."""
+    assert mode in FUSION_MODES, "mode: one of %s" % sorted(FUSION_MODES)
+    rrf_c = float(rrf_c)
+    assert 0.0 <= rrf_c < math.inf, "rrf_c: a finite value >= 0"
+    if weights is not None:
+        weights = torch.as_tensor(weights).to(dtype=torch.float32)
+        assert weights.dim() in (1, 2), "weights: [n_lists] or [n_users, n_lists]"
+    return Fusion(mode, weights, rrf_c)
+
+
+def _fusion_args(fusion, n_users, n_lists, dev):
+    """-> (the nann_fusion struct, what it borrows)"""
+    w = fusion.weights
+    if w is not None:
+        w = w.to(device=dev, dtype=torch.float32).contiguous()
+        assert tuple(w.shape) in ((n_lists,), (n_users, n_lists)), "weights: [n_lists] or [n_users, n_lists]"
+    f = _lib.Fusion(C.sizeof(_lib.Fusion), FUSION_MODES[fusion.mode], fusion.rrf_c, int(w is not None and w.dim() == 2),
+                    w.data_ptr() if w is not None and w.numel() else None)
+    return f, w
+
+
+class FusedResult:
+    """Outputs of fuse_topk / fuse_results / search_multi_fused / search_all_multi_fused, [n_users, k] device tensors: the k
+    best DISTINCT rows of a user by the score accumulated over the lists that contain a row, n_out[u] valid entries at the head
+    of row u and zeros behind.  lists: int64, the u64 mask of the lists that contain the row (bit l = list l; bit 63 is the
+    sign).  status: i32[n_users, n_vec], what the inner search of search_multi_fused reported per vector (None elsewhere);
+    plan: its planner's choice (None elsewhere).  item_ids is None for a fuse_topk without an index."""
+    __slots__ = ("item_ids", "scores", "index", "lists", "n_out", "status", "plan", "_ws")
+
+    def __init__(self, item_ids, scores, index, lists, n_out, status=None, plan=None, ws=None):
+        self.item_ids, self.scores, self.index, self.lists, self.n_out = item_ids, scores, index, lists, n_out
+        self.status, self.plan, self._ws = status, plan, ws
+
+
+def _fused_outputs(n_users, k, dev, item_ids=True):
+    kk = max(int(k), 0)
+    return (torch.zeros((n_users, kk), dtype=torch.int64, device=dev) if item_ids else None,
+            torch.zeros((n_users, kk), dtype=torch.float32, device=dev), torch.zeros((n_users, kk), dtype=torch.int32, device=dev),
+            torch.zeros((n_users, kk), dtype=torch.int64, device=dev), torch.zeros(n_users, dtype=torch.int32, device=dev))
+
+
+def fuse_topk(scores, rows, fusion, k, n_valid=None, index=None):
+    """Fused top-k (nann_fuse_topk): scores f32 / rows i32 [n_users, n_lists, k_in] CUDA tensors, a user's n_lists result lists
+    from anywhere, on any scales; only the first n_valid[u][l] (i32[n_users, n_lists]; None: k_in) entries of a list count, and
+    rows outside [0, index.n_items) -- without an index: negative rows -- are dropped.  Within a list a row counts once, at its
+    first entry; every list that contains a row adds one term to the row's score (make_fusion), in list order, and the k rows
+    with the largest sums are returned, descending, ties -> the row that appears first -> FusedResult (item_ids only with an
+    index).  n_lists <= FUSE_MAX_LISTS, n_lists * k_in <= UNION_MAX_IN, k <= 1024.  Asynchronous on torch's current stream."""
+    dev = scores.device
+    scores = scores.to(dtype=torch.float32).contiguous()
+    rows = rows.to(device=dev, dtype=torch.int32).contiguous()
+    assert scores.dim() == 3 and rows.shape == scores.shape, "scores, rows: [n_users, n_lists, k_in]"
+    n_users, n_lists, k_in = scores.shape
+    if n_valid is not None:
+        n_valid = n_valid.to(device=dev, dtype=torch.int32).contiguous()
+        assert n_valid.shape == (n_users, n_lists), "n_valid: [n_users, n_lists]"
+    k = int(k)
+    f, _borrowed = _fusion_args(fusion, n_users, n_lists, dev)
+    out_ids, out_scores, out_index, out_lists, n_out = _fused_outputs(n_users, k, dev, index is not None)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_fuse_topk_workspace_bytes(n_users, n_lists, k_in, C.byref(nbytes)), "fuse_topk")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    n_items = int(index.n_items) if index is not None else (1 << 31) - 1
+    with torch.cuda.device(dev):
+        _check(lib().nann_fuse_topk(_ptr(scores), _ptr(rows), _ptr(n_valid), n_users, n_lists, k_in, n_items,
+                                    _ptr(index.item_ids) if index is not None else None, k, C.byref(f), _ptr(out_index),
+                                    _ptr(out_scores), _ptr(out_ids), _ptr(out_lists), _ptr(n_out), _ptr(ws), ws.numel(), _stream()),
+               "fuse_topk")
+    return FusedResult(out_ids, out_scores, out_index, out_lists, n_out, ws=ws)
+
+
+def _stack_results(results):
+    """the index / scores of result objects [n_users, k_i], padded to the widest -> (scores f32, rows i32) [n_users, n_results,
+    k_max] and n_valid i32[n_users, n_results]: a result's n_out, or its width where it has none"""
+    assert len(results) > 0, "results: at least one"
+    n_users = int(results[0].index.shape[0])
+    dev = results[0].index.device
+    width = max(int(r.index.shape[1]) for r in results)
+    scores = torch.zeros((n_users, len(results), width), dtype=torch.float32, device=dev)
+    rows = torch.zeros((n_users, len(results), width), dtype=torch.int32, device=dev)
+    n_valid = torch.zeros((n_users, len(results)), dtype=torch.int32, device=dev)
+    for l, r in enumerate(results):
+        assert r.index.dim() == 2 and r.index.shape == r.scores.shape and int(r.index.shape[0]) == n_users, \
+            "results: index and scores [n_users, k] of one batch"
+        w = int(r.index.shape[1])
+        scores[:, l, :w] = r.scores.to(device=dev, dtype=torch.float32)
+        rows[:, l, :w] = r.index.to(device=dev, dtype=torch.int32)
+        n_out = getattr(r, "n_out", None)
+        n_valid[:, l] = n_out.to(device=dev, dtype=torch.int32) if n_out is not None else w
+    return scores, rows, n_valid
+
+
+def fuse_results(results, fusion, k, index):
+    """Hybrid retrieval: fuse what several searches of ONE batch returned -- a Python list of result objects of any search here
+    (SearchResult, SearchAllResult, CandidateResult, MultiResult, ...), list l = results[l].  Their index / scores are padded
+    to the widest, a result's n_out (its width where it has none) says how many of its entries count, and fuse_topk does the
+    rest -> FusedResult; bit l of result.lists = results[l] holds the row."""
+    scores, rows, n_valid = _stack_results(results)
+    return fuse_topk(scores, rows, fusion, k, n_valid=n_valid, index=index)
+
+
+def search_multi_fused(index, scorer, q, level_topn, fusion, k=None, options=None):
+    """search_multi with the fuse in the place of the union (nann_search_multi_fused): q f32[n_users, n_vec, d]; search() runs
+    unchanged over the n_users * n_vec vectors at the fetch width F = level_topn[5], then each user's n_vec lists are fused
+    (make_fusion): the k (default F) rows with the largest accumulated score -> FusedResult; result.lists names the vectors whose
+    list holds the row, result.status [n_users, n_vec] what the inner search reported -- a failed vector contributes nothing.
+    A row beyond depth F in a vector's list loses that vector's term: F is the caller's trade-off.  n_vec <= FUSE_MAX_LISTS,
+    n_vec * F <= UNION_MAX_IN, k <= 1024.  Asynchronous on torch's current stream."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    assert q.dim() == 3, "q: [n_users, n_vec, d]"
+    n_users, n_vec = int(q.shape[0]), int(q.shape[1])
+    t, tq, k_fetch = _level_topn_args(level_topn, n_users * n_vec, dev)
+    k = int(k) if k is not None else k_fetch
+    f, _borrowed = _fusion_args(fusion, n_users, n_vec, dev)
+    out_ids, out_scores, out_index, out_lists, n_out = _fused_outputs(n_users, k, dev)
+    status = torch.zeros((n_users, n_vec), dtype=torch.int32, device=dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_multi_fused_workspace_bytes(index.handle, t, n_users, n_vec, C.byref(nbytes)), "search_multi_fused")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    plan = _lib.SearchPlan()
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_multi_fused(index.handle, scorer.handle, _ptr(q), n_users, n_vec, t, _ptr(tq), _ptr(ws), ws.numel(),
+                                             _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(out_lists), _ptr(n_out),
+                                             _ptr(status), None, C.byref(options) if options is not None else None, C.byref(plan),
+                                             k, C.byref(f), _stream()), "search_multi_fused")
+    return FusedResult(out_ids, out_scores, out_index, out_lists, n_out, status, _plan_dict(plan), ws)
+
+
+def search_all_multi_fused(index, scorer, q, k, fusion, fetch=None, options=None):
+    """Exhaustive multi-vector search, fused (nann_search_all_multi_fused): search_all over the n_users * n_vec vectors of q
+    f32[n_users, n_vec, d] at `fetch` (default k), the per-vector depth, then the fuse per user at k -> FusedResult.  Unlike the
+    union's, this answer depends on the depth: a row beyond `fetch` in a vector's list loses that vector's term.  n_vec <=
+    FUSE_MAX_LISTS, n_vec * fetch <= UNION_MAX_IN.  Asynchronous on torch's current stream."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    assert q.dim() == 3, "q: [n_users, n_vec, d]"
+    n_users, n_vec, k = int(q.shape[0]), int(q.shape[1]), int(k)
+    fetch = int(fetch) if fetch is not None else k
+    f, _borrowed = _fusion_args(fusion, n_users, n_vec, dev)
+    out_ids, out_scores, out_index, out_lists, n_out = _fused_outputs(n_users, k, dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_all_multi_fused_workspace_bytes(index.handle, scorer.handle, n_users, n_vec, fetch, C.byref(nbytes)),
+           "search_all_multi_fused")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_all_multi_fused(index.handle, scorer.handle, _ptr(q), n_users, n_vec, fetch, k, C.byref(f),
+                                                 _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(out_lists), _ptr(n_out),
+                                                 _ptr(ws), ws.numel(), C.byref(options) if options is not None else None,
+                                                 _stream()), "search_all_multi_fused")
+    return FusedResult(out_ids, out_scores, out_index, out_lists, n_out, ws=ws)
 
 
 class Groups:

@@ -266,6 +266,55 @@ int nann_set_preprojection(int32_t enabled);
 int nann_user_seq_mean(const void* comm_seq_f16, int64_t n_queries, int32_t seq_len, int32_t d,
                        float* q, nann_stream_t stream);
 
+/* ---- user interests: cluster a behaviour sequence into query vectors -------------------------------------------------
+ * comm_seq f16[n_users, seq_len, d] -> q f32[n_users, n_vec, d], the layout nann_search_multi takes for q, and weights
+ * f32[n_users, n_vec], the layout nann_fusion takes for per-user weights: the user side of the multi-vector calls, as
+ * nann_user_seq_mean is the user side of nann_search.  A history that mixes two tastes has its mean in the empty space
+ * between them; here it gets one vector per taste.  The reference has no such call; the contract below is this library's own
+ * and is held bit for bit against a numpy model (tests/interests_model.py).
+ *
+ * Per user.  Every step is a single f32 operation, with no FMA contraction, in the order given.
+ *   pad rows      a row whose d halves are all +-0 is pad, as in nann_user_seq_mean: it belongs to no interest, assign = -1.
+ *                 m = the number of non-pad rows.
+ *   dist(r, c)    for k ascending from acc = +0.0f: t = (float)x[r][k] - c[k]; acc = acc + t * t.  This one chain is the
+ *                 whole definition: no tree, no lanes.
+ *   first seed    mean = what nann_user_seq_mean returns for this user, bit for bit.  Seed 0 is the non-pad row with the
+ *                 greatest dist(r, mean), ties to the lowest r.
+ *   more seeds    seed j is the non-pad row with the greatest min over the seeds so far of dist(r, seed), ties to the lowest
+ *                 r; if that greatest value is 0, seeding stops.  A seed's centroid is its row converted to f32, so n_seed <=
+ *                 min(n_vec, distinct non-pad rows).  Farthest-point seeding is deterministic and needs no RNG state; its
+ *                 weakness is that an outlier becomes a seed.
+ *   n_vec == 1    there is nothing to separate: the one centroid is the mean itself and no seed row is chosen.
+ *   Lloyd rounds  n_iter of them.  In each, every non-pad row goes to the centroid with the least dist, ties to the lowest
+ *                 cluster number; then every cluster with members gets, per column, acc from +0.0f over its member rows in
+ *                 ascending r and one divide by (float)count; a cluster without members keeps its centroid.  (A round that
+ *                 moves no row may end the rounds: the result is the same.)
+ *   final pass    one more assignment against the final centroids; clusters it leaves empty are dropped.
+ *   order         the rest in descending member count, ties to the lower cluster number.  n_interests[u] = how many remain;
+ *                 weights[u][c] = (float)count_c / (float)m; assign[u][r] = the output slot of row r.  Slots c >=
+ *                 n_interests[u] hold a copy of slot 0's vector with weight 0.0f -- "a user with fewer interests repeats one
+ *                 of them", as nann_search_multi puts it.  A user with m == 0 gets all-zero q, zero weights, n_interests = 0
+ *                 and assign = -1 everywhere.
+ * Consequences: with n_vec == 1, q is nann_user_seq_mean's output bit for bit for every n_iter, with weight 1; with n_iter ==
+ * 0 and n_vec >= 2, q holds the seed rows themselves; a user's answer does not depend on its batch.  NaN / inf in comm_seq
+ * are outside the contract.  Asynchronous on `stream`, no host read-back.  weights, n_interests and assign are optional
+ * (NULL: not written).  Any d >= 1 and any alignment of comm_seq_f16 work: d % 8 != 0 or a base off the 16-byte grid takes
+ * 2-byte loads instead of 16-byte ones, the same bits.
+ * Nothing is launched and nothing is written by a refused call: n_users < 0, seq_len < 1, d < 1, n_vec < 1 or n_iter < 0 ->
+ * NANN_ERR_BAD_ARGUMENT; n_vec > NANN_INTERESTS_MAX_VEC, n_iter > NANN_INTERESTS_MAX_ITER, n_users > 2^31 - 1, or a shape
+ * beyond the kernel's LDS budget -> NANN_ERR_UNSUPPORTED; n_users == 0 -> NANN_OK; a null comm_seq_f16 or q with work to do ->
+ * NANN_ERR_BAD_ARGUMENT.  (Where several apply: the sizes first, their NANN_ERR_BAD_ARGUMENT before their
+ * NANN_ERR_UNSUPPORTED, then the early NANN_OK, then the null pointers.)  The LDS budget: one workgroup holds a user's whole
+ * history and its centroids in 64 KB -- 256 + 4 seq_len ((ceil(d / 2) | 1) + n_vec + 2) + 4 d (n_vec + 1) bytes; 200 x 128 x 8,
+ * 50 x 256 x 16 and 600 x 16 x 4 (seq_len x d x n_vec) all fit. */
+#define NANN_INTERESTS_MAX_VEC 16
+#define NANN_INTERESTS_MAX_ITER 32
+int nann_user_seq_interests(const void* comm_seq_f16, int64_t n_users, int32_t seq_len, int32_t d,
+                            int32_t n_vec, int32_t n_iter,
+                            float* q /*[n_users, n_vec, d]*/, float* weights /*[n_users, n_vec] or NULL*/,
+                            int32_t* n_interests /*[n_users] or NULL*/, int32_t* assign /*[n_users, seq_len] or NULL*/,
+                            nann_stream_t stream);
+
 /* Score n rows against ONE query vector q f32[d] (rows are scored
  * independently, f32 logits -- the contract PadToStatic/SliceToDynamic rely
  * on).  indices == NULL: rows = item_emb[n, d] as BlazeXlaOp receives them
@@ -826,7 +875,8 @@ int nann_union_topk(const float* scores, const int32_t* rows, const int32_t* n_v
  * status included, as in nann_union_topk.  A user with fewer than n_vec interests repeats one of them: duplicates collapse, the answer is that of
  * the distinct vectors.  Filters compose from the parts: nann_search_filtered over the n_users * n_vec vectors, then
  * nann_union_topk with n_valid = its n_out.  There is no _model form: a comm_seq is ONE user sequence, which a model turns into
- * one query (l2 / mlp: its mean) or scores as a whole (attention); several interest vectors are the caller's user tower's. */
+ * one query (l2 / mlp: its mean) or scores as a whole (attention); several interest vectors come from the caller's user tower, or from that sequence through
+ * nann_user_seq_interests. */
 int nann_search_multi_workspace_bytes(const nann_index* ix, const int32_t level_topn[6] /*[host]*/, int64_t n_users,
                                       int32_t n_vec, int64_t* nbytes);
 int nann_search_multi(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_users, int32_t n_vec,

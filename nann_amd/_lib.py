@@ -25,6 +25,8 @@ NUM_PHASES = 19
 UNION_MAX_IN = 8192  # NANN_UNION_MAX_IN: most entries (n_lists * k_in) a user brings to nann_union_topk
 FUSE_MAX_LISTS = 64  # NANN_FUSE_MAX_LISTS: most lists a user brings to nann_fuse_topk (out_lists is one u64 per entry)
 FUSE_SUM, FUSE_SUM_FLOOR, FUSE_MINMAX, FUSE_RRF = 0, 1, 2, 3
+INTERESTS_MAX_VEC = 16   # NANN_INTERESTS_MAX_VEC: most interest vectors nann_user_seq_interests makes of a sequence
+INTERESTS_MAX_ITER = 32  # NANN_INTERESTS_MAX_ITER: most Lloyd rounds it runs
 PHASE_NAMES = ("zero", "walk", "expand", "score", "topk", "other", "tk_load", "tk_search",
                "tk_collect", "tk_sort", "ex_pass1", "ex_loop", "ex_walkbusy",
                "ex_lookup", "ex_load", "ex_insert", "ex_bar_a", "ex_check", "ex_rank")
@@ -35,7 +37,7 @@ SYMBOLS = [
     "nann_memcpy", "nann_stream_synchronize", "nann_stream_create", "nann_stream_destroy", "nann_host_malloc",
     "nann_host_free", "nann_huge_const_load", "nann_group_gather_count",
     "nann_group_gather_fill", "nann_group_gather_unique_scratch_bytes", "nann_group_gather_unique", "nann_bitmap_ref_difference", "nann_bloom_filter_difference", "nann_gather_rows", "nann_topk",
-    "nann_scorer_create", "nann_scorer_destroy", "nann_user_seq_mean", "nann_score",
+    "nann_scorer_create", "nann_scorer_destroy", "nann_user_seq_mean", "nann_user_seq_interests", "nann_score",
     "nann_index_create", "nann_index_destroy", "nann_index_info", "nann_index_probe_info", "nann_search_workspace_bytes",
     "nann_search", "nann_search_v", "nann_search_ex", "nann_search_opt", "nann_search_options_init", "nann_search_reruns", "nann_search_refined", "nann_search_model_opt", "nann_set_traversal_mode", "nann_set_search_reserve", "nann_search_model_workspace_bytes",
     "nann_search_model", "nann_search_model_v",
@@ -315,6 +317,9 @@ def lib():
         L.nann_search_candidates_model_workspace_bytes.restype = C.c_int
         L.nann_search_candidates_model.argtypes = list(L.nann_search_candidates.argtypes)
         L.nann_search_candidates_model.restype = C.c_int
+        # (comm_seq_f16, n_users, seq_len, d, n_vec, n_iter, q, weights, n_interests, assign, stream)
+        L.nann_user_seq_interests.argtypes = [C.c_void_p, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 5
+        L.nann_user_seq_interests.restype = C.c_int
         # (n_users, n_lists, k_in, *nbytes) / (scores, rows, n_valid, n_users, n_lists, k_in, n_items, item_ids, k, out_index,
         #  out_scores, out_item_ids, out_list, n_out, workspace, workspace_bytes, stream)
         L.nann_union_topk_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]

@@ -27,7 +27,8 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 # re-ranking (nann_mmr.h: one kernel per (d, row dtype, metric) over the L2 / inner-product scorer) is part of nann_cand.o.  The attribute
 # predicates (nann_predicate.h: a scatter, a compaction and a count next to the filter's) are part of nann_filter.o as well.  The fused
 # top-k of a user's result lists (nann_fuse.h: one kernel, the union's table with an accumulator per row, over wg_topk) is part of
-# nann_cand.o, included by nann_cand_inst.hip behind the union whose constants it shares.  The inner-product
+# nann_cand.o, included by nann_cand_inst.hip behind the union whose constants it shares.  The user interests (nann_interests.h:
+# one kernel that clusters a behaviour sequence, with its entry point) ride in nann_cand.o too, the quickest object to rebuild.  The inner-product
 # traversal (nann_ip_inst.hip: the L2 file's four plans with the other scorer, as heavy as an L2 object per row dtype) rides in the
 # three LIGHTEST objects, one dtype each -- f16 with the filter kernels, bf16 with the attention candidate scorer, f32 with the
 # attention scan -- not in the nann_l2_* objects that bound a build from scratch.
@@ -48,7 +49,7 @@ UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_flat.hip", {}), ("nann_tr
          ("nann_filter.o", [("nann_filter_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "0", "NANN_IP_NAME": "f16"})]),
          ("nann_cand.o", [("nann_cand_inst.hip", {})]),
          ("nann_cand_attn.o", [("nann_cand_attn_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "1", "NANN_IP_NAME": "bf16"})])]
-DEPS = ["nann_hip.hip", "nann_flat.hip", "nann_traverse.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_ip_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_range.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_groupcap.h", "nann_predicate.h", "nann_filter_inst.hip", "nann_cand.h", "nann_union.h", "nann_fuse.h", "nann_mmr.h", "nann_cand_inst.hip", "nann_cand_attn_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
+DEPS = ["nann_hip.hip", "nann_flat.hip", "nann_traverse.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_ip_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_range.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_groupcap.h", "nann_predicate.h", "nann_filter_inst.hip", "nann_cand.h", "nann_union.h", "nann_fuse.h", "nann_mmr.h", "nann_interests.h", "nann_cand_inst.hip", "nann_cand_attn_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
         "nann_attn.h", "nann_attn_kernels.h", "nann_search.h", "nann_order.h", "nann_order_kernels.h", os.path.join("host", "nann_graphdef.h"), os.path.join("host", "nann_graphdef_text.h"), os.path.join("host", "nann_blaze_options.h"), os.path.join("host", "nann_npy.h"), os.path.join("host", "nann_projcache.h"),
         os.path.join("..", "..", "include", "nann_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-fast-math", "-ffp-contract=off"]

@@ -2,15 +2,18 @@
 // dtype), the MLP scorer in both precisions and the per-query top-k; workspace layout and the launch sequence of a call.  Also
 // the union top-k (nann_union.h), a per-user selection over wg_topk like k_cand_topk, and its launch; and the MMR re-ranking
 // (nann_mmr.h), a per-query selection over the L2 / inner-product scorer for the (d, row dtype) set of k_cand_score_l2, and its launch.
-// And the fused top-k (nann_fuse.h), the union's sibling with an accumulator per row, and its launch.
+// And the fused top-k (nann_fuse.h), the union's sibling with an accumulator per row, and its launch.  And the user side of the
+// multi-vector calls (nann_interests.h): the kernel that clusters a behaviour sequence into interest vectors, with its entry point.
 #define NANN_CAND_IMPL
 #define NANN_UNION_IMPL
 #define NANN_MMR_IMPL
 #define NANN_FUSE_IMPL
+#define NANN_INTERESTS_IMPL
 #include "nann_cand.h"
 #include "nann_union.h"
 #include "nann_mmr.h"
 #include "nann_fuse.h"
+#include "nann_interests.h"
 
 #include <algorithm>
 

@@ -450,6 +450,30 @@ def user_seq_mean(comm_seq):
     return q
 
 
+INTERESTS_MAX_VEC, INTERESTS_MAX_ITER = _lib.INTERESTS_MAX_VEC, _lib.INTERESTS_MAX_ITER
+
+
+def user_seq_interests(comm_seq, n_vec, n_iter=8, want_assign=False):
+    """comm_seq f16[B, L, d] -> (q f32[B, n_vec, d], weights f32[B, n_vec], n_interests i32[B][, assign i32[B, L]])
+    (nann_user_seq_interests): the history rows of a user clustered into at most n_vec interest vectors -- farthest-point
+    seeds, n_iter Lloyd rounds --, ordered by descending share of the history; q is what retrieval.search_multi takes,
+    weights (each vector's share of the non-pad rows; they sum to 1) what retrieval.make_fusion takes per user.  Slots
+    beyond n_interests[b] repeat slot 0 with weight 0; assign[b][r] is the slot of history row r, -1 for a pad row.
+    n_vec == 1: q is user_seq_mean's output.  n_vec <= INTERESTS_MAX_VEC, n_iter <= INTERESTS_MAX_ITER.  Asynchronous on
+    torch's current stream."""
+    s = _dev(comm_seq, torch.float16)
+    b, l, d = s.shape
+    n_vec, n_iter = int(n_vec), int(n_iter)
+    q = torch.empty((b, max(n_vec, 0), d), dtype=torch.float32, device=s.device)
+    w = torch.empty((b, max(n_vec, 0)), dtype=torch.float32, device=s.device)
+    n = torch.empty((b,), dtype=torch.int32, device=s.device)
+    a = torch.empty((b, l), dtype=torch.int32, device=s.device) if want_assign else None
+    with torch.cuda.device(s.device):
+        _check(lib().nann_user_seq_interests(_ptr(s), b, l, d, n_vec, n_iter, _ptr(q), _ptr(w), _ptr(n), _ptr(a), _stream()),
+               "user_seq_interests")
+    return (q, w, n, a) if want_assign else (q, w, n)
+
+
 def blaze_score(scorer, q, item_emb=None, table=None, indices=None):
     """The BlazeXlaOp contract for one user (forward(), build_opt_graph.py:91-107):
     f32 logits, one per candidate row, rows scored independently.

@@ -951,6 +951,47 @@ def search_all_multi_fused(index, scorer, q, k, fusion, fetch=None, options=None
     return FusedResult(out_ids, out_scores, out_index, out_lists, n_out, ws=ws)
 
 
+class Interests:
+    """What ops.user_seq_interests made of a batch of behaviour sequences (search_seq_multi / search_all_seq_multi return it
+    next to their result): q f32[n_users, n_vec, d], the interest vectors the search ran on; weights f32[n_users, n_vec], each
+    vector's share of the user's non-pad history rows; n_interests i32[n_users], how many of the n_vec slots are distinct
+    interests (the others repeat slot 0 with weight 0)."""
+    __slots__ = ("q", "weights", "n_interests")
+
+    def __init__(self, q, weights, n_interests):
+        self.q, self.weights, self.n_interests = q, weights, n_interests
+
+
+def _seq_interests(index, comm_seq, n_vec, n_iter, fusion):
+    """-> (Interests, the fusion to run: one that brings no weights gets the interests' as its per-user weights)"""
+    q, w, n = ops.user_seq_interests(torch.as_tensor(comm_seq).to(index.device), n_vec, n_iter=n_iter)
+    if fusion is not None and fusion.weights is None:
+        fusion = Fusion(fusion.mode, w, fusion.rrf_c)
+    return Interests(q, w, n), fusion
+
+
+def search_seq_multi(index, scorer, comm_seq, n_vec, level_topn, k=None, fusion=None, n_iter=8, options=None):
+    """Multi-vector traversal from a behaviour sequence: comm_seq f16[n_users, L, d] -> ops.user_seq_interests (at most n_vec
+    interest vectors per user, n_iter Lloyd rounds), then search_multi over them -> (MultiResult, Interests).  With a Fusion
+    (make_fusion) search_multi_fused runs in the union's place -> (FusedResult, Interests); a Fusion whose weights is None gets
+    the interests' weights as its per-user weights, one that brings weights keeps them.  A composition in Python: two
+    calls on torch's current stream, no host read-back between them."""
+    interests, fusion = _seq_interests(index, comm_seq, n_vec, n_iter, fusion)
+    if fusion is None:
+        return search_multi(index, scorer, interests.q, level_topn, k=k, options=options), interests
+    return search_multi_fused(index, scorer, interests.q, level_topn, fusion, k=k, options=options), interests
+
+
+def search_all_seq_multi(index, scorer, comm_seq, n_vec, k, fusion=None, fetch=None, n_iter=8, options=None):
+    """search_seq_multi over the exhaustive forms, its ground truth: ops.user_seq_interests, then search_all_multi at k ->
+    (MultiResult, Interests), or with a Fusion search_all_multi_fused at (k, fetch) -> (FusedResult, Interests); the Fusion's
+    weights as in search_seq_multi."""
+    interests, fusion = _seq_interests(index, comm_seq, n_vec, n_iter, fusion)
+    if fusion is None:
+        return search_all_multi(index, scorer, interests.q, k, options=options), interests
+    return search_all_multi_fused(index, scorer, interests.q, k, fusion, fetch=fetch, options=options), interests
+
+
 class Groups:
     """What make_groups returns: the tensors of a nann_groups (they may live on the CPU: testable without a GPU) and its
     ctypes struct, which borrows their memory.

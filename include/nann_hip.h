@@ -1392,6 +1392,17 @@ int nann_sharded_topk_workspace_bytes(int32_t world, int64_t n_queries, int32_t 
 int nann_sharded_topk(nann_comm* c, const float* scores, const int64_t* ids, const int32_t* status,
                       int64_t n_queries, int32_t k_in, int32_t k_out, void* workspace,
                       int64_t workspace_bytes, float* out_scores, int64_t* out_ids, nann_stream_t stream);
+/* The merge step of nann_sharded_topk on its own, for a host whose transport is not RCCL (MPI, sockets, a gather of its own):
+ * recv (device) holds `world` records, record s at recv + s * record_bytes, each laid out as nann_sharded_topk packs it --
+ * scores f32[n_queries, k_in], then at byte n_queries * k_in * 4 the ids i64[n_queries, k_in]; a query that failed on the
+ * shard carries (-inf, 0).  record_bytes: a multiple of 4, at least nann_sharded_topk_workspace_bytes(1, ...) / 2 (the record
+ * padded to 256 bytes, which is the stride nann_sharded_topk gathers with), else NANN_ERR_CAPACITY.  Same kernel, same order
+ * and same limits as nann_sharded_topk (k_out in [0, 1024], k_out <= world * k_in <= 16384); n_queries == 0 or k_out == 0 does
+ * nothing.  Asynchronous on `stream`.  Held, like nann_sharded_topk, nann_merge_topk and nann_topk with k > 1024, to the plain
+ * model of tests/merge_model.py on the cases of tests/merge_cases.py, records of shards that differ among them
+ * (tests/test_merge_gpu.py; tests/test_merge_model_cpu.py shows on the host that those cases tell a wrong merge from a right one). */
+int nann_merge_records(const void* recv, int64_t record_bytes, int32_t world, int64_t n_queries, int32_t k_in, int32_t k_out,
+                       float* out_scores, int64_t* out_ids, nann_stream_t stream);
 
 /* ---- 8(f1): HNSW index construction on the device -------------------------------------------------
  * What the reference does on the host with faiss.IndexHNSWFlat(d, M).add(embeddings)

@@ -129,6 +129,28 @@ __global__ __launch_bounds__(256) void k_loopback_wait(unsigned int us) {
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(64);
 }
 
+// what a merge of `world` lists of k_in takes (nann_sharded_topk, nann_merge_records)
+static int check_merge_shape(int world, int k_in, int k_out) {
+  const long long n_in = (long long)world * k_in;
+  if (k_out < 0 || k_out > kMaxK) return fail(NANN_ERR_UNSUPPORTED, "k_out must be in [0, 1024]");
+  if (n_in < k_out) return fail(NANN_ERR_TOPK_K_GT_N, "fewer candidates than k_out");
+  if (n_in > kTopkEPT * kNT) return fail(NANN_ERR_UNSUPPORTED, "world * k_in > 16384");
+  return NANN_OK;
+}
+
+// the one launch of k_merge_records: world * k_in scores of a query in dynamic LDS (beyond 48 KB: opted in)
+static int launch_merge_records(const unsigned char* recv, size_t stride, int world, long long n_queries, int k_in, int k_out,
+                                float* out_scores, int64_t* out_ids, hipStream_t st) {
+  const size_t lds = (size_t)world * k_in * 4;
+  if (lds > 48 * 1024)
+    NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_records),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_merge_records, dim3((unsigned)n_queries), dim3(kNT), lds, st, recv, (unsigned long long)stride,
+                     world, n_queries, k_in, k_out, out_scores, out_ids);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
 struct nann_comm {
   ncclComm_t comm = nullptr;
   int world = 1, rank = 0;
@@ -253,10 +275,10 @@ int nann_sharded_topk(nann_comm* c, const float* scores, const int64_t* ids, con
     if (rc) return rc;
   }
   const int world = c->world;
-  const long long n_in = (long long)world * k_in;
-  if (k_out < 0 || k_out > kMaxK) return fail(NANN_ERR_UNSUPPORTED, "k_out must be in [0, 1024]");
-  if (n_in < k_out) return fail(NANN_ERR_TOPK_K_GT_N, "fewer candidates than k_out");
-  if (n_in > kTopkEPT * kNT) return fail(NANN_ERR_UNSUPPORTED, "world * k_in > 16384");
+  {
+    const int rc = check_merge_shape(world, k_in, k_out);
+    if (rc) return rc;
+  }
   if (n_queries <= 0 || k_out == 0) return NANN_OK;
   const size_t rb = rec_bytes(n_queries, k_in);
   if (!workspace || workspace_bytes < (int64_t)(rb * (size_t)(world + 1)))
@@ -281,18 +303,31 @@ int nann_sharded_topk(nann_comm* c, const float* scores, const int64_t* ids, con
     return fail(NANN_ERR_BAD_ARGUMENT, "nann_sharded_topk: communicator without RCCL state");
   }
   if (c->timing) NANN_HIP_TRY(hipEventRecord(c->ev[2], st));
-  const size_t lds = (size_t)n_in * 4;
-  if (lds > 48 * 1024)
-    NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_records),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_merge_records, dim3((unsigned)n_queries), dim3(kNT), lds, st, recv, (unsigned long long)rb,
-                     world, (long long)n_queries, (int)k_in, (int)k_out, out_scores, out_ids);
-  NANN_HIP_TRY(hipGetLastError());
+  {
+    const int rc = launch_merge_records(recv, rb, world, n_queries, k_in, k_out, out_scores, out_ids, st);
+    if (rc) return rc;
+  }
   if (c->timing) { NANN_HIP_TRY(hipEventRecord(c->ev[3], st)); c->timed_once = true; }
   if (!c->done_ev) NANN_HIP_TRY(hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming));
   NANN_HIP_TRY(hipEventRecord(c->done_ev, st));
   c->exchanged = true;
   return NANN_OK;
+}
+
+int nann_merge_records(const void* recv, int64_t record_bytes, int32_t world, int64_t n_queries, int32_t k_in, int32_t k_out,
+                       float* out_scores, int64_t* out_ids, nann_stream_t stream) {
+  if (!recv || !out_scores || !out_ids) return fail(NANN_ERR_BAD_ARGUMENT, "nann_merge_records: null argument");
+  if (world < 1 || k_in < 0 || n_queries < 0) return fail(NANN_ERR_BAD_ARGUMENT, "nann_merge_records: bad argument");
+  {
+    const int rc = check_merge_shape(world, k_in, k_out);
+    if (rc) return rc;
+  }
+  if (n_queries == 0 || k_out == 0) return NANN_OK;
+  if (record_bytes < (int64_t)rec_bytes(n_queries, k_in))
+    return fail(NANN_ERR_CAPACITY, "record_bytes smaller than one rank's record (nann_sharded_topk_workspace_bytes(1, ...) / 2)");
+  if (record_bytes & 3) return fail(NANN_ERR_BAD_ARGUMENT, "nann_merge_records: record_bytes must be a multiple of 4");
+  return launch_merge_records(static_cast<const unsigned char*>(recv), (size_t)record_bytes, world, n_queries, k_in, k_out,
+                              out_scores, out_ids, reinterpret_cast<hipStream_t>(stream));
 }
 
 int nann_comm_abort(nann_comm* c) {

@@ -91,6 +91,20 @@ def merge_records_host(recv, n_queries, k_in, k_out):
     return merge_host(sc, ii, k_out)
 
 
+def merge_records_device(recv, n_queries, k_in, k_out):
+    """k_merge_records itself (nann_merge_records): recv uint8[world, record_bytes] on a GPU (rank-major, as an all-gather of
+    any transport leaves it; rows may be longer than the padded record) -> (scores f32[B, k_out], ids i64[B, k_out]) there,
+    the same bits as merge_records_host."""
+    assert recv.is_cuda and recv.dtype == torch.uint8 and recv.dim() == 2 and recv.stride(1) == 1
+    out_s = torch.empty((n_queries, k_out), dtype=torch.float32, device=recv.device)
+    out_i = torch.empty((n_queries, k_out), dtype=torch.int64, device=recv.device)
+    with torch.cuda.device(recv.device):
+        _check(lib().nann_merge_records(_ptr(recv), C.c_int64(recv.stride(0)), C.c_int32(recv.shape[0]), C.c_int64(n_queries),
+                                        C.c_int32(k_in), C.c_int32(k_out), _ptr(out_s), _ptr(out_i), _stream()),
+               "merge records")
+    return out_s, out_i
+
+
 class Comm:
     """nann_comm: the library's own RCCL communicator.  Collective: every rank constructs it.
     The 128-byte id travels from rank 0 through the existing torch.distributed group (any
@@ -254,13 +268,17 @@ class ShardedSearch:
                 t.record_stream(cs)  # the caching allocator must not hand these out again before the exchange read them
             return out
         if self.transport == "records":
-            # the device path's record layout and merge with host stand-ins for its kernels and a torch.distributed
-            # all-gather of the raw bytes (CPU tests of the N-rank flow: tests/test_shard_cpu.py)
+            # the device path's record layout with a torch.distributed all-gather of the raw bytes in the place of RCCL's.  A
+            # result on a GPU is merged there by the product's kernel (nann_merge_records: the N-rank flow on one GPU,
+            # tests/test_multi_gpu.py), one on the host by its stand-in (CPU tests: tests/test_shard_cpu.py)
             nq, k = result.scores.shape
             rec = torch.as_tensor(pack_record_host(result.scores.cpu().numpy(), result.item_ids.cpu().numpy(),
                                                    result.status.cpu().numpy() if result.status is not None else None))
             recv = torch.empty(self.world * rec.numel(), dtype=torch.uint8)
             dist.all_gather_into_tensor(recv, rec, group=self.group)
+            if result.scores.is_cuda:
+                s, i = merge_records_device(recv.view(self.world, rec.numel()).to(result.scores.device), nq, k, self.k)
+                return i, s
             s, i = merge_records_host(recv.view(self.world, rec.numel()).numpy(), nq, k, self.k)
             return torch.as_tensor(i), torch.as_tensor(s)
         scores = result.scores

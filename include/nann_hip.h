@@ -534,6 +534,9 @@ typedef struct {
   int32_t table;                 /* 1: a pre-projected table is read */
   float est_visited;             /* the planner's estimate of a level's visited ids (hash-set capacity: 16K / 32K slots) */
   float worst_visited;           /* the bound from the index's maximum degrees */
+  int32_t lean;                  /* 1: the main launch is the lean instantiation of the L2 / inner-product hash-set kernel, its
+                                  * phase timers off at compile time (a plain call: uniform level_topn, no phase_ticks, at most
+                                  * 2^20 items; NANN_LEAN_KERNEL=0 switches it off); results are the general kernel's bit for bit */
 } nann_search_plan;
 void nann_search_options_init(nann_search_options* o);
 /* nann_search_v + phase_ticks (uniform level_topn only) + options + plan.  level_topn == NULL: level_topn_max for all. */

@@ -95,7 +95,7 @@ class SearchPlan(C.Structure):
     """nann_search_plan: what the planner chose for a call"""
     _fields_ = [("visited_set", C.c_int32), ("fallback_visited_set", C.c_int32), ("threads", C.c_int32),
                 ("workgroups", C.c_int32), ("phased", C.c_int32), ("table", C.c_int32),
-                ("est_visited", C.c_float), ("worst_visited", C.c_float)]
+                ("est_visited", C.c_float), ("worst_visited", C.c_float), ("lean", C.c_int32)]
 
 
 class Filter(C.Structure):

@@ -31,25 +31,33 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 # one kernel that clusters a behaviour sequence, with its entry point) ride in nann_cand.o too, the quickest object to rebuild.  The inner-product
 # traversal (nann_ip_inst.hip: the L2 file's four plans with the other scorer, as heavy as an L2 object per row dtype) rides in the
 # three LIGHTEST objects, one dtype each -- f16 with the filter kernels, bf16 with the attention candidate scorer, f32 with the
-# attention scan -- not in the nann_l2_* objects that bound a build from scratch.
-UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_flat.hip", {}), ("nann_traverse.hip", {}), ("nann_comm.hip", {}), ("nann_hnsw_build.hip", {})]),
+# attention scan -- not in the nann_l2_* objects that bound a build from scratch.  The lean instantiations of the L2 and the inner-product
+# hash-set kernels (nann_lean_inst.hip: two plans per (scorer, row dtype), half an L2 object each) ride in the six objects that were
+# the quickest to build -- two in nann_cand.o, one each in nann_scan.o, nann_core.o, nann_mlp_d128.o and nann_attn_split.o -- so that
+# none of them outlasts the evaluation objects, which bound a build from scratch.
+def _lean(scorer, dt, name):
+    return ("nann_lean_inst.hip", {"NANN_LEAN_SC": scorer, "NANN_LEAN_DT": dt, "NANN_LEAN_NAME": name})
+
+
+UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_flat.hip", {}), ("nann_traverse.hip", {}), ("nann_comm.hip", {}), ("nann_hnsw_build.hip", {}),
+                          _lean("kScorerIp", "1", "ip_bf16")]),
          ("nann_l2_f16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "0", "NANN_L2_NAME": "f16"})]),
          ("nann_l2_bf16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "1", "NANN_L2_NAME": "bf16"})]),
          ("nann_l2_f32.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "2", "NANN_L2_NAME": "f32"})]),
          ("nann_mlp_d64_res.o", [("nann_mlp_inst.hip", {"NANN_MLP_D": "64"}), ("nann_mlp_res_inst.hip", {})]),
-         ("nann_mlp_d128.o", [("nann_mlp_inst.hip", {"NANN_MLP_D": "128"})]),
+         ("nann_mlp_d128.o", [("nann_mlp_inst.hip", {"NANN_MLP_D": "128"}), _lean("NANN_SCORER_L2", "2", "l2_f32")]),
          ("nann_mlp_d256.o", [("nann_mlp_inst.hip", {"NANN_MLP_D": "256"})]),
          ("nann_attn.o", [("nann_attn_inst.hip", {})]),
-         ("nann_attn_split.o", [("nann_attn_split_inst.hip", {})]),
+         ("nann_attn_split.o", [("nann_attn_split_inst.hip", {}), _lean("kScorerIp", "2", "ip_f32")]),
          ("nann_eval.o", [("nann_eval_inst.hip", {})]),
          ("nann_eval_lds.o", [("nann_eval_lds_inst.hip", {})]),
          ("nann_eval_win.o", [("nann_eval_win_inst.hip", {})]),
-         ("nann_scan.o", [("nann_scan_inst.hip", {})]),
+         ("nann_scan.o", [("nann_scan_inst.hip", {}), _lean("NANN_SCORER_L2", "1", "l2_bf16")]),
          ("nann_scan_attn.o", [("nann_scan_attn_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "2", "NANN_IP_NAME": "f32"})]),
          ("nann_filter.o", [("nann_filter_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "0", "NANN_IP_NAME": "f16"})]),
-         ("nann_cand.o", [("nann_cand_inst.hip", {})]),
+         ("nann_cand.o", [("nann_cand_inst.hip", {}), _lean("NANN_SCORER_L2", "0", "l2_f16"), _lean("kScorerIp", "0", "ip_f16")]),
          ("nann_cand_attn.o", [("nann_cand_attn_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "1", "NANN_IP_NAME": "bf16"})])]
-DEPS = ["nann_hip.hip", "nann_flat.hip", "nann_traverse.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_ip_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_range.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_groupcap.h", "nann_predicate.h", "nann_filter_inst.hip", "nann_cand.h", "nann_union.h", "nann_fuse.h", "nann_mmr.h", "nann_interests.h", "nann_cand_inst.hip", "nann_cand_attn_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
+DEPS = ["nann_hip.hip", "nann_flat.hip", "nann_traverse.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_ip_inst.hip", "nann_lean_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_range.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_groupcap.h", "nann_predicate.h", "nann_filter_inst.hip", "nann_cand.h", "nann_union.h", "nann_fuse.h", "nann_mmr.h", "nann_interests.h", "nann_cand_inst.hip", "nann_cand_attn_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
         "nann_attn.h", "nann_attn_kernels.h", "nann_search.h", "nann_order.h", "nann_order_kernels.h", os.path.join("host", "nann_graphdef.h"), os.path.join("host", "nann_graphdef_text.h"), os.path.join("host", "nann_blaze_options.h"), os.path.join("host", "nann_npy.h"), os.path.join("host", "nann_projcache.h"),
         os.path.join("..", "..", "include", "nann_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-fast-math", "-ffp-contract=off"]
@@ -132,6 +140,8 @@ RULES = [
     # The inner-product twin of the hash-set kernel (k_search<.., VIS=2, SC=12 (kScorerIp), 512>, nann_ip_inst.hip): the same two
     # workgroups per CU, lost the same way.
     ("ip_occupancy", r"k_searchILi\d+ELi\d+ELi2ELi12ELi512E", None, 4, "the inner-product hash-set kernel"),
+    # The lean instantiations of both (k_search_lean<.., VIS=2, SC, 512>, nann_lean_inst.hip): what a plain call launches.
+    ("lean_occupancy", r"k_search_leanILi\d+ELi\d+ELi2ELi(0|12)ELi512E", None, 4, "the lean hash-set kernel"),
     # The inner-product scan (k_scan_ip, nann_scan.h) stages the table as k_scan_l2 does and is held to the same.
     ("scan_ip_scratch", r"k_scan_ip", 0, None, "the inner-product scan kernel"),
 ]

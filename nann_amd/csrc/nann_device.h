@@ -119,7 +119,10 @@ enum { PH_ZERO = 0, PH_WALK, PH_EXPAND, PH_SCORE, PH_TOPK, PH_OTHER,
        PH_TK_LOAD, PH_TK_SEARCH, PH_TK_COLLECT, PH_TK_SORT, PH_EX_PASS1, PH_EX_LOOP, PH_EX_WALKBUSY,
        PH_EX_LOOKUP, PH_EX_LOAD, PH_EX_INSERT, PH_EX_BARA, PH_EX_CHECK, PH_EX_RANK,  // hash-set expand, per piece
        PH_COUNT };
-struct PhaseTimer {
+// TIMED = false: the timer of the lean kernels -- no members, every call a no-op, so no mark costs a mask test, a branch or a
+// register (the general kernels switch theirs at run time with `on`).
+template <bool TIMED>
+struct PhaseTimerT {
   long long* ticks;  // LDS, [PH_COUNT]
   long long last;
   bool on;
@@ -144,11 +147,32 @@ struct PhaseTimer {
   }
   __device__ __forceinline__ long long now() const { return on ? (long long)clock64() : 0; }
 };
+template <>
+struct PhaseTimerT<false> {
+  __device__ __forceinline__ void start(long long*, bool) {}
+  __device__ __forceinline__ void mark(int) {}
+  __device__ __forceinline__ void sub(int, long long&) {}
+  __device__ __forceinline__ long long now() const { return 0; }
+};
+typedef PhaseTimerT<true> PhaseTimer;
 // The view of the timer the building blocks take BY VALUE (a pointer to the PhaseTimer object,
 // nullable, kept it in scratch memory: every mark cost a scratch load even with timing off).
-struct SubTimer {
+template <bool TIMED>
+struct SubTimerT;
+template <>
+struct SubTimerT<false> {  // what no_timer() returns: off at compile time
+  static constexpr bool on = false;
+  __device__ __forceinline__ SubTimerT() {}
+  __device__ __forceinline__ SubTimerT(long long*, bool) {}
+  __device__ __forceinline__ long long now() const { return 0; }
+  __device__ __forceinline__ void sub(int, long long&) const {}
+};
+template <>
+struct SubTimerT<true> {
   long long* ticks;
   bool on;
+  __device__ __forceinline__ SubTimerT(long long* t, bool enable) : ticks(t), on(enable) {}
+  __device__ __forceinline__ SubTimerT(SubTimerT<false>) : ticks(nullptr), on(false) {}  // (`cond ? no_timer() : pt`)
   __device__ __forceinline__ long long now() const { return on ? (long long)clock64() : 0; }
   __device__ __forceinline__ void sub(int phase, long long& t0) const {
     if (on && threadIdx.x == 0) {
@@ -158,7 +182,8 @@ struct SubTimer {
     }
   }
 };
-__device__ __forceinline__ SubTimer no_timer() { return SubTimer{nullptr, false}; }
+typedef SubTimerT<true> SubTimer;
+__device__ __forceinline__ SubTimerT<false> no_timer() { return SubTimerT<false>(); }
 
 // ---------------------------------------------------------------------------
 // scalar conversions (exact)
@@ -446,13 +471,13 @@ __device__ __forceinline__ int wg_filter_chunk(ExpandWalkScratch* S, int n_c, ui
 }
 
 
-template <bool kLdsBm, int NT = kNT>
+template <bool kLdsBm, int NT = kNT, bool TIMED = false>
 __device__ __forceinline__ int wg_expand_walk(const int32_t* frontier, int n_frontier,
                                               const int32_t* __restrict__ values,
                                               const int64_t* __restrict__ row_splits,
                                               uint32_t n_items, uint32_t* bm, int32_t* out,
                                               unsigned char* scratch, int* gathered,
-                                              SubTimer pt = no_timer()) {
+                                              SubTimerT<TIMED> pt = SubTimerT<TIMED>()) {
   ExpandWalkScratch* S = reinterpret_cast<ExpandWalkScratch*>(scratch);
   long long tsub = pt.now();
   const int tid = local_tid(), lane = tid & 63, wave = tid >> 6;
@@ -744,12 +769,12 @@ __device__ __forceinline__ int wg_mark_hash(const int32_t* list, int n, uint32_t
 // All NT threads.  Contract as wg_expand_walk; vis_count (uniform, in/out) = ids in the set.
 // Returns ids kept (appended to out[0..)), -1 on an out-of-range id, -2 when the set could overflow
 // (or the round's list is longer than the start-bit mask).
-template <int NT, int SLOTS, bool TAG>
+template <int NT, int SLOTS, bool TAG, bool TIMED>
 __device__ __forceinline__ int wg_expand_hash_impl(const int32_t* frontier, int n_frontier,
                                               const int32_t* __restrict__ values,
                                               const int64_t* __restrict__ row_splits, uint32_t n_items,
                                               uint32_t* vis, int id_bits, int& vis_count, int32_t* out,
-                                              unsigned char* scratch, int* gathered, SubTimer pt) {
+                                              unsigned char* scratch, int* gathered, SubTimerT<TIMED> pt) {
   using Scratch = ExpandHashScratch<NT, SLOTS>;
   constexpr int PER = Scratch::PER;
   constexpr int NWV = NT / 64;
@@ -964,12 +989,12 @@ __device__ __forceinline__ int wg_expand_hash_impl(const int32_t* frontier, int 
   return any_bad ? -1 : base;
 }
 
-template <int NT, int SLOTS>
+template <int NT, int SLOTS, bool TIMED>
 __device__ __forceinline__ int wg_expand_hash(const int32_t* frontier, int n_frontier,
                                               const int32_t* __restrict__ values,
                                               const int64_t* __restrict__ row_splits, uint32_t n_items,
                                               uint32_t* vis, int id_bits, int& vis_count, int32_t* out,
-                                              unsigned char* scratch, int* gathered, SubTimer pt) {
+                                              unsigned char* scratch, int* gathered, SubTimerT<TIMED> pt) {
   if (id_bits <= kVisDirectBits)  // uniform: entries hold the id (two loop bodies: the tag form costs configs[1] 2 %)
     return wg_expand_hash_impl<NT, SLOTS, false>(frontier, n_frontier, values, row_splits, n_items, vis, id_bits,
                                                  vis_count, out, scratch, gathered, pt);
@@ -1328,11 +1353,11 @@ static_assert(sizeof(ExpandWalkScratch) <= kPhaseScratch, "phase scratch too sma
 // NS = register slots per thread (n <= NS * kNT); NS == 0 re-reads keys from memory.
 // SCL = the first n scores are also in LDS (lds_scores); requires NS > 0.
 // BIN: rank the selected pairs bin by bin (TopkScratchT::bins)
-template <int NS, bool SCL, int NT, int KCAP = kMaxK, bool BIN = false>
+template <int NS, bool SCL, int NT, int KCAP = kMaxK, bool BIN = false, bool TIMED = false>
 __device__ __forceinline__ int wg_topk_impl(const int32_t* ids, const float* scores,
                                             const float* lds_scores, int n, int k, int32_t* out_pos,
                                             int32_t* out_ids, float* out_scores, const int64_t* id_map,
-                                            int64_t* out_mapped, unsigned char* scratch, SubTimer pt,
+                                            int64_t* out_mapped, unsigned char* scratch, SubTimerT<TIMED> pt,
                                             int n_all = 0x7fffffff, uint32_t floor_key = 0u) {
   // (BIN only) positions >= n_all take part only with a key above floor_key: a row that is a sorted list of >= k kept results
   // followed by candidates needs only the candidates that beat the worst kept result -- TopKV2 breaks ties towards the lower
@@ -1630,11 +1655,11 @@ __device__ __forceinline__ int wg_topk_impl(const int32_t* ids, const float* sco
 }
 
 // lds_scores != nullptr: the first n scores are mirrored in LDS (n <= kLdsScores)
-template <int NT = kNT, int KCAP = kMaxK, bool BIN = false>
+template <int NT = kNT, int KCAP = kMaxK, bool BIN = false, bool TIMED = false>
 __device__ __forceinline__ int wg_topk(const int32_t* ids, const float* scores, const float* lds_scores,
                                        int n, int k, int32_t* out_pos, int32_t* out_ids,
                                        float* out_scores, const int64_t* id_map, int64_t* out_mapped,
-                                       unsigned char* scratch, SubTimer pt = no_timer()) {
+                                       unsigned char* scratch, SubTimerT<TIMED> pt = SubTimerT<TIMED>()) {
   if (k < 0 || k > KCAP) return 7;  // NANN_ERR_BAD_ARGUMENT
   if (n < k) return 4;               // NANN_ERR_TOPK_K_GT_N, topk_op.cc:67-71
   if (k == 0) return 0;

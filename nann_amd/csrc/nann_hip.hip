@@ -745,7 +745,7 @@ typedef nann::ProjTableT<HipProjBackend> ProjTable;
 // Every knob of the planner is a field of nann_search_options (include/nann_hip.h, round 5); a field left at -1 takes the
 // PROCESS DEFAULT: what nann_set_traversal_mode / nann_set_search_reserve / nann_set_preprojection last stored, else the
 // environment read ONCE below (A/B tooling: NANN_PREPROJECT=0, NANN_SEARCH_SLOT_RESERVE=n, NANN_MLP_FORM=fused|phased,
-// NANN_PHASE_SMALL32=0, NANN_QUERY_ORDER=0), else the built-in value.  plan_search and the launchers only ever see the resolved struct.
+// NANN_PHASE_SMALL32=0, NANN_QUERY_ORDER=0, NANN_LEAN_KERNEL=0), else the built-in value.  plan_search and the launchers only ever see the resolved struct.
 struct SearchOpt {
   int mode;        // nann_traversal_mode
   int reserve;     // workgroup slots the persistent grids leave free
@@ -753,16 +753,18 @@ struct SearchOpt {
   int mlp_form;    // nann_mlp_form
   int small32;     // 1: at most one query per CU -> one 1024-thread workgroup per CU for the traversal (stages)
   int order;       // 1: L2 hash-set plans run a batch larger than their slots in locality order (nann_order.h)
+  int lean;        // 1: a plain L2 / inner-product call on a hash-set plan launches k_search_lean (nann_search.h)
 };
 static std::atomic<int> g_traversal_mode{-1}, g_slot_reserve{-1}, g_preproject{-1};
 static const SearchOpt& env_defaults() {
   static const SearchOpt d = [] {
-    SearchOpt o{NANN_TRAVERSAL_AUTO, 0, 1, NANN_MLP_FORM_AUTO, 1, 1};
+    SearchOpt o{NANN_TRAVERSAL_AUTO, 0, 1, NANN_MLP_FORM_AUTO, 1, 1, 1};
     if (const char* e = std::getenv("NANN_PREPROJECT")) o.preproject = !(e[0] == '0' && e[1] == 0);
     if (const char* e = std::getenv("NANN_SEARCH_SLOT_RESERVE")) o.reserve = std::max(0, std::atoi(e));
     if (const char* e = std::getenv("NANN_MLP_FORM")) o.mlp_form = std::string(e) == "fused" ? NANN_MLP_FORM_FUSED : std::string(e) == "phased" ? NANN_MLP_FORM_PHASED : NANN_MLP_FORM_AUTO;
     if (const char* e = std::getenv("NANN_PHASE_SMALL32")) o.small32 = !(e[0] == '0');
     if (const char* e = std::getenv("NANN_QUERY_ORDER")) o.order = !(e[0] == '0');
+    if (const char* e = std::getenv("NANN_LEAN_KERNEL")) o.lean = !(e[0] == '0');
     return o;
   }();
   return d;

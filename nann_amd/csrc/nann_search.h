@@ -233,7 +233,9 @@ constexpr int phase_scratch() {
   return base;
 }
 
-template <int LPR, int DT, int VIS, int SC, int NT>
+// LEAN: the instantiation a plain call takes (k_search_lean below): the phase timers are off at COMPILE time -- no mark is a
+// mask test and a branch, no clock value is held in registers -- and nothing else differs.  Every result is the general form's.
+template <int LPR, int DT, int VIS, int SC, int NT, bool LEAN = false>
 __device__ __forceinline__ int search_one(const SearchArgs& a, int qi, const SlotView& sv, uint32_t* bm,
                                           unsigned char* scratch, float* qv, int32_t* ctr,
                                           long long* ticks) {
@@ -259,9 +261,9 @@ __device__ __forceinline__ int search_one(const SearchArgs& a, int qi, const Slo
   // bitmap kernels, L2: candidate scores are mirrored in LDS for the selection; the MLP uses that
   // space for its weight slices (and its selection time is negligible next to the MFMAs)
   float* lds_scores = (is_flat(SC) && !HASH) ? reinterpret_cast<float*>(scratch + kLdsScoresOff) : nullptr;
-  PhaseTimer timer;
+  PhaseTimerT<!LEAN> timer;
   timer.start(ticks, a.phase_ticks != nullptr);
-  const SubTimer pt{ticks, a.phase_ticks != nullptr};
+  const SubTimerT<!LEAN> pt(ticks, a.phase_ticks != nullptr);
   auto mark = [&](int phase) { timer.mark(phase); };
 
   if constexpr (!is_attn(SC)) {
@@ -608,8 +610,9 @@ static_assert(offsetof(WsHeader, refined) == 136 && offsetof(WsHeader, pqueue) =
 // Second launch bound = waves per SIMD the register allocation must leave room for: the 16K-slot
 // hash-set kernel lives off TWO 512-thread workgroups per CU (16 waves = 4 per SIMD -> at most 128
 // VGPRs; at 130 the second workgroup silently stops fitting and the kernel runs at half occupancy).
-template <int LPR, int DT, int VIS, int SC, int NT>
-__global__ __launch_bounds__(NT, ((VIS == VIS_LDS_HASH && (is_flat(SC) || SC == kScorerMlpPhase)) ? 2 : 1) * NT / 256) void k_search(SearchArgs a) {
+// The body of k_search and of k_search_lean (LEAN: search_one).
+template <int LPR, int DT, int VIS, int SC, int NT, bool LEAN>
+__device__ __forceinline__ void search_queries(const SearchArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool HASH = VIS == VIS_LDS_HASH || VIS == VIS_LDS_HASH32;
   constexpr int kScratchBytes = phase_scratch<VIS, SC, NT>();
@@ -684,7 +687,7 @@ __global__ __launch_bounds__(NT, ((VIS == VIS_LDS_HASH && (is_flat(SC) || SC == 
     const int qi = misc[0];
     if (qi >= a.n_queries) break;
     if constexpr (PHASED) bind_slot((unsigned long long)qi);
-    const int st = search_one<LPR, DT, VIS, SC, NT>(a, qi, sv, bm, scratch, qv, s_ctr, s_ticks);
+    const int st = search_one<LPR, DT, VIS, SC, NT, LEAN>(a, qi, sv, bm, scratch, qv, s_ctr, s_ticks);
     __syncthreads();
     if constexpr (PHASED) {
       if (st == kPhaseSkip) continue;  // (finished by an earlier stage)
@@ -716,6 +719,19 @@ __global__ __launch_bounds__(NT, ((VIS == VIS_LDS_HASH && (is_flat(SC) || SC == 
   }
 }
 
+template <int LPR, int DT, int VIS, int SC, int NT>
+__global__ __launch_bounds__(NT, ((VIS == VIS_LDS_HASH && (is_flat(SC) || SC == kScorerMlpPhase)) ? 2 : 1) * NT / 256) void k_search(SearchArgs a) {
+  search_queries<LPR, DT, VIS, SC, NT, false>(a);
+}
+
+// The lean instantiation (nann_lean_inst.hip): flat scorers on the two hash-set plans, the main launch of a call that asks for no
+// phase ticks (lean_eligible below).  Same launch bounds as k_search.
+template <int LPR, int DT, int VIS, int SC, int NT>
+__global__ __launch_bounds__(NT, (VIS == VIS_LDS_HASH ? 2 : 1) * NT / 256) void k_search_lean(SearchArgs a) {
+  static_assert(is_flat(SC) && (VIS == VIS_LDS_HASH || VIS == VIS_LDS_HASH32), "lean: flat scorers, hash-set plans");
+  search_queries<LPR, DT, VIS, SC, NT, true>(a);
+}
+
 struct SearchPlan {
   int max_cand, max_raw, pool_cap;
   int vis;             // VIS_*
@@ -738,15 +754,22 @@ struct SearchPlan {
   float est_visited, worst_visited;  // the planner's estimate of a level's visited ids / the bound from max degrees
 };
 
-template <int LPR, int DT, int VIS, int SC, int NT>
-inline int launch_search_as(int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st) {
-  auto kern = k_search<LPR, DT, VIS, SC, NT>;
+template <int NT>
+inline int launch_search_kernel(void (*kern)(SearchArgs), int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st) {
   if (lds_bytes > 48 * 1024)
     NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
   hipLaunchKernelGGL(kern, dim3(slots), dim3(NT), lds_bytes, st, a);
   NANN_HIP_TRY(hipGetLastError());
   return NANN_OK;
+}
+template <int LPR, int DT, int VIS, int SC, int NT>
+inline int launch_search_as(int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st) {
+  return launch_search_kernel<NT>(k_search<LPR, DT, VIS, SC, NT>, slots, lds_bytes, a, st);
+}
+template <int LPR, int DT, int VIS, int SC, int NT>
+inline int launch_search_lean_as(int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st) {
+  return launch_search_kernel<NT>(k_search_lean<LPR, DT, VIS, SC, NT>, slots, lds_bytes, a, st);
 }
 
 // bitmap kernels (either residence) at NT threads
@@ -765,6 +788,21 @@ int launch_search_l2_f32(int lpr, int vis, int nt, int slots, size_t lds_bytes, 
 int launch_search_ip_f16(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
 int launch_search_ip_bf16(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
 int launch_search_ip_f32(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
+// the lean instantiations of both (k_search_lean) live in nann_lean_inst.hip, one per (scorer, row dtype), riding in light
+// objects: (vis, nt) in {(VIS_LDS_HASH, 512), (VIS_LDS_HASH32, 1024)}.  The caller checks lean_eligible() first.
+int launch_search_lean_l2_f16(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
+int launch_search_lean_l2_bf16(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
+int launch_search_lean_l2_f32(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
+int launch_search_lean_ip_f16(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
+int launch_search_lean_ip_bf16(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
+int launch_search_lean_ip_f32(int lpr, int vis, int nt, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
+// when k_search_lean stands in for k_search: a hash-set plan's main launch without a tick buffer (the kernel needs no more than
+// that; the scorer is the caller's to check) -- and, as measured so far, the plain call only: the launch's own level_topn on a
+// shard whose ids the set holds directly (compiling the tag form and a.tq out as well bought nothing measurable,
+// so both stayed in; whether the timers' gain carries over to those calls has not been measured)
+inline bool lean_eligible(int vis, const SearchArgs& a) {
+  return (vis == VIS_LDS_HASH || vis == VIS_LDS_HASH32) && !a.redo && !a.tq && !a.phase_ticks && a.id_bits <= kVisDirectBits;
+}
 // MLP instantiations live in nann_mlp_inst.hip (one object per embedding dim): bitmap kernels, 512 threads
 int launch_search_mlp_d64(int dt, int split, int vis, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);
 int launch_search_mlp_d128(int dt, int split, int vis, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st);

@@ -233,14 +233,24 @@ static int plan_search(const nann_index* ix, const int32_t t[6], int64_t n_queri
 
 // L2 instantiations live in nann_l2_inst.hip (one object per row dtype), MLP ones in
 // nann_mlp_inst.hip (one per embedding dim): the heavy kernels compile in parallel.
-// kind: nann_scorer_kind
+// kind: nann_scorer_kind.  lean: the caller found the launch eligible (takes_lean_kernel): k_search_lean instead of k_search.
 static int launch_search_any(int lpr, int dt, int kind, int split, int vis, int nt, int slots, size_t lds_bytes,
-                             const SearchArgs& a, hipStream_t st) {
+                             const SearchArgs& a, hipStream_t st, bool lean = false) {
   if (kind == NANN_SCORER_MLP) {
     if (lpr == 8) return launch_search_mlp_d64(dt, split, vis, slots, lds_bytes, a, st);
     if (lpr == 16) return launch_search_mlp_d128(dt, split, vis, slots, lds_bytes, a, st);
     if (lpr == 32) return launch_search_mlp_d256(dt, split, vis, slots, lds_bytes, a, st);
     return fail(NANN_ERR_UNSUPPORTED, "MLP scorer: d <= 256 only");
+  }
+  if (lean && kind == NANN_SCORER_IP) {
+    if (dt == NANN_F16) return launch_search_lean_ip_f16(lpr, vis, nt, slots, lds_bytes, a, st);
+    if (dt == NANN_BF16) return launch_search_lean_ip_bf16(lpr, vis, nt, slots, lds_bytes, a, st);
+    return launch_search_lean_ip_f32(lpr, vis, nt, slots, lds_bytes, a, st);
+  }
+  if (lean && kind == NANN_SCORER_L2) {
+    if (dt == NANN_F16) return launch_search_lean_l2_f16(lpr, vis, nt, slots, lds_bytes, a, st);
+    if (dt == NANN_BF16) return launch_search_lean_l2_bf16(lpr, vis, nt, slots, lds_bytes, a, st);
+    return launch_search_lean_l2_f32(lpr, vis, nt, slots, lds_bytes, a, st);
   }
   if (kind == NANN_SCORER_IP) {
     if (dt == NANN_F16) return launch_search_ip_f16(lpr, vis, nt, slots, lds_bytes, a, st);
@@ -251,6 +261,11 @@ static int launch_search_any(int lpr, int dt, int kind, int split, int vis, int 
   if (dt == NANN_F16) return launch_search_l2_f16(lpr, vis, nt, slots, lds_bytes, a, st);
   if (dt == NANN_BF16) return launch_search_l2_bf16(lpr, vis, nt, slots, lds_bytes, a, st);
   return launch_search_l2_f32(lpr, vis, nt, slots, lds_bytes, a, st);
+}
+// A plain call -- flat scorer, hash-set plan, the launch's own level_topn, no tick buffer, ids the set holds directly -- takes
+// the lean kernel for its main launch (NANN_LEAN_KERNEL=0: never); every other launch, the capacity rerun among them, the general one.
+static bool takes_lean_kernel(const SearchOpt& opt, int kind, int vis, const SearchArgs& a) {
+  return opt.lean && (kind == NANN_SCORER_L2 || kind == NANN_SCORER_IP) && lean_eligible(vis, a);
 }
 
 // ---- the two refusals every walk has (`who`: the call whose <who>_workspace_bytes() names the size) -------------------------
@@ -392,6 +407,7 @@ static int search_impl(const nann_index* ix, const ScoredBy& by, const float* q,
     plan_out->table = tab ? 1 : 0;
     plan_out->est_visited = p.est_visited;
     plan_out->worst_visited = p.worst_visited;
+    plan_out->lean = 0;  // (set where the launch is chosen, below)
   }
   const int64_t need_slots = p.phased ? std::max<int64_t>(std::min<int64_t>(n_queries, kPhaseChunk), p.fb_slots) : std::max(p.slots, p.fb_slots);
   // (against the plan this call runs, not the widest one nann_search_workspace_bytes sized for: a shorter workspace may do)
@@ -513,8 +529,10 @@ static int search_impl(const nann_index* ix, const ScoredBy& by, const float* q,
     return both([&](int vis, int, int slots, size_t lds) {
       return launch_search_mlp_res(exact, vis, slots, lds, a, st);
     });
+  if (plan_out) plan_out->lean = takes_lean_kernel(opt, scorer->desc.kind, p.vis, a) ? 1 : 0;
   return both([&](int vis, int nt, int slots, size_t lds) {
-    return launch_search_any(ix->desc.d / 8, dt, scorer->desc.kind, mlp_split, vis, nt, slots, lds, a, st);
+    return launch_search_any(ix->desc.d / 8, dt, scorer->desc.kind, mlp_split, vis, nt, slots, lds, a, st,
+                             takes_lean_kernel(opt, scorer->desc.kind, vis, a));
   });
 }
 

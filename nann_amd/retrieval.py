@@ -219,7 +219,8 @@ _VIS_NAMES = {v: k for k, v in TRAVERSAL_MODES.items()}
 def _plan_dict(p):
     return {"visited_set": _VIS_NAMES.get(p.visited_set, p.visited_set), "fallback_visited_set": _VIS_NAMES.get(p.fallback_visited_set),
             "threads": p.threads, "workgroups": p.workgroups, "phased": bool(p.phased), "table": bool(p.table),
-            "est_visited": round(float(p.est_visited), 1), "worst_visited": round(float(p.worst_visited), 1)}
+            "est_visited": round(float(p.est_visited), 1), "worst_visited": round(float(p.worst_visited), 1),
+            "lean": int(p.lean)}
 
 
 class Filter:

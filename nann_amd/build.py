@@ -9,38 +9,34 @@ OUT_DIR = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 # translation units: (object name, [(source, {macro: value} defined around its #include), ...]) -- compiled in parallel, then
 # linked.  A unit of several sources is compiled through a generated wrapper (_build/<obj>.d/unit.hip) that includes them
-# one after the other.  Round 5: 13 units -> 9: the three small host-facing files share one object, the
-# resident-layer-2 MLP kernels ride with the d = 64 MLP instances.  Round 6: 12 units -- the evaluation traversal's LDS forms are
-# units of their own, and the bf16 and f32 L2 instances are two again (their shared unit had become the longest: it alone bounded
-# a build from scratch at ~6 min on 8 cores).  The exhaustive search (nann_scan.h) is a unit of its own, the thirteenth; its scan
-# under the attention model (k_scan_attn), which instantiates the attention block scorers, the fourteenth.  The kernels of filtered
-# retrieval (nann_filter.h: two scatters and the compaction), which touch no search kernel, the fifteenth.  The candidate-list search
-# (nann_cand.h: the plan, its scorers over a ragged batch of row lists and the per-query top-k) the sixteenth; its scorer under the
-# attention model (k_cand_score_attn), which instantiates the attention block scorers once more, the seventeenth.  The host side of
-# the exhaustive and the candidate-list search (nann_flat.hip) is a source of nann_core.o, behind nann_hip.hip whose file-scope
-# types and helpers it uses; the host side of the traversal family (nann_traverse.hip: serving, filtered and evaluation traversal,
-# the index probe and the batch order) the next one, behind nann_flat.hip whose resolve_filter it uses.  The
-# selection kernels of the range search (nann_range.h: count, scan, splits, fill over a chunk's scores) are part of nann_scan.o,
-# included by nann_scan_inst.hip behind the scans whose score buffer they read.  The union top-k of a user's result lists
-# (nann_union.h: one kernel over wg_topk) is part of nann_cand.o, next to the other per-query selection.  The group cap
-# (nann_groupcap.h: one kernel of the shape of k_filter_compact) is part of nann_filter.o, included by nann_filter_inst.hip.  The MMR
-# re-ranking (nann_mmr.h: one kernel per (d, row dtype, metric) over the L2 / inner-product scorer) is part of nann_cand.o.  The attribute
-# predicates (nann_predicate.h: a scatter, a compaction and a count next to the filter's) are part of nann_filter.o as well.  The fused
-# top-k of a user's result lists (nann_fuse.h: one kernel, the union's table with an accumulator per row, over wg_topk) is part of
-# nann_cand.o, included by nann_cand_inst.hip behind the union whose constants it shares.  The user interests (nann_interests.h:
-# one kernel that clusters a behaviour sequence, with its entry point) ride in nann_cand.o too, the quickest object to rebuild.  The inner-product
-# traversal (nann_ip_inst.hip: the L2 file's four plans with the other scorer, as heavy as an L2 object per row dtype) rides in the
-# three LIGHTEST objects, one dtype each -- f16 with the filter kernels, bf16 with the attention candidate scorer, f32 with the
-# attention scan -- not in the nann_l2_* objects that bound a build from scratch.  The lean instantiations of the L2 and the inner-product
-# hash-set kernels (nann_lean_inst.hip: two plans per (scorer, row dtype), half an L2 object each) ride in the six objects that were
-# the quickest to build -- two in nann_cand.o, one each in nann_scan.o, nann_core.o, nann_mlp_d128.o and nann_attn_split.o -- so that
-# none of them outlasts the evaluation objects, which bound a build from scratch.
+# one after the other.  Seventeen objects:
+#   nann_core.o        the host side, one unit: the core of the C ABI (nann_hip.hip), the drop-in ops (nann_ops.hip), the scorers and
+#                      the model loader (nann_scorers.hip), the flat retrieval calls (nann_flat.hip), the traversal family
+#                      (nann_traverse.hip), the RCCL exchange (nann_comm.hip), the HNSW builder (nann_hnsw_build.hip).  Each
+#                      compiles on its own -- what they share is declared in nann_host.h --; their order here is the order
+#                      of the kernels in the object's metadata and nothing else
+#   nann_l2_*.o        the fused traversal under the L2 scorer, one object per row dtype (one object for all three was the
+#                      longest to build)
+#   nann_eval*.o       the evaluation traversal: slot form and attention model; LDS form; LDS form in windows.  These three
+#                      bound a build from scratch
+#   nann_mlp_d*.o      the MLP traversal per embedding dim; the resident-layer-2 kernels ride with d = 64
+#   nann_attn.o, nann_attn_split.o   the attention model, f32 and split-f16 form
+#   nann_scan.o        the exhaustive search, with the range selection (nann_range.h); nann_scan_attn.o its scan under the
+#                      attention model
+#   nann_filter.o      filtered retrieval, with the group cap (nann_groupcap.h) and the attribute predicates (nann_predicate.h)
+#   nann_cand.o        the candidate-list search, with the union and the fused top-k (nann_union.h, nann_fuse.h), the MMR
+#                      re-ranking (nann_mmr.h) and the user interests (nann_interests.h); nann_cand_attn.o its scorer under the
+#                      attention model
+# The inner-product traversal (nann_ip_inst.hip, as heavy as an L2 object per row dtype) rides in the three LIGHTEST objects,
+# one dtype each -- f16 in nann_filter.o, bf16 in nann_cand_attn.o, f32 in nann_scan_attn.o -- and the lean instantiations of
+# the L2 and inner-product hash-set kernels (nann_lean_inst.hip, half an L2 object each) in the six that were quickest to
+# build, so that no object outlasts the evaluation objects.
 def _lean(scorer, dt, name):
     return ("nann_lean_inst.hip", {"NANN_LEAN_SC": scorer, "NANN_LEAN_DT": dt, "NANN_LEAN_NAME": name})
 
 
-UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_flat.hip", {}), ("nann_traverse.hip", {}), ("nann_comm.hip", {}), ("nann_hnsw_build.hip", {}),
-                          _lean("kScorerIp", "1", "ip_bf16")]),
+UNITS = [("nann_core.o", [("nann_ops.hip", {}), ("nann_hip.hip", {}), ("nann_scorers.hip", {}), ("nann_flat.hip", {}), ("nann_traverse.hip", {}),
+                          ("nann_comm.hip", {}), ("nann_hnsw_build.hip", {}), _lean("kScorerIp", "1", "ip_bf16")]),
          ("nann_l2_f16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "0", "NANN_L2_NAME": "f16"})]),
          ("nann_l2_bf16.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "1", "NANN_L2_NAME": "bf16"})]),
          ("nann_l2_f32.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "2", "NANN_L2_NAME": "f32"})]),
@@ -57,9 +53,16 @@ UNITS = [("nann_core.o", [("nann_hip.hip", {}), ("nann_flat.hip", {}), ("nann_tr
          ("nann_filter.o", [("nann_filter_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "0", "NANN_IP_NAME": "f16"})]),
          ("nann_cand.o", [("nann_cand_inst.hip", {}), _lean("NANN_SCORER_L2", "0", "l2_f16"), _lean("kScorerIp", "0", "ip_f16")]),
          ("nann_cand_attn.o", [("nann_cand_attn_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "1", "NANN_IP_NAME": "bf16"})])]
-DEPS = ["nann_hip.hip", "nann_flat.hip", "nann_traverse.hip", "nann_mlp_inst.hip", "nann_mlp_res_inst.hip", "nann_mlp5.h", "nann_mlp6.h", "nann_l2_inst.hip", "nann_ip_inst.hip", "nann_lean_inst.hip", "nann_attn_inst.hip", "nann_attn_split_inst.hip", "nann_attn_split.h", "nann_attn_proj.h", "nann_eval_inst.hip", "nann_eval_lds_inst.hip", "nann_eval_win_inst.hip", "nann_eval.h", "nann_scan.h", "nann_range.h", "nann_scan_inst.hip", "nann_scan_attn_inst.hip", "nann_filter.h", "nann_groupcap.h", "nann_predicate.h", "nann_filter_inst.hip", "nann_cand.h", "nann_union.h", "nann_fuse.h", "nann_mmr.h", "nann_interests.h", "nann_cand_inst.hip", "nann_cand_attn_inst.hip", "nann_comm.hip", "nann_hnsw_build.hip", "nann_device.h", "nann_mlp.h", "nann_mlp2.h", "nann_mlp3.h",
-        "nann_attn.h", "nann_attn_kernels.h", "nann_search.h", "nann_order.h", "nann_order_kernels.h", os.path.join("host", "nann_graphdef.h"), os.path.join("host", "nann_graphdef_text.h"), os.path.join("host", "nann_blaze_options.h"), os.path.join("host", "nann_npy.h"), os.path.join("host", "nann_projcache.h"),
-        os.path.join("..", "..", "include", "nann_hip.h")]
+
+
+def _deps():
+    """Every file the library is built from: the .h and .hip of csrc/, the .h of csrc/host/, the public header."""
+    here = [f for f in os.listdir(SRC_DIR) if f.endswith((".h", ".hip"))]
+    host = [os.path.join("host", f) for f in os.listdir(os.path.join(SRC_DIR, "host")) if f.endswith(".h")]
+    return sorted(here + host) + [os.path.join("..", "..", "include", "nann_hip.h")]
+
+
+DEPS = _deps()
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-fast-math", "-ffp-contract=off"]
 
 

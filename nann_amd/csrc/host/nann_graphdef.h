@@ -18,7 +18,7 @@
 // left (Const | Identity | Reshape | Transpose | Mul | Add | AddV2 | Sub | Rsqrt), with the variable name as
 // the fallback.  Both the folded and the merely frozen form load.
 //
-// Host code, plain C++17, no HIP: included by nann_hip.hip (nann_model_load) and by the CPU test hook in
+// Host code, plain C++17, no HIP: included by nann_scorers.hip (nann_model_load) and by the CPU test hook in
 // host/nann_graphdef_c.cpp.
 #pragma once
 #include <cmath>

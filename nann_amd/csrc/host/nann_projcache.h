@@ -14,7 +14,7 @@
 //     caller runs the kernels that read the embedding rows.
 //
 // The logic is a template over the device API so that tests/test_projcache_cpu.py can hammer it from several threads
-// against a mock device that checks the invariants (libnann_host.so, nann_projcache_c.cpp); nann_hip.hip instantiates it
+// against a mock device that checks the invariants (libnann_host.so, nann_projcache_c.cpp); nann_host.h instantiates it
 // with HIP.  Backend:
 //   typedef Stream, Event;
 //   static bool malloc(void** p, size_t bytes);  static void free(void* p);

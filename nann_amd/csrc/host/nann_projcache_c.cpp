@@ -1,5 +1,5 @@
 // nann_projcache_c.cpp -- CPU-side stress hook for the pre-projected tables' lifecycle (nann_projcache.h), in
-// libnann_host.so: the SAME cache template nann_hip.hip instantiates with HIP, here against a mock device that checks
+// libnann_host.so: the SAME cache template nann_host.h instantiates with HIP, here against a mock device that checks
 // the invariants the round-3 cache broke (eviction could free a table another thread had already fetched
 // for a launch it had not made yet):
 //   * a table is never freed while a launch that reads it is in flight,

@@ -121,7 +121,7 @@ __device__ __forceinline__ CandItem cand_item(const CandQuery* __restrict__ plan
 
 }  // namespace nann
 
-#ifdef NANN_CAND_IMPL  // the kernels: nann_cand_inst.hip only (nann_hip.hip takes the declarations above)
+#ifdef NANN_CAND_IMPL  // the kernels: nann_cand_inst.hip only (nann_flat.hip takes the declarations above)
 namespace nann {
 
 constexpr int kCandNT = 256;  // threads of k_cand_plan and k_cand_score_l2

@@ -9,13 +9,10 @@
 // the MMR re-ranking on its own (nann_mmr_topk; kernel in nann_mmr.h) and behind the same search (nann_search_all_diverse,
 // nann_search_all_model_diverse); the attribute predicates on their own (nann_predicate_topk, nann_predicate_count; kernels in
 // nann_predicate.h) and inside the filtered exhaustive search (nann_search_all_where, nann_search_all_model_where).
-// resolve_predicates is defined here; the traversal's _where forms (nann_traverse.hip) use it too.
 //
-// Compiled into nann_core.o behind nann_hip.hip, as ONE translation unit with it (build.py writes the wrapper), on the terms
-// nann_comm.hip lives there: this file uses nann_hip.hip's file-scope types and helpers directly -- nann_index, nann_scorer,
-// nann_model, fail, device_info, as_stream, check_options / resolve_options, mlp_projection / attn_projection /
-// projection_used, ScoredBy / scored_by -- and no header stands between the two.  resolve_filter is defined here; the filtered
-// traversal (nann_traverse.hip, behind this file in the unit) uses it too.
+// A source of nann_core.o.  What it takes from the other host sources, and what the traversal's forms (nann_traverse.hip) take
+// from it -- resolve_filter, resolve_predicates, resolve_groups, resolve_diversity, mmr_index, union_check, fuse_shape_check,
+// fusion_check, fusion_into -- is declared in nann_host.h.
 //
 // Every entry point is one walk over the steps below, each written once:
 //   flat_by            who scores the call, from a nann_scorer or a nann_model: scored_by, and what the flat kernels take
@@ -31,6 +28,7 @@
 // The ORDER in which a call looks at its arguments is part of its contract -- with two faults present, which one the caller is
 // told -- and the families differ in it for no deeper reason than their history.  The walks keep every order as it was and say
 // where they branch for it (tests/test_flat_contract_gpu.py pins them).
+#include "nann_host.h"
 #include "nann_scan.h"
 #include "nann_cand.h"
 #include "nann_union.h"
@@ -46,7 +44,7 @@
 using namespace nann;
 
 // ---- who scores a call ---------------------------------------------------------------------------------------------------
-// ScoredBy (nann_hip.hip: the scorer or the attention scorer, mean_of, cache, what, mismatch), and what the flat kernels take
+// ScoredBy (nann_host.h: the scorer or the attention scorer, mean_of, cache, what, mismatch), and what the flat kernels take
 struct FlatBy : ScoredBy {
   int kind = NANN_SCORER_L2;     // the scorer's nann_scorer_kind, or kScanAttn for the attention model
   int exact = 0;                 // MLP / attention: the f32 form (also the MLP's certified precision), else split-f16
@@ -143,12 +141,12 @@ static int resolve_filter_rows(const nann_filter* f, long long n_items, FilterAr
   }
   return NANN_OK;
 }
-static int resolve_filter(const nann_filter* f, const nann_index* ix, FilterArgs* out) {
+int nann::resolve_filter(const nann_filter* f, const nann_index* ix, FilterArgs* out) {
   return resolve_filter_rows(f, (long long)ix->desc.n_items, out);
 }
 
 // the caller's nann_predicates as the kernels take it (nann_predicate.h); NULL holds no condition.  Touches nothing but the struct.
-static int resolve_predicates(const nann_predicates* p, PredArgs* out) {
+int nann::resolve_predicates(const nann_predicates* p, PredArgs* out) {
   *out = PredArgs{};
   if (!p) return NANN_OK;
   if (p->struct_bytes != 0 && p->struct_bytes != (int32_t)sizeof(nann_predicates)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_predicates: struct_bytes");
@@ -175,7 +173,7 @@ static int resolve_predicates(const nann_predicates* p, PredArgs* out) {
 }
 
 // the caller's nann_groups into the launch arguments of the cap (nann_groupcap.h).  `who`: the entry point in a message.
-static int resolve_groups(const nann_groups* g, const char* who, GroupCapArgs* a) {
+int nann::resolve_groups(const nann_groups* g, const char* who, GroupCapArgs* a) {
   if (!g) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null nann_groups");
   if (g->struct_bytes != 0 && g->struct_bytes != (int32_t)sizeof(nann_groups)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_groups: struct_bytes");
   if (!g->group_of_row) return fail(NANN_ERR_BAD_ARGUMENT, "nann_groups: group_of_row is null");
@@ -484,7 +482,7 @@ static int flat_cand(const nann_index* ix, const nann_scorer* scorer, const nann
 
 // ---- union top-k (nann_union.h): a user's n_lists result lists -> the k best distinct rows -----------------------------------
 // the shape of a union: n_in = n_lists * k_in entries per user.  `who`: the entry point in a message.
-static int union_check(int64_t n_users, int64_t n_lists, int64_t k_in, int64_t k, const char* who) {
+int nann::union_check(int64_t n_users, int64_t n_lists, int64_t k_in, int64_t k, const char* who) {
   if (n_users < 0 || n_lists < 0 || k_in < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": negative size");
   if (k < 0) return flat_bad_k((int32_t)k);
   if (k > n_lists * k_in) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k exceeds the n_lists * k_in entries a user brings");
@@ -560,14 +558,14 @@ static int flat_all_multi(const nann_index* ix, const nann_scorer* scorer, const
 
 // ---- fused top-k (nann_fuse.h): a user's n_lists result lists -> the k best distinct rows by an accumulated score -------------
 // the shape of a fuse: the union's refusals in their order, then the width of out_lists
-static int fuse_shape_check(int64_t n_users, int64_t n_lists, int64_t k_in, int64_t k, const char* who) {
+int nann::fuse_shape_check(int64_t n_users, int64_t n_lists, int64_t k_in, int64_t k, const char* who) {
   const int rc = union_check(n_users, n_lists, k_in, k, who);
   if (rc) return rc;
   if (n_lists > NANN_FUSE_MAX_LISTS) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": at most NANN_FUSE_MAX_LISTS = 64 lists per user");
   return NANN_OK;
 }
 // the caller's nann_fusion: null, struct_bytes, mode, rrf_c, weights_per_user, in this order.  Nothing of it is dereferenced.
-static int fusion_check(const nann_fusion* f, const char* who) {
+int nann::fusion_check(const nann_fusion* f, const char* who) {
   if (!f) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null fusion");
   if (f->struct_bytes != 0 && f->struct_bytes != (int32_t)sizeof(nann_fusion)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_fusion: struct_bytes");
   if (f->mode < NANN_FUSE_SUM || f->mode > NANN_FUSE_RRF) return fail(NANN_ERR_BAD_ARGUMENT, "nann_fusion: unknown mode");
@@ -576,7 +574,7 @@ static int fusion_check(const nann_fusion* f, const char* who) {
   if (f->weights_per_user != 0 && f->weights_per_user != 1) return fail(NANN_ERR_BAD_ARGUMENT, "nann_fusion: weights_per_user must be 0 or 1");
   return NANN_OK;
 }
-static void fusion_into(const nann_fusion* f, FuseArgs* a) {
+void nann::fusion_into(const nann_fusion* f, FuseArgs* a) {
   a->mode = f->mode;
   a->rrf_c = f->rrf_c;
   a->weights = f->weights;
@@ -725,7 +723,7 @@ static int flat_all_grouped(const nann_index* ix, const nann_scorer* scorer, con
 // ---- MMR re-ranking (nann_mmr.h) ---------------------------------------------------------------------------------------------
 // the caller's nann_diversity into the launch arguments: null, struct_bytes, sim, lambda, in this order.  `who`: the entry point
 // in a message.  Touches nothing but the struct.
-static int resolve_diversity(const nann_diversity* dv, const char* who, MmrArgs* a) {
+int nann::resolve_diversity(const nann_diversity* dv, const char* who, MmrArgs* a) {
   if (!dv) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null nann_diversity");
   if (dv->struct_bytes != 0 && dv->struct_bytes != (int32_t)sizeof(nann_diversity)) return fail(NANN_ERR_BAD_ARGUMENT, "nann_diversity: struct_bytes");
   if (dv->sim == NANN_SCORER_MLP) return fail(NANN_ERR_UNSUPPORTED, "nann_diversity: the similarity is NANN_SCORER_L2 or NANN_SCORER_IP, not a learned scorer");
@@ -737,7 +735,7 @@ static int resolve_diversity(const nann_diversity* dv, const char* who, MmrArgs*
   return NANN_OK;
 }
 // the index's fields the step reads; its d against the kernel's instances
-static int mmr_index(const nann_index* ix, const char* who, MmrArgs* a) {
+int nann::mmr_index(const nann_index* ix, const char* who, MmrArgs* a) {
   const int d = ix->desc.d;
   if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
   if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");

@@ -62,21 +62,11 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/nann_hip.h"
-#include "nann_device.h"
+#include "nann_host.h"
 
-namespace nann {
-int fail(int code, const std::string& msg);  // nann_hip.hip
-}
 using namespace nann;
 
 namespace {
-
-#define HB_TRY(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) return fail(NANN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int kHbWaves = 4;          // wavefronts (= nodes) per workgroup
 constexpr int kHbVisSlots = 4096;    // visited-set slots per wavefront (16 KB): ef_construction x degree ids at most, kept < 3/4 full
@@ -524,7 +514,7 @@ struct HbOwned {
 template <typename T>
 int dev_alloc(T** p, size_t n, HbOwned* owned) {
   void* q = nullptr;
-  HB_TRY(hipMalloc(&q, std::max<size_t>(n * sizeof(T), 16)));
+  HIP_TRY(hipMalloc(&q, std::max<size_t>(n * sizeof(T), 16)));
   owned->ptrs.push_back(q);
   *p = static_cast<T*>(q);
   return NANN_OK;
@@ -534,7 +524,7 @@ template <int LPR, int DT, int MT>
 int run_batch_level(const HbGraph& g, const HbBatch& b, hipStream_t st) {
   const unsigned blocks = (unsigned)((b.n + kHbWaves - 1) / kHbWaves);
   hipLaunchKernelGGL((k_hb_search<LPR, DT, MT>), dim3(blocks), dim3(kHbWaves * 64), 0, st, g, b);
-  HB_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return NANN_OK;
 }
 
@@ -545,10 +535,10 @@ int run_backlink(const HbGraph& g, int level, const uint32_t* dst, const uint32_
   const size_t lds = per_wave * kHbWaves;
   auto kern = k_hb_backlink<LPR, DT, MT>;
   if (lds > 48 * 1024)
-    HB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const unsigned blocks = (unsigned)((max_runs + kHbWaves - 1) / kHbWaves);
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(kHbWaves * 64), lds, st, g, level, dst, src, rf, rl, n_runs);
-  HB_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return NANN_OK;
 }
 
@@ -832,10 +822,10 @@ int run_repair(const HbRepair& r, hipStream_t st) {
   const size_t lds = ((size_t)kHbMaxCand * r.d * 2 + 1024) * kHbWaves;  // k_hb_backlink's budget
   auto kern = k_hb_repair<LPR, DT, MT>;
   if (lds > 48 * 1024)
-    HB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const unsigned blocks = (unsigned)((r.n_work + kHbWaves - 1) / kHbWaves);
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(kHbWaves * 64), lds, st, r);
-  HB_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return NANN_OK;
 }
 

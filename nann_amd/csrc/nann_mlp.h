@@ -41,13 +41,13 @@ struct MlpParams {  // device pointers
   const float* w3;
   int d, h1, h2;
   // split-f16 form (NANN_MLP_SPLIT_F16): the item half of W1 and all of W2, times 2^7, as f16 (hi, lo) planes
-  // packed on the host in MFMA A-fragment order (pack_split_weights in nann_hip.hip)
+  // packed on the host in MFMA A-fragment order (pack_split_weights in nann_scorers.hip)
   const uint4* p1;  // [h1/32 tiles][d/16 chunks][hi, lo][64 lanes] x 8 halves
   const uint4* p2;  // [h1/32 tiles][2 chunks][h2/32 tiles][hi, lo][64 lanes] x 8 halves
   // exact form with W2 resident in LDS (nann_mlp5.h): f32 A fragments of v_mfma_f32_32x32x2_f32, four chain steps per 16 bytes
   const float4* p2x;  // [h1/32 tiles][h2/32 tiles][4][64 lanes] x 4 floats
   // certified form (NANN_MLP_CERTIFIED, nann_mlp6.h): the filter's bound B = k1s sum_j |2^7 h1_j| cb[j] + k0
-  const float* cb;  // [h1] c_j = sum_m |W2_jm| |w3_m| max(1, |alpha2_m|), rounded up (nann_hip.hip certified_bound)
+  const float* cb;  // [h1] c_j = sum_m |W2_jm| |w3_m| max(1, |alpha2_m|), rounded up (nann_scorers.hip certified_bound)
   float k1s, k0;
 };
 

@@ -93,7 +93,7 @@ __device__ __forceinline__ void wg_mlp_res_leave(uint4* lds, const uint4* park, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// split-f16, W2 resident.  W2 = the scorer's p2 planes ([t][q][m][hi, lo][lane] uint4, nann_hip.hip pack_split_weights)
+// split-f16, W2 resident.  W2 = the scorer's p2 planes ([t][q][m][hi, lo][lane] uint4, nann_scorers.hip pack_split_weights)
 // in LDS; V staged by wg_mlp_res_vectors.  No barrier inside; every wavefront returns on its own.
 //
 // What the loop costs, in shader cycles per scored row of the workgroup (timing builds r4b / r4c, normalised by the rows

@@ -92,7 +92,7 @@ struct PhaseScoreArgs {
 //   |s~ - s| <= K1 sum_j |h_j| c_j + K0,  c_j = sum_m w_jm |w3_m| M_m,
 //     K1 = a1 + [3u(1 + u) + gamma_129 (1 + 3u(1 + u))](1 + gamma_257 + a1) + [u + gamma_129 (1 + u)](1 + gamma_257)
 //     K0 = K1 sum_m |w3_m| M_m |b2_m| + 2 zeta sum_j c_j
-// (about 1.03e-3 per unit of sum_j |h_j| c_j).  The host (certified_bound, nann_hip.hip) evaluates it in double and stores
+// (about 1.03e-3 per unit of sum_j |h_j| c_j).  The host (certified_bound, nann_scorers.hip) evaluates it in double and stores
 // K1 2^-7 (the kernel sums |2^7 h_j|), K0 and c_j rounded up, with 1e-3 of margin for the f32 evaluation of B; the kernel
 // then widens B by 2^-20 (|s~| + B) so that s~ -/+ B stay bounds after their own rounding.  Overflow anywhere -- h1 beyond
 // f16, W2 beyond f16 (|w| > 511), b2 or alpha2 large enough that an f32 value of the exact form overflows (the filter's

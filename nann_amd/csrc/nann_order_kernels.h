@@ -1,4 +1,4 @@
-// The kernels of the batch order (nann_order.h): compiled into the core object only (nann_hip.hip).
+// The kernels of the batch order (nann_order.h): compiled into the core object only (nann_traverse.hip).
 #pragma once
 #include "nann_order.h"
 

@@ -82,7 +82,7 @@ int launch_scan_attn(const ScanArgs& a, const float* kt, const float* upad, int 
 
 }  // namespace nann
 
-#ifdef NANN_SCAN_IMPL  // the kernels: nann_scan_inst.hip only (nann_hip.hip takes the declarations above)
+#ifdef NANN_SCAN_IMPL  // the kernels: nann_scan_inst.hip only (nann_flat.hip takes the declarations above)
 namespace nann {
 
 constexpr int kScanRows = 256;          // rows per workgroup of k_scan_l2 = its threads

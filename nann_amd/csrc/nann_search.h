@@ -1,5 +1,5 @@
 // nann_search.h -- the fused traversal kernel (build_opt_graph.py:109-149) and its launch
-// helper, shared by the translation units that instantiate it (nann_hip.hip: L2 scorer;
+// helper, shared by the translation units that instantiate it (nann_l2_inst.hip: L2 scorer;
 // nann_mlp_inst.hip: MLP scorer, one object per embedding dim so they compile in parallel).
 #pragma once
 #ifndef NANN_REPEAT_SCORE
@@ -36,7 +36,7 @@ struct OpResult {
 };
 
 
-int fail(int code, const std::string& msg);  // sets nann_last_error(); defined in nann_hip.hip
+int fail(int code, const std::string& msg);  // sets nann_last_error(); defined in nann_hip.hip; what else the host sources share: nann_host.h
 
 #define NANN_HIP_TRY(expr)                                                                 \
   do {                                                                                     \

@@ -5,13 +5,11 @@
 // kernels in nann_search.h), the evaluation traversal (nann_search_eval, nann_search_eval_ex, nann_search_eval_model; nann_eval.h), each
 // with its *_workspace_bytes, and what nann_index_create measures for them: the probe and the pivots of the batch order.
 //
-// Compiled into nann_core.o behind nann_hip.hip and nann_flat.hip, as ONE translation unit with them (build.py writes the
-// wrapper), on the terms nann_flat.hip lives there: this file uses nann_hip.hip's file-scope types and helpers directly and
-// nann_flat.hip's resolve_filter and resolve_predicates, and no header stands between them.  nann_index_create calls probe_index and choose_pivots
-// through declarations.
+// A source of nann_core.o.  What it takes from the other host sources (nann_flat.hip's resolve_* and shape checks among it), and
+// what they take from it -- probe_index and choose_pivots for nann_index_create, launch_order -- is declared in nann_host.h.
 //
 // Every entry point is one walk -- traverse, traverse_filtered around it, evaluate -- over the steps below, each written once:
-//   scored_by (nann_hip.hip)  who scores the call.  The flat family's too: FlatBy derives from ScoredBy; flat_by adds what only
+//   scored_by (nann_host.h)   who scores the call.  The flat family's too: FlatBy derives from ScoredBy; flat_by adds what only
 //                      its kernels take, and keeps its own refusals (a null handle, an unknown kind) where the flat calls pin them
 //   slots_bytes, traverse_bytes, eval_bytes   the layout of a workspace, [header | slots | tail | batch order] [staged model
 //                      query] [filter staging]: every *_workspace_bytes, workspace check and carve-off takes its number from it
@@ -23,7 +21,7 @@
 // The ORDER in which a call looks at its arguments is part of its contract -- with two faults present, which one the caller is
 // told -- and the scorer and the model forms differ in it for no deeper reason than their history.  The walks keep every order
 // as it was and say where they branch for it (tests/test_traverse_contract_gpu.py pins them).
-#include "nann_search.h"
+#include "nann_host.h"
 #include "nann_eval.h"
 #include "nann_order_kernels.h"
 #include "nann_filter.h"
@@ -565,7 +563,7 @@ __global__ void k_order_gather(const void* emb, int dt, int d, const int32_t* ro
 
 // key and order kernels on `st`: key[n] (scratch), perm[n], the segment heads and the workspace header zeroed
 static_assert(sizeof(WsHeader) <= kOrderHeaderWords * 4 && kOrderHeaderWords * 4 == 256, "k_order_perm clears the header");
-static int launch_order(const nann_index* ix, const float* q, int n, int32_t* key, int32_t* perm, unsigned int* heads,
+int nann::launch_order(const nann_index* ix, const float* q, int n, int32_t* key, int32_t* perm, unsigned int* heads,
                         unsigned int* header, hipStream_t st) {
   const int d = ix->desc.d, P = ix->n_pivots;
   const size_t lds = ((size_t)d * P + kOrderMaxPivots + (size_t)kOrderKeyQueries * d) * 4;
@@ -579,7 +577,7 @@ static int launch_order(const nann_index* ix, const float* q, int n, int32_t* ke
   return NANN_OK;
 }
 
-static void choose_pivots(nann_index* ix, const std::vector<int32_t>& enter) {
+void nann::choose_pivots(nann_index* ix, const std::vector<int32_t>& enter) {
   const int d = ix->desc.d;
   const int P = order_pivots((int64_t)enter.size(), d);
   if (P < 2) return;
@@ -633,7 +631,7 @@ static void choose_pivots(nann_index* ix, const std::vector<int32_t>& enter) {
   ix->n_pivots = (int)piv.size();
 }
 
-static void probe_index(nann_index* ix) {
+void nann::probe_index(nann_index* ix) {
   ix->probe_valid = false;
   // opt-out: NANN_INDEX_PROBE=0 -- the planner then falls back to its degree-based guess.  The probe allocates,
   // launches on the NULL stream and copies back with blocking copies: it SYNCHRONISES the device (include/nann_hip.h says so).

@@ -39,7 +39,7 @@ def test_weights_directory_spelling(tmp_path):
     ops.save_scorer_dir(str(tmp_path), "mlp", synth.make_mlp_weights(64), precision="certified")
     assert open(tmp_path / "precision.txt").read().split() == ["certified"]
     assert open(tmp_path / "scorer.txt").read().split() == ["mlp"]
-    src = open(os.path.join(ROOT, "nann_amd", "csrc", "nann_hip.hip")).read()
+    src = open(os.path.join(ROOT, "nann_amd", "csrc", "nann_scorers.hip")).read()
     # both weights-directory forms (precision.txt, <graph>.precision) read the word
     assert src.count('prec == "certified"') == 2
 

@@ -1301,6 +1301,47 @@ int nann_search_all_multi_fused(const nann_index* ix, const nann_scorer* scorer,
                                 int32_t* out_index, uint64_t* out_lists, int32_t* n_out, void* workspace,
                                 int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream);
 
+/* ---- scalar-quantised exhaustive search: an int8 code table, a wide approximate fetch on the integer matrix cores, an exact
+ * re-rank.  Added to ABI version 6: new symbols only.
+ * The code of a vector x (a row widened exactly from its 16 bits, or a query's f32 vector), every step ONE IEEE f32 operation,
+ * round to nearest:  amax = max_j |x_j|;  scale = amax / 127.0f;  code_j = clamp(rintf(x_j / scale), -127, 127), and scale = 0
+ * with every code 0 where amax == 0;  norm = sum_j code_j^2 (i32).  Non-finite inputs are outside the contract.
+ * The approximate score of a query (cq, sq, nq) against a row (cx, sx, nx), with the exact integer D = sum_j cq_j cx_j:
+ *   NANN_SCORER_IP   s = (sq * sx) * (float)D
+ *   NANN_SCORER_L2   a = (sq * sq) * (float)nq,  b = (sx * sx) * (float)nx,  c = ((2 * sq) * sx) * (float)D,  s = c - (a + b)
+ * every product, sum and difference one f32 operation; the conversions are exact (|D|, norms <= 127^2 * 512 < 2^24).
+ *
+ * A nann_sq8 holds codes i8[n_items, d], scales f32[n_items] and norms i32[n_items] of an index's rows in device memory.  It
+ * BORROWS the index: the index must outlive it, and a table made before the index's rows were refreshed in place is STALE --
+ * re-create it.  The index's rows are f16 or bf16 and d is 64, 128, 256 or 512; an f32-row index -> NANN_ERR_UNSUPPORTED.
+ * nann_sq8_create encodes asynchronously on `stream`; nann_sq8_destroy(NULL) is a no-op.
+ * nann_sq8_info: out = {n_items, d, device bytes held, 0}.  nann_sq8_view: the three device arrays, borrowed (any may be NULL).
+ * nann_sq8_encode: the codes of n f32 vectors of d elements (device arrays in and out), what the search does to its queries. */
+typedef struct nann_sq8 nann_sq8;
+int nann_sq8_create(const nann_index* ix, nann_stream_t stream, nann_sq8** out);
+void nann_sq8_destroy(nann_sq8* t);
+int nann_sq8_info(const nann_sq8* t, int64_t out[4] /*[host]*/);
+int nann_sq8_view(const nann_sq8* t, const int8_t** codes, const float** scales, const int32_t** norms);
+int nann_sq8_encode(const float* x, int64_t n, int32_t d, int8_t* codes, float* scales, int32_t* norms, nann_stream_t stream);
+
+/* The search.  Fetch stage: the `fetch` best rows of every query by APPROXIMATE score, TopKV2 order (ties -> lower row), into
+ * out_fetch_index i32[n_queries, fetch] / out_fetch_scores f32[n_queries, fetch] (either may be NULL).  Result: the k best of
+ * those rows by EXACT score -- the bits nann_score gives for that (query, row) -- ties -> lower row number, into out_item_ids
+ * i64[n_queries, k] (required), out_scores, out_index (may be NULL).  The scorer is NANN_SCORER_L2 or NANN_SCORER_IP; an MLP
+ * scorer -> NANN_ERR_UNSUPPORTED.  The checks are nann_search_all's, held against fetch (fetch > n_items -> NANN_ERR_TOPK_K_GT_N,
+ * fetch > 1024 -> NANN_ERR_UNSUPPORTED, negative sizes -> NANN_ERR_BAD_ARGUMENT), and k outside [0, fetch] or a table that was
+ * not made from `ix` -> NANN_ERR_BAD_ARGUMENT; k == 0 or n_queries == 0 -> NANN_OK, nothing written.  The workspace rule is
+ * nann_search_all's (256-byte aligned; smaller than nann_search_all_sq8_workspace_bytes gives -> NANN_ERR_CAPACITY) and its
+ * size is bounded by a chunk of queries, not by n_queries.  A query's answer does not depend on its batch.  Asynchronous on
+ * `stream`, no host read-back, re-entrant.  The result is the exact top k iff every row of it was fetched: `fetch` is the
+ * caller's trade-off between recall and the width of the selection. */
+int nann_search_all_sq8_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, int64_t n_queries,
+                                        int32_t fetch, int32_t k, int64_t* nbytes);
+int nann_search_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                        int32_t fetch, int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                        int32_t* out_fetch_index, float* out_fetch_scores, void* workspace, int64_t workspace_bytes,
+                        const nann_search_options* options, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

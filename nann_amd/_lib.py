@@ -76,6 +76,8 @@ SYMBOLS = [
     "nann_hnsw_build_device_metric", "nann_hnsw_append_device_metric",
     "nann_hnsw_remove_count", "nann_hnsw_remove_device",
     "nann_hnsw_update_device", "nann_hnsw_orphan_bits",
+    "nann_sq8_create", "nann_sq8_destroy", "nann_sq8_info", "nann_sq8_view", "nann_sq8_encode",
+    "nann_search_all_sq8_workspace_bytes", "nann_search_all_sq8",
 ]
 
 
@@ -365,6 +367,24 @@ def lib():
         L.nann_search_all_multi_fused.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Fusion)] + \
                                                  [C.c_void_p] * 6 + [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
         L.nann_search_all_multi_fused.restype = C.c_int
+        # the int8 code table: (ix, stream, *out) / (t) / (t, out[4]) / (t, *codes, *scales, *norms) / (x, n, d, codes, scales,
+        # norms, stream); the search over it: (ix, t, scorer, n_queries, fetch, k, *nbytes) / (ix, t, scorer, q, n_queries, fetch,
+        # k, out_item_ids, out_scores, out_index, out_fetch_index, out_fetch_scores, workspace, workspace_bytes, options, stream)
+        L.nann_sq8_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.nann_sq8_create.restype = C.c_int
+        L.nann_sq8_destroy.argtypes = [C.c_void_p]
+        L.nann_sq8_destroy.restype = None
+        L.nann_sq8_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.nann_sq8_info.restype = C.c_int
+        L.nann_sq8_view.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
+        L.nann_sq8_view.restype = C.c_int
+        L.nann_sq8_encode.argtypes = [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 4
+        L.nann_sq8_encode.restype = C.c_int
+        L.nann_search_all_sq8_workspace_bytes.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+        L.nann_search_all_sq8_workspace_bytes.restype = C.c_int
+        L.nann_search_all_sq8.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + \
+                                         [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
+        L.nann_search_all_sq8.restype = C.c_int
         # (item_embs, n_old, n_new, d, emb_dtype, M, ef_construction, keep_pruned, levels, adj0, up_row, adj_up, stream)
         L.nann_hnsw_append_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 5
         L.nann_hnsw_append_device.restype = C.c_int

@@ -21,8 +21,8 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 #                      bound a build from scratch
 #   nann_mlp_d*.o      the MLP traversal per embedding dim; the resident-layer-2 kernels ride with d = 64
 #   nann_attn.o, nann_attn_split.o   the attention model, f32 and split-f16 form
-#   nann_scan.o        the exhaustive search, with the range selection (nann_range.h); nann_scan_attn.o its scan under the
-#                      attention model
+#   nann_scan.o        the exhaustive search, with the range selection (nann_range.h) and the int8 code table and scan
+#                      (nann_sq8.h, nann_sq8_inst.hip); nann_scan_attn.o its scan under the attention model
 #   nann_filter.o      filtered retrieval, with the group cap (nann_groupcap.h) and the attribute predicates (nann_predicate.h)
 #   nann_cand.o        the candidate-list search, with the union and the fused top-k (nann_union.h, nann_fuse.h), the MMR
 #                      re-ranking (nann_mmr.h) and the user interests (nann_interests.h); nann_cand_attn.o its scorer under the
@@ -48,7 +48,7 @@ UNITS = [("nann_core.o", [("nann_ops.hip", {}), ("nann_hip.hip", {}), ("nann_sco
          ("nann_eval.o", [("nann_eval_inst.hip", {})]),
          ("nann_eval_lds.o", [("nann_eval_lds_inst.hip", {})]),
          ("nann_eval_win.o", [("nann_eval_win_inst.hip", {})]),
-         ("nann_scan.o", [("nann_scan_inst.hip", {}), _lean("NANN_SCORER_L2", "1", "l2_bf16")]),
+         ("nann_scan.o", [("nann_scan_inst.hip", {}), ("nann_sq8_inst.hip", {}), _lean("NANN_SCORER_L2", "1", "l2_bf16")]),
          ("nann_scan_attn.o", [("nann_scan_attn_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "2", "NANN_IP_NAME": "f32"})]),
          ("nann_filter.o", [("nann_filter_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "0", "NANN_IP_NAME": "f16"})]),
          ("nann_cand.o", [("nann_cand_inst.hip", {}), _lean("NANN_SCORER_L2", "0", "l2_f16"), _lean("kScorerIp", "0", "ip_f16")]),
@@ -147,6 +147,9 @@ RULES = [
     ("lean_occupancy", r"k_search_leanILi\d+ELi\d+ELi2ELi(0|12)ELi512E", None, 4, "the lean hash-set kernel"),
     # The inner-product scan (k_scan_ip, nann_scan.h) stages the table as k_scan_l2 does and is held to the same.
     ("scan_ip_scratch", r"k_scan_ip", 0, None, "the inner-product scan kernel"),
+    # The int8 scan (k_scan_sq8, nann_sq8.h) keeps the B fragments of a wavefront's 32 rows, d / 8 registers, across its sweep over
+    # the query tiles; spilled, every MFMA of the sweep would wait for a reload from private memory.
+    ("scan_sq8_scratch", r"k_scan_sq8", 0, None, "the int8 scan kernel"),
 ]
 
 
@@ -198,6 +201,10 @@ def _check_ip_occupancy(log_path):
 
 def _check_scan_ip_scratch(log_path):
     check_resources(log_path, _rule("scan_ip_scratch"))
+
+
+def _check_scan_sq8_scratch(log_path):
+    check_resources(log_path, _rule("scan_sq8_scratch"))
 
 
 def unit_command(obj, parts, odir, extra_flags=(), save_temps=True):

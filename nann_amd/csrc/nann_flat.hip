@@ -8,7 +8,9 @@
 // nann_groupcap.h) and behind the filtered exhaustive search at a fetch width (nann_search_all_grouped, nann_search_all_model_grouped);
 // the MMR re-ranking on its own (nann_mmr_topk; kernel in nann_mmr.h) and behind the same search (nann_search_all_diverse,
 // nann_search_all_model_diverse); the attribute predicates on their own (nann_predicate_topk, nann_predicate_count; kernels in
-// nann_predicate.h) and inside the filtered exhaustive search (nann_search_all_where, nann_search_all_model_where).
+// nann_predicate.h) and inside the filtered exhaustive search (nann_search_all_where, nann_search_all_model_where); the int8
+// code table of an index (nann_sq8_create, ..) and the exhaustive search over it with an exact re-rank (nann_search_all_sq8;
+// kernels in nann_sq8.h).
 //
 // A source of nann_core.o.  What it takes from the other host sources, and what the traversal's forms (nann_traverse.hip) take
 // from it -- resolve_filter, resolve_predicates, resolve_groups, resolve_diversity, mmr_index, union_check, fuse_shape_check,
@@ -35,7 +37,9 @@
 #include "nann_fuse.h"
 #include "nann_groupcap.h"
 #include "nann_mmr.h"
+#include "nann_sq8.h"
 
+#include <algorithm>
 #include <cfloat>
 
 #include <memory>
@@ -796,6 +800,80 @@ static int flat_all_diverse(const nann_index* ix, const nann_scorer* scorer, con
   return launch_mmr(a, (long long)n, as_stream(stream));
 }
 
+// ---- scalar-quantised exhaustive search (nann_sq8.h): per chunk the int8 scan and nann_search_all's selection at k = fetch, the
+// fetched rows in ascending order, then the candidate-list search over them at k ---------------------------------------------
+// workspace: [the ScanLayout at k = fetch | Sq8Layout: the chunk's encoded queries, fetch lists, sorted lists, row_splits,
+// status, and the candidate-list search's CandLayout for one chunk].  Nothing in it grows with n_queries beyond a chunk.
+static int flat_sq8_check(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, int64_t n, int32_t fetch, int32_t k,
+                          const char* who, FlatBy* by) {
+  if (!t) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  int rc = flat_by(ix, scorer, nullptr, who, by);
+  if (rc) return rc;
+  if (by->kind == NANN_SCORER_MLP)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": the scorer is NANN_SCORER_L2 or NANN_SCORER_IP, not a learned scorer");
+  rc = flat_check(ix, scorer, nullptr, n, fetch, false, 0, who, by);  // (nann_search_all's checks, held against fetch)
+  if (rc) return rc;
+  if (k < 0 || k > fetch) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k must lie in [0, fetch]");
+  if (t->uid != ix->uid || t->n_items != ix->desc.n_items || t->d != ix->desc.d)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the code table was made from another index");
+  if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many queries in one call");
+  return NANN_OK;
+}
+static Sq8Layout flat_sq8_bytes(const nann_index* ix, const FlatBy& by, int64_t n, int32_t fetch, ScanLayout* L) {
+  *L = scan_layout((long long)ix->desc.n_items, ix->desc.d, by.kind, (long long)n, fetch);
+  return sq8_layout(*L, ix->desc.d, fetch, cand_layout(by.kind, L->chunk, (long long)L->chunk * fetch).total);
+}
+
+static int flat_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, const float* q, int64_t n, int32_t fetch,
+                        int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_fetch_index,
+                        float* out_fetch_scores, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
+                        nann_stream_t stream, const char* who) {
+  FlatBy by;
+  int rc = flat_sq8_check(ix, t, scorer, n, fetch, k, who, &by);
+  if (rc) return rc;
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!q || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  ScanLayout L;
+  const Sq8Layout S = flat_sq8_bytes(ix, by, n, fetch, &L);
+  rc = flat_workspace(workspace, workspace_bytes, S.total, who, "");
+  if (rc) return rc;
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  Sq8Args a = {};
+  a.codes = t->codes;
+  a.scales = t->scales;
+  a.norms = t->norms;
+  a.item_ids = ix->desc.item_ids;
+  a.n_items = (long long)ix->desc.n_items;
+  a.d = ix->desc.d;
+  a.metric = by.kind == NANN_SCORER_IP ? MT_IP : MT_L2;
+  CandArgs ca = {};
+  flat_rows_of(ix, &ca);
+  ca.cus = di.cus;
+  ca.kind = by.kind;
+  ca.row_splits = reinterpret_cast<const int64_t*>(ws + S.off_splits);
+  ca.rows = reinterpret_cast<const int32_t*>(ws + S.off_sorted);
+  int32_t* status = reinterpret_cast<int32_t*>(ws + S.off_status);  // (always 0: the lists are the fetch stage's own)
+  for (int64_t c0 = 0; c0 < n; c0 += L.chunk) {
+    const int n_q = (int)std::min<int64_t>(L.chunk, n - c0);
+    const float* qc = q + (size_t)c0 * a.d;
+    rc = launch_sq8_fetch(a, L, S, qc, n_q, fetch, ws, out_fetch_index ? out_fetch_index + (size_t)c0 * fetch : nullptr,
+                          out_fetch_scores ? out_fetch_scores + (size_t)c0 * fetch : nullptr, st);
+    if (rc) return rc;
+    ca.n_cand = (long long)n_q * fetch;
+    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + S.off_cand, out_item_ids + (size_t)c0 * k,
+                     out_scores ? out_scores + (size_t)c0 * k : nullptr, out_index ? out_index + (size_t)c0 * k : nullptr, nullptr,
+                     nullptr, status, st);
+    if (rc) return rc;
+  }
+  return NANN_OK;
+}
+
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
 extern "C" {
 
@@ -1203,6 +1281,78 @@ int nann_search_candidates_model(const nann_index* ix, const nann_model* m, cons
                                  const nann_search_options* options, nann_stream_t stream) {
   return flat_cand(ix, nullptr, m, comm_seq_f16, n_users, k, cand, out_item_ids, out_scores, out_index, out_pos, n_out, status,
                    workspace, workspace_bytes, options, stream, "nann_search_candidates_model");
+}
+
+// ---- the int8 code table and the search over it (nann_sq8.h) ---------------------------------------------------------------
+int nann_sq8_create(const nann_index* ix, nann_stream_t stream, nann_sq8** out) {
+  const char* who = "nann_sq8_create";
+  if (!ix || !out) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  *out = nullptr;
+  const int d = ix->desc.d, dt = ix->desc.emb_dtype;
+  if (dt != NANN_F16 && dt != NANN_BF16) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": 16-bit rows (f16, bf16) only");
+  if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
+  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  std::unique_ptr<nann_sq8, void (*)(nann_sq8*)> t(new nann_sq8(), nann_sq8_destroy);
+  t->uid = ix->uid;
+  t->n_items = ix->desc.n_items;
+  t->d = d;
+  const size_t n = (size_t)std::max<int64_t>(t->n_items, 1);  // (an empty index: one element each, never read)
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->codes), n * d));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->scales), n * 4));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->norms), n * 4));
+  t->bytes = (int64_t)(n * d + n * 8);
+  const int rc = launch_sq8_encode(ix->desc.item_embs, dt, (long long)t->n_items, d, t->codes, t->scales, t->norms, as_stream(stream));
+  if (rc) return rc;
+  *out = t.release();
+  return NANN_OK;
+}
+void nann_sq8_destroy(nann_sq8* t) {
+  if (!t) return;
+  if (t->codes) (void)hipFree(t->codes);
+  if (t->scales) (void)hipFree(t->scales);
+  if (t->norms) (void)hipFree(t->norms);
+  delete t;
+}
+int nann_sq8_info(const nann_sq8* t, int64_t out[4]) {
+  if (!t || !out) return fail(NANN_ERR_BAD_ARGUMENT, "nann_sq8_info: null argument");
+  out[0] = t->n_items;
+  out[1] = t->d;
+  out[2] = t->bytes;
+  out[3] = 0;
+  return NANN_OK;
+}
+int nann_sq8_view(const nann_sq8* t, const int8_t** codes, const float** scales, const int32_t** norms) {
+  if (!t) return fail(NANN_ERR_BAD_ARGUMENT, "nann_sq8_view: null argument");
+  if (codes) *codes = t->codes;
+  if (scales) *scales = t->scales;
+  if (norms) *norms = t->norms;
+  return NANN_OK;
+}
+int nann_sq8_encode(const float* x, int64_t n, int32_t d, int8_t* codes, float* scales, int32_t* norms, nann_stream_t stream) {
+  const char* who = "nann_sq8_encode";
+  if (n < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n < 0");
+  if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
+  if (n == 0) return NANN_OK;
+  if (!x || !codes || !scales || !norms) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  return launch_sq8_encode(x, NANN_F32, (long long)n, d, codes, scales, norms, as_stream(stream));
+}
+int nann_search_all_sq8_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, int64_t n_queries,
+                                        int32_t fetch, int32_t k, int64_t* nbytes) {
+  const char* who = "nann_search_all_sq8_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  const int rc = flat_sq8_check(ix, t, scorer, n_queries, fetch, k, who, &by);
+  if (rc) return rc;
+  ScanLayout L;
+  *nbytes = n_queries == 0 || k == 0 ? 0 : (int64_t)flat_sq8_bytes(ix, by, n_queries, fetch, &L).total;
+  return NANN_OK;
+}
+int nann_search_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                        int32_t fetch, int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                        int32_t* out_fetch_index, float* out_fetch_scores, void* workspace, int64_t workspace_bytes,
+                        const nann_search_options* options, nann_stream_t stream) {
+  return flat_all_sq8(ix, t, scorer, q, n_queries, fetch, k, out_item_ids, out_scores, out_index, out_fetch_index, out_fetch_scores,
+                      workspace, workspace_bytes, options, stream, "nann_search_all_sq8");
 }
 
 }  // extern "C"

@@ -147,6 +147,18 @@ struct nann_index {
   int n_pivots = 0;
 };
 
+// the int8 code table of an index's rows (nann_flat.hip; kernels in nann_sq8.h).  Borrows the index: `uid` is the index's at
+// creation, what a call holds its index against.
+struct nann_sq8 {
+  uint64_t uid = 0;
+  int64_t n_items = 0;
+  int32_t d = 0;
+  int8_t* codes = nullptr;    // i8[n_items, d]
+  float* scales = nullptr;    // f32[n_items]
+  int32_t* norms = nullptr;   // i32[n_items]
+  int64_t bytes = 0;          // device bytes held
+};
+
 namespace nann {
 
 // ---- nann_hip.hip: who scores a call ---------------------------------------------------------------------------------------

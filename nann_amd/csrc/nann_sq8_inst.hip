@@ -1,0 +1,104 @@
+// nann_sq8_inst.hip -- the kernels of the scalar-quantised exhaustive search (nann_sq8.h): the encoder for every input dtype, the
+// int8 MFMA scan for every (d, metric), the row sort; workspace layout and the launch sequence of a chunk's fetch stage.  Rides in
+// nann_scan.o behind nann_scan_inst.hip: the slab top-k and the merge it launches are that file's kernels.
+#ifndef NANN_SCAN_IMPL
+#define NANN_SCAN_IMPL
+#endif
+#define NANN_SQ8_IMPL
+#include "nann_sq8.h"
+
+#include <algorithm>
+
+namespace nann {
+
+namespace {
+inline size_t sq8_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+}  // namespace
+
+Sq8Layout sq8_layout(const ScanLayout& L, int d, int fetch, size_t cand_bytes) {
+  Sq8Layout S = {};
+  const size_t c = (size_t)L.chunk, cf = c * (size_t)fetch;
+  S.off_qcodes = sq8_up256(L.total);
+  S.off_qscales = S.off_qcodes + sq8_up256(c * d);
+  S.off_qnorms = S.off_qscales + sq8_up256(c * 4);
+  S.off_ids = S.off_qnorms + sq8_up256(c * 4);
+  S.off_fscores = S.off_ids + sq8_up256(cf * 8);
+  S.off_frows = S.off_fscores + sq8_up256(cf * 4);
+  S.off_sorted = S.off_frows + sq8_up256(cf * 4);
+  S.off_splits = S.off_sorted + sq8_up256(cf * 4);
+  S.off_status = S.off_splits + sq8_up256((c + 1) * 8);
+  S.off_cand = S.off_status + sq8_up256(c * 4);
+  S.total = S.off_cand + sq8_up256(cand_bytes);
+  return S;
+}
+
+int launch_sq8_encode(const void* x, int dt, long long n, int d, int8_t* codes, float* scales, int32_t* norms, hipStream_t st) {
+  if (n <= 0) return NANN_OK;
+  if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, "nann_sq8: d must be 64, 128, 256 or 512");
+  const unsigned grid = (unsigned)std::min<long long>((n + kSq8NT / 64 - 1) / (kSq8NT / 64), 1 << 16);
+  if (dt == NANN_F16) hipLaunchKernelGGL(k_sq8_encode<DT_F16>, dim3(grid), dim3(kSq8NT), 0, st, x, n, d, codes, scales, norms);
+  else if (dt == NANN_BF16) hipLaunchKernelGGL(k_sq8_encode<DT_BF16>, dim3(grid), dim3(kSq8NT), 0, st, x, n, d, codes, scales, norms);
+  else if (dt == NANN_F32) hipLaunchKernelGGL(k_sq8_encode<DT_F32>, dim3(grid), dim3(kSq8NT), 0, st, x, n, d, codes, scales, norms);
+  else return fail(NANN_ERR_BAD_ARGUMENT, "nann_sq8: unknown dtype");
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+template <int NS, int METRIC>
+static int launch_scan_sq8_as(const Sq8Args& a, const int8_t* qcodes, const float* qscales, const int32_t* qnorms, int n_q,
+                              float* scores, hipStream_t st) {
+  auto kern = k_scan_sq8<NS, METRIC>;
+  constexpr int lds = sq8_scan_lds(NS * 32);
+  static_assert(lds <= 80 * 1024, "two workgroups per CU");
+  if (lds > 64 * 1024)  // (only d = 512 is beyond the default limit)
+    NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  const long long blocks = (a.n_items + kSq8RowsPerWg - 1) / kSq8RowsPerWg;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kSq8NT), (size_t)lds, st, a.codes, a.scales, a.norms, a.n_items, qcodes,
+                     qscales, qnorms, n_q, scores);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+template <int METRIC>
+static int launch_scan_sq8(const Sq8Args& a, const int8_t* qcodes, const float* qscales, const int32_t* qnorms, int n_q,
+                           float* scores, hipStream_t st) {
+  switch (a.d / 32) {
+    case 2: return launch_scan_sq8_as<2, METRIC>(a, qcodes, qscales, qnorms, n_q, scores, st);
+    case 4: return launch_scan_sq8_as<4, METRIC>(a, qcodes, qscales, qnorms, n_q, scores, st);
+    case 8: return launch_scan_sq8_as<8, METRIC>(a, qcodes, qscales, qnorms, n_q, scores, st);
+    case 16: return launch_scan_sq8_as<16, METRIC>(a, qcodes, qscales, qnorms, n_q, scores, st);
+    default: return fail(NANN_ERR_UNSUPPORTED, "nann_search_all_sq8: d must be 64, 128, 256 or 512");
+  }
+}
+
+int launch_sq8_fetch(const Sq8Args& a, const ScanLayout& L, const Sq8Layout& S, const float* q, int n_q, int fetch,
+                     unsigned char* ws, int32_t* out_fetch_index, float* out_fetch_scores, hipStream_t st) {
+  if (n_q < 1 || n_q > kScanMaxChunk || fetch < 1 || fetch > kMaxK) return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_sq8: chunk shape");
+  float* scores = reinterpret_cast<float*>(ws + L.off_scores);
+  float* cand_scores = reinterpret_cast<float*>(ws + L.off_cand_scores);
+  int32_t* cand_rows = reinterpret_cast<int32_t*>(ws + L.off_cand_rows);
+  int8_t* qcodes = reinterpret_cast<int8_t*>(ws + S.off_qcodes);
+  float* qscales = reinterpret_cast<float*>(ws + S.off_qscales);
+  int32_t* qnorms = reinterpret_cast<int32_t*>(ws + S.off_qnorms);
+  int rc = launch_sq8_encode(q, NANN_F32, n_q, a.d, qcodes, qscales, qnorms, st);
+  if (rc) return rc;
+  rc = a.metric == MT_IP ? launch_scan_sq8<MT_IP>(a, qcodes, qscales, qnorms, n_q, scores, st)
+                         : launch_scan_sq8<MT_L2>(a, qcodes, qscales, qnorms, n_q, scores, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_scan_slab_topk, dim3((unsigned)((long long)n_q * L.n_slabs)), dim3(kNT), 0, st, scores, a.n_items, L.n_slabs,
+                     fetch, cand_scores, cand_rows);
+  NANN_HIP_TRY(hipGetLastError());
+  int64_t* f_ids = reinterpret_cast<int64_t*>(ws + S.off_ids);
+  float* f_scores = reinterpret_cast<float*>(ws + S.off_fscores);
+  int32_t* f_rows = reinterpret_cast<int32_t*>(ws + S.off_frows);
+  hipLaunchKernelGGL(k_scan_merge, dim3((unsigned)n_q), dim3(kNT), 0, st, cand_scores, cand_rows, L.n_slabs * fetch, fetch, a.item_ids,
+                     f_ids, f_scores, f_rows);
+  NANN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_sq8_sort_rows, dim3((unsigned)n_q), dim3(kSq8NT), 0, st, f_rows, f_scores, fetch,
+                     reinterpret_cast<int32_t*>(ws + S.off_sorted), reinterpret_cast<long long*>(ws + S.off_splits), out_fetch_index,
+                     out_fetch_scores);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+}  // namespace nann

@@ -474,6 +474,20 @@ def user_seq_interests(comm_seq, n_vec, n_iter=8, want_assign=False):
     return (q, w, n, a) if want_assign else (q, w, n)
 
 
+def sq8_encode(x):
+    """x f32[n, d] -> (codes i8[n, d], scales f32[n], norms i32[n]) (nann_sq8_encode): the int8 code of every vector --
+    scale = max|x| / 127, code = clamp(rint(x / scale), -127, 127), norm = sum code^2, each step one f32 operation -- as
+    retrieval.search_all_sq8 encodes its queries.  d is 64, 128, 256 or 512.  Asynchronous on torch's current stream."""
+    x = _dev(x, torch.float32)
+    n, d = x.shape
+    codes = torch.empty((n, d), dtype=torch.int8, device=x.device)
+    scales = torch.empty((n,), dtype=torch.float32, device=x.device)
+    norms = torch.empty((n,), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().nann_sq8_encode(_ptr(x), n, d, _ptr(codes), _ptr(scales), _ptr(norms), _stream()), "sq8_encode")
+    return codes, scales, norms
+
+
 def blaze_score(scorer, q, item_emb=None, table=None, indices=None):
     """The BlazeXlaOp contract for one user (forward(), build_opt_graph.py:91-107):
     f32 logits, one per candidate row, rows scored independently.
@@ -529,7 +543,7 @@ class HugeConst:
 def _wrap_device_pointer(ptr, shape, dtype, owner):
     """torch view of library-owned HBM via __cuda_array_interface__."""
     typestr = {torch.float16: "<f2", torch.float32: "<f4", torch.float64: "<f8", torch.int32: "<i4",
-               torch.int64: "<i8"}[dtype]
+               torch.int64: "<i8", torch.int8: "|i1"}[dtype]
 
     class _Holder:
         pass

@@ -451,6 +451,102 @@ def _flat_all(index, handle, x, k, options, filter, symbol, what, predicates=Non
     return SearchAllResult(out_ids, out_scores, out_index, ws, n_out)
 
 
+class Sq8:
+    """The int8 code table of an index's rows (nann_sq8; make_sq8).  It borrows the index -- the object keeps it alive -- and
+    is STALE once the index's rows were refreshed in place: make a new one.  codes() i8[n_items, d], scales() f32[n_items],
+    norms() i32[n_items] are torch views of the table's device memory, valid until release()."""
+
+    def __init__(self, index):
+        self.index = index
+        self.handle = C.c_void_p(0)
+        with torch.cuda.device(index.device):
+            _check(lib().nann_sq8_create(index.handle, _stream(), C.byref(self.handle)), "make_sq8")
+        info = (C.c_int64 * 4)()
+        _check(lib().nann_sq8_info(self.handle, info))
+        self.n_items, self.d, self.nbytes = int(info[0]), int(info[1]), int(info[2])
+
+    def _views(self):
+        if not self.handle.value:
+            raise ValueError("Sq8: released")
+        p = [C.c_void_p(0) for _ in range(3)]
+        _check(lib().nann_sq8_view(self.handle, *[C.byref(v) for v in p]))
+        return [v.value for v in p]
+
+    def _wrap(self, ptr, shape, dtype):
+        with torch.cuda.device(self.index.device):
+            return ops._wrap_device_pointer(ptr, shape, dtype, self)
+
+    def codes(self):
+        return self._wrap(self._views()[0], (self.n_items, self.d), torch.int8)
+
+    def scales(self):
+        return self._wrap(self._views()[1], (self.n_items,), torch.float32)
+
+    def norms(self):
+        return self._wrap(self._views()[2], (self.n_items,), torch.int32)
+
+    def release(self):
+        """Free the table's device memory (the views die with it).  Synchronise streams that still read it first."""
+        if self.handle.value:
+            lib().nann_sq8_destroy(self.handle)
+            self.handle = C.c_void_p(0)
+
+    def __del__(self):
+        try:  # at interpreter shutdown the module globals may already be gone
+            if getattr(self, "handle", None) and self.handle.value:
+                lib().nann_sq8_destroy(self.handle)
+                self.handle = C.c_void_p(0)
+        except Exception:
+            pass
+
+
+def make_sq8(index):
+    """The int8 code table of `index`'s rows (nann_sq8_create): per row d codes, a scale and a norm -- half the bytes of the
+    16-bit rows next to them, which the re-rank of search_all_sq8 still reads.  f16 / bf16 rows, d in {64, 128, 256, 512};
+    an f32 index raises ops.UnimplementedError.  Encoded on torch's current stream.  Re-create it after the rows of the
+    index were refreshed in place."""
+    return Sq8(index)
+
+
+class Sq8Result:
+    """Outputs of search_all_sq8: item_ids i64[B, k], scores f32[B, k] (exact, nann_score's bits), index i32[B, k]; with
+    return_fetch the approximate stage's lists fetch_index i32[B, fetch], fetch_scores f32[B, fetch], else None."""
+    __slots__ = ("item_ids", "scores", "index", "fetch_index", "fetch_scores", "fetch", "_ws")
+
+    def __init__(self, item_ids, scores, index, fetch_index, fetch_scores, fetch, ws=None):
+        self.item_ids, self.scores, self.index = item_ids, scores, index
+        self.fetch_index, self.fetch_scores, self.fetch, self._ws = fetch_index, fetch_scores, fetch, ws
+
+
+def search_all_sq8(index, sq8, scorer, q, k, fetch=None, options=None, return_fetch=False):
+    """Scalar-quantised exhaustive search (nann_search_all_sq8): every row's int8 code scored against the query's on the
+    integer matrix cores, the `fetch` best rows by that approximate score re-ranked by the EXACT score, top k of those --
+    descending, ties -> lower internal row number; the scores are search_all's bits for the rows returned.  `scorer`: an l2
+    or ip ops.Scorer with q f32[B, d] (an MLP scorer raises ops.UnimplementedError).  sq8: make_sq8(index).
+    fetch=None means min(4 * k, 1024, n_items): a convenience default, NOT a tuned one -- recall against search_all grows
+    with fetch, and so does the selection's time; measure on your corpus (tools/sq8_rate.py).  k <= fetch <= 1024.
+    return_fetch: also return the approximate stage's lists.  Asynchronous on torch's current stream."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    b, k = q.shape[0], int(k)
+    fetch = min(4 * k, 1024, int(index.n_items)) if fetch is None else int(fetch)
+    kk, ff = max(k, 0), max(fetch, 0)
+    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
+    f_index = torch.empty((b, ff), dtype=torch.int32, device=dev) if return_fetch else None
+    f_scores = torch.empty((b, ff), dtype=torch.float32, device=dev) if return_fetch else None
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_all_sq8_workspace_bytes(index.handle, sq8.handle, scorer.handle, b, fetch, k, C.byref(nbytes)),
+           "search_all_sq8")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_all_sq8(index.handle, sq8.handle, scorer.handle, _ptr(q), b, fetch, k, _ptr(out_ids),
+                                         _ptr(out_scores), _ptr(out_index), _ptr(f_index), _ptr(f_scores), _ptr(ws), ws.numel(),
+                                         C.byref(options) if options is not None else None, _stream()), "search_all_sq8")
+    return Sq8Result(out_ids, out_scores, out_index, f_index, f_scores, fetch, ws)
+
+
 def search_all_model(index, model, comm_seq, k, options=None):
     """Exhaustive search under a model (nann_search_all_model; the reference's test_all job, main.py:194-237, which scores
     its own attention + DNN model): every item of `index` scored for every user of comm_seq f16[B, seq_len, E], top k per

@@ -116,10 +116,18 @@ class Failed(Exception):
         self.status = status
 
 
-def py_search(g, q, t, score):
+NUM_ROUNDS = 5  # NANN_NUM_ROUNDS: the entry layer, level 1, three level-0 rounds
+
+
+def py_search(g, q, t, score, counters=False):
     """One query through the serving schedule, written with sets and sorted() as tests/test_oracle_schedule.py writes it.
     g: dict with nb_values / nb_row_splits (level 0, level 1), enter_points, item_ids; score(ids list) -> list of f32.
-    -> (item ids, scores f32, internal rows); raises Failed(status) where the reference's graph fails the request."""
+    -> (item ids, scores f32, internal rows); raises Failed(status) where the reference's graph fails the request.
+    counters=True: -> (item ids, scores, rows, int64[3, NUM_ROUNDS]) -- per round the frontier F (rows whose neighbour lists
+    are read), the gathered ids G (duplicates and visited ones included) and the scored rows S, as oracle.search_batch lays
+    them out: the entry round scores every enter point and reads no list."""
+    ctr = np.zeros((3, NUM_ROUNDS), np.int64)
+
     def diff(values, visited):
         out = []
         for v in values:
@@ -150,20 +158,26 @@ def py_search(g, q, t, score):
         return out
 
     ep = np.asarray(g["enter_points"]).tolist()
+    ctr[2, 0] = len(ep)
     R, sR = topk(ep, forward(ep), t[0])
     C = nbrs(1, R)
+    ctr[0, 1], ctr[1, 1] = len(R), len(C)
     vis = set()
     R = diff(R, vis)
     C = diff(C, vis)
+    ctr[2, 1] = len(C)
     P, sP = topk(R + C, sR + forward(C), t[1])
     vis = set()
     B = diff(P, vis)
     for i in range(3):
-        C = diff(nbrs(0, B), vis)
+        G = nbrs(0, B)
+        C = diff(G, vis)
+        ctr[:, 2 + i] = len(B), len(G), len(C)
         B, sB = topk(C, forward(C), t[2 + i])
         P, sP = P + B, sP + sB
     P, sP = topk(P, sP, t[5])
-    return np.asarray(g["item_ids"])[np.asarray(P)], np.asarray(sP, np.float32), np.asarray(P, np.int32)
+    out = (np.asarray(g["item_ids"])[np.asarray(P)], np.asarray(sP, np.float32), np.asarray(P, np.int32))
+    return out + (ctr,) if counters else out
 
 
 def scaled_rows(x, seed):

@@ -246,3 +246,17 @@ def test_schedule_restatement_equals_the_oracle(oracle, golden_dir):
                 continue
             assert rc == 0
             assert (ids == pids).all() and (idx == pidx).all() and (scores.view(np.uint32) == ps.view(np.uint32)).all()
+    # and on the corpus of the traversal matrix (traverse_matrix.py), in every row dtype, with the per-round F / G / S counters
+    # that py_search(counters=True) adds: oracle.search_batch's, for both level_topn of the matrix
+    import traverse_matrix as W
+    for d in W.DIMS:
+        for dtype in W.DTYPES:
+            for t in (W.TOPN, W.TOPN_ODD):
+                est, eids, esc, eidx, ectr = W.oracle_batch(d, dtype, t)
+                pst, pids, ps, pidx, pctr = W.py_batch(d, dtype, R.l2_scores, t)
+                ok = est == 0
+                assert (pst == est).all() and ok.sum() >= W.MIN_OK // 2, (d, dtype, t, est)
+                assert (pids[ok] == eids[ok]).all() and (pidx[ok] == eidx[ok]).all(), (d, dtype, t)
+                assert (ps[ok].view(np.uint32) == esc[ok].view(np.uint32)).all(), (d, dtype, t)
+                assert pctr.shape == ectr.shape == (W.NQ, 3, oracle.NUM_ROUNDS) and (pctr[ok] == ectr[ok]).all(), (d, dtype, t)
+                assert pctr[ok][:, 2].min() > 0 and (pctr[ok][:, :2, 0] == 0).all()  # every round scores; the entry round reads no list

@@ -357,7 +357,9 @@ def test_cpp_serving_host_with_a_model(oracle, tmp_path, kind):
                                           (128, "bf16", 256, 200), (512, "f16", 32, 20), (512, "f32", 32, 20), (512, "bf16", 32, 20)])
 def test_search_row_dtypes_and_dims(oracle, d, dtype, ef, k, mode):
     """bf16 / f32 rows, 256-d (BASELINE configs[4] shape: 256-d bf16, ef_search=256) and the widest rows the library takes
-    (512-d: 64 lanes per row) through the fused traversal."""
+    (512-d: 64 lanes per row) through the fused traversal.  These are plain calls, so the `lds_hash` half runs the LEAN kernel
+    (k_search_lean) and no general hash-set kernel at all; the `lds_bitmap` half runs k_search.  The general hash-set kernels at
+    these widths and dtypes, and `lds_hash32` / `hbm_bitmap`, are launched by test_traverse_matrix_gpu.py."""
     from nann_amd import retrieval
     g, _, _ = synth_index(20000, d, min(ef, 64))
     x = g["item_embs"].astype(np.float32)

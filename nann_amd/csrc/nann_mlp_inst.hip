@@ -70,9 +70,12 @@ int NANN_CAT(launch_score_mlp_d, NANN_MLP_D)(int dt, int split, unsigned blocks,
   else
 #undef NANN_LAUNCH_SCORE2
 #endif
+#if NANN_MLP_D > 128  // (d <= 128: every split call took the second mapping above)
   if (dt == NANN_F16 && split) NANN_LAUNCH_SCORE(DT_F16, true);
-  else if (dt == NANN_F16) NANN_LAUNCH_SCORE(DT_F16, false);
   else if (dt == NANN_BF16 && split) NANN_LAUNCH_SCORE(DT_BF16, true);
+  else
+#endif
+  if (dt == NANN_F16) NANN_LAUNCH_SCORE(DT_F16, false);
   else if (dt == NANN_BF16) NANN_LAUNCH_SCORE(DT_BF16, false);
   else return fail(NANN_ERR_UNSUPPORTED, "MLP scorer: item rows must be f16 or bf16");
 #undef NANN_LAUNCH_SCORE

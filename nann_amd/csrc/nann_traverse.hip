@@ -399,7 +399,9 @@ static int search_impl(const nann_index* ix, const ScoredBy& by, const float* q,
     plan_out->visited_set = v == VIS_LDS_HASH ? NANN_TRAVERSAL_LDS_HASH : v == VIS_LDS_HASH32 ? NANN_TRAVERSAL_LDS_HASH32
                             : v == VIS_LDS_BITMAP ? NANN_TRAVERSAL_LDS_BITMAP : NANN_TRAVERSAL_HBM_BITMAP;
     plan_out->fallback_visited_set = p.fb_vis == VIS_LDS_BITMAP ? NANN_TRAVERSAL_LDS_BITMAP : NANN_TRAVERSAL_HBM_BITMAP;
-    plan_out->threads = ph ? (p.phase_vis == VIS_LDS_HASH32 ? kNT : 512) : ((mlp || attn) && p.nt == kNT ? 512 : p.nt);
+    // (the split-f16 hash-set kernel that reads the embedding rows runs its second mapping at d <= 128: launch_search_mlp_d64 / _d128)
+    const bool mlp2 = mlp_split && !mlp_res && p.vis == VIS_LDS_HASH && ix->desc.d <= 128;
+    plan_out->threads = ph ? (p.phase_vis == VIS_LDS_HASH32 ? kNT : 512) : mlp2 ? kMlp2NT : ((mlp || attn) && p.nt == kNT ? 512 : p.nt);
     plan_out->workgroups = ph ? p.phase_slots : p.slots;
     plan_out->phased = ph ? 1 : 0;
     plan_out->table = tab ? 1 : 0;

@@ -119,13 +119,15 @@ class Failed(Exception):
 NUM_ROUNDS = 5  # NANN_NUM_ROUNDS: the entry layer, level 1, three level-0 rounds
 
 
-def py_search(g, q, t, score, counters=False):
+def py_search(g, q, t, score, counters=False, on_cut=None):
     """One query through the serving schedule, written with sets and sorted() as tests/test_oracle_schedule.py writes it.
     g: dict with nb_values / nb_row_splits (level 0, level 1), enter_points, item_ids; score(ids list) -> list of f32.
     -> (item ids, scores f32, internal rows); raises Failed(status) where the reference's graph fails the request.
     counters=True: -> (item ids, scores, rows, int64[3, NUM_ROUNDS]) -- per round the frontier F (rows whose neighbour lists
     are read), the gathered ids G (duplicates and visited ones included) and the scored rows S, as oracle.search_batch lays
-    them out: the entry round scores every enter point and reads no list."""
+    them out: the entry round scores every enter point and reads no list.
+    on_cut(kept, dropped): called at every top-k cut with the k-th score kept and the best score dropped (None where the cut
+    drops nothing) -- what mlp_matrix.decisive measures its margins on."""
     ctr = np.zeros((3, NUM_ROUNDS), np.int64)
 
     def diff(values, visited):
@@ -139,7 +141,10 @@ def py_search(g, q, t, score, counters=False):
     def topk(ids, scores, k):
         if len(scores) < k:
             raise Failed(ERR_TOPK_K_GT_N)
-        order = sorted(range(len(scores)), key=lambda i: (-(scores[i] + 0.0), i))[:k]
+        order = sorted(range(len(scores)), key=lambda i: (-(scores[i] + 0.0), i))
+        if on_cut is not None and k > 0:
+            on_cut(scores[order[k - 1]], scores[order[k]] if len(order) > k else None)
+        order = order[:k]
         return [ids[i] for i in order], [scores[i] for i in order]
 
     def forward(ids):

@@ -1350,12 +1350,30 @@ int nann_search_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scor
  * the worst kept result, an exhausted frontier is not an error.  Arrays are indexed by level
  * (config.py:50-58); num_scoring_per_level[2] must be 1, top_k_per_level and topk_eval in [1, 2048].
  * Outputs [n_queries, topk_eval] (out_scores / out_index may be NULL); n_out[q] = valid rows of
- * query q (the rest is zero); status[q] as nann_search (NANN_ERR_CAPACITY: more than 1024 new nodes
- * tie at the threshold of one round).  Bit-identical to oracle_search_eval for the l2 and exact mlp
+ * query q (the rest is zero); status[q] as nann_search (NANN_ERR_CAPACITY: more than 2048 new nodes
+ * tie at the threshold of a round that is not its level's last).  Bit-identical to oracle_search_eval for the l2 and exact mlp
  * scorers.  workspace: nann_search_eval_workspace_bytes(ix, model or NULL, n_queries).
  * nann_search_eval_model: comm_seq f16[n_queries, seq_len, E] in, as nann_search_model. */
 int nann_search_eval_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_queries,
                                      int64_t* nbytes);
+/* The plan a nann_search_eval* call with these arguments runs, from the host alone (nothing is launched): exactly one of
+ * scorer / m is given.  form: 0 = `seen` in each slot's HBM (every MLP and attention call; L2 on indices of more than 8
+ * windows or with a neighbour row of 65 536 entries or more, and under NANN_EVAL_SEEN=hbm), 1 = the L2 form with `seen`
+ * in LDS, one window (up to 1 015 808 items), 2 = the same sweeping the id space in n_windows windows.  slots = workgroups
+ * launched, threads = their size, use_dirty = form 0 keeps the second-level bitmap of `seen` (else it scans `seen` whole).
+ * Refuses what the call refuses by its scorer (NANN_SCORER_IP, NANN_MODEL_IP, an unknown kind, a handle that disagrees with
+ * the index); what a call refuses by its other arguments or at its launch (an MLP of d = 512) is the call's to report.
+ * Added without a change of nann_abi_version(). */
+typedef struct nann_eval_plan {
+  int32_t struct_bytes; /* out: sizeof(nann_eval_plan) of the library */
+  int32_t form;
+  int32_t n_windows;
+  int32_t slots;
+  int32_t threads;
+  int32_t use_dirty;
+} nann_eval_plan;
+int nann_search_eval_plan(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n_queries,
+                          nann_eval_plan* out);
 int nann_search_eval(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,
                      const int32_t num_scoring_per_level[3], const int32_t top_k_per_level[3],
                      int32_t topk_eval, void* workspace, int64_t workspace_bytes, int64_t* out_item_ids,

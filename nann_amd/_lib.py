@@ -42,7 +42,7 @@ SYMBOLS = [
     "nann_search", "nann_search_v", "nann_search_ex", "nann_search_opt", "nann_search_options_init", "nann_search_reruns", "nann_search_refined", "nann_search_model_opt", "nann_set_traversal_mode", "nann_set_search_reserve", "nann_search_model_workspace_bytes",
     "nann_search_model", "nann_search_model_v",
     "nann_scorer_prepare", "nann_scorer_release", "nann_scorer_table_bytes", "nann_set_preprojection",
-    "nann_model_prepare", "nann_model_release", "nann_model_table_bytes", "nann_search_eval_workspace_bytes", "nann_search_eval", "nann_search_eval_ex", "nann_search_eval_model",
+    "nann_model_prepare", "nann_model_release", "nann_model_table_bytes", "nann_search_eval_workspace_bytes", "nann_search_eval_plan", "nann_search_eval", "nann_search_eval_ex", "nann_search_eval_model",
     "nann_search_all_workspace_bytes", "nann_search_all", "nann_search_all_model_workspace_bytes", "nann_search_all_model",
     "nann_search_all_filtered_workspace_bytes", "nann_search_all_filtered", "nann_search_all_model_filtered_workspace_bytes",
     "nann_search_all_model_filtered", "nann_search_filtered_workspace_bytes", "nann_search_filtered",
@@ -98,6 +98,12 @@ class SearchPlan(C.Structure):
     _fields_ = [("visited_set", C.c_int32), ("fallback_visited_set", C.c_int32), ("threads", C.c_int32),
                 ("workgroups", C.c_int32), ("phased", C.c_int32), ("table", C.c_int32),
                 ("est_visited", C.c_float), ("worst_visited", C.c_float), ("lean", C.c_int32)]
+
+
+class EvalPlan(C.Structure):
+    """nann_eval_plan: the form of the evaluation traversal a call runs (nann_search_eval_plan)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("form", C.c_int32), ("n_windows", C.c_int32), ("slots", C.c_int32),
+                ("threads", C.c_int32), ("use_dirty", C.c_int32)]
 
 
 class Filter(C.Structure):
@@ -385,6 +391,9 @@ def lib():
         L.nann_search_all_sq8.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + \
                                          [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
         L.nann_search_all_sq8.restype = C.c_int
+        # (ix, scorer or NULL, model or NULL, n_queries, *plan)
+        L.nann_search_eval_plan.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.POINTER(EvalPlan)]
+        L.nann_search_eval_plan.restype = C.c_int
         # (item_embs, n_old, n_new, d, emb_dtype, M, ef_construction, keep_pruned, levels, adj0, up_row, adj_up, stream)
         L.nann_hnsw_append_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 5
         L.nann_hnsw_append_device.restype = C.c_int

@@ -1237,6 +1237,8 @@ int nann_search_model_where(const nann_index* ix, const nann_model* m, const voi
 // workspace: the most slots any plan of this index takes.
 struct EvalPlan {
   int cat_cap = 0, slots = 0, seen_lds = 0, n_windows = 1;
+  int use_dirty = 0;  // the second-level bitmap of `seen` fits the phase scratch (what the slot form asks; the LDS form always has it)
+  int threads = 0;    // eval_plans: the workgroup size of the instance that runs
   unsigned long long slot_bytes = 0;
   uint32_t vis_words = 0, lds_words = 0, win_owners = 0;
 };
@@ -1264,13 +1266,17 @@ static int eval_plan(const nann_index* ix, int64_t n_queries, bool l2, EvalPlan*
   // workgroups per CU: two (the slot form: 2048 threads) unless the LDS bitmap leaves room for one
   const int per_cu = p->seen_lds ? 1 : 2;
   p->slots = (int)std::max<int64_t>(1, std::min<int64_t>(n_queries, (int64_t)di.cus * per_cu));
+  // the second-level bitmap (nann_eval.h, round 6): one bit per word of `seen`, overlaid on the phase scratch behind the scan
+  // scratch -- 256 bytes + 4 per owner of 1 024 items, so it fits shards of up to 256 x (eval_dirty_room() - 256) = 4 718 592
+  // items (tests/eval_matrix.py restates the figure); beyond, the slot form keeps round 4's full scans
+  p->use_dirty = 256 + (size_t)((ix->bm_words + 31u) >> 5) * 4 <= eval_dirty_room() ? 1 : 0;
   return NANN_OK;
 }
 
-static int eval_impl(const nann_index* ix, const ScoredBy& by, const float* q, const float* kt, const float* upad, int64_t n_queries, const int32_t num_scoring[3],
-                     const int32_t top_k[3], int32_t topk_eval, void* workspace, int64_t workspace_bytes,
-                     int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* n_out, int32_t* status,
-                     int32_t* counters, hipStream_t st) {
+// What a call of the evaluation traversal may be scored by (eval_scored_by) and the plan it runs (eval_plans): the one copy
+// of the checks and of the choice, which eval_impl launches with and nann_search_eval_plan reports.  pl: the plan of this call;
+// sizing: the plan the workspace was sized by (nann_search_eval_workspace_bytes).
+static int eval_scored_by(const ScoredBy& by, int64_t n_queries) {
   const nann_scorer* scorer = by.scorer;
   const nann_attn_scorer* attn = by.at;
   if (n_queries > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, "too many queries in one call");
@@ -1279,6 +1285,29 @@ static int eval_impl(const nann_index* ix, const ScoredBy& by, const float* q, c
     return fail(NANN_ERR_UNSUPPORTED, "nann_search_eval: the inner-product scorer (NANN_SCORER_IP) is not supported by the evaluation traversal");
   if (!attn && scorer->desc.kind != NANN_SCORER_L2 && scorer->desc.kind != NANN_SCORER_MLP)
     return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_eval: unknown scorer kind");
+  return NANN_OK;
+}
+static int eval_model_kind(const nann_model* m, const char* who) {
+  if (m->kind == NANN_MODEL_IP)  // (before the mean of the users' sequences is launched)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": an inner-product model (NANN_MODEL_IP) is not supported by the evaluation traversal");
+  return NANN_OK;
+}
+static int eval_plans(const nann_index* ix, const ScoredBy& by, int64_t n_queries, EvalPlan* pl, EvalPlan* sizing) {
+  const bool l2 = !by.at && by.scorer->desc.kind == NANN_SCORER_L2;
+  int rc = eval_plan(ix, n_queries, l2, pl);
+  if (!rc) rc = eval_plan(ix, n_queries, false, sizing);  // (the workspace the caller sized: nann_search_eval_workspace_bytes)
+  pl->threads = by.at ? kAttnNT : l2 ? kNT : kMlpNT;      // (launch_eval_attn / launch_eval_l2 / launch_eval_mlp_d*)
+  return rc;
+}
+
+static int eval_impl(const nann_index* ix, const ScoredBy& by, const float* q, const float* kt, const float* upad, int64_t n_queries, const int32_t num_scoring[3],
+                     const int32_t top_k[3], int32_t topk_eval, void* workspace, int64_t workspace_bytes,
+                     int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* n_out, int32_t* status,
+                     int32_t* counters, hipStream_t st) {
+  const nann_scorer* scorer = by.scorer;
+  const nann_attn_scorer* attn = by.at;
+  int rc = eval_scored_by(by, n_queries);
+  if (rc) return rc;
   if (num_scoring[2] != 1) return fail(NANN_ERR_BAD_ARGUMENT, "num_scoring_per_level[2] must be 1 (model.py:347)");
   for (int l = 0; l < 3; ++l)
     if (top_k[l] < 1 || top_k[l] > kEvalMaxK || num_scoring[l] < 0)
@@ -1287,8 +1316,7 @@ static int eval_impl(const nann_index* ix, const ScoredBy& by, const float* q, c
   EvalArgs a;
   const bool l2 = !attn && scorer->desc.kind == NANN_SCORER_L2;
   EvalPlan pl, sizing;
-  int rc = eval_plan(ix, n_queries, l2, &pl);
-  if (!rc) rc = eval_plan(ix, n_queries, false, &sizing);  // (the workspace the caller sized: nann_search_eval_workspace_bytes)
+  rc = eval_plans(ix, by, n_queries, &pl, &sizing);
   if (rc) return rc;
   const int slots = pl.slots, seen_lds = pl.seen_lds;
   a.cat_cap = pl.cat_cap;
@@ -1301,9 +1329,7 @@ static int eval_impl(const nann_index* ix, const ScoredBy& by, const float* q, c
   for (int l = 0; l < 3; ++l) { a.num_scoring[l] = num_scoring[l]; a.top_k[l] = top_k[l]; }
   a.topk_eval = topk_eval;
   a.ws = static_cast<unsigned char*>(workspace);
-  // the second-level bitmap (nann_eval.h, round 6): one bit per word of `seen`, overlaid on the phase scratch behind the scan
-  // scratch -- it fits shards of up to ~7 M items; beyond, the slot form keeps round 4's full scans
-  a.use_dirty = 256 + (size_t)((ix->bm_words + 31u) >> 5) * 4 <= eval_dirty_room() ? 1 : 0;
+  a.use_dirty = pl.use_dirty;
   a.vis_words = pl.vis_words;
   a.lds_words = pl.lds_words;
   a.win_owners = pl.win_owners;
@@ -1371,10 +1397,10 @@ static int evaluate(const nann_index* ix, const nann_scorer* scorer, const nann_
   if (!model)
     return eval_impl(ix, by, static_cast<const float*>(x), nullptr, nullptr, n_queries, num_scoring, top_k, topk_eval, workspace,
                      workspace_bytes, out_item_ids, out_scores, out_index, n_out, status, counters, st);
-  if (m->kind == NANN_MODEL_IP)  // (before the mean of the users' sequences is launched)
-    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": an inner-product model (NANN_MODEL_IP) is not supported by the evaluation traversal");
+  int rc = eval_model_kind(m, who);
+  if (rc) return rc;
   TraverseBytes b;
-  int rc = eval_bytes(ix, m, n_queries, &b);
+  rc = eval_bytes(ix, m, n_queries, &b);
   if (rc) return rc;
   if (workspace_bytes < b.total) return short_workspace("nann_search_eval");
   const float *q = nullptr, *kt = nullptr, *upad = nullptr;
@@ -1392,6 +1418,25 @@ int nann_search_eval_workspace_bytes(const nann_index* ix, const nann_model* m, 
   const int rc = eval_bytes(ix, m, n_queries, &b);
   if (rc) return rc;
   *nbytes = b.total;
+  return NANN_OK;
+}
+int nann_search_eval_plan(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n_queries,
+                          nann_eval_plan* out) {
+  const char* who = "nann_search_eval_plan";
+  if (!ix || !out || (!scorer == !m)) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": an index, a plan and one of scorer / model");
+  const ScoredBy by = scored_by(ix, scorer, m);
+  if (by.mismatch) return disagree(by);
+  int rc = m ? eval_model_kind(m, who) : NANN_OK;
+  if (!rc) rc = eval_scored_by(by, n_queries);
+  EvalPlan pl, sizing;
+  if (!rc) rc = eval_plans(ix, by, std::max<int64_t>(n_queries, 0), &pl, &sizing);
+  if (rc) return rc;
+  out->struct_bytes = (int32_t)sizeof(nann_eval_plan);
+  out->form = pl.seen_lds;
+  out->n_windows = pl.n_windows;
+  out->slots = pl.slots;
+  out->threads = pl.threads;
+  out->use_dirty = pl.use_dirty;
   return NANN_OK;
 }
 int nann_search_eval(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries,

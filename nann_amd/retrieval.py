@@ -1703,6 +1703,22 @@ class EvalResult:
         self.item_ids, self.scores, self.index, self.n_out, self.status = item_ids, scores, index, n_out, status
 
 
+EVAL_FORMS = ("slot", "lds", "windows")
+
+
+def search_eval_plan(index, scorer, n_queries):
+    """The plan search_eval runs for a batch of n_queries users of (index, scorer | model), asked of the host alone
+    (nann_search_eval_plan: nothing is launched) -> dict(form 0 slot / 1 lds / 2 windows, form_name, n_windows, slots, threads,
+    use_dirty).  Raises what search_eval raises for the scorer (the inner product is unsupported)."""
+    is_model = isinstance(scorer, ops.Model)
+    p = _lib.EvalPlan()
+    _check(lib().nann_search_eval_plan(index.handle, None if is_model else scorer.handle, scorer.handle if is_model else None,
+                                       C.c_int64(int(n_queries)), C.byref(p)), "search_eval_plan")
+    assert p.struct_bytes == C.sizeof(_lib.EvalPlan), p.struct_bytes
+    return {"form": p.form, "form_name": EVAL_FORMS[p.form], "n_windows": p.n_windows, "slots": p.slots, "threads": p.threads,
+            "use_dirty": p.use_dirty}
+
+
 def search_eval(index, scorer, q, num_scoring=(3, 1, 1), top_k_per_level=(400, 200, 100), topk_eval=200, want_counters=False):
     """Model.retrieval() (model.py:299-362) for a batch of users in ONE kernel (nann_search_eval /
     nann_search_eval_model).  `scorer`: ops.Scorer with q f32[B, d], or ops.Model with q = comm_seq

@@ -78,8 +78,9 @@ int launch_search_attn_split(int d, int dt, int vis, int slots, size_t lds_bytes
 }
 
 int launch_search_attn_proj(int vis, int slots, size_t lds_bytes, const SearchArgs& a, hipStream_t st) {
-  // the scorer never reads the embedding table: the <16, f16> instance serves every d and row dtype
-  if (vis == VIS_LDS_HASH) return launch_search_as<16, DT_F16, VIS_LDS_HASH, kScorerAttnProj, kAttnNT>(slots, lds_bytes, a, st);
+  // the scorer never reads the embedding table: the <16, f16> instance serves every d and row dtype.  Bitmap plans only: on
+  // the 16K-slot hash plan the split form runs launch_search_attn_res, and the overflow rerun's plan is always a bitmap
+  // (plan_search: fb_vis) -- a hash-set instance of this form was reachable by no call
   if (vis == VIS_LDS_BITMAP || vis == VIS_HBM_BITMAP)
     return launch_search_bitmap<16, DT_F16, kScorerAttnProj, kAttnNT>(vis, slots, lds_bytes, a, st);
   return fail(NANN_ERR_UNSUPPORTED, "attention traversal: no kernel for this plan");

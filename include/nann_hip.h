@@ -1342,6 +1342,48 @@ int nann_search_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scor
                         int32_t* out_fetch_index, float* out_fetch_scores, void* workspace, int64_t workspace_bytes,
                         const nann_search_options* options, nann_stream_t stream);
 
+/* ---- certified scalar-quantised search: nann_search_all's exact bits at the int8 scan's cost.  Added to ABI
+ * version 6: new symbols only.
+ * A nann_sq8_bounds holds two device arrays over the rows of a code table, each f32[n_items]:
+ *   err[i]  >= |x_i - scale_i codes_i|_2 (the real-valued quantisation error of row i)     xhat[i] >= scale_i sqrt(norm_i)
+ * both upper bounds by construction (an explicit inflation covers every rounding of their f32 evaluation).  It BORROWS the index
+ * and the table, which must outlive it, and goes STALE with the table.  nann_sq8_bounds_create computes asynchronously on
+ * `stream`; a table that was not made from `ix` -> NANN_ERR_BAD_ARGUMENT.  nann_sq8_bounds_destroy(NULL) is a no-op.
+ * nann_sq8_bounds_view: the two device arrays, borrowed (either may be NULL).
+ *
+ * nann_search_all_sq8_exact, per query and without a host read-back:
+ *   (a) nann_search_all_sq8's fetch stage and exact re-rank at `fetch`; tau = the exact score of the k-th entry, a lower bound of
+ *       the true k-th best score;
+ *   (b) a pass over the approximate scores of EVERY row keeps the rows whose exact f32 score a rigorous bound cannot put below
+ *       tau -- the survivors, ties at tau among them; out_n_survivors[q] = their number, whatever `cap`;
+ *   (c) out_certified[q] = 1 iff tau and the query's terms are finite and n_survivors[q] <= cap.  A certified query's outputs are
+ *       the exact top k of its survivors: nann_search_all's result BIT FOR BIT -- item ids, scores, index, TopKV2 order with ties
+ *       to the lower row.  An uncertified query's outputs are exactly what nann_search_all_sq8 returns at the same fetch.
+ * out_item_ids i64[n_queries, k], out_certified i32[n_queries] and out_n_survivors i32[n_queries] are required; out_scores and
+ * out_index may be NULL.  Nothing is written beyond a query's k outputs and its two words.
+ * The checks are nann_search_all_sq8's (k <= fetch <= min(1024, n_items), an MLP scorer -> NANN_ERR_UNSUPPORTED, ...), and: a NULL
+ * bounds object, bounds made from another index or table, or cap < fetch -> NANN_ERR_BAD_ARGUMENT; cap beyond the longest list a
+ * candidate-list search takes per query, (2^31 - 1) / (queries per chunk, at most 128) -> NANN_ERR_UNSUPPORTED.  A cap above
+ * n_items counts as n_items.  n_queries == 0 or k == 0 -> NANN_OK, nothing written.  Workspace: 256-byte aligned, smaller than
+ * nann_search_all_sq8_exact_workspace_bytes gives -> NANN_ERR_CAPACITY; bounded by a chunk of queries (it holds chunk * cap row
+ * numbers).  A query's answer does not depend on its batch.  Asynchronous on `stream`, re-entrant.
+ * nann_search_all_sq8_exact_layout (tests, tools): out = {queries per chunk, cap as counted, offset of the LAST chunk's final
+ * row_splits i64[chunk + 1], of its final lists i32, of its query terms, bytes per query term {tau, eq, qhat, w f32; ok,
+ * certified i32; 8 bytes unused}, offset of stage (a)'s scores f32[chunk, k], workspace bytes}. */
+typedef struct nann_sq8_bounds nann_sq8_bounds;
+int nann_sq8_bounds_create(const nann_index* ix, const nann_sq8* t, nann_stream_t stream, nann_sq8_bounds** out);
+void nann_sq8_bounds_destroy(nann_sq8_bounds* b);
+int nann_sq8_bounds_view(const nann_sq8_bounds* b, const float** err, const float** xhat);
+int nann_search_all_sq8_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
+                                              const nann_scorer* scorer, int64_t n_queries, int32_t fetch, int64_t cap, int32_t k,
+                                              int64_t* nbytes);
+int nann_search_all_sq8_exact_layout(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                     int64_t n_queries, int32_t fetch, int64_t cap, int32_t k, int64_t out[8] /*[host]*/);
+int nann_search_all_sq8_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                              const float* q, int64_t n_queries, int32_t fetch, int64_t cap, int32_t k, int64_t* out_item_ids,
+                              float* out_scores, int32_t* out_index, int32_t* out_certified, int32_t* out_n_survivors,
+                              void* workspace, int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

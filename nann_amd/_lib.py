@@ -78,6 +78,8 @@ SYMBOLS = [
     "nann_hnsw_update_device", "nann_hnsw_orphan_bits",
     "nann_sq8_create", "nann_sq8_destroy", "nann_sq8_info", "nann_sq8_view", "nann_sq8_encode",
     "nann_search_all_sq8_workspace_bytes", "nann_search_all_sq8",
+    "nann_sq8_bounds_create", "nann_sq8_bounds_destroy", "nann_sq8_bounds_view",
+    "nann_search_all_sq8_exact_workspace_bytes", "nann_search_all_sq8_exact_layout", "nann_search_all_sq8_exact",
 ]
 
 
@@ -391,6 +393,23 @@ def lib():
         L.nann_search_all_sq8.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + \
                                          [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
         L.nann_search_all_sq8.restype = C.c_int
+        # the certified form: (ix, t, stream, *out) / (b) / (b, *err, *xhat); (ix, t, b, scorer, n_queries, fetch, cap, k, *nbytes or
+        # out[8]) / (ix, t, b, scorer, q, n_queries, fetch, cap, k, out_item_ids, out_scores, out_index, out_certified,
+        # out_n_survivors, workspace, workspace_bytes, options, stream)
+        L.nann_sq8_bounds_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.nann_sq8_bounds_create.restype = C.c_int
+        L.nann_sq8_bounds_destroy.argtypes = [C.c_void_p]
+        L.nann_sq8_bounds_destroy.restype = None
+        L.nann_sq8_bounds_view.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 2
+        L.nann_sq8_bounds_view.restype = C.c_int
+        head = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int64, C.c_int32]
+        L.nann_search_all_sq8_exact_workspace_bytes.argtypes = head + [C.POINTER(C.c_int64)]
+        L.nann_search_all_sq8_exact_workspace_bytes.restype = C.c_int
+        L.nann_search_all_sq8_exact_layout.argtypes = head + [C.POINTER(C.c_int64)]
+        L.nann_search_all_sq8_exact_layout.restype = C.c_int
+        L.nann_search_all_sq8_exact.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 6 + \
+                                               [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
+        L.nann_search_all_sq8_exact.restype = C.c_int
         # (ix, scorer or NULL, model or NULL, n_queries, *plan)
         L.nann_search_eval_plan.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.POINTER(EvalPlan)]
         L.nann_search_eval_plan.restype = C.c_int

@@ -21,8 +21,8 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 #                      bound a build from scratch
 #   nann_mlp_d*.o      the MLP traversal per embedding dim; the resident-layer-2 kernels ride with d = 64
 #   nann_attn.o, nann_attn_split.o   the attention model, f32 and split-f16 form
-#   nann_scan.o        the exhaustive search, with the range selection (nann_range.h) and the int8 code table and scan
-#                      (nann_sq8.h, nann_sq8_inst.hip); nann_scan_attn.o its scan under the attention model
+#   nann_scan.o        the exhaustive search, with the range selection (nann_range.h) and the int8 code table, scan and
+#                      certified survivor pass (nann_sq8.h, nann_sq8_inst.hip); nann_scan_attn.o its scan under the attention model
 #   nann_filter.o      filtered retrieval, with the group cap (nann_groupcap.h) and the attribute predicates (nann_predicate.h)
 #   nann_cand.o        the candidate-list search, with the union and the fused top-k (nann_union.h, nann_fuse.h), the MMR
 #                      re-ranking (nann_mmr.h) and the user interests (nann_interests.h); nann_cand_attn.o its scorer under the
@@ -150,6 +150,10 @@ RULES = [
     # The int8 scan (k_scan_sq8, nann_sq8.h) keeps the B fragments of a wavefront's 32 rows, d / 8 registers, across its sweep over
     # the query tiles; spilled, every MFMA of the sweep would wait for a reload from private memory.
     ("scan_sq8_scratch", r"k_scan_sq8", 0, None, "the int8 scan kernel"),
+    # The survivor pass of the certified int8 search (k_sq8_surv_count / k_sq8_surv_fill, nann_sq8.h) streams the chunk's score buffer
+    # twice and holds a block's eight positions per thread in registers; a frame in private memory would add its traffic to a pass that
+    # is nothing but memory traffic.
+    ("sq8_surv_scratch", r"k_sq8_surv_(count|fill)", 0, None, "the survivor pass"),
 ]
 
 

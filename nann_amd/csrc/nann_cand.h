@@ -69,6 +69,9 @@ struct CandLayout {
   size_t off_scores, off_plan, off_items, off_u, total;
 };
 CandLayout cand_layout(int kind, long long n_queries, long long n_cand);
+// the longest list a query of a call of n_queries may bring when every query brings one as long: list positions are 32-bit
+// (CandQuery, and the n_cand a call takes)
+inline long long cand_max_list(long long n_queries) { return 0x7fffffffll / (n_queries > 0 ? n_queries : 1); }
 int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status,
                 hipStream_t st);

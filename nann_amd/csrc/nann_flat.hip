@@ -10,7 +10,7 @@
 // nann_search_all_model_diverse); the attribute predicates on their own (nann_predicate_topk, nann_predicate_count; kernels in
 // nann_predicate.h) and inside the filtered exhaustive search (nann_search_all_where, nann_search_all_model_where); the int8
 // code table of an index (nann_sq8_create, ..) and the exhaustive search over it with an exact re-rank (nann_search_all_sq8;
-// kernels in nann_sq8.h).
+// kernels in nann_sq8.h), and its certified form that returns nann_search_all's bits (nann_sq8_bounds, nann_search_all_sq8_exact).
 //
 // A source of nann_core.o.  What it takes from the other host sources, and what the traversal's forms (nann_traverse.hip) take
 // from it -- resolve_filter, resolve_predicates, resolve_groups, resolve_diversity, mmr_index, union_check, fuse_shape_check,
@@ -40,6 +40,7 @@
 #include "nann_sq8.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
 
 #include <memory>
@@ -874,6 +875,89 @@ static int flat_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scor
   return NANN_OK;
 }
 
+// ---- the certified form (nann_search_all_sq8_exact; nann_sq8.h) -----------------------------------------------
+// Per chunk: flat_all_sq8's two steps with the result kept in the workspace (stage a), the survivor pass over the score buffer
+// the scan has left in the ScanLayout (stage b), and the candidate-list search over the final lists (stage c).
+// workspace: Sq8ExactLayout.  Nothing in it grows with n_queries beyond a chunk.
+static int flat_sq8_exact_check(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer, int64_t n,
+                                int32_t fetch, int64_t cap, int32_t k, const char* who, FlatBy* by, ScanLayout* L, Sq8ExactLayout* X) {
+  if (!b) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  int rc = flat_sq8_check(ix, t, scorer, n, fetch, k, who, by);
+  if (rc) return rc;
+  if (b->uid != ix->uid || b->serial != t->serial || b->n_items != t->n_items)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the bounds were made from another index or code table");
+  if (cap < fetch) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least fetch");
+  *L = scan_layout((long long)ix->desc.n_items, ix->desc.d, by->kind, (long long)n, fetch);
+  if (cap > cand_max_list(L->chunk))  // (a chunk's final lists are one candidate-list search)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": cap beyond the longest list of a candidate-list search, " +
+                                          std::to_string(cand_max_list(L->chunk)) + " at this chunk");
+  *X = sq8_exact_layout(*L, by->kind, ix->desc.d, fetch, (long long)cap, k, (long long)ix->desc.n_items);
+  return NANN_OK;
+}
+
+static int flat_all_sq8_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                              const float* q, int64_t n, int32_t fetch, int64_t cap, int32_t k, int64_t* out_item_ids,
+                              float* out_scores, int32_t* out_index, int32_t* out_certified, int32_t* out_n_survivors,
+                              void* workspace, int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream,
+                              const char* who) {
+  FlatBy by;
+  ScanLayout L;
+  Sq8ExactLayout X;
+  int rc = flat_sq8_exact_check(ix, t, b, scorer, n, fetch, cap, k, who, &by, &L, &X);
+  if (rc) return rc;
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!q || !out_item_ids || !out_certified || !out_n_survivors) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  rc = flat_workspace(workspace, workspace_bytes, X.total, who, "");
+  if (rc) return rc;
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  const Sq8Layout& S = X.S;
+  Sq8Args a = {};
+  a.codes = t->codes;
+  a.scales = t->scales;
+  a.norms = t->norms;
+  a.item_ids = ix->desc.item_ids;
+  a.n_items = (long long)ix->desc.n_items;
+  a.d = ix->desc.d;
+  a.metric = by.kind == NANN_SCORER_IP ? MT_IP : MT_L2;
+  CandArgs ca = {};
+  flat_rows_of(ix, &ca);
+  ca.cus = di.cus;
+  ca.kind = by.kind;
+  int32_t* status = reinterpret_cast<int32_t*>(ws + S.off_status);  // (always 0: the lists are the call's own)
+  for (int64_t c0 = 0; c0 < n; c0 += L.chunk) {
+    const int n_q = (int)std::min<int64_t>(L.chunk, n - c0);
+    const float* qc = q + (size_t)c0 * a.d;
+    // (a) the fetch stage and its exact re-rank, as nann_search_all_sq8 runs them; the result stays in the workspace
+    rc = launch_sq8_fetch(a, L, S, qc, n_q, fetch, ws, nullptr, nullptr, st);
+    if (rc) return rc;
+    ca.row_splits = reinterpret_cast<const int64_t*>(ws + S.off_splits);
+    ca.rows = reinterpret_cast<const int32_t*>(ws + S.off_sorted);
+    ca.n_cand = (long long)n_q * fetch;
+    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + S.off_cand,
+                     reinterpret_cast<int64_t*>(ws + X.off_a_ids), reinterpret_cast<float*>(ws + X.off_a_scores), nullptr, nullptr,
+                     nullptr, status, st);
+    if (rc) return rc;
+    // (b) the survivors of every query, or its fetch list, as compact lists in ascending row order
+    rc = launch_sq8_survivors(a, L, X, qc, b->err, b->xhat, n_q, fetch, k, ws, out_certified + c0, out_n_survivors + c0, st);
+    if (rc) return rc;
+    // (c) the exact top k of the lists
+    ca.row_splits = reinterpret_cast<const int64_t*>(ws + X.off_xsplits);
+    ca.rows = reinterpret_cast<const int32_t*>(ws + X.off_rows);
+    ca.n_cand = (long long)n_q * X.cap;
+    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + S.off_cand, out_item_ids + (size_t)c0 * k,
+                     out_scores ? out_scores + (size_t)c0 * k : nullptr, out_index ? out_index + (size_t)c0 * k : nullptr, nullptr,
+                     nullptr, status, st);
+    if (rc) return rc;
+  }
+  return NANN_OK;
+}
+
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
 extern "C" {
 
@@ -1293,7 +1377,9 @@ int nann_sq8_create(const nann_index* ix, nann_stream_t stream, nann_sq8** out) 
   if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
   if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
   std::unique_ptr<nann_sq8, void (*)(nann_sq8*)> t(new nann_sq8(), nann_sq8_destroy);
+  static std::atomic<uint64_t> next_serial{1};
   t->uid = ix->uid;
+  t->serial = next_serial.fetch_add(1);
   t->n_items = ix->desc.n_items;
   t->d = d;
   const size_t n = (size_t)std::max<int64_t>(t->n_items, 1);  // (an empty index: one element each, never read)
@@ -1353,6 +1439,79 @@ int nann_search_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scor
                         const nann_search_options* options, nann_stream_t stream) {
   return flat_all_sq8(ix, t, scorer, q, n_queries, fetch, k, out_item_ids, out_scores, out_index, out_fetch_index, out_fetch_scores,
                       workspace, workspace_bytes, options, stream, "nann_search_all_sq8");
+}
+
+
+// ---- the certified form: the per-row error terms and the search (nann_sq8.h) -------------------------------------
+int nann_sq8_bounds_create(const nann_index* ix, const nann_sq8* t, nann_stream_t stream, nann_sq8_bounds** out) {
+  const char* who = "nann_sq8_bounds_create";
+  if (!ix || !t || !out) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  *out = nullptr;
+  if (t->uid != ix->uid || t->n_items != ix->desc.n_items || t->d != ix->desc.d)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the code table was made from another index");
+  std::unique_ptr<nann_sq8_bounds, void (*)(nann_sq8_bounds*)> b(new nann_sq8_bounds(), nann_sq8_bounds_destroy);
+  b->uid = ix->uid;
+  b->serial = t->serial;
+  b->n_items = t->n_items;
+  const size_t n = (size_t)std::max<int64_t>(t->n_items, 1);  // (an empty index: one element each, never read)
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->err), n * 4));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->xhat), n * 4));
+  const int rc = launch_sq8_row_err(ix->desc.item_embs, ix->desc.emb_dtype, (long long)t->n_items, t->d, t->codes, t->scales, t->norms,
+                                    b->err, b->xhat, as_stream(stream));
+  if (rc) return rc;
+  *out = b.release();
+  return NANN_OK;
+}
+void nann_sq8_bounds_destroy(nann_sq8_bounds* b) {
+  if (!b) return;
+  if (b->err) (void)hipFree(b->err);
+  if (b->xhat) (void)hipFree(b->xhat);
+  delete b;
+}
+int nann_sq8_bounds_view(const nann_sq8_bounds* b, const float** err, const float** xhat) {
+  if (!b) return fail(NANN_ERR_BAD_ARGUMENT, "nann_sq8_bounds_view: null argument");
+  if (err) *err = b->err;
+  if (xhat) *xhat = b->xhat;
+  return NANN_OK;
+}
+int nann_search_all_sq8_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
+                                              const nann_scorer* scorer, int64_t n_queries, int32_t fetch, int64_t cap, int32_t k,
+                                              int64_t* nbytes) {
+  const char* who = "nann_search_all_sq8_exact_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  ScanLayout L;
+  Sq8ExactLayout X;
+  const int rc = flat_sq8_exact_check(ix, t, b, scorer, n_queries, fetch, cap, k, who, &by, &L, &X);
+  if (rc) return rc;
+  *nbytes = n_queries == 0 || k == 0 ? 0 : (int64_t)X.total;
+  return NANN_OK;
+}
+int nann_search_all_sq8_exact_layout(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                     int64_t n_queries, int32_t fetch, int64_t cap, int32_t k, int64_t out[8]) {
+  const char* who = "nann_search_all_sq8_exact_layout";
+  if (!out) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  ScanLayout L;
+  Sq8ExactLayout X;
+  const int rc = flat_sq8_exact_check(ix, t, b, scorer, n_queries, fetch, cap, k, who, &by, &L, &X);
+  if (rc) return rc;
+  out[0] = L.chunk;
+  out[1] = X.cap;
+  out[2] = (int64_t)X.off_xsplits;
+  out[3] = (int64_t)X.off_rows;
+  out[4] = (int64_t)X.off_terms;
+  out[5] = (int64_t)sizeof(Sq8QTerms);
+  out[6] = (int64_t)X.off_a_scores;
+  out[7] = (int64_t)X.total;
+  return NANN_OK;
+}
+int nann_search_all_sq8_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                              const float* q, int64_t n_queries, int32_t fetch, int64_t cap, int32_t k, int64_t* out_item_ids,
+                              float* out_scores, int32_t* out_index, int32_t* out_certified, int32_t* out_n_survivors,
+                              void* workspace, int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream) {
+  return flat_all_sq8_exact(ix, t, b, scorer, q, n_queries, fetch, cap, k, out_item_ids, out_scores, out_index, out_certified,
+                            out_n_survivors, workspace, workspace_bytes, options, stream, "nann_search_all_sq8_exact");
 }
 
 }  // extern "C"

@@ -157,6 +157,16 @@ struct nann_sq8 {
   float* scales = nullptr;    // f32[n_items]
   int32_t* norms = nullptr;   // i32[n_items]
   int64_t bytes = 0;          // device bytes held
+  uint64_t serial = 0;        // process-unique: what a nann_sq8_bounds holds its table against
+};
+
+// the per-row error terms of a code table (nann_flat.hip; k_sq8_row_err in nann_sq8.h).  Borrows index and table: `uid` and
+// `serial` are theirs at creation.
+struct nann_sq8_bounds {
+  uint64_t uid = 0, serial = 0;
+  int64_t n_items = 0;
+  float* err = nullptr;       // f32[n_items]: >= |x_i - scale_i codes_i|
+  float* xhat = nullptr;      // f32[n_items]: >= scale_i sqrt(norm_i)
 };
 
 namespace nann {

@@ -61,6 +61,61 @@ int launch_sq8_encode(const void* x, int dt, long long n, int d, int8_t* codes, 
 int launch_sq8_fetch(const Sq8Args& a, const ScanLayout& L, const Sq8Layout& S, const float* q, int n_q, int fetch,
                      unsigned char* ws, int32_t* out_fetch_index, float* out_fetch_scores, hipStream_t st);
 
+
+// ---- the certified form (nann_search_all_sq8_exact): the fetch stage and its exact re-rank give a cut tau_q,
+// a survivor pass over the chunk's score buffer keeps every row whose exact score the bound cannot put below tau_q, and the
+// candidate-list search over the survivors returns nann_search_all's bits.
+//
+// Per row (k_sq8_row_err, nann_sq8_bounds; the same kernel gives a chunk's queries theirs), every step ONE f32 operation:
+//   lane l of the row's wavefront, elements j = l, l + 64, ... in that order:  p = scale * (float)code_j;  r = x_j - p;
+//   acc = acc + r * r (from +0);  then acc = acc + shfl_xor(acc, o) for o = 32, 16, 8, 4, 2, 1;  e0 = sqrt(acc)
+//   xhat = (scale * sqrt((float)norm)) * kSq8Infl + kSq8Abs
+//   err  = (e0 + 2^-23 * xhat) * kSq8Infl + kSq8Abs
+// sqrt is sqrtf, which the build rounds correctly (hipcc's default; __fsqrt_rn is the hardware's approximate root here).
+// The inflations make the stored values upper bounds of the real |x - scale code| and scale sqrt(norm) (lemma 1).
+constexpr float kSq8Infl = 1.0f + 0x1p-18f;   // covers up to 32 roundings of a sum of non-negative terms
+constexpr float kSq8Infl2 = 1.0f + 0x1p-20f;  // covers up to 8
+constexpr float kSq8Abs = 0x1p-60f;           // covers what underflows in a row's squares and products
+constexpr float kSq8Tiny = 0x1p-100f;         // covers what underflows in a score, approximate or exact
+
+// the terms of one query of a chunk (k_sq8_exact_terms), read by the survivor predicate
+struct Sq8QTerms {
+  float tau;    // the exact score of the k-th entry of the re-ranked fetch list: a lower bound of the true k-th best score
+  float eq;     // >= |q - sq cq|
+  float qhat;   // >= sq sqrt(nq)
+  float w;      // L2: >= sqrt((-tau + tiny) / (1 - G)) + eq, the radius a row's code must lie beyond.  IP: >= qhat + eq
+  int32_t ok;   // tau, eq and qhat are finite (L2: and tau <= 0)
+  int32_t certified;  // ok and at most cap survivors (k_sq8_exact_lists, behind the count)
+  int32_t pad[2];
+};
+// G: the relative error of the exact scorer's f32 accumulation over d terms and one subtraction each, (d + 4) 2^-24 >=
+// gamma_(d + 2) (exact in f32)
+inline float sq8_gamma(int d) { return (float)(d + 4) * 0x1p-24f; }
+
+// workspace of a certified call: [Sq8Layout, its CandLayout sized for chunk * cap positions | what follows]
+struct Sq8ExactLayout {
+  Sq8Layout S;
+  int n_blocks;                         // range_n_blocks(n_items)
+  long long cap;                        // min(cap, n_items): most survivors of a certified query
+  size_t off_qerr, off_qxhat;           // f32[chunk] each: the chunk's queries through k_sq8_row_err
+  size_t off_a_ids, off_a_scores;       // stage (a): i64[chunk, k], f32[chunk, k]
+  size_t off_terms;                     // Sq8QTerms[chunk]
+  size_t off_counts;                    // i32[chunk, n_blocks] block counts, then prefixes; i32[chunk] totals behind
+  size_t off_xsplits;                   // i64[chunk + 1]: the compact row_splits of the final lists
+  size_t off_rows;                      // i32[chunk * cap]: the final lists, survivors or the sorted fetch list
+  size_t total;
+};
+Sq8ExactLayout sq8_exact_layout(const ScanLayout& L, int kind, int d, int fetch, long long cap, int k, long long n_items);
+
+// err, xhat f32[n] of n vectors and their codes (dt: NANN_F16 / NANN_BF16 / NANN_F32)
+int launch_sq8_row_err(const void* x, int dt, long long n, int d, const int8_t* codes, const float* scales, const int32_t* norms,
+                       float* err, float* xhat, hipStream_t st);
+// behind a chunk's launch_sq8_fetch and its launch_cand at k into off_a_*: the query terms, the survivor count, the block
+// prefixes, certified / n_survivors of the chunk (out_*: this chunk's slice), the compact row_splits and the final lists
+int launch_sq8_survivors(const Sq8Args& a, const ScanLayout& L, const Sq8ExactLayout& X, const float* q, const float* err,
+                         const float* xhat, int n_q, int fetch, int k, unsigned char* ws, int32_t* out_certified,
+                         int32_t* out_n_survivors, hipStream_t st);
+
 }  // namespace nann
 
 #ifdef NANN_SQ8_IMPL  // the kernels: nann_sq8_inst.hip only (nann_flat.hip takes the declarations above)
@@ -226,6 +281,239 @@ __global__ __launch_bounds__(kSq8NT) void k_sq8_sort_rows(const int32_t* __restr
   if (tid == 0) {
     splits[qi] = (long long)qi * fetch;
     splits[qi + 1] = (long long)(qi + 1) * fetch;
+  }
+}
+
+// ---- the certified form ---------------------------------------------------------------------------------------------------
+// one wavefront per vector, shaped like k_sq8_encode; the order of every step is the one stated at the head of this file
+template <int DT>
+__global__ __launch_bounds__(kSq8NT) void k_sq8_row_err(const void* __restrict__ x, long long n, int d, const int8_t* __restrict__ codes,
+                                                        const float* __restrict__ scales, const int32_t* __restrict__ norms,
+                                                        float* __restrict__ err, float* __restrict__ xhat) {
+  const int lane = threadIdx.x & 63;
+  const int per = d >> 6;  // d / 64 <= 8
+  for (long long v = (long long)blockIdx.x * (kSq8NT / 64) + (threadIdx.x >> 6); v < n; v += (long long)gridDim.x * (kSq8NT / 64)) {
+    const float scale = scales[v];
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < kMaxD / 64; ++i) {
+      if (i < per) {
+        const size_t at = (size_t)v * d + i * 64 + lane;
+        const float p = __fmul_rn(scale, (float)codes[at]);
+        const float r = __fsub_rn(sq8_load<DT>(x, at), p);
+        acc = __fadd_rn(acc, __fmul_rn(r, r));
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc = __fadd_rn(acc, __shfl_xor(acc, o));
+    if (lane == 0) {
+      const float e0 = sqrtf(acc);
+      const float xh = __fadd_rn(__fmul_rn(__fmul_rn(scale, sqrtf((float)norms[v])), kSq8Infl), kSq8Abs);
+      xhat[v] = xh;
+      err[v] = __fadd_rn(__fmul_rn(__fadd_rn(e0, __fmul_rn(0x1p-23f, xh)), kSq8Infl), kSq8Abs);
+    }
+  }
+}
+
+// one thread per query of the chunk: tau from stage (a)'s scores f32[n_q, k], the query's error terms, the radius / norm term
+template <int METRIC>
+__global__ __launch_bounds__(kSq8NT) void k_sq8_exact_terms(const float* __restrict__ a_scores, int k, const float* __restrict__ qerr,
+                                                            const float* __restrict__ qxhat, int n_q, float g,
+                                                            Sq8QTerms* __restrict__ terms) {
+  const int qi = blockIdx.x * kSq8NT + threadIdx.x;
+  if (qi >= n_q) return;
+  Sq8QTerms t = {};
+  t.tau = a_scores[(size_t)qi * k + (k - 1)];
+  t.eq = qerr[qi];
+  t.qhat = qxhat[qi];
+  const float big = 3.402823466e+38f;
+  bool ok = fabsf(t.tau) <= big && fabsf(t.eq) <= big && fabsf(t.qhat) <= big;  // (a NaN fails every comparison)
+  if constexpr (METRIC == MT_L2) {
+    ok = ok && t.tau <= 0.0f;
+    const float t2 = __fmul_rn(__fadd_rn(-t.tau, kSq8Tiny), __fadd_rn(1.0f, __fmul_rn(2.0f, g)));
+    const float rho = __fmul_rn(sqrtf(t2), kSq8Infl2);
+    t.w = __fmul_rn(__fadd_rn(rho, t.eq), kSq8Infl2);
+  } else {
+    t.w = __fmul_rn(__fadd_rn(t.qhat, t.eq), kSq8Infl2);
+  }
+  t.ok = ok ? 1 : 0;
+  terms[qi] = t;
+}
+
+// The survivor predicate: false only where the exact f32 score of the row is provably below tau.  a: the
+// approximate score; err, xhat: the row's terms.  Every comparison is written so that a NaN keeps the row; a row ties tau survives.
+template <int METRIC>
+__device__ __forceinline__ bool sq8_survives(float a, float err, float xhat, const Sq8QTerms& t, float g) {
+  if (!(fabsf(a) <= 3.402823466e+38f)) return true;  // (an overflowed or NaN score bounds nothing)
+  if constexpr (METRIC == MT_L2) {
+    const float w = __fadd_rn(t.qhat, xhat);
+    const float dl = __fadd_rn(__fmul_rn(__fmul_rn(w, w), 0x1p-20f), kSq8Tiny);  // >= |a - (-|qhat_vec - xhat_vec|^2)|
+    const float lo = __fsub_rn(-a, dl);                                            // a lower bound of |qhat_vec - xhat_vec|^2
+    const float s = __fadd_rn(t.w, err);
+    const float hi = __fmul_rn(__fmul_rn(s, s), kSq8Infl);
+    return !(lo > hi);
+  } else {
+    const float cross = __fadd_rn(__fadd_rn(__fmul_rn(t.eq, xhat), __fmul_rn(err, t.qhat)), __fmul_rn(t.eq, err));
+    const float gt = __fmul_rn(g, __fmul_rn(t.w, __fadd_rn(xhat, err)));
+    const float p = __fadd_rn(__fadd_rn(__fadd_rn(cross, gt), __fmul_rn(0x1p-22f, fabsf(a))), kSq8Tiny);
+    const float ub = __fadd_rn(a, __fmul_rn(p, kSq8Infl));
+    return !(ub < t.tau);
+  }
+}
+
+// What a thread holds of block blockIdx.x of query blockIdx.y, after range_load (nann_range.h): the same 16-byte aligned walk
+// over the score buffer; bit j of m[p] says that element j of pass p is a row of the query and survives.
+struct Sq8SurvBlock {
+  size_t at[kRangePasses];
+  unsigned m[kRangePasses];
+  size_t begin;
+};
+template <int METRIC>
+__device__ __forceinline__ void sq8_surv_load(const float* __restrict__ scores, long long n_items, const float* __restrict__ err,
+                                              const float* __restrict__ xhat, const Sq8QTerms t, float g, Sq8SurvBlock* b) {
+  const size_t begin = (size_t)blockIdx.y * (size_t)n_items, end = begin + (size_t)n_items;
+  const size_t g0 = (begin >> 2) + (size_t)blockIdx.x * (kRangeBlockRows / 4);
+  b->begin = begin;
+#pragma unroll
+  for (int p = 0; p < kRangePasses; ++p) {
+    const size_t at = (g0 + (size_t)p * kRangeNT + threadIdx.x) * 4;
+    b->at[p] = at;
+    b->m[p] = 0u;
+    if (at < end) {  // (the 16 bytes begin inside the row or up to three positions in front of it, and end within 16 B of its end)
+      const f32x4v s = *reinterpret_cast<const f32x4v*>(scores + at);
+      if (at >= begin && at + 3 < end) {
+        // all four positions are rows of the query: their terms are 16 contiguous bytes of each array, at a 4-byte alignment
+        // that depends on the query (begin mod 4) -- one load each where the target takes unaligned vector loads
+        const size_t row = at - begin;
+        f32x4v e, xh;
+        __builtin_memcpy(&e, err + row, 16);
+        __builtin_memcpy(&xh, xhat + row, 16);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (sq8_survives<METRIC>(s[j], e[j], xh[j], t, g)) b->m[p] |= 1u << j;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (at + j >= begin && at + j < end) {
+            const size_t row = at + j - begin;  // < n_items: the loads below are inside the two arrays
+            if (sq8_survives<METRIC>(s[j], err[row], xhat[row], t, g)) b->m[p] |= 1u << j;
+          }
+        }
+      }
+    }
+  }
+}
+
+// counts[query][block] = survivors of the block (k_range_count's shape)
+template <int METRIC>
+__global__ __launch_bounds__(kRangeNT) void k_sq8_surv_count(const float* __restrict__ scores, long long n_items,
+                                                             const float* __restrict__ err, const float* __restrict__ xhat,
+                                                             const Sq8QTerms* __restrict__ terms, float g,
+                                                             int32_t* __restrict__ counts) {
+  __shared__ int wave_cnt[kRangeNT / 64];
+  Sq8SurvBlock b;
+  sq8_surv_load<METRIC>(scores, n_items, err, xhat, terms[blockIdx.y], g, &b);
+  int c = 0;
+#pragma unroll
+  for (int p = 0; p < kRangePasses; ++p)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c += __popcll(__ballot((b.m[p] >> j) & 1u));
+  if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+#pragma unroll
+    for (int w = 0; w < kRangeNT / 64; ++w) t += wave_cnt[w];
+    counts[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
+  }
+}
+
+// One workgroup per chunk, behind k_range_scan: certified and n_survivors of every query, the compact row_splits of the final
+// lists -- a certified query's survivors, else its fetch list -- and the sorted fetch lists of the uncertified queries copied
+// into their places.  n_q <= kScanMaxChunk <= kSq8NT.
+__global__ __launch_bounds__(kSq8NT) void k_sq8_exact_lists(const int32_t* __restrict__ totals, Sq8QTerms* __restrict__ terms,
+                                                            int n_q, int fetch, long long cap, const int32_t* __restrict__ sorted,
+                                                            long long* __restrict__ xsplits, int32_t* __restrict__ rows,
+                                                            int32_t* __restrict__ out_certified,
+                                                            int32_t* __restrict__ out_n_survivors) {
+  __shared__ long long len[kSq8NT];
+  __shared__ long long begin[kSq8NT + 1];
+  __shared__ int cert[kSq8NT];
+  const int tid = threadIdx.x;
+  int total = 0, c = 1;
+  if (tid < n_q) {
+    total = totals[tid];
+    c = terms[tid].ok != 0 && (long long)total <= cap ? 1 : 0;
+    terms[tid].certified = c;
+    out_certified[tid] = c;
+    out_n_survivors[tid] = total;
+  }
+  cert[tid] = c;
+  len[tid] = tid < n_q ? (c ? (long long)total : (long long)fetch) : 0;
+  __syncthreads();
+  long long sum = 0;
+  for (int j = 0; j < tid; ++j) sum += len[j];
+  begin[tid] = sum;
+  if (tid < n_q) xsplits[tid] = sum;
+  if (tid == n_q - 1) xsplits[n_q] = sum + len[tid];
+  __syncthreads();
+  for (int qi = 0; qi < n_q; ++qi) {
+    if (cert[qi]) continue;
+    for (int i = tid; i < fetch; i += kSq8NT) rows[begin[qi] + i] = sorted[(size_t)qi * fetch + i];  // (fetch <= cap: inside the list's room)
+  }
+}
+
+// The survivors of a block to their places in the query's list, ascending row order, no atomics (k_range_fill's shape).
+// prefix = counts behind k_range_scan, totals = the queries' sums behind them.  An uncertified query's list is its fetch list:
+// nothing is written for it.
+template <int METRIC>
+__global__ __launch_bounds__(kRangeNT) void k_sq8_surv_fill(const float* __restrict__ scores, long long n_items,
+                                                            const float* __restrict__ err, const float* __restrict__ xhat,
+                                                            const Sq8QTerms* __restrict__ terms, float g,
+                                                            const int32_t* __restrict__ prefix, const int32_t* __restrict__ totals,
+                                                            const long long* __restrict__ xsplits, long long cap,
+                                                            int32_t* __restrict__ rows) {
+  constexpr int W = kRangeNT / 64;
+  __shared__ int cnt[kRangePasses * W];
+  // (uniform over the workgroup) nothing to place: an uncertified query, or a block without a survivor -- most blocks of a
+  // large corpus -- leaves before it reads a score
+  const size_t pb = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+  const int block_end = blockIdx.x + 1 < gridDim.x ? prefix[pb + 1] : totals[blockIdx.y];
+  if (terms[blockIdx.y].certified == 0 || block_end == prefix[pb]) return;
+  Sq8SurvBlock b;
+  sq8_surv_load<METRIC>(scores, n_items, err, xhat, terms[blockIdx.y], g, &b);
+  const int wave = threadIdx.x >> 6;
+  int rank[kRangePasses];  // survivors of the pass's wavefront in the lanes below this one
+#pragma unroll
+  for (int p = 0; p < kRangePasses; ++p) {
+    int below = 0, all = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned long long m = __ballot((b.m[p] >> j) & 1u);
+      below += range_lanes_below(m);
+      all += __popcll(m);
+    }
+    rank[p] = below;
+    if ((threadIdx.x & 63) == 0) cnt[p * W + wave] = all;
+  }
+  __syncthreads();
+  const long long q_begin = xsplits[blockIdx.y];
+  const long long room = min(cap, xsplits[blockIdx.y + 1] - q_begin);  // the list's length: the survivor count iff certified
+  const bool certified = terms[blockIdx.y].certified != 0;
+  const long long in_q = prefix[pb];
+#pragma unroll
+  for (int p = 0; p < kRangePasses; ++p) {
+    int base = 0;
+#pragma unroll
+    for (int i = 0; i < kRangePasses * W; ++i)
+      if (i < p * W + wave) base += cnt[i];
+    long long pos = in_q + base + rank[p];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (!((b.m[p] >> j) & 1u)) continue;
+      if (certified && pos >= 0 && pos < room) rows[q_begin + pos] = (int32_t)(b.at[p] + j - b.begin);  // the guard of the store
+      ++pos;
+    }
   }
 }
 

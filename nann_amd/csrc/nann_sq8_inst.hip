@@ -1,11 +1,13 @@
 // nann_sq8_inst.hip -- the kernels of the scalar-quantised exhaustive search (nann_sq8.h): the encoder for every input dtype, the
-// int8 MFMA scan for every (d, metric), the row sort; workspace layout and the launch sequence of a chunk's fetch stage.  Rides in
+// int8 MFMA scan for every (d, metric), the row sort; workspace layout and the launch sequence of a chunk's fetch stage; the
+// certified form's row-error kernel, query terms and survivor pass (count, k_range_scan, lists, fill).  Rides in
 // nann_scan.o behind nann_scan_inst.hip: the slab top-k and the merge it launches are that file's kernels.
 #ifndef NANN_SCAN_IMPL
 #define NANN_SCAN_IMPL
 #endif
 #define NANN_SQ8_IMPL
 #include "nann_sq8.h"
+#include "nann_cand.h"
 
 #include <algorithm>
 
@@ -99,6 +101,86 @@ int launch_sq8_fetch(const Sq8Args& a, const ScanLayout& L, const Sq8Layout& S, 
                      out_fetch_scores);
   NANN_HIP_TRY(hipGetLastError());
   return NANN_OK;
+}
+
+// ---- the certified form ---------------------------------------------------------------------------------------------------
+Sq8ExactLayout sq8_exact_layout(const ScanLayout& L, int kind, int d, int fetch, long long cap, int k, long long n_items) {
+  Sq8ExactLayout X = {};
+  const size_t c = (size_t)L.chunk;
+  X.cap = std::min(cap, n_items);
+  X.n_blocks = range_n_blocks(n_items);
+  // one CandLayout serves both candidate-list searches of a chunk: the fetch lists (chunk * fetch positions), then the final
+  // lists (at most chunk * cap, fetch <= cap)
+  X.S = sq8_layout(L, d, fetch, cand_layout(kind, L.chunk, (long long)L.chunk * X.cap).total);
+  X.off_qerr = X.S.total;
+  X.off_qxhat = X.off_qerr + sq8_up256(c * 4);
+  X.off_a_ids = X.off_qxhat + sq8_up256(c * 4);
+  X.off_a_scores = X.off_a_ids + sq8_up256(c * (size_t)k * 8);
+  X.off_terms = X.off_a_scores + sq8_up256(c * (size_t)k * 4);
+  X.off_counts = X.off_terms + sq8_up256(c * sizeof(Sq8QTerms));
+  X.off_xsplits = X.off_counts + range_counts_bytes(L.chunk, n_items);
+  X.off_rows = X.off_xsplits + sq8_up256((c + 1) * 8);
+  X.total = X.off_rows + sq8_up256(c * (size_t)X.cap * 4);
+  return X;
+}
+
+int launch_sq8_row_err(const void* x, int dt, long long n, int d, const int8_t* codes, const float* scales, const int32_t* norms,
+                       float* err, float* xhat, hipStream_t st) {
+  if (n <= 0) return NANN_OK;
+  if (!(d == 64 || d == 128 || d == 256 || d == 512)) return fail(NANN_ERR_UNSUPPORTED, "nann_sq8_bounds: d must be 64, 128, 256 or 512");
+  const unsigned grid = (unsigned)std::min<long long>((n + kSq8NT / 64 - 1) / (kSq8NT / 64), 1 << 16);
+  if (dt == NANN_F16) hipLaunchKernelGGL(k_sq8_row_err<DT_F16>, dim3(grid), dim3(kSq8NT), 0, st, x, n, d, codes, scales, norms, err, xhat);
+  else if (dt == NANN_BF16) hipLaunchKernelGGL(k_sq8_row_err<DT_BF16>, dim3(grid), dim3(kSq8NT), 0, st, x, n, d, codes, scales, norms, err, xhat);
+  else if (dt == NANN_F32) hipLaunchKernelGGL(k_sq8_row_err<DT_F32>, dim3(grid), dim3(kSq8NT), 0, st, x, n, d, codes, scales, norms, err, xhat);
+  else return fail(NANN_ERR_BAD_ARGUMENT, "nann_sq8_bounds: unknown dtype");
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+template <int METRIC>
+static int launch_sq8_survivors_as(const Sq8Args& a, const ScanLayout& L, const Sq8ExactLayout& X, const float* q, const float* err,
+                                   const float* xhat, int n_q, int fetch, int k, unsigned char* ws, int32_t* out_certified,
+                                   int32_t* out_n_survivors, hipStream_t st) {
+  const float* scores = reinterpret_cast<const float*>(ws + L.off_scores);
+  float* qerr = reinterpret_cast<float*>(ws + X.off_qerr);
+  float* qxhat = reinterpret_cast<float*>(ws + X.off_qxhat);
+  Sq8QTerms* terms = reinterpret_cast<Sq8QTerms*>(ws + X.off_terms);
+  int32_t* counts = reinterpret_cast<int32_t*>(ws + X.off_counts);
+  int32_t* totals = counts + (size_t)n_q * X.n_blocks;
+  long long* xsplits = reinterpret_cast<long long*>(ws + X.off_xsplits);
+  int32_t* rows = reinterpret_cast<int32_t*>(ws + X.off_rows);
+  const float g = sq8_gamma(a.d);
+  // the queries' own error terms, from the codes launch_sq8_fetch has left in the workspace
+  int rc = launch_sq8_row_err(q, NANN_F32, n_q, a.d, reinterpret_cast<const int8_t*>(ws + X.S.off_qcodes),
+                              reinterpret_cast<const float*>(ws + X.S.off_qscales), reinterpret_cast<const int32_t*>(ws + X.S.off_qnorms),
+                              qerr, qxhat, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_sq8_exact_terms<METRIC>, dim3((unsigned)((n_q + kSq8NT - 1) / kSq8NT)), dim3(kSq8NT), 0, st,
+                     reinterpret_cast<const float*>(ws + X.off_a_scores), k, qerr, qxhat, n_q, g, terms);
+  NANN_HIP_TRY(hipGetLastError());
+  const dim3 grid((unsigned)X.n_blocks, (unsigned)n_q);
+  hipLaunchKernelGGL(k_sq8_surv_count<METRIC>, grid, dim3(kRangeNT), 0, st, scores, a.n_items, err, xhat, terms, g, counts);
+  NANN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_range_scan, dim3((unsigned)n_q), dim3(kRangeNT), 0, st, counts, X.n_blocks, totals);
+  NANN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_sq8_exact_lists, dim3(1), dim3(kSq8NT), 0, st, totals, terms, n_q, fetch, X.cap,
+                     reinterpret_cast<const int32_t*>(ws + X.S.off_sorted), xsplits, rows, out_certified, out_n_survivors);
+  NANN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_sq8_surv_fill<METRIC>, grid, dim3(kRangeNT), 0, st, scores, a.n_items, err, xhat, terms, g, counts, totals,
+                     xsplits, X.cap, rows);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+int launch_sq8_survivors(const Sq8Args& a, const ScanLayout& L, const Sq8ExactLayout& X, const float* q, const float* err,
+                         const float* xhat, int n_q, int fetch, int k, unsigned char* ws, int32_t* out_certified,
+                         int32_t* out_n_survivors, hipStream_t st) {
+  static_assert(kScanMaxChunk <= kSq8NT && kScanMaxChunk <= kRangeNT, "one workgroup walks a chunk's queries");
+  if (n_q < 1 || n_q > kScanMaxChunk || k < 1 || k > fetch || X.cap < fetch)
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_sq8_exact: chunk shape");
+  return a.metric == MT_IP
+             ? launch_sq8_survivors_as<MT_IP>(a, L, X, q, err, xhat, n_q, fetch, k, ws, out_certified, out_n_survivors, st)
+             : launch_sq8_survivors_as<MT_L2>(a, L, X, q, err, xhat, n_q, fetch, k, ws, out_certified, out_n_survivors, st);
 }
 
 }  // namespace nann

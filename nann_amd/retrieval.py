@@ -547,6 +547,101 @@ def search_all_sq8(index, sq8, scorer, q, k, fetch=None, options=None, return_fe
     return Sq8Result(out_ids, out_scores, out_index, f_index, f_scores, fetch, ws)
 
 
+class Sq8Bounds:
+    """The per-row error terms of a code table (nann_sq8_bounds; make_sq8_bounds): err() f32[n_items] >= |x_i - scale_i codes_i|,
+    xhat() f32[n_items] >= scale_i sqrt(norm_i), torch views of device memory valid until release().  It borrows the index and
+    the table -- the object keeps both alive -- and goes STALE with the table."""
+
+    def __init__(self, index, sq8):
+        self.index, self.sq8 = index, sq8
+        self.handle = C.c_void_p(0)
+        with torch.cuda.device(index.device):
+            _check(lib().nann_sq8_bounds_create(index.handle, sq8.handle, _stream(), C.byref(self.handle)), "make_sq8_bounds")
+        self.n_items = sq8.n_items
+
+    def _views(self):
+        if not self.handle.value:
+            raise ValueError("Sq8Bounds: released")
+        p = [C.c_void_p(0) for _ in range(2)]
+        _check(lib().nann_sq8_bounds_view(self.handle, *[C.byref(v) for v in p]))
+        with torch.cuda.device(self.index.device):
+            return [ops._wrap_device_pointer(v.value, (self.n_items,), torch.float32, self) for v in p]
+
+    def err(self):
+        return self._views()[0]
+
+    def xhat(self):
+        return self._views()[1]
+
+    def release(self):
+        """Free the device memory (the views die with it).  Synchronise streams that still read it first."""
+        if self.handle.value:
+            lib().nann_sq8_bounds_destroy(self.handle)
+            self.handle = C.c_void_p(0)
+
+    def __del__(self):
+        try:  # at interpreter shutdown the module globals may already be gone
+            if getattr(self, "handle", None) and self.handle.value:
+                lib().nann_sq8_bounds_destroy(self.handle)
+                self.handle = C.c_void_p(0)
+        except Exception:
+            pass
+
+
+def make_sq8_bounds(index, sq8):
+    """The error terms of `sq8`'s rows (nann_sq8_bounds_create), what search_all_sq8_exact certifies with: 8 bytes per row.
+    Computed on torch's current stream.  Re-create it with the table."""
+    return Sq8Bounds(index, sq8)
+
+
+class Sq8ExactResult:
+    """Outputs of search_all_sq8_exact: item_ids i64[B, k], scores f32[B, k], index i32[B, k]; certified i32[B] (1: the row is
+    search_all's, bit for bit), n_survivors i32[B] (rows the bound could not exclude, whatever the cap)."""
+    __slots__ = ("item_ids", "scores", "index", "certified", "n_survivors", "fetch", "cap", "_ws")
+
+    def __init__(self, item_ids, scores, index, certified, n_survivors, fetch, cap, ws=None):
+        self.item_ids, self.scores, self.index = item_ids, scores, index
+        self.certified, self.n_survivors, self.fetch, self.cap, self._ws = certified, n_survivors, fetch, cap, ws
+
+
+def search_all_sq8_exact(index, sq8, bounds, scorer, q, k, fetch=None, cap=2048, fallback=True, options=None):
+    """Certified scalar-quantised exhaustive search (nann_search_all_sq8_exact): search_all's result BIT FOR BIT -- item ids,
+    scores, index, ties to the lower row -- from the int8 scan.  Per query: search_all_sq8's fetch and exact re-rank at `fetch`
+    give a cut; every row whose exact score a rigorous error bound cannot put below the cut survives; the exact top k of the
+    survivors is the answer.  result.certified[b] == 1 iff at most `cap` rows survived (and the query is finite); an uncertified
+    row of the result is search_all_sq8's answer at the same fetch.  `scorer`: an l2 or ip ops.Scorer with q f32[B, d]; sq8:
+    make_sq8(index); bounds: make_sq8_bounds(index, sq8).  fetch=None means min(max(k, 1), 1024, n_items); k <= fetch <= cap.
+    fallback=True: the wrapper reads `certified` back -- ONE synchronisation of the stream with the host -- and re-runs the
+    uncertified queries through search_all, so that the result is exact for EVERY query (certified and n_survivors stay as the
+    device call left them).  fallback=False: asynchronous on torch's current stream, nothing read back."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    b, k = q.shape[0], int(k)
+    fetch = min(max(k, 1), 1024, int(index.n_items)) if fetch is None else int(fetch)
+    cap = int(cap)
+    kk = max(k, 0)
+    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
+    certified = torch.zeros(b, dtype=torch.int32, device=dev)
+    n_surv = torch.zeros(b, dtype=torch.int32, device=dev)
+    nbytes = C.c_int64(0)
+    bh = bounds.handle if bounds is not None else None
+    _check(lib().nann_search_all_sq8_exact_workspace_bytes(index.handle, sq8.handle, bh, scorer.handle, b, fetch, cap, k,
+                                                           C.byref(nbytes)), "search_all_sq8_exact")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_all_sq8_exact(index.handle, sq8.handle, bh, scorer.handle, _ptr(q), b, fetch, cap, k, _ptr(out_ids),
+                                               _ptr(out_scores), _ptr(out_index), _ptr(certified), _ptr(n_surv), _ptr(ws), ws.numel(),
+                                               C.byref(options) if options is not None else None, _stream()), "search_all_sq8_exact")
+    if fallback and b > 0 and k > 0:
+        todo = torch.nonzero(certified == 0).flatten()  # (the synchronisation)
+        if todo.numel() > 0:
+            r = search_all(index, scorer, q[todo], k, options=options)
+            out_ids[todo], out_scores[todo], out_index[todo] = r.item_ids, r.scores, r.index
+    return Sq8ExactResult(out_ids, out_scores, out_index, certified, n_surv, fetch, cap, ws)
+
+
 def search_all_model(index, model, comm_seq, k, options=None):
     """Exhaustive search under a model (nann_search_all_model; the reference's test_all job, main.py:194-237, which scores
     its own attention + DNN model): every item of `index` scored for every user of comm_seq f16[B, seq_len, E], top k per

@@ -1384,6 +1384,42 @@ int nann_search_all_sq8_exact(const nann_index* ix, const nann_sq8* t, const nan
                               float* out_scores, int32_t* out_index, int32_t* out_certified, int32_t* out_n_survivors,
                               void* workspace, int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream);
 
+/* ---- certified scalar-quantised RANGE search: nann_search_all_range's exact result from the int8 scan.  Added
+ * to ABI version 6: new symbols only.
+ * The caller's threshold is the cut, so there is no fetch stage and no top-k.  Per query, without a host read-back:
+ *   (a) the int8 scan, and a pass over the approximate scores of EVERY row that keeps the rows whose exact f32 score the bound of
+ *       nann_search_all_sq8_exact cannot put below tau = thresholds[q] -- the survivors, rows scoring exactly tau among them;
+ *       out_n_survivors[q] = their number, the true count whatever `cap`;
+ *   (b) out_certified[q] = 1 iff the threshold and the query's terms are finite and n_survivors[q] <= min(cap, n_items).  A
+ *       non-finite threshold (NaN, +inf, -inf) is never certified.
+ *       NANN_SCORER_L2 with a finite threshold above +0: out_certified[q] = 1, out_n_survivors[q] = 0 and an empty segment,
+ *       whatever the pass counted -- the scorer stores 0.0f - (a sum of squares), so no score exceeds +0 and a NaN score matches
+ *       nothing.  A threshold of +0 or -0 takes the normal path;
+ *   (c) a certified query's segment is exactly what nann_search_all_range with filter = NULL returns for it: the rows with
+ *       score >= threshold and score != -inf, in ascending row order, the scores nann_score's bits, with item ids and index.  An
+ *       uncertified query's segment is EMPTY (its count in out_row_splits is 0): the caller sees out_certified[q] == 0 and runs
+ *       that query through nann_search_all_range.
+ * q, thresholds, capacity and the ragged outputs are nann_search_all_range's, word for word: out_row_splits i64[n_queries + 1]
+ * holds the true totals whatever the capacity, a position at or beyond `capacity` is never written, the positions in
+ * [min(total, capacity), capacity) are left untouched, capacity == 0 with NULL entry outputs is a count-only call, and a query's
+ * segment does not depend on its batch.  out_certified i32[n_queries] and out_n_survivors i32[n_queries] are required.
+ * There is NO filter argument: a denied row is marked by a score of -inf, while the survivor pass keeps every row whose
+ * approximate score is not finite; combining the two needs an argument of its own.
+ * Checks, all in front of the first launch: nann_search_all_range's own; an MLP scorer or an index with f32 rows ->
+ * NANN_ERR_UNSUPPORTED; a NULL table or bounds, a table or bounds made from another index or table, cap < 1, or a NULL
+ * out_certified / out_n_survivors while n_queries > 0 -> NANN_ERR_BAD_ARGUMENT; cap beyond the longest list a candidate-list search
+ * takes per query, (2^31 - 1) / (queries per chunk, at most 128) -> NANN_ERR_UNSUPPORTED; a workspace smaller than
+ * nann_search_all_range_sq8_exact_workspace_bytes gives -> NANN_ERR_CAPACITY (256-byte aligned; it holds an f32 and an i32 per
+ * (query of a chunk, cap position) and is bounded by a chunk of queries); n_queries == 0 -> NANN_OK, nothing written.  A cap above
+ * n_items counts as n_items.  Asynchronous on `stream`, re-entrant. */
+int nann_search_all_range_sq8_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
+                                                    const nann_scorer* scorer, int64_t n_queries, int64_t cap, int64_t* nbytes);
+int nann_search_all_range_sq8_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                    const float* q, int64_t n_queries, const float* thresholds, int64_t cap, int64_t capacity,
+                                    int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                    int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
+                                    const nann_search_options* options, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

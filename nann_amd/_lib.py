@@ -80,6 +80,7 @@ SYMBOLS = [
     "nann_search_all_sq8_workspace_bytes", "nann_search_all_sq8",
     "nann_sq8_bounds_create", "nann_sq8_bounds_destroy", "nann_sq8_bounds_view",
     "nann_search_all_sq8_exact_workspace_bytes", "nann_search_all_sq8_exact_layout", "nann_search_all_sq8_exact",
+    "nann_search_all_range_sq8_exact_workspace_bytes", "nann_search_all_range_sq8_exact",
 ]
 
 
@@ -410,6 +411,13 @@ def lib():
         L.nann_search_all_sq8_exact.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 6 + \
                                                [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
         L.nann_search_all_sq8_exact.restype = C.c_int
+        # the range form: (ix, t, b, scorer, n, cap, *nbytes) / (ix, t, b, scorer, q, n, thresholds, cap, capacity, out_row_splits,
+        #  out_item_ids, out_scores, out_index, out_certified, out_n_survivors, workspace, workspace_bytes, options, stream)
+        L.nann_search_all_range_sq8_exact_workspace_bytes.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+        L.nann_search_all_range_sq8_exact_workspace_bytes.restype = C.c_int
+        L.nann_search_all_range_sq8_exact.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 7 + \
+                                                     [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
+        L.nann_search_all_range_sq8_exact.restype = C.c_int
         # (ix, scorer or NULL, model or NULL, n_queries, *plan)
         L.nann_search_eval_plan.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.POINTER(EvalPlan)]
         L.nann_search_eval_plan.restype = C.c_int

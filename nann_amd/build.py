@@ -154,6 +154,9 @@ RULES = [
     # twice and holds a block's eight positions per thread in registers; a frame in private memory would add its traffic to a pass that
     # is nothing but memory traffic.
     ("sq8_surv_scratch", r"k_sq8_surv_(count|fill)", 0, None, "the survivor pass"),
+    # The range form of the certified int8 search (k_sq8_range_lists / k_sq8_range_count / k_sq8_range_fill, nann_sq8.h): the
+    # selection holds a block's eight scores per thread in registers, as the survivor pass does, and is held to the same.
+    ("sq8_range_scratch", r"k_sq8_range_(lists|count|fill)", 0, None, "the certified range selection"),
 ]
 
 

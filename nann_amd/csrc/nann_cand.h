@@ -75,6 +75,9 @@ inline long long cand_max_list(long long n_queries) { return 0x7fffffffll / (n_q
 int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status,
                 hipStream_t st);
+// steps 1 and 2 of launch_cand without its top-k: the plan, and the exact score of every list position in L's score buffer, in
+// position order (the range form of the certified int8 search selects from them by a cut, nann_sq8.h)
+int launch_cand_scores(const CandArgs& a, const CandLayout& L, const float* q, long long n_queries, unsigned char* ws, hipStream_t st);
 // steps 1 and 3 on their own (nann_cand_inst.hip): launch_cand's, and the attention form's around its chunks
 int launch_cand_plan(const int64_t* row_splits, long long n_queries, long long n_cand, int rows_per_item, CandQuery* plan,
                      long long* item_off, hipStream_t st);

@@ -79,9 +79,7 @@ int launch_cand_topk(const CandQuery* plan, const int32_t* rows, const float* sc
   return NANN_OK;
 }
 
-int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
-                int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status,
-                hipStream_t st) {
+int launch_cand_scores(const CandArgs& a, const CandLayout& L, const float* q, long long n_queries, unsigned char* ws, hipStream_t st) {
   if (a.kind != NANN_SCORER_L2 && a.kind != NANN_SCORER_MLP && a.kind != NANN_SCORER_IP)
     return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_candidates: unknown scorer kind");
   const bool mlp = a.kind == NANN_SCORER_MLP, ip = a.kind == NANN_SCORER_IP;
@@ -117,8 +115,16 @@ int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long lon
     }
     NANN_HIP_TRY(hipGetLastError());
   }
-  return launch_cand_topk(s.plan, a.rows, s.scores, n_queries, k, a.item_ids, out_item_ids, out_scores, out_index, out_pos, n_out,
-                          status, st);
+  return NANN_OK;
+}
+
+int launch_cand(const CandArgs& a, const CandLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
+                int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status,
+                hipStream_t st) {
+  const int rc = launch_cand_scores(a, L, q, n_queries, ws, st);
+  if (rc) return rc;
+  return launch_cand_topk(reinterpret_cast<const CandQuery*>(ws + L.off_plan), a.rows, reinterpret_cast<const float*>(ws + L.off_scores),
+                          n_queries, k, a.item_ids, out_item_ids, out_scores, out_index, out_pos, n_out, status, st);
 }
 
 // ---- the union top-k (nann_union.h) -----------------------------------------------------------------------------------

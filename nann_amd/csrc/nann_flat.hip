@@ -10,7 +10,8 @@
 // nann_search_all_model_diverse); the attribute predicates on their own (nann_predicate_topk, nann_predicate_count; kernels in
 // nann_predicate.h) and inside the filtered exhaustive search (nann_search_all_where, nann_search_all_model_where); the int8
 // code table of an index (nann_sq8_create, ..) and the exhaustive search over it with an exact re-rank (nann_search_all_sq8;
-// kernels in nann_sq8.h), and its certified form that returns nann_search_all's bits (nann_sq8_bounds, nann_search_all_sq8_exact).
+// kernels in nann_sq8.h), its certified form that returns nann_search_all's bits (nann_sq8_bounds, nann_search_all_sq8_exact) and
+// the certified range form that returns nann_search_all_range's (nann_search_all_range_sq8_exact).
 //
 // A source of nann_core.o.  What it takes from the other host sources, and what the traversal's forms (nann_traverse.hip) take
 // from it -- resolve_filter, resolve_predicates, resolve_groups, resolve_diversity, mmr_index, union_check, fuse_shape_check,
@@ -958,6 +959,84 @@ static int flat_all_sq8_exact(const nann_index* ix, const nann_sq8* t, const nan
   return NANN_OK;
 }
 
+// ---- the certified range form (nann_search_all_range_sq8_exact; nann_sq8.h) ------------------------------------
+// The caller's threshold is the cut: per chunk the int8 scan and the survivor pass at tau = thresholds[q], the candidate-list
+// search's scorer over the survivor lists, and the ragged selection over those exact scores.  No fetch stage, no top-k.
+// workspace: Sq8RangeLayout behind the ScanLayout at k = 0.  Nothing in it grows with n_queries beyond a chunk.
+static int flat_sq8_range_check(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer, int64_t n,
+                                int64_t cap, const char* who, FlatBy* by, ScanLayout* L, Sq8RangeLayout* R) {
+  if (ix && ix->desc.emb_dtype == NANN_F32) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": 16-bit rows (f16, bf16) only");
+  if (!b) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  int rc = flat_sq8_check(ix, t, scorer, n, 0, 0, who, by);  // (nann_search_all_range's checks of the shape: there is no k)
+  if (rc) return rc;
+  if (b->uid != ix->uid || b->serial != t->serial || b->n_items != t->n_items)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the bounds were made from another index or code table");
+  if (cap < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least 1");
+  *L = scan_layout((long long)ix->desc.n_items, ix->desc.d, by->kind, (long long)n, 0);
+  if (cap > cand_max_list(L->chunk))  // (a chunk's survivor lists are one candidate-list plan)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": cap beyond the longest list of a candidate-list search, " +
+                                          std::to_string(cand_max_list(L->chunk)) + " at this chunk");
+  *R = sq8_range_layout(*L, by->kind, ix->desc.d, (long long)cap, (long long)ix->desc.n_items);
+  return NANN_OK;
+}
+
+static int flat_range_sq8_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                const float* q, int64_t n, const float* thresholds, int64_t cap, int64_t capacity,
+                                int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
+                                const nann_search_options* options, nann_stream_t stream, const char* who) {
+  FlatBy by;
+  ScanLayout L;
+  Sq8RangeLayout R;
+  int rc = flat_sq8_range_check(ix, t, b, scorer, n, cap, who, &by, &L, &R);
+  if (rc) return rc;
+  if (capacity < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": capacity < 0");
+  if (n == 0) return NANN_OK;
+  if (!q || !thresholds || !out_row_splits || !out_certified || !out_n_survivors)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (capacity > 0 && !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": out_item_ids is null while capacity > 0");
+  rc = check_options(options);
+  if (rc) return rc;
+  rc = flat_workspace(workspace, workspace_bytes, R.total, who, "");
+  if (rc) return rc;
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  Sq8Args a = {};
+  a.codes = t->codes;
+  a.scales = t->scales;
+  a.norms = t->norms;
+  a.item_ids = ix->desc.item_ids;
+  a.n_items = (long long)ix->desc.n_items;
+  a.d = ix->desc.d;
+  a.metric = by.kind == NANN_SCORER_IP ? MT_IP : MT_L2;
+  CandArgs ca = {};
+  flat_rows_of(ix, &ca);
+  ca.cus = di.cus;
+  ca.kind = by.kind;
+  ca.row_splits = reinterpret_cast<const int64_t*>(ws + R.off_xsplits);
+  ca.rows = reinterpret_cast<const int32_t*>(ws + R.off_rows);
+  for (int64_t c0 = 0; c0 < n; c0 += L.chunk) {
+    const int n_q = (int)std::min<int64_t>(L.chunk, n - c0);
+    const float* qc = q + (size_t)c0 * a.d;
+    // the survivors of every certified query as compact lists in ascending row order; an uncertified query's list is empty
+    rc = launch_sq8_range_survivors(a, L, R, qc, thresholds + c0, b->err, b->xhat, n_q, ws, out_certified + c0, out_n_survivors + c0, st);
+    if (rc) return rc;
+    // their exact scores, by list position
+    ca.n_cand = (long long)n_q * R.cap;
+    const CandLayout CL = cand_layout(by.kind, n_q, ca.n_cand);
+    rc = launch_cand_scores(ca, CL, qc, n_q, ws + R.off_cand, st);
+    if (rc) return rc;
+    // the rows at or above the threshold, into the caller's ragged outputs
+    rc = launch_sq8_range_select(a, R, R.off_cand + CL.off_scores, thresholds, (long long)c0, n_q, (long long)capacity, ws,
+                                 out_row_splits, out_item_ids, out_scores, out_index, st);
+    if (rc) return rc;
+  }
+  return NANN_OK;
+}
+
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
 extern "C" {
 
@@ -1512,6 +1591,29 @@ int nann_search_all_sq8_exact(const nann_index* ix, const nann_sq8* t, const nan
                               void* workspace, int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream) {
   return flat_all_sq8_exact(ix, t, b, scorer, q, n_queries, fetch, cap, k, out_item_ids, out_scores, out_index, out_certified,
                             out_n_survivors, workspace, workspace_bytes, options, stream, "nann_search_all_sq8_exact");
+}
+
+// ---- the certified range form (nann_sq8.h) ------------------------------------------------------------------------
+int nann_search_all_range_sq8_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
+                                                    const nann_scorer* scorer, int64_t n_queries, int64_t cap, int64_t* nbytes) {
+  const char* who = "nann_search_all_range_sq8_exact_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  ScanLayout L;
+  Sq8RangeLayout R;
+  const int rc = flat_sq8_range_check(ix, t, b, scorer, n_queries, cap, who, &by, &L, &R);
+  if (rc) return rc;
+  *nbytes = n_queries == 0 ? 0 : (int64_t)R.total;
+  return NANN_OK;
+}
+int nann_search_all_range_sq8_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                    const float* q, int64_t n_queries, const float* thresholds, int64_t cap, int64_t capacity,
+                                    int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                    int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
+                                    const nann_search_options* options, nann_stream_t stream) {
+  return flat_range_sq8_exact(ix, t, b, scorer, q, n_queries, thresholds, cap, capacity, out_row_splits, out_item_ids, out_scores,
+                              out_index, out_certified, out_n_survivors, workspace, workspace_bytes, options, stream,
+                              "nann_search_all_range_sq8_exact");
 }
 
 }  // extern "C"

@@ -57,6 +57,10 @@ Sq8Layout sq8_layout(const ScanLayout& L, int d, int fetch, size_t cand_bytes);
 
 // codes, scales, norms of n vectors of d elements (dt: NANN_F16 / NANN_BF16 / NANN_F32)
 int launch_sq8_encode(const void* x, int dt, long long n, int d, int8_t* codes, float* scales, int32_t* norms, hipStream_t st);
+// steps 1 and 2 of one chunk of n_q queries: the queries' codes, scales and norms, and the approximate score of every row into
+// scores f32[n_q, n_items] (the ScanLayout's buffer)
+int launch_sq8_scan(const Sq8Args& a, const float* q, int n_q, int8_t* qcodes, float* qscales, int32_t* qnorms, float* scores,
+                    hipStream_t st);
 // the fetch stage of one chunk of n_q queries: steps 1-3 above.  out_fetch_*: this chunk's slice of the caller's arrays, or null.
 int launch_sq8_fetch(const Sq8Args& a, const ScanLayout& L, const Sq8Layout& S, const float* q, int n_q, int fetch,
                      unsigned char* ws, int32_t* out_fetch_index, float* out_fetch_scores, hipStream_t st);
@@ -80,12 +84,12 @@ constexpr float kSq8Tiny = 0x1p-100f;         // covers what underflows in a sco
 
 // the terms of one query of a chunk (k_sq8_exact_terms), read by the survivor predicate
 struct Sq8QTerms {
-  float tau;    // the exact score of the k-th entry of the re-ranked fetch list: a lower bound of the true k-th best score
+  float tau;    // the exact score of the k-th entry of the re-ranked fetch list: a lower bound of the true k-th best score (the range form: the threshold)
   float eq;     // >= |q - sq cq|
   float qhat;   // >= sq sqrt(nq)
   float w;      // L2: >= sqrt((-tau + tiny) / (1 - G)) + eq, the radius a row's code must lie beyond.  IP: >= qhat + eq
   int32_t ok;   // tau, eq and qhat are finite (L2: and tau <= 0)
-  int32_t certified;  // ok and at most cap survivors (k_sq8_exact_lists, behind the count)
+  int32_t certified;  // ok and at most cap survivors (k_sq8_exact_lists, behind the count); the range form: the query has a list to fill
   int32_t pad[2];
 };
 // G: the relative error of the exact scorer's f32 accumulation over d terms and one subtraction each, (d + 4) 2^-24 >=
@@ -115,6 +119,47 @@ int launch_sq8_row_err(const void* x, int dt, long long n, int d, const int8_t* 
 int launch_sq8_survivors(const Sq8Args& a, const ScanLayout& L, const Sq8ExactLayout& X, const float* q, const float* err,
                          const float* xhat, int n_q, int fetch, int k, unsigned char* ws, int32_t* out_certified,
                          int32_t* out_n_survivors, hipStream_t st);
+
+
+// ---- the certified range form (nann_search_all_range_sq8_exact): the caller's threshold IS the cut, so there is
+// no fetch stage and no top-k.  Per chunk: the int8 scan; the query terms at tau = thresholds[q] (k_sq8_exact_terms at k = 1); the
+// survivor pass (k_sq8_surv_count, k_range_scan, k_sq8_surv_fill, unchanged) with k_sq8_range_lists in the place of
+// k_sq8_exact_lists; the candidate-list search's plan and scorer over the survivor lists (launch_cand_scores, no top-k), which
+// leaves the exact scores in list-position order = row order; and the ragged selection over them:
+//   k_sq8_range_count  grid (block of kRangeBlockRows positions of the list buffer, query): the matches of the block by
+//                      k_range_count's rule, s >= t and s != -inf; a block beyond the query's list writes 0 and leaves unloaded
+//   k_range_scan, k_range_splits (nann_range.h, with the chunk's c0): the block prefixes and the call-wide row_splits
+//   k_sq8_range_fill   the same grid: every match to row_splits[query] + (block prefix) + (rank in block), ballots and
+//                      range_lanes_below, no atomic, EVERY store behind pos < capacity
+// A block is a run of positions of the list buffer that begins on a 16-byte boundary, as in nann_range.h: a query's list begins
+// wherever the lists in front of it end.
+// L2 and a finite threshold above +0 (k_sq8_range_lists): the scorer stores 0 - (a sum of squares), no score exceeds +0 and a NaN
+// matches nothing, so the query is certified with no survivor and an empty list, whatever the survivor count says.
+// workspace of a call: [the ScanLayout at k = 0 | what follows], every part a multiple of 256 bytes.  Sized by the chunk.
+struct Sq8RangeLayout {
+  int n_blocks;                                   // range_n_blocks(n_items): blocks of a query in the survivor pass
+  int n_lblocks;                                  // range_n_blocks(cap): blocks of a query's list in the selection
+  long long cap;                                  // min(cap, n_items): most survivors of a certified query
+  size_t off_qcodes, off_qscales, off_qnorms;     // the chunk's encoded queries
+  size_t off_qerr, off_qxhat;                     // f32[chunk] each: the chunk's queries through k_sq8_row_err
+  size_t off_terms;                               // Sq8QTerms[chunk]
+  size_t off_counts;                              // i32[chunk, n_blocks] survivor counts, then prefixes; i32[chunk] totals behind
+  size_t off_xsplits;                             // i64[chunk + 1]: the compact row_splits of the survivor lists
+  size_t off_rows;                                // i32[chunk * cap]: the survivor lists
+  size_t off_cand;                                // CandLayout for chunk * cap positions: the exact scores f32[chunk * cap] first
+  size_t off_rcounts;                             // i32[chunk, n_lblocks] match counts, then prefixes; i32[chunk] totals behind
+  size_t total;
+};
+Sq8RangeLayout sq8_range_layout(const ScanLayout& L, int kind, int d, long long cap, long long n_items);
+// One chunk, up to the survivor lists: scan, query terms at thr (this chunk's slice of the thresholds), survivor pass, lists.
+int launch_sq8_range_survivors(const Sq8Args& a, const ScanLayout& L, const Sq8RangeLayout& R, const float* q, const float* thr,
+                               const float* err, const float* xhat, int n_q, unsigned char* ws, int32_t* out_certified,
+                               int32_t* out_n_survivors, hipStream_t st);
+// One chunk, behind launch_cand_scores over the survivor lists: the ragged selection.  thr, row_splits: the call's arrays (c0
+// picks the chunk's part).  Entry outputs may be null when capacity == 0.
+int launch_sq8_range_select(const Sq8Args& a, const Sq8RangeLayout& R, size_t off_scores, const float* thr, long long c0, int n_q,
+                            long long capacity, unsigned char* ws, int64_t* row_splits, int64_t* out_item_ids, float* out_scores,
+                            int32_t* out_index, hipStream_t st);
 
 }  // namespace nann
 
@@ -512,6 +557,144 @@ __global__ __launch_bounds__(kRangeNT) void k_sq8_surv_fill(const float* __restr
     for (int j = 0; j < 4; ++j) {
       if (!((b.m[p] >> j) & 1u)) continue;
       if (certified && pos >= 0 && pos < room) rows[q_begin + pos] = (int32_t)(b.at[p] + j - b.begin);  // the guard of the store
+      ++pos;
+    }
+  }
+}
+
+// ---- the certified range form ---------------------------------------------------------------------------------------------
+// One workgroup per chunk, behind k_range_scan, in the place of k_sq8_exact_lists: certified and n_survivors of every query and
+// the compact row_splits of the survivor lists, where an uncertified query has length 0.  terms[].tau is the query's threshold
+// (k_sq8_exact_terms at k = 1).  L2 and a finite threshold above +0: certified, no survivor, an empty list (the head of this
+// part).  terms[].certified, which k_sq8_surv_fill reads, says that the query has a list to fill.  n_q <= kScanMaxChunk <= kSq8NT.
+__global__ __launch_bounds__(kSq8NT) void k_sq8_range_lists(const int32_t* __restrict__ totals, Sq8QTerms* __restrict__ terms, int n_q,
+                                                            int metric, long long cap, long long* __restrict__ xsplits,
+                                                            int32_t* __restrict__ out_certified,
+                                                            int32_t* __restrict__ out_n_survivors) {
+  __shared__ long long len[kSq8NT];
+  const int tid = threadIdx.x;
+  long long l = 0;
+  if (tid < n_q) {
+    const Sq8QTerms t = terms[tid];
+    const float big = 3.402823466e+38f;
+    const bool finite = fabsf(t.tau) <= big && fabsf(t.eq) <= big && fabsf(t.qhat) <= big;  // (a NaN fails every comparison)
+    const bool above = metric == MT_L2 && finite && t.tau > 0.0f;
+    const int total = above ? 0 : totals[tid];
+    const int c = above || (t.ok != 0 && (long long)total <= cap) ? 1 : 0;
+    l = c ? (long long)total : 0;
+    terms[tid].certified = l > 0 ? 1 : 0;
+    out_certified[tid] = c;
+    out_n_survivors[tid] = total;
+  }
+  len[tid] = l;
+  __syncthreads();
+  long long sum = 0;
+  for (int j = 0; j < tid; ++j) sum += len[j];
+  if (tid < n_q) xsplits[tid] = sum;
+  if (tid == n_q - 1) xsplits[n_q] = sum + l;
+}
+
+// range_load (nann_range.h) over a query's LIST: block blockIdx.x of the positions [begin, end) of the list buffer, the same
+// 16-byte aligned walk -- the first block begins up to three positions in front of the list -- and the same match rule.
+__device__ __forceinline__ size_t sq8_list_block(size_t begin) { return ((begin >> 2) + (size_t)blockIdx.x * (kRangeBlockRows / 4)) * 4; }
+__device__ __forceinline__ void sq8_list_load(const float* __restrict__ scores, size_t begin, size_t end, float thr, RangeBlock* b) {
+  const size_t g0 = sq8_list_block(begin) >> 2;
+  b->begin = begin;
+#pragma unroll
+  for (int p = 0; p < kRangePasses; ++p) {
+    const size_t at = (g0 + (size_t)p * kRangeNT + threadIdx.x) * 4;
+    b->at[p] = at;
+    b->m[p] = 0u;
+    b->s[p] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    if (at < end) {  // (the 16 bytes begin inside the list or up to three positions in front of it, and end within 16 B of its end)
+      b->s[p] = *reinterpret_cast<const f32x4v*>(scores + at);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float s = b->s[p][j];
+        const bool in = at + j >= begin && at + j < end;
+        if (in && s >= thr && s != -__builtin_inff()) b->m[p] |= 1u << j;
+      }
+    }
+  }
+}
+
+// counts[query][block] = matches of the block of the query's list; scores: the exact scores by list position
+__global__ __launch_bounds__(kRangeNT) void k_sq8_range_count(const float* __restrict__ scores, const long long* __restrict__ xsplits,
+                                                              const float* __restrict__ thr, long long c0,
+                                                              int32_t* __restrict__ counts) {
+  __shared__ int wave_cnt[kRangeNT / 64];
+  const size_t begin = (size_t)xsplits[blockIdx.y], end = (size_t)xsplits[blockIdx.y + 1];
+  const size_t cb = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+  if (sq8_list_block(begin) >= end) {  // (uniform over the workgroup) a block beyond the list: nothing is loaded
+    if (threadIdx.x == 0) counts[cb] = 0;
+    return;
+  }
+  RangeBlock b;
+  sq8_list_load(scores, begin, end, thr[c0 + blockIdx.y], &b);
+  int c = 0;
+#pragma unroll
+  for (int p = 0; p < kRangePasses; ++p)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c += __popcll(__ballot((b.m[p] >> j) & 1u));
+  if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+#pragma unroll
+    for (int w = 0; w < kRangeNT / 64; ++w) t += wave_cnt[w];
+    counts[cb] = t;
+  }
+}
+
+// The matches of a block to their places (k_range_fill's shape).  prefix = counts behind k_range_scan; rows: the survivor lists,
+// by the same positions as scores.
+__global__ __launch_bounds__(kRangeNT) void k_sq8_range_fill(const float* __restrict__ scores, const long long* __restrict__ xsplits,
+                                                             const int32_t* __restrict__ rows, const float* __restrict__ thr,
+                                                             long long c0, const int32_t* __restrict__ prefix,
+                                                             const int64_t* __restrict__ row_splits, long long capacity,
+                                                             const int64_t* __restrict__ item_ids, long long n_items,
+                                                             int64_t* __restrict__ out_item_ids, float* __restrict__ out_scores,
+                                                             int32_t* __restrict__ out_index) {
+  constexpr int W = kRangeNT / 64;
+  __shared__ int cnt[kRangePasses * W];
+  const size_t begin = (size_t)xsplits[blockIdx.y], end = (size_t)xsplits[blockIdx.y + 1];
+  if (sq8_list_block(begin) >= end) return;  // (uniform over the workgroup)
+  RangeBlock b;
+  sq8_list_load(scores, begin, end, thr[c0 + blockIdx.y], &b);
+  const int wave = threadIdx.x >> 6;
+  int rank[kRangePasses];  // matches of the pass's wavefront in the lanes below this one
+#pragma unroll
+  for (int p = 0; p < kRangePasses; ++p) {
+    int below = 0, all = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned long long m = __ballot((b.m[p] >> j) & 1u);
+      below += range_lanes_below(m);
+      all += __popcll(m);
+    }
+    rank[p] = below;
+    if ((threadIdx.x & 63) == 0) cnt[p * W + wave] = all;
+  }
+  __syncthreads();
+  const long long q_base = (long long)row_splits[c0 + blockIdx.y] + prefix[(size_t)blockIdx.y * gridDim.x + blockIdx.x];
+#pragma unroll
+  for (int p = 0; p < kRangePasses; ++p) {
+    int base = 0;
+#pragma unroll
+    for (int i = 0; i < kRangePasses * W; ++i)
+      if (i < p * W + wave) base += cnt[i];
+    long long pos = q_base + base + rank[p];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (!((b.m[p] >> j) & 1u)) continue;
+      if (pos >= 0 && pos < capacity) {  // the guard of every store below: a position at or beyond capacity is dropped
+        const int32_t r = rows[b.at[p] + j];  // (a matching position lies inside the list: a survivor's row number)
+        if ((uint32_t)r < (uint32_t)n_items) {  // (always: k_sq8_surv_fill has written every position of the list)
+          out_item_ids[pos] = item_ids[r];
+          if (out_scores) out_scores[pos] = b.s[p][j];
+          if (out_index) out_index[pos] = r;
+        }
+      }
       ++pos;
     }
   }

@@ -747,14 +747,132 @@ def _flat_range(index, handle, x, thresholds, capacity, filter, options, sort, s
     elif not counted:
         call(0, None, None, None)
     total = int(splits[b].item()) if b else 0
-    if sort and min(total, capacity) > 1:
-        n = min(total, capacity)
-        seg = torch.searchsorted(splits[1:].contiguous(), torch.arange(n, device=dev), right=True)  # the query of every entry
-        # stable sorts, last key first: row ascending (the entries already are, within a query), score descending, query ascending
-        order = torch.sort(scores[:n], descending=True, stable=True).indices
-        order = order[torch.sort(seg[order], stable=True).indices]
-        ids[:n], scores[:n], rows[:n] = ids[:n][order], scores[:n][order], rows[:n][order]
+    if sort:
+        _range_sort(splits, ids, scores, rows, min(total, capacity))
     return RangeResult(splits, ids, scores, rows, total, total > capacity, ws)
+
+
+def _range_sort(splits, ids, scores, rows, n):
+    """the first n entries of a ragged result, each segment reordered by (score descending, row ascending), in place"""
+    if n <= 1:
+        return
+    seg = torch.searchsorted(splits[1:].contiguous(), torch.arange(n, device=splits.device), right=True)  # the query of every entry
+    # stable sorts, last key first: row ascending (the entries already are, within a query), score descending, query ascending
+    order = torch.sort(scores[:n], descending=True, stable=True).indices
+    order = order[torch.sort(seg[order], stable=True).indices]
+    ids[:n], scores[:n], rows[:n] = ids[:n][order], scores[:n][order], rows[:n][order]
+
+
+class Sq8RangeResult(RangeResult):
+    """Outputs of search_all_range_sq8_exact: a RangeResult with certified i32[B] (1: the query's segment is search_all_range's,
+    bit for bit; 0: the segment is empty unless the fallback has filled it) and n_survivors i32[B] (rows the bound could not put
+    below the threshold, whatever the cap).  total and truncated are read from row_splits on first use -- a synchronisation,
+    which a call with fallback=False has not paid before."""
+    __slots__ = ("certified", "n_survivors", "cap", "capacity", "_total")
+
+    def __init__(self, row_splits, item_ids, scores, index, certified, n_survivors, cap, capacity, total=None, ws=None):
+        self.row_splits, self.item_ids, self.scores, self.index, self._ws = row_splits, item_ids, scores, index, ws
+        self.certified, self.n_survivors, self.cap, self.capacity, self._total = certified, n_survivors, cap, capacity, total
+
+    @property
+    def total(self):
+        if self._total is None:
+            self._total = int(self.row_splits[-1].item())
+        return self._total
+
+    @property
+    def truncated(self):
+        return self.total > self.capacity
+
+
+def search_all_range_sq8_exact(index, sq8, bounds, scorer, q, thresholds, cap=4096, capacity=None, fallback=True, options=None,
+                               sort=False):
+    """Certified scalar-quantised range search (nann_search_all_range_sq8_exact): search_all_range's result BIT FOR BIT -- rows
+    in ascending row order, score bits, item ids, counts -- from the int8 scan.  The threshold is the cut: per query every row
+    whose exact score a rigorous error bound cannot put below thresholds[b] survives, the survivors alone are scored exactly,
+    and those at or above the threshold are returned -> Sq8RangeResult.  result.certified[b] == 1 iff at most min(cap, n_items)
+    rows survived and the threshold and the query are finite; an uncertified query's segment is EMPTY.  Under an l2 scorer a
+    finite threshold above 0 is certified with an empty segment (no l2 score exceeds 0).  `scorer`: an l2 or ip ops.Scorer with
+    q f32[B, d]; sq8: make_sq8(index); bounds: make_sq8_bounds(index, sq8).  There is no filter.
+    cap=4096 is a convenience default, NOT a tuned value: the workspace holds 8 bytes per (query of a chunk, cap position), and
+    the survivors outnumber the matches by a factor that depends on the corpus (tools/sq8_range_rate.py measures it).
+    capacity=None means B * min(cap, n_items): that size cannot truncate a certified result, so there is ONE call, the index is
+    scored once and nothing synchronises -- what search_all_range's count-then-fill cannot offer.
+    fallback=True: the wrapper reads `certified` back -- ONE synchronisation -- runs the uncertified queries through
+    search_all_range and splices their segments in, in query order, so that the result equals search_all_range's for EVERY query
+    (certified and n_survivors stay as the device call left them).  fallback=False: asynchronous on torch's current stream.
+    sort=True reorders each segment by (score descending, row ascending) with torch on the device."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    b, cap = q.shape[0], int(cap)
+    if isinstance(thresholds, (int, float)):
+        thr = torch.full((b,), float(thresholds), dtype=torch.float32, device=dev)
+    else:
+        thr = torch.as_tensor(thresholds).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert thr.numel() == b, "thresholds: one per query of the batch"
+    fit = capacity is None  # (the fallback then sizes the spliced result to its total)
+    capacity = b * max(min(cap, int(index.n_items)), 0) if fit else int(capacity)
+    assert capacity >= 0, "capacity >= 0"
+    L = lib()
+    nbytes = C.c_int64(0)
+    bh = bounds.handle if bounds is not None else None
+    th = sq8.handle if sq8 is not None else None
+    _check(L.nann_search_all_range_sq8_exact_workspace_bytes(index.handle, th, bh, scorer.handle, b, cap, C.byref(nbytes)),
+           "search_all_range_sq8_exact")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    splits = torch.zeros(b + 1, dtype=torch.int64, device=dev)
+    ids = torch.zeros(capacity, dtype=torch.int64, device=dev)
+    scores = torch.zeros(capacity, dtype=torch.float32, device=dev)
+    rows = torch.zeros(capacity, dtype=torch.int32, device=dev)
+    certified = torch.zeros(b, dtype=torch.int32, device=dev)
+    n_surv = torch.zeros(b, dtype=torch.int32, device=dev)
+    some = capacity > 0
+    with torch.cuda.device(dev):
+        _check(L.nann_search_all_range_sq8_exact(index.handle, th, bh, scorer.handle, _ptr(q), b, _ptr(thr), cap, capacity,
+                                                 _ptr(splits), _ptr(ids) if some else None, _ptr(scores) if some else None,
+                                                 _ptr(rows) if some else None, _ptr(certified), _ptr(n_surv), _ptr(ws), ws.numel(),
+                                                 C.byref(options) if options is not None else None, _stream()),
+               "search_all_range_sq8_exact")
+    total = None
+    if fallback and b > 0:
+        todo = torch.nonzero(certified == 0).flatten()  # (the synchronisation)
+        if todo.numel() > 0:
+            splits, ids, scores, rows = _range_splice(splits, ids, scores, rows, None if fit else capacity, todo,
+                                                      search_all_range(index, scorer, q[todo], thr[todo], options=options))
+            capacity = ids.numel()
+        total = int(splits[b].item())
+    if sort and b > 0:
+        _range_sort(splits, ids, scores, rows, min(int(splits[b].item()) if total is None else total, capacity))
+    return Sq8RangeResult(splits, ids, scores, rows, certified, n_surv, cap, capacity, total if b else 0, ws)
+
+
+def _range_splice(splits, ids, scores, rows, capacity, todo, other):
+    """A ragged result whose segments of the queries `todo` are empty, with the segments of `other` -- a full (untruncated) ragged
+    result over exactly those queries -- put in their places, in query order; the entries are the head [0, capacity) of the whole
+    (capacity=None: the whole)."""
+    dev, b = splits.device, splits.numel() - 1
+    counts = splits[1:] - splits[:-1]
+    o_begin = torch.zeros(b, dtype=torch.int64, device=dev)
+    o_begin[todo] = other.row_splits[:-1]
+    counts[todo] = other.row_splits[1:] - other.row_splits[:-1]
+    from_other = torch.zeros(b, dtype=torch.bool, device=dev)
+    from_other[todo] = True
+    new_splits = torch.zeros(b + 1, dtype=torch.int64, device=dev)
+    new_splits[1:] = torch.cumsum(counts, 0)
+    n = int(new_splits[b].item())
+    if capacity is None:
+        capacity = n
+    n = min(n, capacity)
+    seg = torch.searchsorted(new_splits[1:].contiguous(), torch.arange(n, device=dev), right=True)  # the query of every entry
+    off = torch.arange(n, device=dev) - new_splits[seg]
+    # an entry of a certified query lay at or in front of its new place: inside the head the first call has filled
+    src = torch.where(from_other[seg], ids.numel() + o_begin[seg] + off, splits[seg] + off)
+    out = []
+    for mine, theirs in ((ids, other.item_ids), (scores, other.scores), (rows, other.index)):
+        fresh = torch.zeros(capacity, dtype=mine.dtype, device=dev)
+        fresh[:n] = torch.cat([mine, theirs])[src]
+        out.append(fresh)
+    return [new_splits] + out
 
 
 # candidates per work item of the scoring kernels of search_candidates (csrc/nann_cand.h: kCandRows, kCandMlpRows)

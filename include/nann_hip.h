@@ -1420,6 +1420,42 @@ int nann_search_all_range_sq8_exact(const nann_index* ix, const nann_sq8* t, con
                                     int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
                                     const nann_search_options* options, nann_stream_t stream);
 
+/* ---- wide exhaustive search: the exact top k for k up to NANN_WIDE_MAX_K rows per query.  Added to ABI
+ * version 6: new symbols only; nann_search_all and every call built on it keep their limit of 1024.
+ * nann_search_all_wide / nann_search_all_model_wide take nann_search_all[_model]_where's arguments, checks and check order, with
+ * k <= NANN_WIDE_MAX_K in the place of k <= 1024: k < 0 -> NANN_ERR_BAD_ARGUMENT, k > n_items -> NANN_ERR_TOPK_K_GT_N,
+ * k > NANN_WIDE_MAX_K -> NANN_ERR_UNSUPPORTED, a NULL q or out_item_ids -> NANN_ERR_BAD_ARGUMENT, a workspace smaller than
+ * nann_search_all[_model]_wide_workspace_bytes gives -> NANN_ERR_CAPACITY, one that is not 256-byte aligned ->
+ * NANN_ERR_BAD_ARGUMENT; n_queries == 0 or k == 0 -> NANN_OK, nothing written.  Every check stands in front of the first launch,
+ * the mean of an l2 / mlp model included.  `filter` and `predicates` may be NULL; out_scores, out_index and n_out may be NULL.
+ * Every scorer is served: L2, inner product, the MLP in every precision, l2 / mlp / attention models.
+ *   Query i returns the top k of its rows whose score is not -inf, in TopKV2 order: score descending, ties to the lower row, -0
+ *   and +0 tie.  n_out[i] = min(k, such rows); the entries behind it are zeros.  A row scoring -inf -- a denied row's mark, or
+ *   what the scorer gave -- is never returned: nann_search_all_range's rule.  Scores are nann_search_all's bits for the same
+ *   (query, row).  NaN scores are outside the contract.
+ * Asynchronous on `stream`, re-entrant, no read-back; a query's answer does not depend on its batch.  The workspace is bounded
+ * by a chunk of queries: the scores of the chunk, three histograms and two block counters per query, and a staging list of k
+ * (key, row) pairs per query.
+ * nann_select_wide is the selection alone over a caller's matrix values f32[n_rows, n_cols] (device, 16-byte aligned): per row,
+ * out_values f32[n_rows, k] (may be NULL), out_indices i32[n_rows, k] (column numbers), n_out i32[n_rows] (may be NULL), the same
+ * rule.  Any n_cols up to 2^31 - 1 and any n_rows; 0 <= k <= min(n_cols, NANN_WIDE_MAX_K) as above. */
+#define NANN_WIDE_MAX_K 16384
+int nann_search_all_wide_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k,
+                                         int64_t* nbytes);
+int nann_search_all_wide(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                         int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* n_out, void* workspace,
+                         int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                         const nann_predicates* predicates, nann_stream_t stream);
+int nann_search_all_model_wide_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k,
+                                               int64_t* nbytes);
+int nann_search_all_model_wide(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
+                               int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* n_out, void* workspace,
+                               int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                               const nann_predicates* predicates, nann_stream_t stream);
+int nann_select_wide_workspace_bytes(int64_t n_rows, int64_t n_cols, int32_t k, int64_t* nbytes);
+int nann_select_wide(const float* values, int64_t n_rows, int64_t n_cols, int32_t k, float* out_values, int32_t* out_indices,
+                     int32_t* n_out, void* workspace, int64_t workspace_bytes, nann_stream_t stream);
+
 /* ---- 8(f3): the evaluation graph's traversal, one kernel per batch of users ---------------
  * Model.retrieval + search_level (NANN_impls/nann/model.py:299-362), the traversal behind
  * main.py --job-type test: start level scored whole, then levels 1 and 0 with

@@ -24,6 +24,7 @@ NUM_ROUNDS = 5
 NUM_PHASES = 19
 UNION_MAX_IN = 8192  # NANN_UNION_MAX_IN: most entries (n_lists * k_in) a user brings to nann_union_topk
 FUSE_MAX_LISTS = 64  # NANN_FUSE_MAX_LISTS: most lists a user brings to nann_fuse_topk (out_lists is one u64 per entry)
+WIDE_MAX_K = 16384   # NANN_WIDE_MAX_K: largest k of nann_search_all_wide, nann_search_all_model_wide and nann_select_wide
 FUSE_SUM, FUSE_SUM_FLOOR, FUSE_MINMAX, FUSE_RRF = 0, 1, 2, 3
 INTERESTS_MAX_VEC = 16   # NANN_INTERESTS_MAX_VEC: most interest vectors nann_user_seq_interests makes of a sequence
 INTERESTS_MAX_ITER = 32  # NANN_INTERESTS_MAX_ITER: most Lloyd rounds it runs
@@ -81,6 +82,9 @@ SYMBOLS = [
     "nann_sq8_bounds_create", "nann_sq8_bounds_destroy", "nann_sq8_bounds_view",
     "nann_search_all_sq8_exact_workspace_bytes", "nann_search_all_sq8_exact_layout", "nann_search_all_sq8_exact",
     "nann_search_all_range_sq8_exact_workspace_bytes", "nann_search_all_range_sq8_exact",
+    "nann_search_all_wide_workspace_bytes", "nann_search_all_wide",
+    "nann_search_all_model_wide_workspace_bytes", "nann_search_all_model_wide",
+    "nann_select_wide_workspace_bytes", "nann_select_wide",
 ]
 
 
@@ -315,6 +319,21 @@ def lib():
             wb = getattr(L, name + "_workspace_bytes")
             wb.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
             wb.restype = C.c_int
+        # the wide forms: (ix, scorer | model, n, k, *nbytes) / (ix, scorer | model, q | comm_seq_f16, n, k, out_item_ids, out_scores,
+        #  out_index, n_out, workspace, workspace_bytes, options, filter, predicates, stream)
+        for name in ("nann_search_all_wide", "nann_search_all_model_wide"):
+            fn = getattr(L, name)
+            fn.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32] + [C.c_void_p] * 5 + \
+                          [C.c_int64, C.POINTER(SearchOptions), C.POINTER(Filter), C.POINTER(Predicates), C.c_void_p]
+            fn.restype = C.c_int
+            wb = getattr(L, name + "_workspace_bytes")
+            wb.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+            wb.restype = C.c_int
+        # (n_rows, n_cols, k, *nbytes) / (values, n_rows, n_cols, k, out_values, out_indices, n_out, workspace, workspace_bytes, stream)
+        L.nann_select_wide_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+        L.nann_select_wide_workspace_bytes.restype = C.c_int
+        L.nann_select_wide.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]
+        L.nann_select_wide.restype = C.c_int
         # (ix, scorer, n_queries, n_cand, k, *nbytes) / (ix, scorer, q, n_queries, k, cand, out_item_ids, out_scores, out_index,
         #  out_pos, n_out, status, workspace, workspace_bytes, options, stream)
         L.nann_search_candidates_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,

@@ -21,7 +21,7 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 #                      bound a build from scratch
 #   nann_mlp_d*.o      the MLP traversal per embedding dim; the resident-layer-2 kernels ride with d = 64
 #   nann_attn.o, nann_attn_split.o   the attention model, f32 and split-f16 form
-#   nann_scan.o        the exhaustive search, with the range selection (nann_range.h) and the int8 code table, scan and
+#   nann_scan.o        the exhaustive search, with the range and wide selections (nann_range.h, nann_wide.h) and the int8 code table, scan and
 #                      certified survivor pass (nann_sq8.h, nann_sq8_inst.hip); nann_scan_attn.o its scan under the attention model
 #   nann_filter.o      filtered retrieval, with the group cap (nann_groupcap.h) and the attribute predicates (nann_predicate.h)
 #   nann_cand.o        the candidate-list search, with the union and the fused top-k (nann_union.h, nann_fuse.h), the MMR
@@ -157,6 +157,10 @@ RULES = [
     # The range form of the certified int8 search (k_sq8_range_lists / k_sq8_range_count / k_sq8_range_fill, nann_sq8.h): the
     # selection holds a block's eight scores per thread in registers, as the survivor pass does, and is held to the same.
     ("sq8_range_scratch", r"k_sq8_range_(lists|count|fill)", 0, None, "the certified range selection"),
+    # The streaming kernels of the wide selection (k_wide_hist / k_wide_count / k_wide_fill, nann_wide.h) read the chunk's score buffer
+    # five times between them and hold a block's eight scores per thread in registers; a frame in private memory would add its traffic
+    # to passes that are nothing but memory traffic.
+    ("wide_scratch", r"k_wide_(hist|count|fill)", 0, None, "the wide selection"),
 ]
 
 
@@ -212,6 +216,10 @@ def _check_scan_ip_scratch(log_path):
 
 def _check_scan_sq8_scratch(log_path):
     check_resources(log_path, _rule("scan_sq8_scratch"))
+
+
+def _check_wide_scratch(log_path):
+    check_resources(log_path, _rule("wide_scratch"))
 
 
 def unit_command(obj, parts, odir, extra_flags=(), save_temps=True):

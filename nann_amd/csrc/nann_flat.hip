@@ -1,6 +1,7 @@
 // nann_flat.hip -- the host side of the flat retrieval calls, the ones that do not walk the graph: the exhaustive search
 // (nann_search_all, nann_search_all_filtered, nann_search_all_model, nann_search_all_model_filtered; kernels in nann_scan.h),
-// its range form (nann_search_all_range, nann_search_all_range_model; selection kernels in nann_range.h)
+// its range form (nann_search_all_range, nann_search_all_range_model; selection kernels in nann_range.h), its wide form for k up
+// to 16384 (nann_search_all_wide, nann_search_all_model_wide, and the selection alone, nann_select_wide; kernels in nann_wide.h)
 // and the candidate-list search (nann_search_candidates, nann_search_candidates_model; kernels in nann_cand.h), each with its
 // *_workspace_bytes; the union top-k on its own (nann_union_topk; kernel in nann_union.h) and behind the exhaustive search
 // over a user's interest vectors (nann_search_all_multi); the fused top-k in the same two places (nann_fuse_topk,
@@ -88,7 +89,7 @@ static int flat_bad_k(int32_t k) { return fail(NANN_ERR_BAD_ARGUMENT, "Need k >=
 // lists: the candidate family (n_cand rows in all).  The exhaustive family holds k against n_items as TopKV2 does, and names a
 // negative k behind a mismatched handle; the candidate family names it in front.
 static int flat_check(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, int32_t k, bool lists,
-                      int64_t n_cand, const char* who, FlatBy* by) {
+                      int64_t n_cand, const char* who, FlatBy* by, int max_k = kMaxK) {  // max_k: kWideMaxK for the wide form
   const int rc = flat_by(ix, scorer, m, who, by);
   if (rc) return rc;
   if (n < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_" + by->unit + " < 0");
@@ -103,7 +104,7 @@ static int flat_check(const nann_index* ix, const nann_scorer* scorer, const nan
       return fail(NANN_ERR_TOPK_K_GT_N, "input must have at least k columns. Had " + std::to_string(ix->desc.n_items) +
                                             ", needed " + std::to_string(k));
   }
-  if (k > kMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= 1024");
+  if (k > max_k) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= " + std::to_string(max_k));
   if (lists) {
     if (n_cand > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": list positions are 32-bit");
     if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many " + by->unit + " in one call");
@@ -421,6 +422,110 @@ static int flat_range(const nann_index* ix, const nann_scorer* scorer, const nan
   rc = launch_scan(a, L, static_cast<const float*>(x), (long long)n, 0, ws, out_item_ids, out_scores, out_index, st);
   if (tab) projection_used(*by.cache, tab, st);
   return rc;
+}
+
+// ---- wide exhaustive search (nann_wide.h): the top k for k up to kWideMaxK, under a scorer or a model ------------------------
+// The fourth walk over the same steps: nann_search_all_where's checks in its order -- the predicates, flat_check with the wide
+// limit, the nulls, then a model form its workspace before its options and a scorer form its options and filter first -- and, as
+// the range form, every check in front of the first launch, the mean of an l2 / mlp model included.  The workspace is the
+// unfiltered ScanLayout at k = 0 -- no slab lists -- with the histograms, counters and staging list of the selection behind it.
+static size_t flat_wide_bytes(const nann_index* ix, const FlatBy& by, int64_t n, int32_t k, ScanLayout* L) {
+  const size_t scan = flat_all_bytes(ix, by, n, 0, false, L);
+  return scan + wide_bytes(L->chunk, (long long)ix->desc.n_items, k);
+}
+
+static int flat_wide_size(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, int64_t n, int32_t k, int64_t* nbytes,
+                          const char* who) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  const int rc = flat_check(ix, scorer, m, n, k, false, 0, who, &by, kWideMaxK);
+  if (rc) return rc;
+  ScanLayout L;
+  *nbytes = n == 0 || k == 0 ? 0 : (int64_t)flat_wide_bytes(ix, by, n, k, &L);
+  return NANN_OK;
+}
+
+static int flat_wide(const nann_index* ix, const nann_scorer* scorer, const nann_model* m, const void* x, int64_t n, int32_t k,
+                     int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* n_out, void* workspace,
+                     int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                     const nann_predicates* predicates, nann_stream_t stream, const char* who) {
+  PredArgs pa;
+  int rc = resolve_predicates(predicates, &pa);
+  if (rc) return rc;
+  FlatBy by;
+  rc = flat_check(ix, scorer, m, n, k, false, 0, who, &by, kWideMaxK);
+  if (rc) return rc;
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!x || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  ScanLayout L;
+  const size_t need = flat_wide_bytes(ix, by, n, k, &L);
+  ScanFilter sf = {};
+  if (m) {
+    rc = flat_workspace(workspace, workspace_bytes, need, who, "");
+    if (rc) return rc;
+    rc = check_options(options);
+    if (rc) return rc;
+    if (by.mean_of) rc = resolve_filter(filter, ix, &sf.f);  // (an l2 / mlp model goes on as its scorer form: the filter next)
+    if (rc) return rc;
+  } else {
+    rc = check_options(options);
+    if (rc) return rc;
+    rc = resolve_filter(filter, ix, &sf.f);
+    if (rc) return rc;
+    rc = flat_workspace(workspace, workspace_bytes, need, who, "");
+    if (rc) return rc;
+  }
+  hipStream_t st = as_stream(stream);
+  ScanArgs a = {};
+  std::shared_ptr<ProjTable> tab;
+  if (by.cache) {
+    rc = flat_table(by, ix, options, st, who, &tab);
+    if (rc) return rc;
+    DeviceInfo di;
+    rc = device_info(&di);
+    if (rc) return rc;
+    a.proj = tab->table;
+    a.mlp_workgroups = di.cus;
+  }
+  if (m && !by.mean_of) rc = resolve_filter(filter, ix, &sf.f);  // (the attention model: its filter behind its table)
+  if (rc) {
+    if (tab) projection_used(*by.cache, tab, st);
+    return rc;
+  }
+  if (by.mean_of) {  // (behind every check: the mean is the first thing on the stream)
+    const float* q = nullptr;
+    rc = flat_stage_mean(by, x, n, &q, &workspace, &workspace_bytes, stream);
+    if (rc) return rc;
+    x = q;
+  }
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  const ScanWide w = wide_carve(ws + L.total, L.chunk, (long long)ix->desc.n_items, k, n_out);
+  a.wide = &w;
+  if (predicates) sf.pred = &pa;
+  if (sf.f.deny_bits || filter_has_lists(sf.f) || sf.pred) a.filter = &sf;  // (stage and n_out stay null: the wide form reads `f` and `pred` only)
+  flat_rows_of(ix, &a);
+  a.kind = by.kind;
+  a.exact = by.exact;
+  a.mlp = by.mlp;
+  a.attn = by.attn;
+  rc = launch_scan(a, L, static_cast<const float*>(x), (long long)n, k, ws, out_item_ids, out_scores, out_index, st);
+  if (tab) projection_used(*by.cache, tab, st);
+  return rc;
+}
+
+// the selection alone over a caller's matrix: rows in pieces of at most kWideMaxChunk whose block counters stay within 64 MB
+static int select_wide_check(int64_t n_rows, int64_t n_cols, int32_t k, const char* who) {
+  if (n_rows < 0 || n_cols < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": negative size");
+  if (k < 0) return flat_bad_k(k);
+  if (n_cols < k)
+    return fail(NANN_ERR_TOPK_K_GT_N, "input must have at least k columns. Had " + std::to_string(n_cols) + ", needed " + std::to_string(k));
+  if (k > kWideMaxK) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": k <= " + std::to_string(kWideMaxK));
+  if (n_cols > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": column numbers are 32-bit");
+  return NANN_OK;
+}
+static int select_wide_chunk(int64_t n_rows, int64_t n_cols) {
+  const long long by_counts = ((long long)64 << 20) / ((long long)range_n_blocks((long long)n_cols) * 8);
+  return (int)std::max<long long>(1, std::min<long long>({(long long)kWideMaxChunk, (long long)n_rows, by_counts}));
 }
 
 // ---- candidate-list search (nann_cand.h): the top k of every query's own list of rows, under a scorer or a model -------------
@@ -1421,6 +1526,58 @@ int nann_search_all_range_model(const nann_index* ix, const nann_model* m, const
                                 const nann_search_options* options, const nann_filter* filter, nann_stream_t stream) {
   return flat_range(ix, nullptr, m, comm_seq_f16, n_users, thresholds, capacity, out_row_splits, out_item_ids, out_scores,
                     out_index, workspace, workspace_bytes, options, filter, stream, "nann_search_all_range_model");
+}
+
+// ---- wide exhaustive search (nann_wide.h)
+int nann_search_all_wide_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int32_t k, int64_t* nbytes) {
+  return flat_wide_size(ix, scorer, nullptr, n_queries, k, nbytes, "nann_search_all_wide_workspace_bytes");
+}
+int nann_search_all_wide(const nann_index* ix, const nann_scorer* scorer, const float* q, int64_t n_queries, int32_t k,
+                         int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* n_out, void* workspace,
+                         int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                         const nann_predicates* predicates, nann_stream_t stream) {
+  return flat_wide(ix, scorer, nullptr, q, n_queries, k, out_item_ids, out_scores, out_index, n_out, workspace, workspace_bytes,
+                   options, filter, predicates, stream, "nann_search_all_wide");
+}
+int nann_search_all_model_wide_workspace_bytes(const nann_index* ix, const nann_model* m, int64_t n_users, int32_t k, int64_t* nbytes) {
+  return flat_wide_size(ix, nullptr, m, n_users, k, nbytes, "nann_search_all_model_wide_workspace_bytes");
+}
+int nann_search_all_model_wide(const nann_index* ix, const nann_model* m, const void* comm_seq_f16, int64_t n_users, int32_t k,
+                               int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* n_out, void* workspace,
+                               int64_t workspace_bytes, const nann_search_options* options, const nann_filter* filter,
+                               const nann_predicates* predicates, nann_stream_t stream) {
+  return flat_wide(ix, nullptr, m, comm_seq_f16, n_users, k, out_item_ids, out_scores, out_index, n_out, workspace, workspace_bytes,
+                   options, filter, predicates, stream, "nann_search_all_model_wide");
+}
+int nann_select_wide_workspace_bytes(int64_t n_rows, int64_t n_cols, int32_t k, int64_t* nbytes) {
+  const char* who = "nann_select_wide_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  const int rc = select_wide_check(n_rows, n_cols, k, who);
+  if (rc) return rc;
+  *nbytes = n_rows == 0 || k == 0 ? 0 : (int64_t)wide_bytes(select_wide_chunk(n_rows, n_cols), (long long)n_cols, k);
+  return NANN_OK;
+}
+int nann_select_wide(const float* values, int64_t n_rows, int64_t n_cols, int32_t k, float* out_values, int32_t* out_indices,
+                     int32_t* n_out, void* workspace, int64_t workspace_bytes, nann_stream_t stream) {
+  const char* who = "nann_select_wide";
+  int rc = select_wide_check(n_rows, n_cols, k, who);
+  if (rc) return rc;
+  if (n_rows == 0 || k == 0) return NANN_OK;
+  if (!values || !out_indices) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (reinterpret_cast<uintptr_t>(values) & 15u) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": values must be 16-byte aligned");
+  const int chunk = select_wide_chunk(n_rows, n_cols);
+  rc = flat_workspace(workspace, workspace_bytes, wide_bytes(chunk, (long long)n_cols, k), who, "");
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  const size_t limit = (size_t)n_rows * (size_t)n_cols;
+  for (int64_t r0 = 0; r0 < n_rows; r0 += chunk) {
+    const int n_q = (int)std::min<int64_t>(chunk, n_rows - r0);
+    const ScanWide w = wide_carve(static_cast<unsigned char*>(workspace), chunk, (long long)n_cols, k, nullptr);
+    rc = launch_wide(w, values, limit, (long long)n_cols, (long long)r0, n_q, nullptr, nullptr, out_values ? out_values + (size_t)r0 * k : nullptr,
+                     out_indices + (size_t)r0 * k, n_out ? n_out + r0 : nullptr, st);
+    if (rc) return rc;
+  }
+  return NANN_OK;
 }
 
 int nann_search_candidates_workspace_bytes(const nann_index* ix, const nann_scorer* scorer, int64_t n_queries, int64_t n_cand,

@@ -32,6 +32,7 @@
 #include "nann_predicate.h"
 #include "nann_range.h"
 #include "nann_search.h"
+#include "nann_wide.h"
 
 namespace nann {
 
@@ -62,6 +63,9 @@ struct ScanArgs {
                             // (nann_filter.h), and k_filter_compact behind the merge writes the outputs
   const ScanRange* range;   // null: the top k.  Else the range form (nann_range.h): every row at or above the query's cut, in the
                             // place of the slab top-k and the merge; of a filter only `f` is read, and the call's k not at all
+  const ScanWide* wide;     // null: the slab top-k and the merge.  Else the wide form (nann_wide.h): cut, gather and sort in their
+                            // place, for k up to kWideMaxK; of a filter only `f` and `pred` are read (their scatters), and the
+                            // layout is the one of k = 0
 };
 constexpr int kScanAttn = 100;  // ScanArgs::kind of the attention model (no nann_scorer_kind: it has a handle type of its own)
 constexpr size_t kScanAttnUserBytes = (size_t)(256 * kAttnLP + kAttnLP * kAttnE) * 4;  // kt 64 KB + upad 16 KB (nann_attn_prepare)

@@ -1,5 +1,5 @@
 // nann_scan_inst.hip -- the kernels of the exhaustive search (nann_scan.h): the L2 and inner-product scans for every (d, row dtype), the MLP scan
-// in both precisions, the slab top-k and the merge, and the range selection (nann_range.h); workspace layout and the launch
+// in both precisions, the slab top-k and the merge, the range selection (nann_range.h) and the wide selection (nann_wide.h); workspace layout and the launch
 // sequence of a call.
 #define NANN_SCAN_IMPL
 #include "nann_scan.h"
@@ -94,6 +94,35 @@ int launch_range(const ScanRange& r, const float* scores, long long n_items, lon
   return NANN_OK;
 }
 
+int launch_wide(const ScanWide& w, const float* scores, size_t limit, long long n_items, long long q0, int n_q,
+                const int64_t* item_ids, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* n_out, hipStream_t st) {
+  static_assert(kScanMaxChunk <= kWideMaxChunk, "launch_wide: a chunk of the scan is one grid");
+  if (n_q < 1 || n_q > kWideMaxChunk || w.k < 1 || w.k > kWideMaxK) return fail(NANN_ERR_BAD_ARGUMENT, "launch_wide: shape");
+  const dim3 grid((unsigned)w.n_blocks, (unsigned)n_q), nt(kRangeNT);
+  const size_t hq = (size_t)n_q * kWideBins;  // a pass's histograms
+  NANN_HIP_TRY(hipMemsetAsync(w.hist, 0, (size_t)kWidePasses * hq * 4, st));
+  hipLaunchKernelGGL(k_wide_hist<0>, grid, nt, 0, st, scores, limit, n_items, q0, w.state, w.hist);
+  hipLaunchKernelGGL(k_wide_pick<0>, dim3((unsigned)n_q), nt, 0, st, w.hist, w.state, w.k);
+  hipLaunchKernelGGL(k_wide_hist<1>, grid, nt, 0, st, scores, limit, n_items, q0, w.state, w.hist + hq);
+  hipLaunchKernelGGL(k_wide_pick<1>, dim3((unsigned)n_q), nt, 0, st, w.hist + hq, w.state, w.k);
+  hipLaunchKernelGGL(k_wide_hist<2>, grid, nt, 0, st, scores, limit, n_items, q0, w.state, w.hist + 2 * hq);
+  hipLaunchKernelGGL(k_wide_pick<2>, dim3((unsigned)n_q), nt, 0, st, w.hist + 2 * hq, w.state, w.k);
+  NANN_HIP_TRY(hipGetLastError());
+  int32_t* totals = w.counts + (size_t)2 * n_q * w.n_blocks;
+  hipLaunchKernelGGL(k_wide_count, grid, nt, 0, st, scores, limit, n_items, q0, w.state, w.counts);
+  hipLaunchKernelGGL(k_range_scan, dim3((unsigned)(2 * n_q)), nt, 0, st, w.counts, w.n_blocks, totals);
+  hipLaunchKernelGGL(k_wide_fill, grid, nt, 0, st, scores, limit, n_items, q0, w.state, w.counts, w.k, w.stage);
+  NANN_HIP_TRY(hipGetLastError());
+  int P = 1;
+  while (P < w.k) P <<= 1;
+  const size_t lds = (size_t)P * 8;
+  NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_wide_sort), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_wide_sort, dim3((unsigned)n_q), dim3(kWideSortNT), lds, st, w.stage, w.state, w.k, P, scores, n_items, q0, item_ids,
+                     out_item_ids, out_scores, out_index, n_out);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
 int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, hipStream_t st) {
   float* scores = reinterpret_cast<float*>(ws + L.off_scores);
@@ -133,6 +162,14 @@ int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long lon
     }
     if (a.range) {  // every row at or above the cut, not the best k: the ragged outputs are addressed by the call's row_splits
       rc = launch_range(*a.range, scores, a.n_items, c0, n_q, a.item_ids, out_item_ids, out_scores, out_index, st);
+      if (rc) return rc;
+      continue;
+    }
+    if (a.wide) {  // the top k for k up to kWideMaxK: cut, gather, sort; the buffer is readable to the next 256-byte boundary
+      const size_t limit = ((size_t)n_q * (size_t)a.n_items + 3) & ~(size_t)3;
+      rc = launch_wide(*a.wide, scores, limit, a.n_items, 0, n_q, a.item_ids, out_item_ids + (size_t)c0 * k,
+                       out_scores ? out_scores + (size_t)c0 * k : nullptr, out_index ? out_index + (size_t)c0 * k : nullptr,
+                       a.wide->n_out ? a.wide->n_out + c0 : nullptr, st);
       if (rc) return rc;
       continue;
     }

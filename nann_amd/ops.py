@@ -262,6 +262,31 @@ def top_k(values, k):
     return (ov.reshape(shape), oi.reshape(shape)) if not squeeze else (ov[0], oi[0])
 
 
+def select_wide(values, k):
+    """The wide selection on its own (nann_select_wide): values f32[n_rows, n_cols] (or one row) -> (values f32[n_rows, k], indices
+    i32[n_rows, k], n_out i32[n_rows]) for k up to _lib.WIDE_MAX_K = 16384 and rows of any length: per row the top k of the
+    entries that are not -inf, descending, ties -> lower index, -0 and +0 tie; n_out = min(k, such entries), zeros behind."""
+    v = _dev(values, torch.float32)
+    if v.dim() == 0:
+        raise InvalidArgumentError(8, "input must be >= 1-D, got shape []")
+    squeeze = v.dim() == 1
+    v2 = v.reshape(-1, v.shape[-1]).contiguous()
+    if v2.data_ptr() & 15:
+        v2 = v2.clone()
+    k = int(k)
+    n = v2.shape[0]
+    ov = torch.empty((n, max(k, 0)), dtype=torch.float32, device=v.device)
+    oi = torch.empty((n, max(k, 0)), dtype=torch.int32, device=v.device)
+    n_out = torch.zeros(n, dtype=torch.int32, device=v.device)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_select_wide_workspace_bytes(C.c_int64(n), C.c_int64(v2.shape[1]), C.c_int32(k), C.byref(nbytes)), "select_wide")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=v.device)
+    with torch.cuda.device(v.device):
+        _check(lib().nann_select_wide(_ptr(v2), C.c_int64(n), C.c_int64(v2.shape[1]), C.c_int32(k), _ptr(ov), _ptr(oi), _ptr(n_out),
+                                      _ptr(ws), C.c_int64(ws.numel()), _stream()), "select_wide")
+    return (ov, oi, n_out) if not squeeze else (ov[0], oi[0], n_out[0])
+
+
 # ---- a4: the scorer behind BlazeXlaOp ----------------------------------------------
 _DT = {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16, torch.float32: _lib.F32}
 

@@ -15,6 +15,8 @@ per request.  Two equivalent executions of that schedule live here:
                       (the nann_*_filtered calls: the reference has no such feature);
   * `search_all_range()` / `search_all_range_model()` every row scoring at or above a per-query cut instead of the best k,
                       ragged outputs (nann_search_all_range[_model]: the reference has no such call);
+  * `search_all_wide()` / `search_all_model_wide()` the exact top k for k up to 16 384 rows per query, where search_all stops at
+                      1 024; filter= and predicates= are optional (nann_search_all_wide, nann_search_all_model_wide);
   * `search_candidates()` / `search_candidates_model()` the exact top k of every query's own list of rows, under a
                       scorer / under any ops.Model, the attention model included (nann_search_candidates[_model]);
   * `search_multi()` / `search_all_multi()` / `union_topk()` several interest vectors per user: the k best distinct rows by
@@ -666,6 +668,61 @@ def _search_all_model(index, model, comm_seq, k, options, filter):
         raise TypeError("search_all_model: an ops.Model (an ops.Scorer goes through search_all)")
     seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
     return _flat_all(index, model.handle, seq, k, options, filter, "nann_search_all_model", "search_all_model")
+
+
+class WideResult:
+    """Outputs of search_all_wide, [B, k] device tensors: the top k of every query's rows that do not score -inf, TopKV2 order,
+    n_out[b] = min(k, such rows) valid entries at the head of row b and zeros behind."""
+    __slots__ = ("item_ids", "scores", "index", "n_out", "_ws")
+
+    def __init__(self, item_ids, scores, index, n_out, ws=None):
+        self.item_ids, self.scores, self.index, self.n_out, self._ws = item_ids, scores, index, n_out, ws
+
+
+def search_all_wide(index, scorer, q, k, filter=None, predicates=None, options=None):
+    """Exhaustive search for k up to _lib.WIDE_MAX_K = 16384 rows per query (nann_search_all_wide; the reference has no such
+    call): every item of `index` scored as search_all scores it -- the same score bits -- and the exact top k per query, descending,
+    ties to the lower row, by a selection whose cost does not grow with k -> WideResult.  A row scoring -inf is never returned
+    (search_all_range's rule), so a filtered or predicated call needs no separate form: filter (make_filter) and predicates
+    (make_predicates) are optional.  `scorer`: ops.Scorer with q f32[B, d], or an ops.Model of kind l2 / mlp with q = comm_seq (the
+    attention model: search_all_model_wide).  Asynchronous on torch's current stream."""
+    dev = index.device
+    handle = scorer.handle
+    if isinstance(scorer, ops.Model):
+        if scorer.kind == "attention":
+            raise NotImplementedError("search_all_wide: l2 / mlp scorers only; the attention model goes through search_all_model_wide")
+        q = ops.user_seq_mean(q.to(dev))
+        handle = C.c_void_p(lib().nann_model_scorer(scorer.handle))  # (borrowed: the model owns it)
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    return _flat_wide(index, handle, q, k, filter, predicates, options, "nann_search_all_wide", "search_all_wide")
+
+
+def search_all_model_wide(index, model, comm_seq, k, filter=None, predicates=None, options=None):
+    """search_all_wide under a model (nann_search_all_model_wide): comm_seq f16[B, seq_len, E], `model` an ops.Model of any kind,
+    the attention model included -- the score bits of search_all_model."""
+    if not isinstance(model, ops.Model):
+        raise TypeError("search_all_model_wide: an ops.Model (an ops.Scorer goes through search_all_wide)")
+    seq = comm_seq.to(device=index.device, dtype=torch.float16).contiguous()
+    return _flat_wide(index, model.handle, seq, k, filter, predicates, options, "nann_search_all_model_wide", "search_all_model_wide")
+
+
+def _flat_wide(index, handle, x, k, filter, predicates, options, symbol, what):
+    dev = index.device
+    b, k = x.shape[0], int(k)
+    kk = max(k, 0)
+    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
+    n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+    nbytes = C.c_int64(0)
+    _check(getattr(lib(), symbol + "_workspace_bytes")(index.handle, handle, b, k, C.byref(nbytes)), what)
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        pa = _predicates_args(predicates, b, int(index.n_items), dev) if predicates is not None else None
+        _check(getattr(lib(), symbol)(index.handle, handle, _ptr(x), b, k, _ptr(out_ids), _ptr(out_scores), _ptr(out_index),
+                                      _ptr(n_out), _ptr(ws), ws.numel(), C.byref(options) if options is not None else None,
+                                      _filter_args(filter, b, index), pa, _stream()), what)
+    return WideResult(out_ids, out_scores, out_index, n_out, ws)
 
 
 # positions of the score buffer per workgroup of the range selection (csrc/nann_range.h: kRangeBlockRows)

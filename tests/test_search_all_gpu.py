@@ -366,6 +366,7 @@ def test_shards_merge_to_the_whole():
 
 # ---- 8. the headline shape --------------------------------------------------------------------------------------------
 def test_headline_shape_1m(oracle):
+    # (1M rows still give a chunk of kScanMaxChunk = 128 queries; the byte-limited chunk: test_zz_search_all_big_gpu.py)
     import bench
     from nann_amd import ops, retrieval
     from oracle import oracle as O

@@ -1342,6 +1342,40 @@ int nann_search_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scor
                         int32_t* out_fetch_index, float* out_fetch_scores, void* workspace, int64_t workspace_bytes,
                         const nann_search_options* options, nann_stream_t stream);
 
+/* ---- streamed scalar-quantised search: nann_search_all_sq8's fetch-and-re-rank without a score per (query, row) (DESIGN.md
+ * 4.24).  Added to ABI version 6: new symbols only.
+ * Every approximate score is the one defined above, bit for bit.  Per query q, without a host read-back:
+ *   (1) the cut.  n_sample = clamp(sample_rows, fetch, n_items), sample_rows == 0 meaning max(65536, ceil(n_items / 16)); tau_q =
+ *       the fetch-th largest approximate score among the rows [0, n_sample), from nann_search_all_sq8's fetch stage run over that
+ *       prefix of the table.  out_cut[q] = tau_q.  The fetch-th best of a subset is a lower bound of the fetch-th best of the table;
+ *   (2) the survivors.  S_q = every row i of the WHOLE table whose approximate score a(q, i) >= tau_q, in ascending row order.  S_q
+ *       holds at least fetch rows and contains the fetch list nann_search_all_sq8 forms at the same fetch, the rows that tie its
+ *       last score included.  out_n_survivors[q] = |S_q|, the true count whatever `cap`; out_complete[q] = 1 iff |S_q| <=
+ *       min(cap, n_items).  An incomplete query keeps the FIRST min(cap, n_items) rows of S_q in row order (deterministic);
+ *   (3) the result.  The k best rows of the kept list by EXACT score -- nann_score's bits -- ties -> lower row number, into
+ *       out_item_ids i64[n_queries, k] (required), out_scores, out_index (may be NULL).
+ * With n_sample == n_items, S_q is nann_search_all_sq8's fetch list plus the rows that tie its last score: where no row outside
+ * that list ties it, the result is nann_search_all_sq8's at the same fetch and k, bit for bit.  A tau_q that is NaN (non-finite
+ * inputs, outside the contract) leaves S_q empty and the query's outputs zero.
+ * out_complete i32[n_queries] is required; out_n_survivors i32[n_queries] and out_cut f32[n_queries] may be NULL.
+ * Nothing of chunk x n_items elements is allocated: the chunk of queries is the one nann_search_all_sq8 would take at n_sample
+ * rows (128 up to 2^20 sample rows), and besides the sample's score buffer the workspace holds 4 bytes per (query of a chunk,
+ * 1024 rows of the table) and chunk * min(cap, n_items) row numbers and exact scores.  The code table is read twice.
+ * The checks are nann_search_all_sq8's (k <= fetch <= min(1024, n_items), an MLP scorer -> NANN_ERR_UNSUPPORTED, a table from
+ * another index -> NANN_ERR_BAD_ARGUMENT, ...), and: cap < k or sample_rows < 0 -> NANN_ERR_BAD_ARGUMENT; min(cap, n_items) beyond
+ * the longest list a candidate-list search takes per query, (2^31 - 1) / (queries per chunk) -> NANN_ERR_UNSUPPORTED.  k == 0 or
+ * n_queries == 0 -> NANN_OK, nothing written.  Workspace: 256-byte aligned, smaller than
+ * nann_search_all_sq8_stream_workspace_bytes gives -> NANN_ERR_CAPACITY; bounded by a chunk of queries.  A query's answer does not
+ * depend on its batch.  Asynchronous on `stream`, re-entrant.  Rows in no particular order give |S_q| about fetch * n_items /
+ * n_sample; a table whose leading rows are unlike the rest (sorted by similarity to the queries, say) makes the cut low and the
+ * lists long -- that costs completeness, never a wrong row: a complete query's list always contains the fetch list. */
+int nann_search_all_sq8_stream_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, int64_t n_queries,
+                                               int32_t fetch, int64_t sample_rows, int32_t cap, int32_t k, int64_t* nbytes);
+int nann_search_all_sq8_stream(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                               int32_t fetch, int64_t sample_rows, int32_t cap, int32_t k, int64_t* out_item_ids, float* out_scores,
+                               int32_t* out_index, int32_t* out_complete, int32_t* out_n_survivors, float* out_cut, void* workspace,
+                               int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream);
+
 /* ---- certified scalar-quantised search: nann_search_all's exact bits at the int8 scan's cost.  Added to ABI
  * version 6: new symbols only.
  * A nann_sq8_bounds holds two device arrays over the rows of a code table, each f32[n_items]:

@@ -79,6 +79,7 @@ SYMBOLS = [
     "nann_hnsw_update_device", "nann_hnsw_orphan_bits",
     "nann_sq8_create", "nann_sq8_destroy", "nann_sq8_info", "nann_sq8_view", "nann_sq8_encode",
     "nann_search_all_sq8_workspace_bytes", "nann_search_all_sq8",
+    "nann_search_all_sq8_stream_workspace_bytes", "nann_search_all_sq8_stream",
     "nann_sq8_bounds_create", "nann_sq8_bounds_destroy", "nann_sq8_bounds_view",
     "nann_search_all_sq8_exact_workspace_bytes", "nann_search_all_sq8_exact_layout", "nann_search_all_sq8_exact",
     "nann_search_all_range_sq8_exact_workspace_bytes", "nann_search_all_range_sq8_exact",
@@ -413,6 +414,15 @@ def lib():
         L.nann_search_all_sq8.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + \
                                          [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
         L.nann_search_all_sq8.restype = C.c_int
+        # the streamed form: (ix, t, scorer, n_queries, fetch, sample_rows, cap, k, *nbytes) / (ix, t, scorer, q, n_queries, fetch,
+        # sample_rows, cap, k, out_item_ids, out_scores, out_index, out_complete, out_n_survivors, out_cut, workspace,
+        # workspace_bytes, options, stream)
+        L.nann_search_all_sq8_stream_workspace_bytes.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                                                                   C.POINTER(C.c_int64)]
+        L.nann_search_all_sq8_stream_workspace_bytes.restype = C.c_int
+        L.nann_search_all_sq8_stream.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32] + \
+                                                [C.c_void_p] * 7 + [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
+        L.nann_search_all_sq8_stream.restype = C.c_int
         # the certified form: (ix, t, stream, *out) / (b) / (b, *err, *xhat); (ix, t, b, scorer, n_queries, fetch, cap, k, *nbytes or
         # out[8]) / (ix, t, b, scorer, q, n_queries, fetch, cap, k, out_item_ids, out_scores, out_index, out_certified,
         # out_n_survivors, workspace, workspace_bytes, options, stream)

@@ -981,6 +981,85 @@ static int flat_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scor
   return NANN_OK;
 }
 
+// ---- the streamed form (nann_search_all_sq8_stream; nann_sq8.h) -------------------------------------------------
+// Per chunk: flat_all_sq8's fetch stage over the sample only, whose last fetched score is the cut; the count / scan / lists / fill
+// pass over the whole table; the candidate-list search over the survivor lists, as the certified form runs it over its own.
+// workspace: Sq8StreamLayout.  The chunk is the ScanLayout's at n_sample rows; nothing holds chunk * n_items elements.
+static int flat_sq8_stream_check(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, int64_t n, int32_t fetch,
+                                 int64_t sample_rows, int32_t cap, int32_t k, const char* who, FlatBy* by, ScanLayout* L,
+                                 Sq8StreamLayout* X) {
+  int rc = flat_sq8_check(ix, t, scorer, n, fetch, k, who, by);
+  if (rc) return rc;
+  if (cap < k) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least k");
+  if (sample_rows < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": sample_rows must not be negative");
+  if (n == 0 || k == 0) return NANN_OK;  // (nothing to lay out; fetch >= k >= 1 below)
+  const long long n_items = (long long)ix->desc.n_items;
+  const long long n_sample = sq8_stream_sample((long long)sample_rows, fetch, n_items);
+  *L = scan_layout(n_sample, ix->desc.d, by->kind, (long long)n, fetch);
+  if (std::min<long long>(cap, n_items) > cand_max_list(L->chunk))  // (a chunk's survivor lists are one candidate-list search)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": cap beyond the longest list of a candidate-list search, " +
+                                          std::to_string(cand_max_list(L->chunk)) + " at this chunk");
+  *X = sq8_stream_layout(*L, by->kind, ix->desc.d, fetch, (long long)cap, n_items, n_sample);
+  return NANN_OK;
+}
+
+static int flat_all_sq8_stream(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, const float* q, int64_t n,
+                               int32_t fetch, int64_t sample_rows, int32_t cap, int32_t k, int64_t* out_item_ids, float* out_scores,
+                               int32_t* out_index, int32_t* out_complete, int32_t* out_n_survivors, float* out_cut, void* workspace,
+                               int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream, const char* who) {
+  FlatBy by;
+  ScanLayout L;
+  Sq8StreamLayout X;
+  int rc = flat_sq8_stream_check(ix, t, scorer, n, fetch, sample_rows, cap, k, who, &by, &L, &X);
+  if (rc) return rc;
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!q || !out_item_ids || !out_complete) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  rc = flat_workspace(workspace, workspace_bytes, X.total, who, "");
+  if (rc) return rc;
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  Sq8Args a = {};
+  a.codes = t->codes;
+  a.scales = t->scales;
+  a.norms = t->norms;
+  a.item_ids = ix->desc.item_ids;
+  a.n_items = (long long)ix->desc.n_items;
+  a.d = ix->desc.d;
+  a.metric = by.kind == NANN_SCORER_IP ? MT_IP : MT_L2;
+  Sq8Args sample = a;  // the table's first n_sample rows
+  sample.n_items = X.n_sample;
+  CandArgs ca = {};
+  flat_rows_of(ix, &ca);
+  ca.cus = di.cus;
+  ca.kind = by.kind;
+  ca.row_splits = reinterpret_cast<const int64_t*>(ws + X.off_xsplits);
+  ca.rows = reinterpret_cast<const int32_t*>(ws + X.off_rows);
+  int32_t* status = reinterpret_cast<int32_t*>(ws + X.S.off_status);  // (always 0: the lists are the call's own)
+  for (int64_t c0 = 0; c0 < n; c0 += L.chunk) {
+    const int n_q = (int)std::min<int64_t>(L.chunk, n - c0);
+    const float* qc = q + (size_t)c0 * a.d;
+    // the cut: the fetch stage over the sample; it leaves the chunk's encoded queries and the fetch lists in the workspace
+    rc = launch_sq8_fetch(sample, L, X.S, qc, n_q, fetch, ws, nullptr, nullptr, st);
+    if (rc) return rc;
+    // the survivors of every query over the whole table, as compact lists in ascending row order
+    rc = launch_sq8_stream(a, X, n_q, fetch, ws, out_complete + c0, out_n_survivors ? out_n_survivors + c0 : nullptr,
+                           out_cut ? out_cut + c0 : nullptr, st);
+    if (rc) return rc;
+    // the exact top k of the lists
+    ca.n_cand = (long long)n_q * X.cap;
+    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + X.S.off_cand, out_item_ids + (size_t)c0 * k,
+                     out_scores ? out_scores + (size_t)c0 * k : nullptr, out_index ? out_index + (size_t)c0 * k : nullptr, nullptr,
+                     nullptr, status, st);
+    if (rc) return rc;
+  }
+  return NANN_OK;
+}
+
 // ---- the certified form (nann_search_all_sq8_exact; nann_sq8.h) -----------------------------------------------
 // Per chunk: flat_all_sq8's two steps with the result kept in the workspace (stage a), the survivor pass over the score buffer
 // the scan has left in the ScanLayout (stage b), and the candidate-list search over the final lists (stage c).
@@ -1675,6 +1754,27 @@ int nann_search_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scor
                         const nann_search_options* options, nann_stream_t stream) {
   return flat_all_sq8(ix, t, scorer, q, n_queries, fetch, k, out_item_ids, out_scores, out_index, out_fetch_index, out_fetch_scores,
                       workspace, workspace_bytes, options, stream, "nann_search_all_sq8");
+}
+
+// ---- the streamed form (nann_sq8.h) ----------------------------------------------------------------------------
+int nann_search_all_sq8_stream_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, int64_t n_queries,
+                                               int32_t fetch, int64_t sample_rows, int32_t cap, int32_t k, int64_t* nbytes) {
+  const char* who = "nann_search_all_sq8_stream_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  ScanLayout L;
+  Sq8StreamLayout X;
+  const int rc = flat_sq8_stream_check(ix, t, scorer, n_queries, fetch, sample_rows, cap, k, who, &by, &L, &X);
+  if (rc) return rc;
+  *nbytes = n_queries == 0 || k == 0 ? 0 : (int64_t)X.total;
+  return NANN_OK;
+}
+int nann_search_all_sq8_stream(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, const float* q, int64_t n_queries,
+                               int32_t fetch, int64_t sample_rows, int32_t cap, int32_t k, int64_t* out_item_ids, float* out_scores,
+                               int32_t* out_index, int32_t* out_complete, int32_t* out_n_survivors, float* out_cut, void* workspace,
+                               int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream) {
+  return flat_all_sq8_stream(ix, t, scorer, q, n_queries, fetch, sample_rows, cap, k, out_item_ids, out_scores, out_index, out_complete,
+                             out_n_survivors, out_cut, workspace, workspace_bytes, options, stream, "nann_search_all_sq8_stream");
 }
 
 

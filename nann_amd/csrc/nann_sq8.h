@@ -65,6 +65,41 @@ int launch_sq8_scan(const Sq8Args& a, const float* q, int n_q, int8_t* qcodes, f
 int launch_sq8_fetch(const Sq8Args& a, const ScanLayout& L, const Sq8Layout& S, const float* q, int n_q, int fetch,
                      unsigned char* ws, int32_t* out_fetch_index, float* out_fetch_scores, hipStream_t st);
 
+// ---- the streamed form (nann_search_all_sq8_stream): no buffer of chunk x n_items elements.  Per chunk the
+// fetch stage above runs over the SAMPLE, rows [0, n_sample), and leaves tau_q = the fetch-th best approximate score of the
+// sample in its fetch lists (fscores[q][fetch - 1]): a lower bound of the fetch-th best over the whole table.  Then, over the
+// whole table, with the front end of k_scan_sq8 (sq8_scan_front: the same bits) and an epilogue that compares and stores no score:
+//   k_sq8_stream_count  grid = blocks of kSq8RowsPerWg rows: counts[query][block] = rows of the block with a(q, row) >= tau_q.  One
+//                       ballot per accumulator register gives two 32-row masks, one per half-wave = one per query; their
+//                       popcounts go to the wavefront's own column of an LDS table (an entry has ONE writing lane: no atomic)
+//   k_range_scan        (nann_range.h) the block counts -> exclusive prefixes and the queries' totals
+//   k_sq8_stream_lists  one workgroup: n_survivors, complete = total <= cap, tau to the caller, the compact row_splits with
+//                       min(total, cap) per query
+//   k_sq8_stream_fill   the same grid, two phases in one launch.  1: the scores again, every (query, 32-row group) mask into LDS,
+//                       mask[query][group] at a pitch of 33 words, each entry written by one lane once.  2, no MFMA: a half-wave
+//                       per query, a lane per group -- the lane's popcount, a 32-lane exclusive scan, and every set bit b of the
+//                       lane's mask stores row = block_row0 + 32 group + b to the query's list at (block prefix) + (scan) +
+//                       (bits below b), EVERY store behind pos < min(total, cap): ascending row order, no atomic
+// and the candidate-list search over the lists.  Scanning the codes twice is the price of holding nothing per (query, row).
+struct Sq8StreamLayout {
+  Sq8Layout S;                          // the sample's fetch stage (ScanLayout at n_sample in front); its CandLayout sized for chunk * cap
+  long long n_sample;                   // rows of the sample
+  long long cap;                        // min(cap, n_items): most survivors of a complete query
+  int n_blocks;                         // blocks of kSq8RowsPerWg rows of the table
+  size_t off_counts;                    // i32[chunk, n_blocks] block counts, then prefixes; i32[chunk] totals behind
+  size_t off_xsplits;                   // i64[chunk + 1]: the compact row_splits of the survivor lists
+  size_t off_rows;                      // i32[chunk * cap]: the survivor lists
+  size_t total;
+};
+// n_sample of a call: clamp(sample_rows, fetch, n_items), sample_rows == 0 -> max(65 536, ceil(n_items / 16))
+long long sq8_stream_sample(long long sample_rows, int fetch, long long n_items);
+// L: scan_layout at n_sample rows
+Sq8StreamLayout sq8_stream_layout(const ScanLayout& L, int kind, int d, int fetch, long long cap, long long n_items, long long n_sample);
+// behind a chunk's launch_sq8_fetch over the sample (a: the WHOLE table): count, scan, lists, fill.  out_*: this chunk's slice;
+// out_n_survivors and out_cut may be null.
+int launch_sq8_stream(const Sq8Args& a, const Sq8StreamLayout& X, int n_q, int fetch, unsigned char* ws, int32_t* out_complete,
+                      int32_t* out_n_survivors, float* out_cut, hipStream_t st);
+
 
 // ---- the certified form (nann_search_all_sq8_exact): the fetch stage and its exact re-rank give a cut tau_q,
 // a survivor pass over the chunk's score buffer keeps every row whose exact score the bound cannot put below tau_q, and the
@@ -219,15 +254,30 @@ __global__ __launch_bounds__(kSq8NT) void k_sq8_encode(const void* __restrict__ 
   }
 }
 
-// grid: blocks of kSq8RowsPerWg rows.  scores f32[n_q, n_items], n_q <= kScanMaxChunk.
+// The front end of every int8 scan (k_scan_sq8, k_sq8_stream_count, k_sq8_stream_fill): the chunk's queries into LDS, a barrier,
+// then per wavefront and 32-row group the B fragments into registers and, per query tile t, the d / 32 MFMAs; epi(group, row, t,
+// acc, sx, bx) takes a tile's 16 accumulators, converged -- every lane of the wavefront calls it, rows behind the table included
+// (row >= n_items; they hold the last row again), so that an epilogue may ballot.  group = the 32-row group of the workgroup,
+// row = the lane's row.  Register g of lane (r, h) is query sq8_query_of(t, g, h); sq8_score turns it into the approximate score.
+// What a kernel stages into LDS of its own before the call is published by the barrier in here.
 // LDS: qc[kScanMaxChunk][D + 16] the query codes (zeros behind n_q), qs[kScanMaxChunk] = sq (inner product) or 2 sq (L2),
 // qa[kScanMaxChunk] = (sq sq) (float)nq.
-template <int NS, int METRIC>  // NS = d / 32 k-steps
-__global__ __launch_bounds__(kSq8NT) void k_scan_sq8(const int8_t* __restrict__ codes, const float* __restrict__ scales,
-                                                     const int32_t* __restrict__ norms, long long n_items,
-                                                     const int8_t* __restrict__ qcodes, const float* __restrict__ qscales,
-                                                     const int32_t* __restrict__ qnorms, int n_q, float* __restrict__ scores) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+__device__ __forceinline__ int sq8_query_of(int t, int g, int h) { return t * 32 + (g & 3) + 8 * (g >> 2) + 4 * h; }
+template <int METRIC>
+__device__ __forceinline__ float sq8_score(float qs, float qa, float sx, float bx, int D) {
+  const float dot = (float)D;
+  if constexpr (METRIC == MT_IP) {
+    return __fmul_rn(__fmul_rn(qs, sx), dot);
+  } else {
+    const float c = __fmul_rn(__fmul_rn(qs, sx), dot);
+    return __fsub_rn(c, __fadd_rn(qa, bx));
+  }
+}
+template <int NS, int METRIC, class Epi>  // NS = d / 32 k-steps
+__device__ __forceinline__ void sq8_scan_front(unsigned char* smem, const int8_t* __restrict__ codes, const float* __restrict__ scales,
+                                               const int32_t* __restrict__ norms, long long n_items,
+                                               const int8_t* __restrict__ qcodes, const float* __restrict__ qscales,
+                                               const int32_t* __restrict__ qnorms, int n_q, Epi epi) {
   constexpr int D = NS * 32, QS = D + kSq8QPad;
   float* qs = reinterpret_cast<float*>(smem + kScanMaxChunk * QS);
   float* qa = qs + kScanMaxChunk;
@@ -250,7 +300,8 @@ __global__ __launch_bounds__(kSq8NT) void k_scan_sq8(const int8_t* __restrict__ 
   const int n_qt = (n_q + 31) >> 5;
   const long long wg_row0 = (long long)blockIdx.x * kSq8RowsPerWg;
   for (int it = 0; it < kSq8RowsPerWg / (32 * (kSq8NT / 64)); ++it) {
-    const long long row0 = wg_row0 + (long long)(it * (kSq8NT / 64) + wave) * 32;
+    const int group = it * (kSq8NT / 64) + wave;
+    const long long row0 = wg_row0 + (long long)group * 32;
     if (row0 >= n_items) break;  // (uniform over the wavefront)
     const long long row = row0 + r;
     const long long row_ld = row < n_items ? row : n_items - 1;  // (a row behind the table: the last one again, never stored)
@@ -267,25 +318,31 @@ __global__ __launch_bounds__(kSq8NT) void k_scan_sq8(const int8_t* __restrict__ 
         const i32x4v a = *reinterpret_cast<const i32x4v*>(qrow + s * 32);
         acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[s], acc, 0, 0, 0);
       }
-      if (row < n_items) {
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-          const int qi = t * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
-          if (qi < n_q) {
-            const float dot = (float)acc[g];
-            float sc;
-            if constexpr (METRIC == MT_IP) {
-              sc = __fmul_rn(__fmul_rn(qs[qi], sx), dot);
-            } else {
-              const float c = __fmul_rn(__fmul_rn(qs[qi], sx), dot);
-              sc = __fsub_rn(c, __fadd_rn(qa[qi], bx));
-            }
-            scores[(size_t)qi * n_items + row] = sc;
-          }
-        }
-      }
+      epi(group, row, t, acc, sx, bx);
     }
   }
+}
+
+// grid: blocks of kSq8RowsPerWg rows.  scores f32[n_q, n_items], n_q <= kScanMaxChunk.
+template <int NS, int METRIC>
+__global__ __launch_bounds__(kSq8NT) void k_scan_sq8(const int8_t* __restrict__ codes, const float* __restrict__ scales,
+                                                     const int32_t* __restrict__ norms, long long n_items,
+                                                     const int8_t* __restrict__ qcodes, const float* __restrict__ qscales,
+                                                     const int32_t* __restrict__ qnorms, int n_q, float* __restrict__ scores) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const float* qs = reinterpret_cast<const float*>(smem + kScanMaxChunk * (NS * 32 + kSq8QPad));
+  const float* qa = qs + kScanMaxChunk;
+  const int h = (threadIdx.x & 63) >> 5;
+  sq8_scan_front<NS, METRIC>(smem, codes, scales, norms, n_items, qcodes, qscales, qnorms, n_q,
+                             [&](int, long long row, int t, const i32x16v& acc, float sx, float bx) {
+    if (row < n_items) {
+#pragma unroll
+      for (int g = 0; g < 16; ++g) {
+        const int qi = sq8_query_of(t, g, h);
+        if (qi < n_q) scores[(size_t)qi * n_items + row] = sq8_score<METRIC>(qs[qi], qa[qi], sx, bx, acc[g]);
+      }
+    }
+  });
 }
 
 // one workgroup per query: the fetched rows (all distinct) in ascending order by a bitonic sort in LDS; thread 0 of every
@@ -326,6 +383,142 @@ __global__ __launch_bounds__(kSq8NT) void k_sq8_sort_rows(const int32_t* __restr
   if (tid == 0) {
     splits[qi] = (long long)qi * fetch;
     splits[qi + 1] = (long long)(qi + 1) * fetch;
+  }
+}
+
+// ---- the streamed form ----------------------------------------------------------------------------------------------------
+constexpr int kSq8Groups = kSq8RowsPerWg / 32;    // 32-row groups of a workgroup: one per lane of a half-wave in phase 2 of the fill
+constexpr int kSq8MaskPitch = kSq8Groups + 1;     // words between two queries' masks in LDS: odd, a half-wave reads 32 banks
+static_assert(kSq8Groups == 32, "k_sq8_stream_fill: a half-wave holds a query's groups, one per lane");
+// dynamic LDS behind the front end's: count -- cut f32[chunk], cnt i32[wavefronts][chunk]; fill -- cut, mask u32[chunk][pitch]
+__host__ __device__ constexpr int sq8_stream_count_lds(int d) { return sq8_scan_lds(d) + kScanMaxChunk * 4 * (1 + kSq8NT / 64); }
+__host__ __device__ constexpr int sq8_stream_fill_lds(int d) { return sq8_scan_lds(d) + kScanMaxChunk * 4 * (1 + kSq8MaskPitch); }
+
+// The epilogue of both kernels: the survivor masks of a tile's 16 registers.  All 64 lanes arrive (sq8_scan_front); register g
+// gives one ballot whose low word is query sq8_query_of(t, g, 0) over the group's 32 rows and whose high word is query
+// sq8_query_of(t, g, 1).  put(qi, mask) runs in the first lane of each half-wave for its own query, where the mask is not empty.
+template <int METRIC, class Put>
+__device__ __forceinline__ void sq8_stream_masks(const float* qs, const float* qa, const float* cut, long long row, long long n_items,
+                                                 int t, int n_q, const i32x16v& acc, float sx, float bx, Put put) {
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const bool in = row < n_items;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int qi = sq8_query_of(t, g, h);  // < kScanMaxChunk: qs, qa, cut hold every query of a tile
+    const float sc = sq8_score<METRIC>(qs[qi], qa[qi], sx, bx, acc[g]);
+    const unsigned long long m = __ballot(in && qi < n_q && sc >= cut[qi]);
+    if (m == 0) continue;  // (uniform; nearly every ballot of a large table)
+    const unsigned mine = h ? (unsigned)(m >> 32) : (unsigned)m;
+    if (r == 0 && mine != 0) put(qi, mine);
+  }
+}
+
+// cut: tau of query qi at cut[qi * cut_stride] (the fetch lists' last column).  counts i32[n_q, n_blocks].
+template <int NS, int METRIC>
+__global__ __launch_bounds__(kSq8NT) void k_sq8_stream_count(const int8_t* __restrict__ codes, const float* __restrict__ scales,
+                                                             const int32_t* __restrict__ norms, long long n_items,
+                                                             const int8_t* __restrict__ qcodes, const float* __restrict__ qscales,
+                                                             const int32_t* __restrict__ qnorms, int n_q,
+                                                             const float* __restrict__ cut_src, int cut_stride, int n_blocks,
+                                                             int32_t* __restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const float* qs = reinterpret_cast<const float*>(smem + kScanMaxChunk * (NS * 32 + kSq8QPad));
+  const float* qa = qs + kScanMaxChunk;
+  float* cut = reinterpret_cast<float*>(smem + sq8_scan_lds(NS * 32));
+  int* cnt = reinterpret_cast<int*>(cut + kScanMaxChunk);  // [wavefront][query]
+  const int tid = threadIdx.x;
+  for (int i = tid; i < kScanMaxChunk; i += kSq8NT) cut[i] = i < n_q ? cut_src[(size_t)i * cut_stride] : __builtin_inff();
+  for (int i = tid; i < kScanMaxChunk * (kSq8NT / 64); i += kSq8NT) cnt[i] = 0;
+  int* mine = cnt + (tid >> 6) * kScanMaxChunk;
+  sq8_scan_front<NS, METRIC>(smem, codes, scales, norms, n_items, qcodes, qscales, qnorms, n_q,
+                             [&](int, long long row, int t, const i32x16v& acc, float sx, float bx) {
+    // (query qi of this wavefront's column is always written by the same lane: a plain read-modify-write)
+    sq8_stream_masks<METRIC>(qs, qa, cut, row, n_items, t, n_q, acc, sx, bx, [&](int qi, unsigned m) { mine[qi] += __popc(m); });
+  });
+  __syncthreads();
+  for (int qi = tid; qi < n_q; qi += kSq8NT) {
+    int c = 0;
+#pragma unroll
+    for (int w = 0; w < kSq8NT / 64; ++w) c += cnt[w * kScanMaxChunk + qi];
+    counts[(size_t)qi * n_blocks + blockIdx.x] = c;
+  }
+}
+
+// One workgroup per chunk, behind k_range_scan: n_survivors, complete and tau of every query to the caller, and the compact
+// row_splits of the survivor lists, min(total, cap) per query.  n_q <= kScanMaxChunk <= kSq8NT.
+__global__ __launch_bounds__(kSq8NT) void k_sq8_stream_lists(const int32_t* __restrict__ totals, const float* __restrict__ cut_src,
+                                                             int cut_stride, int n_q, long long cap, long long* __restrict__ xsplits,
+                                                             int32_t* __restrict__ out_complete, int32_t* __restrict__ out_n_survivors,
+                                                             float* __restrict__ out_cut) {
+  __shared__ long long len[kSq8NT];
+  const int tid = threadIdx.x;
+  long long l = 0;
+  if (tid < n_q) {
+    const int total = totals[tid];
+    l = min((long long)total, cap);
+    out_complete[tid] = (long long)total <= cap ? 1 : 0;
+    if (out_n_survivors) out_n_survivors[tid] = total;
+    if (out_cut) out_cut[tid] = cut_src[(size_t)tid * cut_stride];
+  }
+  len[tid] = l;
+  __syncthreads();
+  long long sum = 0;
+  for (int j = 0; j < tid; ++j) sum += len[j];
+  if (tid < n_q) xsplits[tid] = sum;
+  if (tid == n_q - 1) xsplits[n_q] = sum + l;
+}
+
+// prefix = counts behind k_range_scan.  rows: the lists at xsplits.
+template <int NS, int METRIC>
+__global__ __launch_bounds__(kSq8NT) void k_sq8_stream_fill(const int8_t* __restrict__ codes, const float* __restrict__ scales,
+                                                            const int32_t* __restrict__ norms, long long n_items,
+                                                            const int8_t* __restrict__ qcodes, const float* __restrict__ qscales,
+                                                            const int32_t* __restrict__ qnorms, int n_q,
+                                                            const float* __restrict__ cut_src, int cut_stride, int n_blocks,
+                                                            const int32_t* __restrict__ prefix, const long long* __restrict__ xsplits,
+                                                            int32_t* __restrict__ rows) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const float* qs = reinterpret_cast<const float*>(smem + kScanMaxChunk * (NS * 32 + kSq8QPad));
+  const float* qa = qs + kScanMaxChunk;
+  float* cut = reinterpret_cast<float*>(smem + sq8_scan_lds(NS * 32));
+  unsigned* mask = reinterpret_cast<unsigned*>(cut + kScanMaxChunk);  // [query][kSq8MaskPitch]
+  const int tid = threadIdx.x;
+  for (int i = tid; i < kScanMaxChunk; i += kSq8NT) cut[i] = i < n_q ? cut_src[(size_t)i * cut_stride] : __builtin_inff();
+  for (int i = tid; i < kScanMaxChunk * kSq8MaskPitch; i += kSq8NT) mask[i] = 0u;  // (a group behind the table is never visited)
+  // phase 1: entry (query, group) is written once, by the lane that holds the query's half of the group's ballot
+  sq8_scan_front<NS, METRIC>(smem, codes, scales, norms, n_items, qcodes, qscales, qnorms, n_q,
+                             [&](int group, long long row, int t, const i32x16v& acc, float sx, float bx) {
+    sq8_stream_masks<METRIC>(qs, qa, cut, row, n_items, t, n_q, acc, sx, bx,
+                             [&](int qi, unsigned m) { mask[qi * kSq8MaskPitch + group] = m; });
+  });
+  __syncthreads();
+  // phase 2: wavefront w takes the query pairs w, w + 4, ...; half-wave h the query 2 pair + h, lane r its group r
+  const int lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const long long wg_row0 = (long long)blockIdx.x * kSq8RowsPerWg;
+  for (int pair = tid >> 6; 2 * pair < n_q; pair += kSq8NT / 64) {
+    const int qi = 2 * pair + h;
+    unsigned m = qi < n_q ? mask[qi * kSq8MaskPitch + r] : 0u;
+    if (__ballot(m != 0u) == 0) continue;  // (uniform)
+    const int c = __popc(m);
+    int below = c;  // inclusive scan over the half-wave's 32 lanes, then exclusive
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) {
+      const int v = __shfl_up(below, o, 32);
+      if (r >= o) below += v;
+    }
+    below -= c;
+    if (m != 0u) {
+      const long long q_begin = xsplits[qi];
+      const long long room = xsplits[qi + 1] - q_begin;  // min(total, cap): the list's length
+      long long pos = (long long)prefix[(size_t)qi * n_blocks + blockIdx.x] + below;
+      const long long row0 = wg_row0 + 32 * r;
+      do {
+        const int b = __ffs(m) - 1;
+        if (pos >= 0 && pos < room) rows[q_begin + pos] = (int32_t)(row0 + b);  // the guard of the store
+        ++pos;
+        m &= m - 1u;
+      } while (m != 0u);
+    }
   }
 }
 

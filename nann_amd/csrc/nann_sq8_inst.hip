@@ -1,8 +1,9 @@
 // nann_sq8_inst.hip -- the kernels of the scalar-quantised exhaustive search (nann_sq8.h): the encoder for every input dtype, the
 // int8 MFMA scan for every (d, metric), the row sort; workspace layout and the launch sequence of a chunk's fetch stage; the
-// certified form's row-error kernel, query terms and survivor pass (count, k_range_scan, lists, fill); the certified range form's
-// lists kernel and ragged selection (count, k_range_scan, k_range_splits, fill).  Rides in
-// nann_scan.o behind nann_scan_inst.hip: the slab top-k and the merge it launches are that file's kernels.
+// streamed form's count / lists / fill pass (k_sq8_stream_*, around k_range_scan); the certified form's row-error kernel, query
+// terms and survivor pass (count, k_range_scan, lists, fill); the certified range form's lists kernel and ragged selection (count,
+// k_range_scan, k_range_splits, fill).  Rides in nann_scan.o behind nann_scan_inst.hip: the slab top-k and the merge it launches
+// are that file's kernels.
 #ifndef NANN_SCAN_IMPL
 #define NANN_SCAN_IMPL
 #endif
@@ -105,6 +106,83 @@ int launch_sq8_fetch(const Sq8Args& a, const ScanLayout& L, const Sq8Layout& S, 
                      out_fetch_scores);
   NANN_HIP_TRY(hipGetLastError());
   return NANN_OK;
+}
+
+// ---- the streamed form ----------------------------------------------------------------------------------------------------
+long long sq8_stream_sample(long long sample_rows, int fetch, long long n_items) {
+  const long long want = sample_rows > 0 ? sample_rows : std::max<long long>(65536, (n_items + 15) / 16);
+  return std::min(std::max<long long>(want, fetch), n_items);
+}
+
+Sq8StreamLayout sq8_stream_layout(const ScanLayout& L, int kind, int d, int fetch, long long cap, long long n_items, long long n_sample) {
+  Sq8StreamLayout X = {};
+  const size_t c = (size_t)L.chunk;
+  X.n_sample = n_sample;
+  X.cap = std::min(cap, n_items);
+  X.n_blocks = (int)((n_items + kSq8RowsPerWg - 1) / kSq8RowsPerWg);
+  X.S = sq8_layout(L, d, fetch, cand_layout(kind, L.chunk, (long long)L.chunk * X.cap).total);
+  X.off_counts = X.S.total;
+  X.off_xsplits = X.off_counts + sq8_up256(c * ((size_t)X.n_blocks + 1) * 4);
+  X.off_rows = X.off_xsplits + sq8_up256((c + 1) * 8);
+  X.total = X.off_rows + sq8_up256(c * (size_t)X.cap * 4);
+  return X;
+}
+
+template <int NS, int METRIC>
+static int launch_sq8_stream_as(const Sq8Args& a, const Sq8StreamLayout& X, int n_q, int fetch, unsigned char* ws,
+                                int32_t* out_complete, int32_t* out_n_survivors, float* out_cut, hipStream_t st) {
+  auto count = k_sq8_stream_count<NS, METRIC>;
+  auto fill = k_sq8_stream_fill<NS, METRIC>;
+  constexpr int lds_count = sq8_stream_count_lds(NS * 32), lds_fill = sq8_stream_fill_lds(NS * 32);
+  static_assert(lds_count <= 80 * 1024, "k_sq8_stream_count: two workgroups per CU");
+  static_assert(lds_fill <= 160 * 1024 && (NS == 16 || lds_fill <= 80 * 1024), "k_sq8_stream_fill: two workgroups per CU up to d = 256, one at 512");
+  if (lds_count > 64 * 1024)  // (only d = 512 is beyond the default limit)
+    NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(count), hipFuncAttributeMaxDynamicSharedMemorySize, lds_count));
+  if (lds_fill > 64 * 1024)
+    NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, lds_fill));
+  // the chunk's encoded queries and the sample's fetch lists, as launch_sq8_fetch has left them: tau_q is the last score of list q
+  const int8_t* qcodes = reinterpret_cast<const int8_t*>(ws + X.S.off_qcodes);
+  const float* qscales = reinterpret_cast<const float*>(ws + X.S.off_qscales);
+  const int32_t* qnorms = reinterpret_cast<const int32_t*>(ws + X.S.off_qnorms);
+  const float* cut = reinterpret_cast<const float*>(ws + X.S.off_fscores) + (fetch - 1);
+  int32_t* counts = reinterpret_cast<int32_t*>(ws + X.off_counts);
+  int32_t* totals = counts + (size_t)n_q * X.n_blocks;
+  long long* xsplits = reinterpret_cast<long long*>(ws + X.off_xsplits);
+  int32_t* rows = reinterpret_cast<int32_t*>(ws + X.off_rows);
+  const dim3 grid((unsigned)X.n_blocks);
+  hipLaunchKernelGGL(count, grid, dim3(kSq8NT), (size_t)lds_count, st, a.codes, a.scales, a.norms, a.n_items, qcodes, qscales, qnorms,
+                     n_q, cut, fetch, X.n_blocks, counts);
+  NANN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_range_scan, dim3((unsigned)n_q), dim3(kRangeNT), 0, st, counts, X.n_blocks, totals);
+  NANN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_sq8_stream_lists, dim3(1), dim3(kSq8NT), 0, st, totals, cut, fetch, n_q, X.cap, xsplits, out_complete,
+                     out_n_survivors, out_cut);
+  NANN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(fill, grid, dim3(kSq8NT), (size_t)lds_fill, st, a.codes, a.scales, a.norms, a.n_items, qcodes, qscales, qnorms, n_q,
+                     cut, fetch, X.n_blocks, counts, xsplits, rows);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+template <int METRIC>
+static int launch_sq8_stream_by(const Sq8Args& a, const Sq8StreamLayout& X, int n_q, int fetch, unsigned char* ws,
+                                int32_t* out_complete, int32_t* out_n_survivors, float* out_cut, hipStream_t st) {
+  switch (a.d / 32) {
+    case 2: return launch_sq8_stream_as<2, METRIC>(a, X, n_q, fetch, ws, out_complete, out_n_survivors, out_cut, st);
+    case 4: return launch_sq8_stream_as<4, METRIC>(a, X, n_q, fetch, ws, out_complete, out_n_survivors, out_cut, st);
+    case 8: return launch_sq8_stream_as<8, METRIC>(a, X, n_q, fetch, ws, out_complete, out_n_survivors, out_cut, st);
+    case 16: return launch_sq8_stream_as<16, METRIC>(a, X, n_q, fetch, ws, out_complete, out_n_survivors, out_cut, st);
+    default: return fail(NANN_ERR_UNSUPPORTED, "nann_search_all_sq8_stream: d must be 64, 128, 256 or 512");
+  }
+}
+
+int launch_sq8_stream(const Sq8Args& a, const Sq8StreamLayout& X, int n_q, int fetch, unsigned char* ws, int32_t* out_complete,
+                      int32_t* out_n_survivors, float* out_cut, hipStream_t st) {
+  static_assert(kScanMaxChunk <= kSq8NT && kScanMaxChunk <= kRangeNT, "one workgroup walks a chunk's queries");
+  if (n_q < 1 || n_q > kScanMaxChunk || fetch < 1 || fetch > kMaxK || X.cap < 1 || X.n_blocks < 1)
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_sq8_stream: chunk shape");
+  return a.metric == MT_IP ? launch_sq8_stream_by<MT_IP>(a, X, n_q, fetch, ws, out_complete, out_n_survivors, out_cut, st)
+                           : launch_sq8_stream_by<MT_L2>(a, X, n_q, fetch, ws, out_complete, out_n_survivors, out_cut, st);
 }
 
 // ---- the certified form ---------------------------------------------------------------------------------------------------

@@ -549,6 +549,59 @@ def search_all_sq8(index, sq8, scorer, q, k, fetch=None, options=None, return_fe
     return Sq8Result(out_ids, out_scores, out_index, f_index, f_scores, fetch, ws)
 
 
+class Sq8StreamResult:
+    """Outputs of search_all_sq8_stream: item_ids i64[B, k], scores f32[B, k] (exact, nann_score's bits), index i32[B, k];
+    complete i32[B] (1: every survivor was re-ranked, as the DEVICE call left it); with return_stats n_survivors i32[B] (rows
+    at or above the cut, whatever the cap) and cut f32[B] (tau: the fetch-th best approximate score of the sample), else None."""
+    __slots__ = ("item_ids", "scores", "index", "complete", "n_survivors", "cut", "fetch", "cap", "_ws")
+
+    def __init__(self, item_ids, scores, index, complete, n_survivors, cut, fetch, cap, ws=None):
+        self.item_ids, self.scores, self.index = item_ids, scores, index
+        self.complete, self.n_survivors, self.cut, self.fetch, self.cap, self._ws = complete, n_survivors, cut, fetch, cap, ws
+
+
+def search_all_sq8_stream(index, sq8, scorer, q, k, fetch=None, sample_rows=None, cap=8192, fallback=True, options=None,
+                          return_stats=False):
+    """Streamed scalar-quantised exhaustive search (nann_search_all_sq8_stream): search_all_sq8's fetch-and-re-rank with no
+    score buffer of queries x n_items.  Per query the `fetch`-th best approximate score among the first `sample_rows` rows is a
+    cut; every row of the table whose approximate score reaches the cut survives, in row order -- a superset of search_all_sq8's
+    fetch list at the same `fetch` -- and the exact top k of the survivors is returned: descending, ties -> lower row, the
+    scores search_all's bits for the rows returned.  sample_rows=None: max(65536, ceil(n_items / 16)); the number of survivors
+    is about fetch * n_items / sample_rows for rows in no particular order.  A query with more than `cap` survivors is
+    INCOMPLETE: the device re-ranks its first `cap` survivors in row order.  fallback=True: the wrapper reads `complete` back
+    -- ONE synchronisation of the stream with the host -- and re-runs the incomplete queries through search_all_sq8 at the same
+    fetch.  fallback=False: asynchronous on torch's current stream, nothing read back.  fetch=None as in search_all_sq8;
+    k <= fetch <= 1024, k <= cap.  return_stats: also return n_survivors and cut."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    b, k = q.shape[0], int(k)
+    fetch = min(4 * k, 1024, int(index.n_items)) if fetch is None else int(fetch)
+    sample_rows = 0 if sample_rows is None else int(sample_rows)
+    cap = int(cap)
+    kk = max(k, 0)
+    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
+    complete = torch.zeros(b, dtype=torch.int32, device=dev)
+    n_surv = torch.zeros(b, dtype=torch.int32, device=dev) if return_stats else None
+    cut = torch.zeros(b, dtype=torch.float32, device=dev) if return_stats else None
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_all_sq8_stream_workspace_bytes(index.handle, sq8.handle, scorer.handle, b, fetch, sample_rows, cap, k,
+                                                            C.byref(nbytes)), "search_all_sq8_stream")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_all_sq8_stream(index.handle, sq8.handle, scorer.handle, _ptr(q), b, fetch, sample_rows, cap, k,
+                                                _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(complete), _ptr(n_surv),
+                                                _ptr(cut), _ptr(ws), ws.numel(), C.byref(options) if options is not None else None,
+                                                _stream()), "search_all_sq8_stream")
+    if fallback and b > 0 and k > 0:
+        todo = torch.nonzero(complete == 0).flatten()  # (the synchronisation)
+        if todo.numel() > 0:
+            r = search_all_sq8(index, sq8, scorer, q[todo], k, fetch=fetch, options=options)
+            out_ids[todo], out_scores[todo], out_index[todo] = r.item_ids, r.scores, r.index
+    return Sq8StreamResult(out_ids, out_scores, out_index, complete, n_surv, cut, fetch, cap, ws)
+
+
 class Sq8Bounds:
     """The per-row error terms of a code table (nann_sq8_bounds; make_sq8_bounds): err() f32[n_items] >= |x_i - scale_i codes_i|,
     xhat() f32[n_items] >= scale_i sqrt(norm_i), torch views of device memory valid until release().  It borrows the index and

@@ -793,6 +793,53 @@ int nann_search_candidates(const nann_index* ix, const nann_scorer* scorer, cons
                            int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace, int64_t workspace_bytes,
                            const nann_search_options* options, nann_stream_t stream);
 
+/* ---- shared-list search: exact top-k over the row lists a query names -------------------------------------------------------
+ * Between nann_search_all (every row for every query) and nann_search_candidates (a private row list per query): the lists are
+ * SHARED -- the cells of a coarse partition (IVF), a category, a seller's stock -- and a query names up to
+ * NANN_LISTS_MAX_PROBE of them.  A list probed by many queries of a batch is fetched once per tile of 16 probing queries, not
+ * once per query (csrc/nann_lists.h).  The reference has no such call.
+ *
+ * nann_partition: the lists, a handle that BORROWS the index.  list_of_row (device i32[n_items]) names the list of every row, a
+ * negative value: in no list.  Built on the device into a CSR -- list_splits i64[n_lists + 1], list_rows i32[n_listed_rows],
+ * every list in ascending row order, the layout a function of list_of_row alone.  A value >= n_lists ->
+ * NANN_ERR_INDEX_OUT_OF_RANGE and nothing is created; null ix / out, null list_of_row with rows, n_lists < 0 ->
+ * NANN_ERR_BAD_ARGUMENT.  Creation synchronises `stream` once (it reads the sizes back); no search call reads anything back.
+ * nann_partition_info: n_lists, n_listed_rows, max_len (the longest list), device bytes held.  nann_partition_view: the CSR's
+ * device pointers (either may be NULL), valid until the handle is destroyed. */
+typedef struct nann_partition nann_partition;
+int nann_partition_create(const nann_index* ix, const int32_t* list_of_row, int32_t n_lists, nann_stream_t stream, nann_partition** out);
+void nann_partition_destroy(nann_partition* p);
+int nann_partition_info(const nann_partition* p, int64_t out[4]);
+int nann_partition_view(const nann_partition* p, const int64_t** list_splits, const int32_t** list_rows);
+
+/* nann_search_lists: probes is device i32[n_queries, n_probe], the lists query i names; a negative value is an unused slot.
+ * The other arguments are nann_search_candidates'.
+ * CONTRACT: query i's answer -- item ids, scores, out_index, out_pos, n_out, bit for bit -- is what nann_search_candidates
+ * returns for the list that is the concatenation of the lists it names, in slot order, each list in its stored order.  So:
+ * TopKV2 order, ties -> the lower position in that concatenation (out_pos); a list named twice is scored twice; a query with no
+ * lists, or only empty ones, gets n_out = 0 and status = 0; a slot >= n_lists fails THAT query -- status[i] =
+ * NANN_ERR_INDEX_OUT_OF_RANGE, n_out[i] = 0, a zeroed row -- and no other answer changes; a query's answer does not depend on
+ * the batch it is in.
+ * L2 and inner-product scorers, every d (64, 128, 256, 512) and row dtype (f16, bf16, f32); the score bits are nann_score's.
+ * An MLP scorer -> NANN_ERR_UNSUPPORTED (not built yet).
+ * Workspace: device, 256-byte aligned, nann_search_lists_workspace_bytes(...) bytes.  With S = max(k, n_probe x max_len), the
+ * longest concatenation a query can name, the queries are processed in chunks of min(128, 512 MiB / 4 S) inside the call; per
+ * query of a chunk the workspace holds 4 S bytes of scores, 8 k bytes per 16384 positions of S, and the plan: per (query, slot)
+ * pair at most one tile of 152 + 64 d bytes (the tile's destinations and its 16 transposed queries).
+ * Nothing is launched for: null ix, partition or scorer, n_queries < 0, n_probe < 0, k < 0, scorer and index disagreeing on d /
+ * dtype, a partition of another index, null probes with slots to read, null q / out_item_ids / status when there is work, a
+ * workspace off the 256-byte grid -> NANN_ERR_BAD_ARGUMENT; k > 1024, n_probe > NANN_LISTS_MAX_PROBE, an MLP scorer, S > 2^31 -
+ * 1025 -> NANN_ERR_UNSUPPORTED; a workspace smaller than nann_search_lists_workspace_bytes() -> NANN_ERR_CAPACITY; n_queries ==
+ * 0 or k == 0 -> NANN_OK, nothing written.  (Where several apply: in nann_search_candidates' order, the partition in the place
+ * of the nann_candidates struct.)  Asynchronous on `stream`, no host read-back, re-entrant on shared handles. */
+#define NANN_LISTS_MAX_PROBE 64
+int nann_search_lists_workspace_bytes(const nann_index* ix, const nann_partition* partition, const nann_scorer* scorer,
+                                      int64_t n_queries, int32_t n_probe, int32_t k, int64_t* nbytes);
+int nann_search_lists(const nann_index* ix, const nann_partition* partition, const nann_scorer* scorer, const float* q,
+                      int64_t n_queries, const int32_t* probes, int32_t n_probe, int32_t k, int64_t* out_item_ids,
+                      float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace,
+                      int64_t workspace_bytes, nann_stream_t stream);
+
 /* ---- candidate-list search under a model: nann_search_candidates for whatever model the node names ---------------------
  * nann_search_candidates with the serving signature's input, as nann_search_all_model is to nann_search_all: comm_seq_f16 is
  * f16[n_users, seq_len, E] (what nann_search_model_opt and nann_search_all_model take), `cand` the same nann_candidates with

@@ -86,6 +86,8 @@ SYMBOLS = [
     "nann_search_all_wide_workspace_bytes", "nann_search_all_wide",
     "nann_search_all_model_wide_workspace_bytes", "nann_search_all_model_wide",
     "nann_select_wide_workspace_bytes", "nann_select_wide",
+    "nann_partition_create", "nann_partition_destroy", "nann_partition_info", "nann_partition_view",
+    "nann_search_lists_workspace_bytes", "nann_search_lists",
 ]
 
 
@@ -407,6 +409,21 @@ def lib():
         L.nann_sq8_info.restype = C.c_int
         L.nann_sq8_view.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
         L.nann_sq8_view.restype = C.c_int
+        # (ix, list_of_row, n_lists, stream, *out) / (ix, partition, scorer, n_queries, n_probe, k, *nbytes) / (ix, partition, scorer,
+        #  q, n_queries, probes, n_probe, k, out_item_ids, out_scores, out_index, out_pos, n_out, status, workspace, bytes, stream)
+        L.nann_partition_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.nann_partition_create.restype = C.c_int
+        L.nann_partition_destroy.argtypes = [C.c_void_p]
+        L.nann_partition_destroy.restype = None
+        L.nann_partition_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.nann_partition_info.restype = C.c_int
+        L.nann_partition_view.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 2
+        L.nann_partition_view.restype = C.c_int
+        L.nann_search_lists_workspace_bytes.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+        L.nann_search_lists_workspace_bytes.restype = C.c_int
+        L.nann_search_lists.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + \
+                                       [C.c_int64, C.c_void_p]
+        L.nann_search_lists.restype = C.c_int
         L.nann_sq8_encode.argtypes = [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 4
         L.nann_sq8_encode.restype = C.c_int
         L.nann_search_all_sq8_workspace_bytes.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]

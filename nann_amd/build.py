@@ -22,7 +22,8 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 #   nann_mlp_d*.o      the MLP traversal per embedding dim; the resident-layer-2 kernels ride with d = 64
 #   nann_attn.o, nann_attn_split.o   the attention model, f32 and split-f16 form
 #   nann_scan.o        the exhaustive search, with the range and wide selections (nann_range.h, nann_wide.h) and the int8 code table, scan and
-#                      streamed and certified survivor passes (nann_sq8.h, nann_sq8_inst.hip); nann_scan_attn.o its scan under the attention model
+#                      streamed and certified survivor passes (nann_sq8.h, nann_sq8_inst.hip), and the shared-list search, whose scans are
+#                      ScanL2's (nann_lists.h, nann_lists_inst.hip); nann_scan_attn.o its scan under the attention model
 #   nann_filter.o      filtered retrieval, with the group cap (nann_groupcap.h) and the attribute predicates (nann_predicate.h)
 #   nann_cand.o        the candidate-list search, with the union and the fused top-k (nann_union.h, nann_fuse.h), the MMR
 #                      re-ranking (nann_mmr.h) and the user interests (nann_interests.h); nann_cand_attn.o its scorer under the
@@ -48,7 +49,7 @@ UNITS = [("nann_core.o", [("nann_ops.hip", {}), ("nann_hip.hip", {}), ("nann_sco
          ("nann_eval.o", [("nann_eval_inst.hip", {})]),
          ("nann_eval_lds.o", [("nann_eval_lds_inst.hip", {})]),
          ("nann_eval_win.o", [("nann_eval_win_inst.hip", {})]),
-         ("nann_scan.o", [("nann_scan_inst.hip", {}), ("nann_sq8_inst.hip", {}), _lean("NANN_SCORER_L2", "1", "l2_bf16")]),
+         ("nann_scan.o", [("nann_scan_inst.hip", {}), ("nann_sq8_inst.hip", {}), ("nann_lists_inst.hip", {}), _lean("NANN_SCORER_L2", "1", "l2_bf16")]),
          ("nann_scan_attn.o", [("nann_scan_attn_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "2", "NANN_IP_NAME": "f32"})]),
          ("nann_filter.o", [("nann_filter_inst.hip", {}), ("nann_ip_inst.hip", {"NANN_IP_DT": "0", "NANN_IP_NAME": "f16"})]),
          ("nann_cand.o", [("nann_cand_inst.hip", {}), _lean("NANN_SCORER_L2", "0", "l2_f16"), _lean("kScorerIp", "0", "ip_f16")]),
@@ -164,6 +165,9 @@ RULES = [
     # five times between them and hold a block's eight scores per thread in registers; a frame in private memory would add its traffic
     # to passes that are nothing but memory traffic.
     ("wide_scratch", r"k_wide_(hist|count|fill)", 0, None, "the wide selection"),
+    # The list scans of the shared-list search (k_lists_scan_l2 / k_lists_scan_ip, nann_lists.h) stage their rows as k_scan_l2 does,
+    # through the same ScanL2, and are held to the same.
+    ("lists_scan_scratch", r"k_lists_scan_(l2|ip)", 0, None, "the list scan kernel"),
 ]
 
 

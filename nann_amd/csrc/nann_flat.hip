@@ -12,7 +12,8 @@
 // nann_predicate.h) and inside the filtered exhaustive search (nann_search_all_where, nann_search_all_model_where); the int8
 // code table of an index (nann_sq8_create, ..) and the exhaustive search over it with an exact re-rank (nann_search_all_sq8;
 // kernels in nann_sq8.h), its certified form that returns nann_search_all's bits (nann_sq8_bounds, nann_search_all_sq8_exact) and
-// the certified range form that returns nann_search_all_range's (nann_search_all_range_sq8_exact).
+// the certified range form that returns nann_search_all_range's (nann_search_all_range_sq8_exact); the row lists over an index
+// (nann_partition_create, ..) and the shared-list search over them (nann_search_lists; kernels in nann_lists.h).
 //
 // A source of nann_core.o.  What it takes from the other host sources, and what the traversal's forms (nann_traverse.hip) take
 // from it -- resolve_filter, resolve_predicates, resolve_groups, resolve_diversity, mmr_index, union_check, fuse_shape_check,
@@ -35,6 +36,7 @@
 #include "nann_host.h"
 #include "nann_scan.h"
 #include "nann_cand.h"
+#include "nann_lists.h"
 #include "nann_union.h"
 #include "nann_fuse.h"
 #include "nann_groupcap.h"
@@ -589,6 +591,54 @@ static int flat_cand(const nann_index* ix, const nann_scorer* scorer, const nann
   }
   if (tab) projection_used(*by.cache, tab, st);
   return rc;
+}
+
+// ---- shared-list search (nann_lists.h): the top k of the concatenation of the partition's lists a query names ---------------
+// The candidate family's walk with the partition in the place of the nann_candidates struct.
+static int flat_lists_check(const nann_index* ix, const nann_partition* part, const nann_scorer* scorer, int64_t n, int32_t n_probe,
+                            int32_t k, const char* who, FlatBy* by) {
+  if (!part) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  const int rc = flat_check(ix, scorer, nullptr, n, k, true, 0, who, by);
+  if (rc) return rc;
+  if (n_probe < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_probe < 0");
+  if (by->kind != NANN_SCORER_L2 && by->kind != NANN_SCORER_IP)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": L2 and inner-product scorers only");
+  if (n_probe > NANN_LISTS_MAX_PROBE) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": n_probe <= " + std::to_string(NANN_LISTS_MAX_PROBE));
+  if (part->uid != ix->uid || part->n_items != ix->desc.n_items)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the partition was made over another index");
+  if ((long long)n_probe * part->max_len > 0x7fffffffll - 1024)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": positions in a query's concatenation are 32-bit");
+  return NANN_OK;
+}
+
+static int flat_lists(const nann_index* ix, const nann_partition* part, const nann_scorer* scorer, const float* q, int64_t n,
+                      const int32_t* probes, int32_t n_probe, int32_t k, int64_t* out_item_ids, float* out_scores,
+                      int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace,
+                      int64_t workspace_bytes, nann_stream_t stream, const char* who) {
+  FlatBy by;
+  int rc = flat_lists_check(ix, part, scorer, n, n_probe, k, who, &by);
+  if (rc) return rc;
+  if (n > 0 && n_probe > 0 && !probes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": probes is null while there are slots");
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!q || !out_item_ids || !status) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  const ListsLayout L = lists_layout((long long)part->max_len, ix->desc.d, (long long)n, n_probe, k);
+  rc = flat_workspace(workspace, workspace_bytes, L.total, who, "");
+  if (rc) return rc;
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  ListsArgs a = {};
+  flat_rows_of(ix, &a);
+  a.kind = by.kind;
+  a.cus = di.cus;
+  a.list_splits = part->list_splits;
+  a.list_rows = part->list_rows;
+  a.n_lists = part->n_lists;
+  a.max_len = (long long)part->max_len;
+  a.probes = probes;
+  a.n_probe = n_probe;
+  return launch_lists(a, L, q, (long long)n, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index, out_pos,
+                      n_out, status, as_stream(stream));
 }
 
 // ---- union top-k (nann_union.h): a user's n_lists result lists -> the k best distinct rows -----------------------------------
@@ -1680,6 +1730,93 @@ int nann_search_candidates_model(const nann_index* ix, const nann_model* m, cons
                                  const nann_search_options* options, nann_stream_t stream) {
   return flat_cand(ix, nullptr, m, comm_seq_f16, n_users, k, cand, out_item_ids, out_scores, out_index, out_pos, n_out, status,
                    workspace, workspace_bytes, options, stream, "nann_search_candidates_model");
+}
+
+// ---- row lists over an index's rows, and the search over them (nann_lists.h) ------------------------------------------------
+int nann_partition_create(const nann_index* ix, const int32_t* list_of_row, int32_t n_lists, nann_stream_t stream, nann_partition** out) {
+  const char* who = "nann_partition_create";
+  if (!ix || !out) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  *out = nullptr;
+  const int64_t n_items = ix->desc.n_items;
+  if (n_lists < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_lists < 0");
+  if (n_items > 0 && !list_of_row) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  hipStream_t st = as_stream(stream);
+  std::unique_ptr<nann_partition, void (*)(nann_partition*)> p(new nann_partition(), nann_partition_destroy);
+  p->uid = ix->uid;
+  p->n_items = n_items;
+  p->n_lists = n_lists;
+  // scratch of the build: the per-group counts / cursors and the sizes that are read back; freed before the call returns
+  const int groups = (int)lists_build_groups((long long)n_items, n_lists);
+  const size_t count_bytes = std::max<size_t>(4, (size_t)groups * (size_t)n_lists * 4);
+  struct Scratch {
+    int32_t* counts = nullptr;
+    long long* info = nullptr;
+    ~Scratch() {
+      if (counts) (void)hipFree(counts);
+      if (info) (void)hipFree(info);
+    }
+  } tmp;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->list_splits), ((size_t)n_lists + 1) * 8));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&tmp.counts), count_bytes));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&tmp.info), 32));
+  HIP_TRY(hipMemsetAsync(tmp.counts, 0, count_bytes, st));
+  HIP_TRY(hipMemsetAsync(tmp.info, 0, 32, st));
+  int rc = launch_lists_count(list_of_row, (long long)n_items, n_lists, groups, tmp.counts, tmp.info, st);
+  if (rc) return rc;
+  rc = launch_lists_splits(n_lists, groups, tmp.counts, p->list_splits, tmp.info, st);
+  if (rc) return rc;
+  long long info[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(info, tmp.info, 32, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // the one read-back: what sizes list_rows here and every workspace later
+  if (info[2] > 0)
+    return fail(NANN_ERR_INDEX_OUT_OF_RANGE, std::string(who) + ": " + std::to_string(info[2]) + " rows name a list >= n_lists");
+  p->n_listed = info[0];
+  p->max_len = info[1];
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->list_rows), (size_t)std::max<int64_t>(p->n_listed, 1) * 4));
+  p->bytes = (int64_t)(((size_t)n_lists + 1) * 8 + (size_t)std::max<int64_t>(p->n_listed, 1) * 4);
+  rc = launch_lists_fill(list_of_row, (long long)n_items, n_lists, groups, tmp.counts, p->list_splits, p->list_rows, st);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(st));  // (the scratch goes with this scope)
+  *out = p.release();
+  return NANN_OK;
+}
+void nann_partition_destroy(nann_partition* p) {
+  if (!p) return;
+  if (p->list_splits) (void)hipFree(p->list_splits);
+  if (p->list_rows) (void)hipFree(p->list_rows);
+  delete p;
+}
+int nann_partition_info(const nann_partition* p, int64_t out[4]) {
+  if (!p || !out) return fail(NANN_ERR_BAD_ARGUMENT, "nann_partition_info: null argument");
+  out[0] = p->n_lists;
+  out[1] = p->n_listed;
+  out[2] = p->max_len;
+  out[3] = p->bytes;
+  return NANN_OK;
+}
+int nann_partition_view(const nann_partition* p, const int64_t** list_splits, const int32_t** list_rows) {
+  if (!p) return fail(NANN_ERR_BAD_ARGUMENT, "nann_partition_view: null argument");
+  if (list_splits) *list_splits = p->list_splits;
+  if (list_rows) *list_rows = p->list_rows;
+  return NANN_OK;
+}
+int nann_search_lists_workspace_bytes(const nann_index* ix, const nann_partition* partition, const nann_scorer* scorer,
+                                      int64_t n_queries, int32_t n_probe, int32_t k, int64_t* nbytes) {
+  const char* who = "nann_search_lists_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  const int rc = flat_lists_check(ix, partition, scorer, n_queries, n_probe, k, who, &by);
+  if (rc) return rc;
+  *nbytes = n_queries == 0 || k == 0 ? 0 : (int64_t)lists_layout((long long)partition->max_len, ix->desc.d, (long long)n_queries, n_probe, k).total;
+  return NANN_OK;
+}
+int nann_search_lists(const nann_index* ix, const nann_partition* partition, const nann_scorer* scorer, const float* q,
+                      int64_t n_queries, const int32_t* probes, int32_t n_probe, int32_t k, int64_t* out_item_ids,
+                      float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace,
+                      int64_t workspace_bytes, nann_stream_t stream) {
+  return flat_lists(ix, partition, scorer, q, n_queries, probes, n_probe, k, out_item_ids, out_scores, out_index, out_pos, n_out,
+                    status, workspace, workspace_bytes, stream, "nann_search_lists");
 }
 
 // ---- the int8 code table and the search over it (nann_sq8.h) ---------------------------------------------------------------

@@ -169,6 +169,17 @@ struct nann_sq8_bounds {
   float* xhat = nullptr;      // f32[n_items]: >= scale_i sqrt(norm_i)
 };
 
+// row lists over an index's rows (nann_flat.hip; kernels in nann_lists.h).  Borrows the index: `uid` is the index's at creation.
+struct nann_partition {
+  uint64_t uid = 0;
+  int64_t n_items = 0;
+  int32_t n_lists = 0;
+  int64_t n_listed = 0, max_len = 0;
+  int64_t* list_splits = nullptr;  // i64[n_lists + 1]
+  int32_t* list_rows = nullptr;    // i32[n_listed], every list in ascending row order
+  int64_t bytes = 0;               // device bytes held
+};
+
 namespace nann {
 
 // ---- nann_hip.hip: who scores a call ---------------------------------------------------------------------------------------

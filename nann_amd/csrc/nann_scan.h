@@ -83,6 +83,9 @@ int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long lon
                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, hipStream_t st);
 // scores f32[n_q, n_items] of the attention model for the users whose kt / upad lie one after the other (nann_scan_attn_inst.hip)
 int launch_scan_attn(const ScanArgs& a, const float* kt, const float* upad, int n_q, float* scores, hipStream_t st);
+// step 2 on its own, over any score buffer f32[n_q, n_cols] (n_cols >= k): cand_* [n_q][scan_n_slabs(n_cols)][k], the lists
+// k_scan_merge takes.  The shared-list search (nann_lists.h) selects from its concatenation buffers with it.
+int launch_scan_slab_topk(const float* scores, long long n_cols, int n_q, int k, float* cand_scores, int32_t* cand_rows, hipStream_t st);
 
 }  // namespace nann
 
@@ -121,8 +124,14 @@ __global__ __launch_bounds__(256) void k_scan_transpose_q(const float* __restric
   }
 }
 
+// which table row stands at place r (0 .. 255) of a workgroup's block: rows row0 .. row0 + 255 of the table, the last one again
+// behind its end.  The hook of ScanL2 -- the shared-list scan (nann_lists.h) gathers through a row list instead.
+struct ScanRowsInOrder {
+  __device__ __forceinline__ long long at(int r, long long row0, long long n_items) const { return min(row0 + r, n_items - 1); }
+};
+
 // METRIC = MT_IP (k_scan_ip): the chunk accumulates acc = fma(q_k, x_k, acc) instead, in the same order and the same tree.
-template <int LPR, int DT, int TQ, int METRIC = MT_L2>
+template <int LPR, int DT, int TQ, int METRIC = MT_L2, class ROWS = ScanRowsInOrder>
 struct ScanL2 {
   static constexpr int NP = TQ / 2;                         // packed pairs of queries
   static constexpr int PJ = DT == DT_F32 ? 4 : 8;           // chunks of 8 elements per 128-byte panel
@@ -134,13 +143,14 @@ struct ScanL2 {
   long long n_items, row0;
   const f32x2* qt;  // this tile's queries: [D][NP] pairs
   unsigned char* lds;
+  ROWS rows;
 
   // rows row0 .. row0 + 255, bytes [panel * 128, +128) of each, into LDS: 8 coalesced 16-byte loads per thread, held in
   // eight NAMED registers across the barrier (an indexed array of HIP's uint4 was left in private memory by hipcc: every
   // staged byte went through scratch; the build refuses a k_scan_l2 with a scratch frame, build.py)
   __device__ __forceinline__ u32x4v stage_load(int panel, int i) const {
     const int g = i * kScanRows + (int)threadIdx.x, r = g >> 3, p = g & 7;
-    const long long row = min(row0 + r, n_items - 1);
+    const long long row = rows.at(r, row0, n_items);
     return *reinterpret_cast<const u32x4v*>(table + (size_t)row * kRowBytes + panel * kScanPanelBytes + p * 16);
   }
   __device__ __forceinline__ void stage_store(int i, u32x4v v) const {

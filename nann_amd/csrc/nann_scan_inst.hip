@@ -123,6 +123,13 @@ int launch_wide(const ScanWide& w, const float* scores, size_t limit, long long 
   return NANN_OK;
 }
 
+int launch_scan_slab_topk(const float* scores, long long n_cols, int n_q, int k, float* cand_scores, int32_t* cand_rows, hipStream_t st) {
+  const int n_slabs = scan_n_slabs(n_cols);
+  hipLaunchKernelGGL(k_scan_slab_topk, dim3((unsigned)((long long)n_q * n_slabs)), dim3(kNT), 0, st, scores, n_cols, n_slabs, k, cand_scores, cand_rows);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
 int launch_scan(const ScanArgs& a, const ScanLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
                 int64_t* out_item_ids, float* out_scores, int32_t* out_index, hipStream_t st) {
   float* scores = reinterpret_cast<float*>(ws + L.off_scores);

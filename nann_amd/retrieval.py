@@ -1101,6 +1101,127 @@ def search_candidates_model(index, model, comm_seq, candidates=None, candidate_i
                             "search_candidates_model", "user", (seq,))
 
 
+LISTS_MAX_PROBE = 64  # NANN_LISTS_MAX_PROBE: most lists a query of search_lists names
+
+
+class Partition:
+    """Row lists over an index's rows (nann_partition; make_partition): a CSR built on the device, every list in ascending row
+    order.  It borrows the index -- the object keeps it alive.  list_splits() i64[n_lists + 1] and list_rows()
+    i32[n_listed_rows] are torch views of its device memory, valid until release()."""
+
+    def __init__(self, index, list_of_row, n_lists):
+        self.index = index
+        self.handle = C.c_void_p(0)
+        lor = torch.as_tensor(list_of_row).to(device=index.device, dtype=torch.int32).contiguous()
+        assert lor.numel() == index.n_items, "one list number per row of the index"
+        with torch.cuda.device(index.device):
+            _check(lib().nann_partition_create(index.handle, _ptr(lor) if lor.numel() else None, int(n_lists), _stream(),
+                                               C.byref(self.handle)), "make_partition")
+        info = (C.c_int64 * 4)()
+        _check(lib().nann_partition_info(self.handle, info))
+        self.n_lists, self.n_listed_rows, self.max_len, self.nbytes = (int(v) for v in info)
+
+    def _view(self, which, shape, dtype):
+        if not self.handle.value:
+            raise ValueError("Partition: released")
+        p = [C.c_void_p(0), C.c_void_p(0)]
+        _check(lib().nann_partition_view(self.handle, C.byref(p[0]), C.byref(p[1])))
+        with torch.cuda.device(self.index.device):
+            return ops._wrap_device_pointer(p[which].value, shape, dtype, self)
+
+    def list_splits(self):
+        return self._view(0, (self.n_lists + 1,), torch.int64)
+
+    def list_rows(self):
+        return self._view(1, (self.n_listed_rows,), torch.int32)
+
+    def release(self):
+        """Free the lists' device memory (the views die with it).  Synchronise streams that still read it first."""
+        if self.handle.value:
+            lib().nann_partition_destroy(self.handle)
+            self.handle = C.c_void_p(0)
+
+    def __del__(self):
+        try:  # at interpreter shutdown the module globals may already be gone
+            if getattr(self, "handle", None) and self.handle.value:
+                lib().nann_partition_destroy(self.handle)
+                self.handle = C.c_void_p(0)
+        except Exception:
+            pass
+
+
+def make_partition(index, list_of_row, n_lists):
+    """Row lists over `index` (nann_partition_create): list_of_row[r] is the list of row r, a negative value "in no list"; a
+    value >= n_lists raises ops.NannError with status 5.  Built on torch's current stream, which the call synchronises once."""
+    return Partition(index, list_of_row, n_lists)
+
+
+def search_lists(index, partition, scorer, q, probes, k):
+    """Shared-list search (nann_search_lists): query b names the lists probes[b, :] of `partition` (a negative value: an unused
+    slot) and gets the exact top k of their concatenation -- slot order, each list in ascending row order -- with the bits,
+    order and counts of search_candidates on that concatenation -> CandidateResult (pos: positions in the concatenation;
+    status 5: the query names a list >= n_lists).  A list that many queries of the batch probe is fetched once per tile of 16
+    of them.  `scorer`: an L2 or inner-product ops.Scorer with q f32[B, d].  Asynchronous on torch's current stream."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    b, k = q.shape[0], int(k)
+    probes = torch.as_tensor(probes).to(device=dev, dtype=torch.int32).reshape(b, -1).contiguous()
+    n_probe = int(probes.shape[1])
+    kk = max(k, 0)
+    out_ids = torch.zeros((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.zeros((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.zeros((b, kk), dtype=torch.int32, device=dev)
+    out_pos = torch.zeros((b, kk), dtype=torch.int32, device=dev)
+    n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+    status = torch.zeros(b, dtype=torch.int32, device=dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_lists_workspace_bytes(index.handle, partition.handle, scorer.handle, b, n_probe, k, C.byref(nbytes)),
+           "search_lists")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_lists(index.handle, partition.handle, scorer.handle, _ptr(q), b,
+                                       _ptr(probes) if probes.numel() else None, n_probe, k, _ptr(out_ids), _ptr(out_scores),
+                                       _ptr(out_index), _ptr(out_pos), _ptr(n_out), _ptr(status), _ptr(ws), ws.numel(), _stream()),
+               "search_lists")
+    return CandidateResult(out_ids, out_scores, out_index, out_pos, n_out, status, ws, (probes, partition))
+
+
+def train_partition(index, n_lists, iters=10, seed=0):
+    """A coarse (IVF) partition of `index`: Lloyd's k-means on its rows, plain torch on the device -- plumbing around
+    make_partition, not a hot path.  Returns (partition, centroids f32[n_lists, d]); every row is in the list of its nearest centroid (L2)."""
+    x = index.item_embs.to(torch.float32)
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    cent = x[torch.randperm(x.shape[0], generator=g)[:n_lists].to(x.device)].clone()
+    assign = None
+    for _ in range(max(int(iters), 1)):
+        assign = _nearest_centroid(x, cent)
+        sums = torch.zeros_like(cent).index_add_(0, assign, x)
+        cnt = torch.bincount(assign, minlength=n_lists).to(torch.float32)
+        cent = torch.where(cnt[:, None] > 0, sums / cnt.clamp(min=1)[:, None], cent)
+    assign = _nearest_centroid(x, cent)
+    return make_partition(index, assign.to(torch.int32), n_lists), cent
+
+
+def _nearest_centroid(x, cent, block=65536):
+    out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
+    c2 = (cent * cent).sum(1)
+    for r0 in range(0, x.shape[0], block):
+        out[r0:r0 + block] = (c2[None, :] - 2.0 * x[r0:r0 + block] @ cent.T).argmin(1)
+    return out
+
+
+def search_partitioned(index, partition, centroids, scorer, q, k, n_probe):
+    """IVF search in one line: rank the centroids for every query in plain torch (by L2 distance, or by inner product under an
+    inner-product scorer), probe the n_probe best lists with search_lists -> CandidateResult."""
+    qf = q.to(device=index.device, dtype=torch.float32)
+    cent = centroids.to(device=index.device, dtype=torch.float32)
+    sim = qf @ cent.T
+    if getattr(scorer, "kind", "l2") != "ip":
+        sim = 2.0 * sim - (cent * cent).sum(1)[None, :]
+    probes = sim.topk(min(int(n_probe), cent.shape[0]), dim=1).indices.to(torch.int32)
+    return search_lists(index, partition, scorer, qf, probes, k)
+
+
 UNION_MAX_IN = _lib.UNION_MAX_IN  # most entries (n_lists * k_in, n_vec * F, n_vec * k) a user brings to a union
 
 

@@ -1501,6 +1501,50 @@ int nann_search_all_range_sq8_exact(const nann_index* ix, const nann_sq8* t, con
                                     int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
                                     const nann_search_options* options, nann_stream_t stream);
 
+/* ---- certified scalar-quantised search WITHOUT a score buffer: the two certified calls above at the streamed form's cost
+ * (DESIGN.md 4.26).  Added to ABI version 6: new symbols only.
+ * The survivor predicate of nann_search_all_sq8_exact is evaluated in the int8 scan itself, on the approximate score the scan has
+ * just formed -- the same bits -- so nothing of chunk x n_items elements is allocated, the code table is read twice (count, fill),
+ * and the chunk of queries does not shrink with n_items.
+ *
+ * nann_search_all_sq8_stream_exact, per query and without a host read-back:
+ *   (a) the cut.  n_sample as in nann_search_all_sq8_stream (clamp(sample_rows, fetch, n_items), 0 meaning max(65536,
+ *       ceil(n_items / 16))); nann_search_all_sq8's fetch stage and exact re-rank at `fetch` over the rows [0, n_sample); tau = the
+ *       exact score of the k-th entry.  It is the score of a row of the table, hence a lower bound of the true k-th best score;
+ *   (b) the rows of the WHOLE table that nann_search_all_sq8_exact's bound cannot put below tau -- the survivors, ties at tau among
+ *       them; out_n_survivors[q] = their number, whatever `cap`;
+ *   (c) out_certified[q] = 1 iff tau and the query's terms are finite and n_survivors[q] <= min(cap, n_items).  A certified query's
+ *       outputs are the exact top k of its survivors: nann_search_all's result BIT FOR BIT -- item ids, scores, index, TopKV2 order
+ *       with ties to the lower row.  An uncertified query's outputs are the exact top k of its sample's fetch list.
+ * A smaller sample gives a lower cut and more survivors -- about k * n_items / n_sample for rows in no particular order, plus what
+ * the bound's slack lets through -- never a wrong row.  Outputs, NULL rules and checks are nann_search_all_sq8_exact's (k <= fetch
+ * <= min(1024, n_items), cap < fetch or bounds from another table -> NANN_ERR_BAD_ARGUMENT, an MLP scorer or a cap beyond the
+ * longest candidate list -> NANN_ERR_UNSUPPORTED, ...), and sample_rows < 0 -> NANN_ERR_BAD_ARGUMENT.  n_queries == 0 or k == 0 ->
+ * NANN_OK, nothing written.  The workspace holds the sample's score buffer (chunk x n_sample), 4 bytes per (query of a chunk, 1024
+ * rows of the table) and chunk * min(cap, n_items) row numbers and exact scores.
+ *
+ * nann_search_all_range_sq8_stream_exact takes nann_search_all_range_sq8_exact's arguments and keeps its contract word for word --
+ * survivors at tau = thresholds[q], out_certified, out_n_survivors, the L2 rule for a finite threshold above +0, the empty segment of
+ * an uncertified query, the ragged outputs, every check -- with no sample, no fetch stage and no score buffer: only the cost differs.
+ * Both: workspace 256-byte aligned, smaller than the _workspace_bytes twin gives -> NANN_ERR_CAPACITY, bounded by a chunk of
+ * queries (128 whatever n_items; the top-k form: while n_sample <= 2^20).  A query's answer does not depend on its batch.
+ * Asynchronous on `stream`, re-entrant. */
+int nann_search_all_sq8_stream_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
+                                                     const nann_scorer* scorer, int64_t n_queries, int32_t fetch, int64_t sample_rows,
+                                                     int64_t cap, int32_t k, int64_t* nbytes);
+int nann_search_all_sq8_stream_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                     const float* q, int64_t n_queries, int32_t fetch, int64_t sample_rows, int64_t cap, int32_t k,
+                                     int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_certified,
+                                     int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
+                                     const nann_search_options* options, nann_stream_t stream);
+int nann_search_all_range_sq8_stream_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
+                                                           const nann_scorer* scorer, int64_t n_queries, int64_t cap, int64_t* nbytes);
+int nann_search_all_range_sq8_stream_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                           const float* q, int64_t n_queries, const float* thresholds, int64_t cap, int64_t capacity,
+                                           int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                           int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
+                                           const nann_search_options* options, nann_stream_t stream);
+
 /* ---- wide exhaustive search: the exact top k for k up to NANN_WIDE_MAX_K rows per query.  Added to ABI
  * version 6: new symbols only; nann_search_all and every call built on it keep their limit of 1024.
  * nann_search_all_wide / nann_search_all_model_wide take nann_search_all[_model]_where's arguments, checks and check order, with

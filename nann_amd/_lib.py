@@ -83,6 +83,8 @@ SYMBOLS = [
     "nann_sq8_bounds_create", "nann_sq8_bounds_destroy", "nann_sq8_bounds_view",
     "nann_search_all_sq8_exact_workspace_bytes", "nann_search_all_sq8_exact_layout", "nann_search_all_sq8_exact",
     "nann_search_all_range_sq8_exact_workspace_bytes", "nann_search_all_range_sq8_exact",
+    "nann_search_all_sq8_stream_exact_workspace_bytes", "nann_search_all_sq8_stream_exact",
+    "nann_search_all_range_sq8_stream_exact_workspace_bytes", "nann_search_all_range_sq8_stream_exact",
     "nann_search_all_wide_workspace_bytes", "nann_search_all_wide",
     "nann_search_all_model_wide_workspace_bytes", "nann_search_all_model_wide",
     "nann_select_wide_workspace_bytes", "nann_select_wide",
@@ -464,6 +466,18 @@ def lib():
         L.nann_search_all_range_sq8_exact.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 7 + \
                                                      [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
         L.nann_search_all_range_sq8_exact.restype = C.c_int
+        # the certified streamed forms: the top-k form takes sample_rows behind fetch, (ix, t, b, scorer, [q,] n_queries, fetch,
+        # sample_rows, cap, k, ...); the range form takes the range form's arguments
+        head = [C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32]
+        L.nann_search_all_sq8_stream_exact_workspace_bytes.argtypes = [C.c_void_p] * 4 + head + [C.POINTER(C.c_int64)]
+        L.nann_search_all_sq8_stream_exact_workspace_bytes.restype = C.c_int
+        L.nann_search_all_sq8_stream_exact.argtypes = [C.c_void_p] * 5 + head + [C.c_void_p] * 6 + \
+                                                      [C.c_int64, C.POINTER(SearchOptions), C.c_void_p]
+        L.nann_search_all_sq8_stream_exact.restype = C.c_int
+        L.nann_search_all_range_sq8_stream_exact_workspace_bytes.argtypes = L.nann_search_all_range_sq8_exact_workspace_bytes.argtypes
+        L.nann_search_all_range_sq8_stream_exact_workspace_bytes.restype = C.c_int
+        L.nann_search_all_range_sq8_stream_exact.argtypes = L.nann_search_all_range_sq8_exact.argtypes
+        L.nann_search_all_range_sq8_stream_exact.restype = C.c_int
         # (ix, scorer or NULL, model or NULL, n_queries, *plan)
         L.nann_search_eval_plan.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.POINTER(EvalPlan)]
         L.nann_search_eval_plan.restype = C.c_int

@@ -161,6 +161,9 @@ RULES = [
     # The range form of the certified int8 search (k_sq8_range_lists / k_sq8_range_count / k_sq8_range_fill, nann_sq8.h): the
     # selection holds a block's eight scores per thread in registers, as the survivor pass does, and is held to the same.
     ("sq8_range_scratch", r"k_sq8_range_(lists|count|fill)", 0, None, "the certified range selection"),
+    # The certified streamed int8 search (k_sq8_cert_count / k_sq8_cert_fill, nann_sq8.h): the streamed kernels with the survivor
+    # predicate in the epilogue.  B fragments live across the sweep, as there; the predicate's terms are a handful of registers.
+    ("sq8_cert_scratch", r"k_sq8_cert_(count|fill)", 0, None, "the certified streamed int8 scan"),
     # The streaming kernels of the wide selection (k_wide_hist / k_wide_count / k_wide_fill, nann_wide.h) read the chunk's score buffer
     # five times between them and hold a block's eight scores per thread in registers; a frame in private memory would add its traffic
     # to passes that are nothing but memory traffic.

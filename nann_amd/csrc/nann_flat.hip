@@ -12,7 +12,8 @@
 // nann_predicate.h) and inside the filtered exhaustive search (nann_search_all_where, nann_search_all_model_where); the int8
 // code table of an index (nann_sq8_create, ..) and the exhaustive search over it with an exact re-rank (nann_search_all_sq8;
 // kernels in nann_sq8.h), its certified form that returns nann_search_all's bits (nann_sq8_bounds, nann_search_all_sq8_exact) and
-// the certified range form that returns nann_search_all_range's (nann_search_all_range_sq8_exact); the row lists over an index
+// the certified range form that returns nann_search_all_range's (nann_search_all_range_sq8_exact), and both without a score buffer
+// (nann_search_all_sq8_stream_exact, nann_search_all_range_sq8_stream_exact); the row lists over an index
 // (nann_partition_create, ..) and the shared-list search over them (nann_search_lists; kernels in nann_lists.h).
 //
 // A source of nann_core.o.  What it takes from the other host sources, and what the traversal's forms (nann_traverse.hip) take
@@ -1271,6 +1272,169 @@ static int flat_range_sq8_exact(const nann_index* ix, const nann_sq8* t, const n
   return NANN_OK;
 }
 
+// ---- the certified streamed forms (nann_search_all_sq8_stream_exact, nann_search_all_range_sq8_stream_exact; nann_sq8.h, DESIGN.md
+// 4.26): the two certified forms above with the survivor predicate in the int8 scan's epilogue.  Nothing holds chunk * n_items.
+static Sq8Args flat_sq8_args(const nann_index* ix, const nann_sq8* t, const FlatBy& by) {
+  Sq8Args a = {};
+  a.codes = t->codes;
+  a.scales = t->scales;
+  a.norms = t->norms;
+  a.item_ids = ix->desc.item_ids;
+  a.n_items = (long long)ix->desc.n_items;
+  a.d = ix->desc.d;
+  a.metric = by.kind == NANN_SCORER_IP ? MT_IP : MT_L2;
+  return a;
+}
+
+// nann_search_all_sq8_exact's checks and the streamed form's sample_rows rule.  workspace: Sq8CertLayout; the chunk is the
+// ScanLayout's at n_sample rows.
+static int flat_sq8_cert_check(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer, int64_t n,
+                               int32_t fetch, int64_t sample_rows, int64_t cap, int32_t k, const char* who, FlatBy* by, ScanLayout* L,
+                               Sq8CertLayout* C) {
+  if (!b) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  int rc = flat_sq8_check(ix, t, scorer, n, fetch, k, who, by);
+  if (rc) return rc;
+  if (b->uid != ix->uid || b->serial != t->serial || b->n_items != t->n_items)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the bounds were made from another index or code table");
+  if (cap < fetch) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least fetch");
+  if (sample_rows < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": sample_rows must not be negative");
+  if (n == 0 || k == 0) return NANN_OK;  // (nothing to lay out; fetch >= k >= 1 below)
+  const long long n_items = (long long)ix->desc.n_items;
+  const long long n_sample = sq8_stream_sample((long long)sample_rows, fetch, n_items);
+  *L = scan_layout(n_sample, ix->desc.d, by->kind, (long long)n, fetch);
+  if (cap > cand_max_list(L->chunk))  // (a chunk's final lists are one candidate-list search)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": cap beyond the longest list of a candidate-list search, " +
+                                          std::to_string(cand_max_list(L->chunk)) + " at this chunk");
+  *C = sq8_cert_layout(*L, by->kind, ix->desc.d, fetch, (long long)cap, k, n_items, n_sample);
+  return NANN_OK;
+}
+
+static int flat_all_sq8_stream_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                     const float* q, int64_t n, int32_t fetch, int64_t sample_rows, int64_t cap, int32_t k,
+                                     int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_certified,
+                                     int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
+                                     const nann_search_options* options, nann_stream_t stream, const char* who) {
+  FlatBy by;
+  ScanLayout L;
+  Sq8CertLayout C;
+  int rc = flat_sq8_cert_check(ix, t, b, scorer, n, fetch, sample_rows, cap, k, who, &by, &L, &C);
+  if (rc) return rc;
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!q || !out_item_ids || !out_certified || !out_n_survivors) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  rc = check_options(options);
+  if (rc) return rc;
+  rc = flat_workspace(workspace, workspace_bytes, C.total, who, "");
+  if (rc) return rc;
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  const Sq8StreamLayout& X = C.X;
+  const Sq8Args a = flat_sq8_args(ix, t, by);
+  Sq8Args sample = a;  // the table's first n_sample rows
+  sample.n_items = X.n_sample;
+  CandArgs ca = {};
+  flat_rows_of(ix, &ca);
+  ca.cus = di.cus;
+  ca.kind = by.kind;
+  int32_t* status = reinterpret_cast<int32_t*>(ws + X.S.off_status);  // (always 0: the lists are the call's own)
+  for (int64_t c0 = 0; c0 < n; c0 += L.chunk) {
+    const int n_q = (int)std::min<int64_t>(L.chunk, n - c0);
+    const float* qc = q + (size_t)c0 * a.d;
+    // the cut: the fetch stage over the sample and the exact re-rank of its lists at k; the result stays in the workspace
+    rc = launch_sq8_fetch(sample, L, X.S, qc, n_q, fetch, ws, nullptr, nullptr, st);
+    if (rc) return rc;
+    ca.row_splits = reinterpret_cast<const int64_t*>(ws + X.S.off_splits);
+    ca.rows = reinterpret_cast<const int32_t*>(ws + X.S.off_sorted);
+    ca.n_cand = (long long)n_q * fetch;
+    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + X.S.off_cand,
+                     reinterpret_cast<int64_t*>(ws + C.off_a_ids), reinterpret_cast<float*>(ws + C.off_a_scores), nullptr, nullptr,
+                     nullptr, status, st);
+    if (rc) return rc;
+    // the survivors of every query over the whole table, or its sample's fetch list, as compact lists in ascending row order
+    rc = launch_sq8_cert(a, C, qc, b->err, b->xhat, n_q, fetch, k, ws, out_certified + c0, out_n_survivors + c0, st);
+    if (rc) return rc;
+    // the exact top k of the lists
+    ca.row_splits = reinterpret_cast<const int64_t*>(ws + X.off_xsplits);
+    ca.rows = reinterpret_cast<const int32_t*>(ws + X.off_rows);
+    ca.n_cand = (long long)n_q * X.cap;
+    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + X.S.off_cand, out_item_ids + (size_t)c0 * k,
+                     out_scores ? out_scores + (size_t)c0 * k : nullptr, out_index ? out_index + (size_t)c0 * k : nullptr, nullptr,
+                     nullptr, status, st);
+    if (rc) return rc;
+  }
+  return NANN_OK;
+}
+
+// nann_search_all_range_sq8_exact's checks.  workspace: a Sq8RangeLayout with no ScanLayout in front; the chunk is sq8_cert_range_chunk(n).
+static int flat_sq8_cert_range_check(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                     int64_t n, int64_t cap, const char* who, FlatBy* by, int* chunk, Sq8RangeLayout* R) {
+  if (ix && ix->desc.emb_dtype == NANN_F32) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": 16-bit rows (f16, bf16) only");
+  if (!b) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  int rc = flat_sq8_check(ix, t, scorer, n, 0, 0, who, by);  // (nann_search_all_range's checks of the shape: there is no k)
+  if (rc) return rc;
+  if (b->uid != ix->uid || b->serial != t->serial || b->n_items != t->n_items)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the bounds were made from another index or code table");
+  if (cap < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least 1");
+  *chunk = sq8_cert_range_chunk((long long)n);
+  if (cap > cand_max_list(*chunk))  // (a chunk's survivor lists are one candidate-list plan)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": cap beyond the longest list of a candidate-list search, " +
+                                          std::to_string(cand_max_list(*chunk)) + " at this chunk");
+  *R = sq8_cert_range_layout(*chunk, by->kind, ix->desc.d, (long long)cap, (long long)ix->desc.n_items);
+  return NANN_OK;
+}
+
+static int flat_range_sq8_stream_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                       const float* q, int64_t n, const float* thresholds, int64_t cap, int64_t capacity,
+                                       int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                       int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
+                                       const nann_search_options* options, nann_stream_t stream, const char* who) {
+  FlatBy by;
+  int chunk = 0;
+  Sq8RangeLayout R;
+  int rc = flat_sq8_cert_range_check(ix, t, b, scorer, n, cap, who, &by, &chunk, &R);
+  if (rc) return rc;
+  if (capacity < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": capacity < 0");
+  if (n == 0) return NANN_OK;
+  if (!q || !thresholds || !out_row_splits || !out_certified || !out_n_survivors)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (capacity > 0 && !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": out_item_ids is null while capacity > 0");
+  rc = check_options(options);
+  if (rc) return rc;
+  rc = flat_workspace(workspace, workspace_bytes, R.total, who, "");
+  if (rc) return rc;
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  const Sq8Args a = flat_sq8_args(ix, t, by);
+  CandArgs ca = {};
+  flat_rows_of(ix, &ca);
+  ca.cus = di.cus;
+  ca.kind = by.kind;
+  ca.row_splits = reinterpret_cast<const int64_t*>(ws + R.off_xsplits);
+  ca.rows = reinterpret_cast<const int32_t*>(ws + R.off_rows);
+  for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+    const int n_q = (int)std::min<int64_t>(chunk, n - c0);
+    const float* qc = q + (size_t)c0 * a.d;
+    // the survivors of every certified query as compact lists in ascending row order; an uncertified query's list is empty
+    rc = launch_sq8_cert_range(a, R, qc, thresholds + c0, b->err, b->xhat, n_q, ws, out_certified + c0, out_n_survivors + c0, st);
+    if (rc) return rc;
+    // their exact scores, by list position
+    ca.n_cand = (long long)n_q * R.cap;
+    const CandLayout CL = cand_layout(by.kind, n_q, ca.n_cand);
+    rc = launch_cand_scores(ca, CL, qc, n_q, ws + R.off_cand, st);
+    if (rc) return rc;
+    // the rows at or above the threshold, into the caller's ragged outputs
+    rc = launch_sq8_range_select(a, R, R.off_cand + CL.off_scores, thresholds, (long long)c0, n_q, (long long)capacity, ws,
+                                 out_row_splits, out_item_ids, out_scores, out_index, st);
+    if (rc) return rc;
+  }
+  return NANN_OK;
+}
+
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
 extern "C" {
 
@@ -2008,6 +2172,51 @@ int nann_search_all_range_sq8_exact(const nann_index* ix, const nann_sq8* t, con
   return flat_range_sq8_exact(ix, t, b, scorer, q, n_queries, thresholds, cap, capacity, out_row_splits, out_item_ids, out_scores,
                               out_index, out_certified, out_n_survivors, workspace, workspace_bytes, options, stream,
                               "nann_search_all_range_sq8_exact");
+}
+
+// ---- the certified streamed forms (nann_sq8.h) ---------------------------------------------------------------------
+int nann_search_all_sq8_stream_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
+                                                     const nann_scorer* scorer, int64_t n_queries, int32_t fetch, int64_t sample_rows,
+                                                     int64_t cap, int32_t k, int64_t* nbytes) {
+  const char* who = "nann_search_all_sq8_stream_exact_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  ScanLayout L;
+  Sq8CertLayout C;
+  const int rc = flat_sq8_cert_check(ix, t, b, scorer, n_queries, fetch, sample_rows, cap, k, who, &by, &L, &C);
+  if (rc) return rc;
+  *nbytes = n_queries == 0 || k == 0 ? 0 : (int64_t)C.total;
+  return NANN_OK;
+}
+int nann_search_all_sq8_stream_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                     const float* q, int64_t n_queries, int32_t fetch, int64_t sample_rows, int64_t cap, int32_t k,
+                                     int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_certified,
+                                     int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
+                                     const nann_search_options* options, nann_stream_t stream) {
+  return flat_all_sq8_stream_exact(ix, t, b, scorer, q, n_queries, fetch, sample_rows, cap, k, out_item_ids, out_scores, out_index,
+                                   out_certified, out_n_survivors, workspace, workspace_bytes, options, stream,
+                                   "nann_search_all_sq8_stream_exact");
+}
+int nann_search_all_range_sq8_stream_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
+                                                           const nann_scorer* scorer, int64_t n_queries, int64_t cap, int64_t* nbytes) {
+  const char* who = "nann_search_all_range_sq8_stream_exact_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  int chunk = 0;
+  Sq8RangeLayout R;
+  const int rc = flat_sq8_cert_range_check(ix, t, b, scorer, n_queries, cap, who, &by, &chunk, &R);
+  if (rc) return rc;
+  *nbytes = n_queries == 0 ? 0 : (int64_t)R.total;
+  return NANN_OK;
+}
+int nann_search_all_range_sq8_stream_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                                           const float* q, int64_t n_queries, const float* thresholds, int64_t cap, int64_t capacity,
+                                           int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
+                                           int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
+                                           const nann_search_options* options, nann_stream_t stream) {
+  return flat_range_sq8_stream_exact(ix, t, b, scorer, q, n_queries, thresholds, cap, capacity, out_row_splits, out_item_ids, out_scores,
+                                     out_index, out_certified, out_n_survivors, workspace, workspace_bytes, options, stream,
+                                     "nann_search_all_range_sq8_stream_exact");
 }
 
 }  // extern "C"

@@ -196,6 +196,42 @@ int launch_sq8_range_select(const Sq8Args& a, const Sq8RangeLayout& R, size_t of
                             long long capacity, unsigned char* ws, int64_t* row_splits, int64_t* out_item_ids, float* out_scores,
                             int32_t* out_index, hipStream_t st);
 
+
+// ---- the certified streamed forms (nann_search_all_sq8_stream_exact, nann_search_all_range_sq8_stream_exact):
+// the certified forms' results without their score buffer of chunk x n_items elements.  The survivor predicate is a function of the
+// approximate score, the row's err and xhat, the query's terms and G; the scan's accumulators hold the score, so the predicate
+// runs in the scan's epilogue and the survivor pass is the streamed form's, with sq8_survives in the place of a(q, row) >= cut:
+//   k_sq8_cert_count   k_sq8_stream_count's grid, LDS columns and single writing lane; the chunk's Sq8QTerms lie in LDS in the place
+//                      of cut[]; a lane loads err and xhat of its row once per 32-row group
+//   k_range_scan, then k_sq8_exact_lists (top-k form) or k_sq8_range_lists (range form), both as they are
+//   k_sq8_cert_fill    k_sq8_stream_fill's two phases; a query whose terms[].certified is 0 gets no store
+// The top-k form takes its cut from a SAMPLE, as the streamed form does: the fetch stage over rows [0, n_sample) and the exact
+// re-rank of its lists at k; tau = the exact score of the k-th entry, the score of a real row, hence a lower bound of the table's
+// k-th best exact score -- all the lemma of 4.21 asks of a cut.  The range form's cut is the caller's threshold: no sample, no fetch.
+// workspace of the top-k form: [Sq8StreamLayout (the sample's ScanLayout in front) | what follows]
+struct Sq8CertLayout {
+  Sq8StreamLayout X;                    // the sample's fetch stage, the block counts, the compact row_splits and the final lists
+  size_t off_qerr, off_qxhat;           // f32[chunk] each: the chunk's queries through k_sq8_row_err
+  size_t off_a_ids, off_a_scores;       // the re-ranked sample lists: i64[chunk, k], f32[chunk, k]
+  size_t off_terms;                     // Sq8QTerms[chunk]
+  size_t total;
+};
+// L: scan_layout at n_sample rows
+Sq8CertLayout sq8_cert_layout(const ScanLayout& L, int kind, int d, int fetch, long long cap, int k, long long n_items, long long n_sample);
+// behind a chunk's launch_sq8_fetch over the sample and its launch_cand at k into off_a_* (a: the WHOLE table): the query terms,
+// count, scan, k_sq8_exact_lists, fill.  out_*: this chunk's slice.
+int launch_sq8_cert(const Sq8Args& a, const Sq8CertLayout& C, const float* q, const float* err, const float* xhat, int n_q, int fetch,
+                    int k, unsigned char* ws, int32_t* out_certified, int32_t* out_n_survivors, hipStream_t st);
+// the range form: its chunk, min(n_queries, 128) whatever n_items, and its workspace, a Sq8RangeLayout with nothing in front whose
+// n_blocks counts the blocks of the int8 scan's workgroups (1024 rows)
+int sq8_cert_range_chunk(long long n_queries);
+Sq8RangeLayout sq8_cert_range_layout(int chunk, int kind, int d, long long cap, long long n_items);
+// One chunk, up to the survivor lists: the queries' codes and terms at thr, count, scan, k_sq8_range_lists, fill.  What follows
+// is the range form's: launch_cand_scores and launch_sq8_range_select.
+int launch_sq8_cert_range(const Sq8Args& a, const Sq8RangeLayout& R, const float* q, const float* thr, const float* err,
+                          const float* xhat, int n_q, unsigned char* ws, int32_t* out_certified, int32_t* out_n_survivors,
+                          hipStream_t st);
+
 }  // namespace nann
 
 #ifdef NANN_SQ8_IMPL  // the kernels: nann_sq8_inst.hip only (nann_flat.hip takes the declarations above)
@@ -468,6 +504,41 @@ __global__ __launch_bounds__(kSq8NT) void k_sq8_stream_lists(const int32_t* __re
   if (tid == n_q - 1) xsplits[n_q] = sum + l;
 }
 
+// Phase 2 of a fill kernel (k_sq8_stream_fill, k_sq8_cert_fill), behind the barrier that publishes mask[query][kSq8MaskPitch]:
+// wavefront w takes the query pairs w, w + 4, ...; half-wave h the query 2 pair + h, lane r its group r.  live(qi): the query
+// has a list to fill.  The list's length is xsplits[qi + 1] - xsplits[qi]; no store goes beyond it.
+template <class Live>
+__device__ __forceinline__ void sq8_masks_to_lists(const unsigned* mask, int n_q, int n_blocks, const int32_t* __restrict__ prefix,
+                                                   const long long* __restrict__ xsplits, int32_t* __restrict__ rows, Live live) {
+  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const long long wg_row0 = (long long)blockIdx.x * kSq8RowsPerWg;
+  for (int pair = tid >> 6; 2 * pair < n_q; pair += kSq8NT / 64) {
+    const int qi = 2 * pair + h;
+    unsigned m = qi < n_q && live(qi) ? mask[qi * kSq8MaskPitch + r] : 0u;
+    if (__ballot(m != 0u) == 0) continue;  // (uniform)
+    const int c = __popc(m);
+    int below = c;  // inclusive scan over the half-wave's 32 lanes, then exclusive
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) {
+      const int v = __shfl_up(below, o, 32);
+      if (r >= o) below += v;
+    }
+    below -= c;
+    if (m != 0u) {
+      const long long q_begin = xsplits[qi];
+      const long long room = xsplits[qi + 1] - q_begin;  // the list's length
+      long long pos = (long long)prefix[(size_t)qi * n_blocks + blockIdx.x] + below;
+      const long long row0 = wg_row0 + 32 * r;
+      do {
+        const int b = __ffs(m) - 1;
+        if (pos >= 0 && pos < room) rows[q_begin + pos] = (int32_t)(row0 + b);  // the guard of the store
+        ++pos;
+        m &= m - 1u;
+      } while (m != 0u);
+    }
+  }
+}
+
 // prefix = counts behind k_range_scan.  rows: the lists at xsplits.
 template <int NS, int METRIC>
 __global__ __launch_bounds__(kSq8NT) void k_sq8_stream_fill(const int8_t* __restrict__ codes, const float* __restrict__ scales,
@@ -492,34 +563,7 @@ __global__ __launch_bounds__(kSq8NT) void k_sq8_stream_fill(const int8_t* __rest
                              [&](int qi, unsigned m) { mask[qi * kSq8MaskPitch + group] = m; });
   });
   __syncthreads();
-  // phase 2: wavefront w takes the query pairs w, w + 4, ...; half-wave h the query 2 pair + h, lane r its group r
-  const int lane = tid & 63, r = lane & 31, h = lane >> 5;
-  const long long wg_row0 = (long long)blockIdx.x * kSq8RowsPerWg;
-  for (int pair = tid >> 6; 2 * pair < n_q; pair += kSq8NT / 64) {
-    const int qi = 2 * pair + h;
-    unsigned m = qi < n_q ? mask[qi * kSq8MaskPitch + r] : 0u;
-    if (__ballot(m != 0u) == 0) continue;  // (uniform)
-    const int c = __popc(m);
-    int below = c;  // inclusive scan over the half-wave's 32 lanes, then exclusive
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-      const int v = __shfl_up(below, o, 32);
-      if (r >= o) below += v;
-    }
-    below -= c;
-    if (m != 0u) {
-      const long long q_begin = xsplits[qi];
-      const long long room = xsplits[qi + 1] - q_begin;  // min(total, cap): the list's length
-      long long pos = (long long)prefix[(size_t)qi * n_blocks + blockIdx.x] + below;
-      const long long row0 = wg_row0 + 32 * r;
-      do {
-        const int b = __ffs(m) - 1;
-        if (pos >= 0 && pos < room) rows[q_begin + pos] = (int32_t)(row0 + b);  // the guard of the store
-        ++pos;
-        m &= m - 1u;
-      } while (m != 0u);
-    }
-  }
+  sq8_masks_to_lists(mask, n_q, n_blocks, prefix, xsplits, rows, [](int) { return true; });
 }
 
 // ---- the certified form ---------------------------------------------------------------------------------------------------
@@ -753,6 +797,114 @@ __global__ __launch_bounds__(kRangeNT) void k_sq8_surv_fill(const float* __restr
       ++pos;
     }
   }
+}
+
+// ---- the certified streamed forms: the survivor predicate in the epilogue of the int8 scan, no score buffer -------------------
+// dynamic LDS behind the front end's: the chunk's query terms Sq8QTerms[chunk] in the place of the streamed kernels' cut[], then
+// count -- cnt i32[wavefronts][chunk]; fill -- mask u32[chunk][pitch]
+static_assert(sizeof(Sq8QTerms) == 32, "two 16-byte pieces per query");
+__host__ __device__ constexpr int sq8_cert_count_lds(int d) { return sq8_scan_lds(d) + kScanMaxChunk * (32 + 4 * (kSq8NT / 64)); }
+__host__ __device__ constexpr int sq8_cert_fill_lds(int d) { return sq8_scan_lds(d) + kScanMaxChunk * (32 + 4 * kSq8MaskPitch); }
+
+// the chunk's terms into LDS, zeros behind n_q (their ballots are gated by qi < n_q); published by the front end's barrier
+__device__ __forceinline__ void sq8_cert_stage_terms(Sq8QTerms* lds, const Sq8QTerms* __restrict__ terms, int n_q) {
+  for (int i = threadIdx.x; i < kScanMaxChunk * 2; i += kSq8NT) {
+    i32x4v v = {0, 0, 0, 0};
+    if ((i >> 1) < n_q) v = reinterpret_cast<const i32x4v*>(terms)[i];
+    reinterpret_cast<i32x4v*>(lds)[i] = v;
+  }
+}
+
+// The epilogue of both kernels: sq8_stream_masks with sq8_survives in the place of the comparison with a cut.  e, xh: err and xhat
+// of the lane's row.  Whatever the terms hold -- ok or not -- goes through the predicate, as in k_sq8_surv_count.
+template <int METRIC, class Put>
+__device__ __forceinline__ void sq8_cert_masks(const float* qs, const float* qa, const Sq8QTerms* terms, float g, long long row,
+                                               long long n_items, int t, int n_q, const i32x16v& acc, float sx, float bx, float e,
+                                               float xh, Put put) {
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const bool in = row < n_items;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int qi = sq8_query_of(t, j, h);  // < kScanMaxChunk: qs, qa, terms hold every query of a tile
+    const float sc = sq8_score<METRIC>(qs[qi], qa[qi], sx, bx, acc[j]);
+    const Sq8QTerms tq = terms[qi];
+    const unsigned long long m = __ballot(in && qi < n_q && sq8_survives<METRIC>(sc, e, xh, tq, g));
+    if (m == 0) continue;  // (uniform; nearly every ballot of a large table)
+    const unsigned mine = h ? (unsigned)(m >> 32) : (unsigned)m;
+    if (r == 0 && mine != 0) put(qi, mine);
+  }
+}
+
+// k_sq8_stream_count's shape.  err, xhat: the rows' terms; a lane loads its row's pair once per 32-row group, at the group's first
+// query tile.  counts i32[n_q, n_blocks] = the survivors of sq8_survives in the block, what k_sq8_surv_count counts from a buffer.
+template <int NS, int METRIC>
+__global__ __launch_bounds__(kSq8NT) void k_sq8_cert_count(const int8_t* __restrict__ codes, const float* __restrict__ scales,
+                                                           const int32_t* __restrict__ norms, long long n_items,
+                                                           const int8_t* __restrict__ qcodes, const float* __restrict__ qscales,
+                                                           const int32_t* __restrict__ qnorms, int n_q, const float* __restrict__ err,
+                                                           const float* __restrict__ xhat, const Sq8QTerms* __restrict__ terms_src,
+                                                           float g, int n_blocks, int32_t* __restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const float* qs = reinterpret_cast<const float*>(smem + kScanMaxChunk * (NS * 32 + kSq8QPad));
+  const float* qa = qs + kScanMaxChunk;
+  Sq8QTerms* terms = reinterpret_cast<Sq8QTerms*>(smem + sq8_scan_lds(NS * 32));
+  int* cnt = reinterpret_cast<int*>(terms + kScanMaxChunk);  // [wavefront][query]
+  const int tid = threadIdx.x;
+  sq8_cert_stage_terms(terms, terms_src, n_q);
+  for (int i = tid; i < kScanMaxChunk * (kSq8NT / 64); i += kSq8NT) cnt[i] = 0;
+  int* mine = cnt + (tid >> 6) * kScanMaxChunk;
+  float e = 0.0f, xh = 0.0f;
+  sq8_scan_front<NS, METRIC>(smem, codes, scales, norms, n_items, qcodes, qscales, qnorms, n_q,
+                             [&](int, long long row, int t, const i32x16v& acc, float sx, float bx) {
+    if (t == 0) {  // (a row behind the table: the last one again, as the front end loads it; never counted)
+      const long long at = row < n_items ? row : n_items - 1;
+      e = err[at];
+      xh = xhat[at];
+    }
+    // (query qi of this wavefront's column is always written by the same lane: a plain read-modify-write)
+    sq8_cert_masks<METRIC>(qs, qa, terms, g, row, n_items, t, n_q, acc, sx, bx, e, xh, [&](int qi, unsigned m) { mine[qi] += __popc(m); });
+  });
+  __syncthreads();
+  for (int qi = tid; qi < n_q; qi += kSq8NT) {
+    int c = 0;
+#pragma unroll
+    for (int w = 0; w < kSq8NT / 64; ++w) c += cnt[w * kScanMaxChunk + qi];
+    counts[(size_t)qi * n_blocks + blockIdx.x] = c;
+  }
+}
+
+// k_sq8_stream_fill's shape.  terms_src[].certified as the lists kernel (k_sq8_exact_lists, k_sq8_range_lists) has left it: a
+// query without it gets no store, as in k_sq8_surv_fill -- its list, if it has one, is its fetch list.
+template <int NS, int METRIC>
+__global__ __launch_bounds__(kSq8NT) void k_sq8_cert_fill(const int8_t* __restrict__ codes, const float* __restrict__ scales,
+                                                          const int32_t* __restrict__ norms, long long n_items,
+                                                          const int8_t* __restrict__ qcodes, const float* __restrict__ qscales,
+                                                          const int32_t* __restrict__ qnorms, int n_q, const float* __restrict__ err,
+                                                          const float* __restrict__ xhat, const Sq8QTerms* __restrict__ terms_src,
+                                                          float g, int n_blocks, const int32_t* __restrict__ prefix,
+                                                          const long long* __restrict__ xsplits, int32_t* __restrict__ rows) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const float* qs = reinterpret_cast<const float*>(smem + kScanMaxChunk * (NS * 32 + kSq8QPad));
+  const float* qa = qs + kScanMaxChunk;
+  Sq8QTerms* terms = reinterpret_cast<Sq8QTerms*>(smem + sq8_scan_lds(NS * 32));
+  unsigned* mask = reinterpret_cast<unsigned*>(terms + kScanMaxChunk);  // [query][kSq8MaskPitch]
+  const int tid = threadIdx.x;
+  sq8_cert_stage_terms(terms, terms_src, n_q);
+  for (int i = tid; i < kScanMaxChunk * kSq8MaskPitch; i += kSq8NT) mask[i] = 0u;  // (a group behind the table is never visited)
+  float e = 0.0f, xh = 0.0f;
+  // phase 1: entry (query, group) is written once, by the lane that holds the query's half of the group's ballot
+  sq8_scan_front<NS, METRIC>(smem, codes, scales, norms, n_items, qcodes, qscales, qnorms, n_q,
+                             [&](int group, long long row, int t, const i32x16v& acc, float sx, float bx) {
+    if (t == 0) {
+      const long long at = row < n_items ? row : n_items - 1;
+      e = err[at];
+      xh = xhat[at];
+    }
+    sq8_cert_masks<METRIC>(qs, qa, terms, g, row, n_items, t, n_q, acc, sx, bx, e, xh,
+                           [&](int qi, unsigned m) { mask[qi * kSq8MaskPitch + group] = m; });
+  });
+  __syncthreads();
+  sq8_masks_to_lists(mask, n_q, n_blocks, prefix, xsplits, rows, [&](int qi) { return terms[qi].certified != 0; });
 }
 
 // ---- the certified range form ---------------------------------------------------------------------------------------------

@@ -2,8 +2,9 @@
 // int8 MFMA scan for every (d, metric), the row sort; workspace layout and the launch sequence of a chunk's fetch stage; the
 // streamed form's count / lists / fill pass (k_sq8_stream_*, around k_range_scan); the certified form's row-error kernel, query
 // terms and survivor pass (count, k_range_scan, lists, fill); the certified range form's lists kernel and ragged selection (count,
-// k_range_scan, k_range_splits, fill).  Rides in nann_scan.o behind nann_scan_inst.hip: the slab top-k and the merge it launches
-// are that file's kernels.
+// k_range_scan, k_range_splits, fill); the certified streamed forms' survivor pass in the scan's epilogue (k_sq8_cert_count /
+// k_sq8_cert_fill around the same scan and lists kernels).  Rides in nann_scan.o behind nann_scan_inst.hip: the slab top-k and the
+// merge it launches are that file's kernels.
 #ifndef NANN_SCAN_IMPL
 #define NANN_SCAN_IMPL
 #endif
@@ -266,25 +267,30 @@ int launch_sq8_survivors(const Sq8Args& a, const ScanLayout& L, const Sq8ExactLa
 }
 
 // ---- the certified range form ---------------------------------------------------------------------------------------------
-Sq8RangeLayout sq8_range_layout(const ScanLayout& L, int kind, int d, long long cap, long long n_items) {
+// base: the bytes in front (a ScanLayout, or nothing); n_blocks: the blocks of a query in the survivor pass
+static Sq8RangeLayout sq8_range_layout_at(size_t base, int chunk, int n_blocks, int kind, int d, long long cap, long long n_items) {
   Sq8RangeLayout R = {};
-  const size_t c = (size_t)L.chunk;
+  const size_t c = (size_t)chunk;
   R.cap = std::min(cap, n_items);
-  R.n_blocks = range_n_blocks(n_items);
+  R.n_blocks = n_blocks;
   R.n_lblocks = range_n_blocks(R.cap);
-  R.off_qcodes = sq8_up256(L.total);
+  R.off_qcodes = sq8_up256(base);
   R.off_qscales = R.off_qcodes + sq8_up256(c * d);
   R.off_qnorms = R.off_qscales + sq8_up256(c * 4);
   R.off_qerr = R.off_qnorms + sq8_up256(c * 4);
   R.off_qxhat = R.off_qerr + sq8_up256(c * 4);
   R.off_terms = R.off_qxhat + sq8_up256(c * 4);
   R.off_counts = R.off_terms + sq8_up256(c * sizeof(Sq8QTerms));
-  R.off_xsplits = R.off_counts + range_counts_bytes(L.chunk, n_items);
+  R.off_xsplits = R.off_counts + sq8_up256(c * ((size_t)n_blocks + 1) * 4);
   R.off_rows = R.off_xsplits + sq8_up256((c + 1) * 8);
   R.off_cand = R.off_rows + sq8_up256(c * (size_t)R.cap * 4);
-  R.off_rcounts = R.off_cand + sq8_up256(cand_layout(kind, L.chunk, (long long)L.chunk * R.cap).total);
-  R.total = R.off_rcounts + range_counts_bytes(L.chunk, R.cap);
+  R.off_rcounts = R.off_cand + sq8_up256(cand_layout(kind, chunk, (long long)chunk * R.cap).total);
+  R.total = R.off_rcounts + range_counts_bytes(chunk, R.cap);
   return R;
+}
+
+Sq8RangeLayout sq8_range_layout(const ScanLayout& L, int kind, int d, long long cap, long long n_items) {
+  return sq8_range_layout_at(L.total, L.chunk, range_n_blocks(n_items), kind, d, cap, n_items);
 }
 
 template <int METRIC>
@@ -356,6 +362,140 @@ int launch_sq8_range_select(const Sq8Args& a, const Sq8RangeLayout& R, size_t of
     NANN_HIP_TRY(hipGetLastError());
   }
   return NANN_OK;
+}
+
+// ---- the certified streamed forms -----------------------------------------------------------------------------------------
+Sq8CertLayout sq8_cert_layout(const ScanLayout& L, int kind, int d, int fetch, long long cap, int k, long long n_items, long long n_sample) {
+  Sq8CertLayout C = {};
+  const size_t c = (size_t)L.chunk;
+  // its CandLayout serves both candidate-list searches of a chunk: the sample's fetch lists, then the final lists (fetch <= cap)
+  C.X = sq8_stream_layout(L, kind, d, fetch, cap, n_items, n_sample);
+  C.off_qerr = C.X.total;
+  C.off_qxhat = C.off_qerr + sq8_up256(c * 4);
+  C.off_a_ids = C.off_qxhat + sq8_up256(c * 4);
+  C.off_a_scores = C.off_a_ids + sq8_up256(c * (size_t)k * 8);
+  C.off_terms = C.off_a_scores + sq8_up256(c * (size_t)k * 4);
+  C.total = C.off_terms + sq8_up256(c * sizeof(Sq8QTerms));
+  return C;
+}
+
+int sq8_cert_range_chunk(long long n_queries) { return (int)std::max<long long>(1, std::min<long long>(kScanMaxChunk, n_queries)); }
+
+Sq8RangeLayout sq8_cert_range_layout(int chunk, int kind, int d, long long cap, long long n_items) {
+  return sq8_range_layout_at(0, chunk, (int)((n_items + kSq8RowsPerWg - 1) / kSq8RowsPerWg), kind, d, cap, n_items);
+}
+
+namespace {
+// what the survivor pass of a chunk reads and writes, top-k or range
+struct Sq8CertPass {
+  const int8_t* qcodes;
+  const float* qscales;
+  const int32_t* qnorms;
+  const float *err, *xhat;  // the rows' terms
+  Sq8QTerms* terms;
+  int n_blocks;
+  int32_t* counts;          // i32[n_q, n_blocks], the totals behind
+  long long* xsplits;
+  int32_t* rows;
+};
+
+// count, scan, lists(totals) -- the form's own kernel between the two passes --, fill
+template <int NS, int METRIC, class Lists>
+int launch_sq8_cert_as(const Sq8Args& a, const Sq8CertPass& p, int n_q, Lists lists, hipStream_t st) {
+  auto count = k_sq8_cert_count<NS, METRIC>;
+  auto fill = k_sq8_cert_fill<NS, METRIC>;
+  constexpr int lds_count = sq8_cert_count_lds(NS * 32), lds_fill = sq8_cert_fill_lds(NS * 32);
+  static_assert(lds_count <= 80 * 1024, "k_sq8_cert_count: two workgroups per CU");
+  static_assert(lds_fill <= 160 * 1024 && (NS == 16 || lds_fill <= 80 * 1024), "k_sq8_cert_fill: two workgroups per CU up to d = 256, one at 512");
+  static_assert(lds_fill <= sq8_stream_fill_lds(NS * 32) + 4096, "the streamed fill's footprint and 4 KB of terms");
+  if (lds_count > 64 * 1024)  // (only d = 512 is beyond the default limit)
+    NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(count), hipFuncAttributeMaxDynamicSharedMemorySize, lds_count));
+  if (lds_fill > 64 * 1024)
+    NANN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, lds_fill));
+  const float g = sq8_gamma(a.d);
+  int32_t* totals = p.counts + (size_t)n_q * p.n_blocks;
+  const dim3 grid((unsigned)p.n_blocks);
+  hipLaunchKernelGGL(count, grid, dim3(kSq8NT), (size_t)lds_count, st, a.codes, a.scales, a.norms, a.n_items, p.qcodes, p.qscales,
+                     p.qnorms, n_q, p.err, p.xhat, p.terms, g, p.n_blocks, p.counts);
+  NANN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_range_scan, dim3((unsigned)n_q), dim3(kRangeNT), 0, st, p.counts, p.n_blocks, totals);
+  NANN_HIP_TRY(hipGetLastError());
+  const int rc = lists(totals);
+  if (rc) return rc;
+  hipLaunchKernelGGL(fill, grid, dim3(kSq8NT), (size_t)lds_fill, st, a.codes, a.scales, a.norms, a.n_items, p.qcodes, p.qscales, p.qnorms,
+                     n_q, p.err, p.xhat, p.terms, g, p.n_blocks, p.counts, p.xsplits, p.rows);
+  NANN_HIP_TRY(hipGetLastError());
+  return NANN_OK;
+}
+
+// the queries' own error terms and the chunk's Sq8QTerms at the cuts tau[qi * k + k - 1], then the pass
+template <int METRIC, class Lists>
+int launch_sq8_cert_by(const Sq8Args& a, const Sq8CertPass& p, const float* q, const float* tau, int k, float* qerr, float* qxhat, int n_q,
+                       Lists lists, hipStream_t st) {
+  const int rc = launch_sq8_row_err(q, NANN_F32, n_q, a.d, p.qcodes, p.qscales, p.qnorms, qerr, qxhat, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_sq8_exact_terms<METRIC>, dim3((unsigned)((n_q + kSq8NT - 1) / kSq8NT)), dim3(kSq8NT), 0, st, tau, k, qerr, qxhat,
+                     n_q, sq8_gamma(a.d), p.terms);
+  NANN_HIP_TRY(hipGetLastError());
+  switch (a.d / 32) {
+    case 2: return launch_sq8_cert_as<2, METRIC>(a, p, n_q, lists, st);
+    case 4: return launch_sq8_cert_as<4, METRIC>(a, p, n_q, lists, st);
+    case 8: return launch_sq8_cert_as<8, METRIC>(a, p, n_q, lists, st);
+    case 16: return launch_sq8_cert_as<16, METRIC>(a, p, n_q, lists, st);
+    default: return fail(NANN_ERR_UNSUPPORTED, "nann_search_all_sq8_stream_exact: d must be 64, 128, 256 or 512");
+  }
+}
+}  // namespace
+
+int launch_sq8_cert(const Sq8Args& a, const Sq8CertLayout& C, const float* q, const float* err, const float* xhat, int n_q, int fetch,
+                    int k, unsigned char* ws, int32_t* out_certified, int32_t* out_n_survivors, hipStream_t st) {
+  const Sq8StreamLayout& X = C.X;
+  if (n_q < 1 || n_q > kScanMaxChunk || k < 1 || k > fetch || X.cap < fetch || X.n_blocks < 1)
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_sq8_stream_exact: chunk shape");
+  // the chunk's encoded queries and sorted fetch lists, as launch_sq8_fetch over the sample has left them
+  Sq8CertPass p = {reinterpret_cast<const int8_t*>(ws + X.S.off_qcodes), reinterpret_cast<const float*>(ws + X.S.off_qscales),
+                   reinterpret_cast<const int32_t*>(ws + X.S.off_qnorms), err, xhat, reinterpret_cast<Sq8QTerms*>(ws + C.off_terms),
+                   X.n_blocks, reinterpret_cast<int32_t*>(ws + X.off_counts), reinterpret_cast<long long*>(ws + X.off_xsplits),
+                   reinterpret_cast<int32_t*>(ws + X.off_rows)};
+  const int32_t* sorted = reinterpret_cast<const int32_t*>(ws + X.S.off_sorted);
+  auto lists = [&](const int32_t* totals) -> int {
+    hipLaunchKernelGGL(k_sq8_exact_lists, dim3(1), dim3(kSq8NT), 0, st, totals, p.terms, n_q, fetch, X.cap, sorted, p.xsplits, p.rows,
+                       out_certified, out_n_survivors);
+    NANN_HIP_TRY(hipGetLastError());
+    return NANN_OK;
+  };
+  const float* tau = reinterpret_cast<const float*>(ws + C.off_a_scores);
+  float* qerr = reinterpret_cast<float*>(ws + C.off_qerr);
+  float* qxhat = reinterpret_cast<float*>(ws + C.off_qxhat);
+  return a.metric == MT_IP ? launch_sq8_cert_by<MT_IP>(a, p, q, tau, k, qerr, qxhat, n_q, lists, st)
+                           : launch_sq8_cert_by<MT_L2>(a, p, q, tau, k, qerr, qxhat, n_q, lists, st);
+}
+
+int launch_sq8_cert_range(const Sq8Args& a, const Sq8RangeLayout& R, const float* q, const float* thr, const float* err,
+                          const float* xhat, int n_q, unsigned char* ws, int32_t* out_certified, int32_t* out_n_survivors,
+                          hipStream_t st) {
+  if (n_q < 1 || n_q > kScanMaxChunk || R.cap < 1 || R.n_blocks < 1)
+    return fail(NANN_ERR_BAD_ARGUMENT, "nann_search_all_range_sq8_stream_exact: chunk shape");
+  int8_t* qcodes = reinterpret_cast<int8_t*>(ws + R.off_qcodes);
+  float* qscales = reinterpret_cast<float*>(ws + R.off_qscales);
+  int32_t* qnorms = reinterpret_cast<int32_t*>(ws + R.off_qnorms);
+  const int rc = launch_sq8_encode(q, NANN_F32, n_q, a.d, qcodes, qscales, qnorms, st);
+  if (rc) return rc;
+  Sq8CertPass p = {qcodes, qscales, qnorms, err, xhat, reinterpret_cast<Sq8QTerms*>(ws + R.off_terms), R.n_blocks,
+                   reinterpret_cast<int32_t*>(ws + R.off_counts), reinterpret_cast<long long*>(ws + R.off_xsplits),
+                   reinterpret_cast<int32_t*>(ws + R.off_rows)};
+  const int metric = a.metric;
+  auto lists = [&](const int32_t* totals) -> int {
+    hipLaunchKernelGGL(k_sq8_range_lists, dim3(1), dim3(kSq8NT), 0, st, totals, p.terms, n_q, metric, R.cap, p.xsplits, out_certified,
+                       out_n_survivors);
+    NANN_HIP_TRY(hipGetLastError());
+    return NANN_OK;
+  };
+  // tau = the query's threshold: k_sq8_exact_terms at k = 1 over this chunk's slice of the thresholds
+  float* qerr = reinterpret_cast<float*>(ws + R.off_qerr);
+  float* qxhat = reinterpret_cast<float*>(ws + R.off_qxhat);
+  return a.metric == MT_IP ? launch_sq8_cert_by<MT_IP>(a, p, q, thr, 1, qerr, qxhat, n_q, lists, st)
+                           : launch_sq8_cert_by<MT_L2>(a, p, q, thr, 1, qerr, qxhat, n_q, lists, st);
 }
 
 }  // namespace nann

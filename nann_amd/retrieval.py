@@ -697,6 +697,46 @@ def search_all_sq8_exact(index, sq8, bounds, scorer, q, k, fetch=None, cap=2048,
     return Sq8ExactResult(out_ids, out_scores, out_index, certified, n_surv, fetch, cap, ws)
 
 
+def search_all_sq8_stream_exact(index, sq8, bounds, scorer, q, k, fetch=None, sample_rows=None, cap=8192, fallback=True, options=None):
+    """Certified scalar-quantised exhaustive search without a score buffer (nann_search_all_sq8_stream_exact): search_all's result
+    BIT FOR BIT, as search_all_sq8_exact gives it, at the cost of search_all_sq8_stream.  The cut is the k-th best EXACT score among
+    the first `sample_rows` rows (search_all_sq8's fetch and re-rank at `fetch` over that prefix); the survivor predicate runs inside
+    the int8 scan over the whole table, so nothing of queries x n_items is stored and a chunk stays at 128 queries whatever
+    n_items.  sample_rows=None: max(65536, ceil(n_items / 16)); a smaller sample means a lower cut and more survivors, never a
+    wrong row.  result.certified[b] == 1 iff at most `cap` rows survived (and the query is finite); an uncertified row of the
+    result is the exact top k of the sample's fetch list.  Arguments, fetch=None and fallback as in search_all_sq8_exact;
+    k <= fetch <= cap -> Sq8ExactResult."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    b, k = q.shape[0], int(k)
+    fetch = min(max(k, 1), 1024, int(index.n_items)) if fetch is None else int(fetch)
+    sample_rows = 0 if sample_rows is None else int(sample_rows)
+    cap = int(cap)
+    kk = max(k, 0)
+    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
+    certified = torch.zeros(b, dtype=torch.int32, device=dev)
+    n_surv = torch.zeros(b, dtype=torch.int32, device=dev)
+    nbytes = C.c_int64(0)
+    bh = bounds.handle if bounds is not None else None
+    _check(lib().nann_search_all_sq8_stream_exact_workspace_bytes(index.handle, sq8.handle, bh, scorer.handle, b, fetch, sample_rows,
+                                                                  cap, k, C.byref(nbytes)), "search_all_sq8_stream_exact")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_all_sq8_stream_exact(index.handle, sq8.handle, bh, scorer.handle, _ptr(q), b, fetch, sample_rows, cap,
+                                                      k, _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(certified),
+                                                      _ptr(n_surv), _ptr(ws), ws.numel(),
+                                                      C.byref(options) if options is not None else None, _stream()),
+               "search_all_sq8_stream_exact")
+    if fallback and b > 0 and k > 0:
+        todo = torch.nonzero(certified == 0).flatten()  # (the synchronisation)
+        if todo.numel() > 0:
+            r = search_all(index, scorer, q[todo], k, options=options)
+            out_ids[todo], out_scores[todo], out_index[todo] = r.item_ids, r.scores, r.index
+    return Sq8ExactResult(out_ids, out_scores, out_index, certified, n_surv, fetch, cap, ws)
+
+
 def search_all_model(index, model, comm_seq, k, options=None):
     """Exhaustive search under a model (nann_search_all_model; the reference's test_all job, main.py:194-237, which scores
     its own attention + DNN model): every item of `index` scored for every user of comm_seq f16[B, seq_len, E], top k per
@@ -912,6 +952,22 @@ def search_all_range_sq8_exact(index, sq8, bounds, scorer, q, thresholds, cap=40
     search_all_range and splices their segments in, in query order, so that the result equals search_all_range's for EVERY query
     (certified and n_survivors stay as the device call left them).  fallback=False: asynchronous on torch's current stream.
     sort=True reorders each segment by (score descending, row ascending) with torch on the device."""
+    return _search_all_range_sq8("search_all_range_sq8_exact", index, sq8, bounds, scorer, q, thresholds, cap, capacity, fallback, options,
+                                 sort)
+
+
+def search_all_range_sq8_stream_exact(index, sq8, bounds, scorer, q, thresholds, cap=4096, capacity=None, fallback=True, options=None,
+                                      sort=False):
+    """Certified scalar-quantised range search without a score buffer (nann_search_all_range_sq8_stream_exact):
+    search_all_range_sq8_exact's arguments, contract and result -- search_all_range's BIT FOR BIT -- with the survivor predicate
+    evaluated inside the int8 scan: nothing of queries x n_items is stored, the code table is read twice, and a chunk stays at
+    128 queries whatever n_items -> Sq8RangeResult."""
+    return _search_all_range_sq8("search_all_range_sq8_stream_exact", index, sq8, bounds, scorer, q, thresholds, cap, capacity, fallback,
+                                 options, sort)
+
+
+def _search_all_range_sq8(name, index, sq8, bounds, scorer, q, thresholds, cap, capacity, fallback, options, sort):
+    """search_all_range_sq8_exact / search_all_range_sq8_stream_exact: the C call nann_<name> and its workspace twin"""
     dev = index.device
     q = q.to(device=dev, dtype=torch.float32).contiguous()
     b, cap = q.shape[0], int(cap)
@@ -927,8 +983,7 @@ def search_all_range_sq8_exact(index, sq8, bounds, scorer, q, thresholds, cap=40
     nbytes = C.c_int64(0)
     bh = bounds.handle if bounds is not None else None
     th = sq8.handle if sq8 is not None else None
-    _check(L.nann_search_all_range_sq8_exact_workspace_bytes(index.handle, th, bh, scorer.handle, b, cap, C.byref(nbytes)),
-           "search_all_range_sq8_exact")
+    _check(getattr(L, "nann_%s_workspace_bytes" % name)(index.handle, th, bh, scorer.handle, b, cap, C.byref(nbytes)), name)
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
     splits = torch.zeros(b + 1, dtype=torch.int64, device=dev)
     ids = torch.zeros(capacity, dtype=torch.int64, device=dev)
@@ -938,11 +993,10 @@ def search_all_range_sq8_exact(index, sq8, bounds, scorer, q, thresholds, cap=40
     n_surv = torch.zeros(b, dtype=torch.int32, device=dev)
     some = capacity > 0
     with torch.cuda.device(dev):
-        _check(L.nann_search_all_range_sq8_exact(index.handle, th, bh, scorer.handle, _ptr(q), b, _ptr(thr), cap, capacity,
-                                                 _ptr(splits), _ptr(ids) if some else None, _ptr(scores) if some else None,
-                                                 _ptr(rows) if some else None, _ptr(certified), _ptr(n_surv), _ptr(ws), ws.numel(),
-                                                 C.byref(options) if options is not None else None, _stream()),
-               "search_all_range_sq8_exact")
+        _check(getattr(L, "nann_" + name)(index.handle, th, bh, scorer.handle, _ptr(q), b, _ptr(thr), cap, capacity, _ptr(splits),
+                                          _ptr(ids) if some else None, _ptr(scores) if some else None, _ptr(rows) if some else None,
+                                          _ptr(certified), _ptr(n_surv), _ptr(ws), ws.numel(),
+                                          C.byref(options) if options is not None else None, _stream()), name)
     total = None
     if fallback and b > 0:
         todo = torch.nonzero(certified == 0).flatten()  # (the synchronisation)

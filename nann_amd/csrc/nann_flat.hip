@@ -29,6 +29,8 @@
 //   flat_stage_mean    an l2 / mlp model: the mean of the sequence into the head of the workspace, the scorer form behind it
 //   flat_table         the pre-projected table of an MLP or attention pair; projection_used hands it back behind the launch
 //   flat_ids_of, flat_rows_of, flat_lists_of   the index's and the lists' fields into ScanArgs / CandArgs / CandAttnArgs
+//   flat_sq8_plan      the six scalar-quantised forms: a form's checks in its order, its chunk and its workspace; flat_sq8_begin,
+//                      flat_sq8_chunks and flat_sq8_topk are the steps flat_all_sq8 and flat_range_sq8 walk behind it
 // A new flat form is an entry point at the bottom that calls flat_all or flat_cand (or a third walk made of the same steps).
 //
 // The ORDER in which a call looks at its arguments is part of its contract -- with two faults present, which one the caller is
@@ -958,10 +960,9 @@ static int flat_all_diverse(const nann_index* ix, const nann_scorer* scorer, con
   return launch_mmr(a, (long long)n, as_stream(stream));
 }
 
-// ---- scalar-quantised exhaustive search (nann_sq8.h): per chunk the int8 scan and nann_search_all's selection at k = fetch, the
-// fetched rows in ascending order, then the candidate-list search over them at k ---------------------------------------------
-// workspace: [the ScanLayout at k = fetch | Sq8Layout: the chunk's encoded queries, fetch lists, sorted lists, row_splits,
-// status, and the candidate-list search's CandLayout for one chunk].  Nothing in it grows with n_queries beyond a chunk.
+// ---- scalar-quantised exhaustive search (nann_sq8.h): the int8 scan over the code table, then the candidate-list search over
+// the rows it keeps ----------------------------------------------------------------------------------------------------------
+// what every form checks, held against fetch (the range forms: at fetch = k = 0)
 static int flat_sq8_check(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, int64_t n, int32_t fetch, int32_t k,
                           const char* who, FlatBy* by) {
   if (!t) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
@@ -977,303 +978,130 @@ static int flat_sq8_check(const nann_index* ix, const nann_sq8* t, const nann_sc
   if (n > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": too many queries in one call");
   return NANN_OK;
 }
-static Sq8Layout flat_sq8_bytes(const nann_index* ix, const FlatBy& by, int64_t n, int32_t fetch, ScanLayout* L) {
-  *L = scan_layout((long long)ix->desc.n_items, ix->desc.d, by.kind, (long long)n, fetch);
-  return sq8_layout(*L, ix->desc.d, fetch, cand_layout(by.kind, L->chunk, (long long)L->chunk * fetch).total);
-}
 
-static int flat_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, const float* q, int64_t n, int32_t fetch,
-                        int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_fetch_index,
-                        float* out_fetch_scores, void* workspace, int64_t workspace_bytes, const nann_search_options* options,
-                        nann_stream_t stream, const char* who) {
+// The six forms of the search are one host path: flat_sq8_plan (the checks, the chunk, the
+// workspace), flat_sq8_begin (options, workspace, launch arguments), flat_sq8_chunks (the loop), and in it flat_all_sq8's or
+// flat_range_sq8's steps.  Per chunk:
+//   plain          the fetch stage over the table (the int8 scan, nann_search_all's selection at k = fetch, the fetched rows in
+//                  ascending order) | the exact top k of the fetch lists.  workspace: ScanLayout at k = fetch, Sq8Layout
+//   stream         the fetch stage over the sample, whose last fetched score is the cut | the survivors of the whole table, in
+//                  the int8 scan's epilogue | the exact top k of the survivor lists.  workspace: Sq8StreamLayout; the chunk is
+//                  the ScanLayout's at n_sample rows, nothing holds chunk * n_items elements
+//   exact          plain's two steps with the result kept in the workspace (stage a) | the survivor pass over the score buffer
+//                  the scan has left in the ScanLayout (stage b) | the exact top k of the final lists (stage c).  workspace:
+//                  Sq8ExactLayout
+//   stream-exact   stream's fetch stage and its exact top k at k, kept in the workspace: the cut | the survivor predicate in the
+//                  int8 scan's epilogue | the exact top k of the final lists.  workspace: Sq8CertLayout; the chunk as stream's
+//   range          the caller's threshold is the cut: the int8 scan and the survivor pass at tau = thresholds[q] | the
+//                  candidate-list search's scorer over the survivor lists | the ragged selection over those exact scores.  No
+//                  fetch stage, no top-k.  workspace: Sq8RangeLayout behind the ScanLayout at k = 0
+//   stream-range   range with the survivor predicate in the scan's epilogue.  workspace: a Sq8RangeLayout with nothing in front;
+//                  the chunk is sq8_cert_range_chunk(n)
+// Nothing in a workspace grows with n_queries beyond a chunk.  The forms differ in which fault they name first, in their cap
+// rule and in what a call with nothing to do still looks at; every branch on the form below keeps one of those differences
+// (tests/test_sq8_contract_gpu.py pins them).
+enum Sq8Form { kSq8Plain, kSq8Stream, kSq8Exact, kSq8StreamExact, kSq8Range, kSq8StreamRange };
+static bool sq8_range(Sq8Form f) { return f == kSq8Range || f == kSq8StreamRange; }
+static bool sq8_bounded(Sq8Form f) { return f != kSq8Plain && f != kSq8Stream; }        // the certified forms: they take the bounds
+static bool sq8_sampled(Sq8Form f) { return f == kSq8Stream || f == kSq8StreamExact; }  // the cut comes from the first n_sample rows
+
+struct Sq8Plan {
   FlatBy by;
-  int rc = flat_sq8_check(ix, t, scorer, n, fetch, k, who, &by);
-  if (rc) return rc;
-  if (n == 0 || k == 0) return NANN_OK;
-  if (!q || !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  rc = check_options(options);
-  if (rc) return rc;
-  ScanLayout L;
-  const Sq8Layout S = flat_sq8_bytes(ix, by, n, fetch, &L);
-  rc = flat_workspace(workspace, workspace_bytes, S.total, who, "");
-  if (rc) return rc;
-  DeviceInfo di;
-  rc = device_info(&di);
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  Sq8Args a = {};
-  a.codes = t->codes;
-  a.scales = t->scales;
-  a.norms = t->norms;
-  a.item_ids = ix->desc.item_ids;
-  a.n_items = (long long)ix->desc.n_items;
-  a.d = ix->desc.d;
-  a.metric = by.kind == NANN_SCORER_IP ? MT_IP : MT_L2;
-  CandArgs ca = {};
-  flat_rows_of(ix, &ca);
-  ca.cus = di.cus;
-  ca.kind = by.kind;
-  ca.row_splits = reinterpret_cast<const int64_t*>(ws + S.off_splits);
-  ca.rows = reinterpret_cast<const int32_t*>(ws + S.off_sorted);
-  int32_t* status = reinterpret_cast<int32_t*>(ws + S.off_status);  // (always 0: the lists are the fetch stage's own)
-  for (int64_t c0 = 0; c0 < n; c0 += L.chunk) {
-    const int n_q = (int)std::min<int64_t>(L.chunk, n - c0);
-    const float* qc = q + (size_t)c0 * a.d;
-    rc = launch_sq8_fetch(a, L, S, qc, n_q, fetch, ws, out_fetch_index ? out_fetch_index + (size_t)c0 * fetch : nullptr,
-                          out_fetch_scores ? out_fetch_scores + (size_t)c0 * fetch : nullptr, st);
-    if (rc) return rc;
-    ca.n_cand = (long long)n_q * fetch;
-    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + S.off_cand, out_item_ids + (size_t)c0 * k,
-                     out_scores ? out_scores + (size_t)c0 * k : nullptr, out_index ? out_index + (size_t)c0 * k : nullptr, nullptr,
-                     nullptr, status, st);
-    if (rc) return rc;
-  }
-  return NANN_OK;
-}
+  int chunk = 0;
+  long long n_sample = 0;                  // rows the fetch stage scans: n_items unless the form is sampled
+  ScanLayout L = {};                       // every form but stream-range; over the sample where the form is sampled
+  Sq8Layout S = {};                        // the fetch stage of the top-k forms: the form's own, or the one inside X / E
+  Sq8StreamLayout X = {};                  // stream, and stream-exact's C.X
+  Sq8ExactLayout E = {};                   // exact
+  Sq8CertLayout C = {};                    // stream-exact
+  Sq8RangeLayout R = {};                   // range, stream-range
+  size_t total = 0;                        // what <who>_workspace_bytes gives, but for a call with nothing to do
+  size_t off_splits = 0, off_rows = 0;     // the final lists: plain's sorted fetch lists, else the survivor lists,
+  long long width = 0;                     // and their positions per query: fetch, else min(cap, n_items)
+  size_t off_a_ids = 0, off_a_scores = 0;  // exact, stream-exact: stage (a)'s result, i64[chunk, k] and f32[chunk, k]
+};
 
-// ---- the streamed form (nann_search_all_sq8_stream; nann_sq8.h) -------------------------------------------------
-// Per chunk: flat_all_sq8's fetch stage over the sample only, whose last fetched score is the cut; the count / scan / lists / fill
-// pass over the whole table; the candidate-list search over the survivor lists, as the certified form runs it over its own.
-// workspace: Sq8StreamLayout.  The chunk is the ScanLayout's at n_sample rows; nothing holds chunk * n_items elements.
-static int flat_sq8_stream_check(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, int64_t n, int32_t fetch,
-                                 int64_t sample_rows, int32_t cap, int32_t k, const char* who, FlatBy* by, ScanLayout* L,
-                                 Sq8StreamLayout* X) {
-  int rc = flat_sq8_check(ix, t, scorer, n, fetch, k, who, by);
+// The checks of a form in the form's order, then its chunk and layout.  sample_rows, cap and -- the range forms -- fetch and k are
+// 0 where the form has none.
+static int flat_sq8_plan(Sq8Form form, const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                         int64_t n, int32_t fetch, int64_t sample_rows, int64_t cap, int32_t k, const char* who, Sq8Plan* P) {
+  if (sq8_range(form) && ix && ix->desc.emb_dtype == NANN_F32)
+    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": 16-bit rows (f16, bf16) only");
+  if (sq8_bounded(form) && !b) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  const int rc = flat_sq8_check(ix, t, scorer, n, fetch, k, who, &P->by);  // (the range forms: nann_search_all_range's checks of the shape)
   if (rc) return rc;
-  if (cap < k) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least k");
-  if (sample_rows < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": sample_rows must not be negative");
-  if (n == 0 || k == 0) return NANN_OK;  // (nothing to lay out; fetch >= k >= 1 below)
+  if (sq8_bounded(form) && (b->uid != ix->uid || b->serial != t->serial || b->n_items != t->n_items))
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the bounds were made from another index or code table");
+  if (form == kSq8Stream && cap < k) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least k");
+  if (sq8_range(form) && cap < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least 1");
+  if ((form == kSq8Exact || form == kSq8StreamExact) && cap < fetch)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least fetch");
+  if (sq8_sampled(form) && sample_rows < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": sample_rows must not be negative");
+  // nothing to lay out (fetch >= k >= 1 below).  The exact and the range forms lay out regardless: their cap is still held against
+  // the chunk, and nann_search_all_sq8_exact_layout reports the layout
+  if ((form == kSq8Plain || sq8_sampled(form)) && (n == 0 || k == 0)) return NANN_OK;
   const long long n_items = (long long)ix->desc.n_items;
-  const long long n_sample = sq8_stream_sample((long long)sample_rows, fetch, n_items);
-  *L = scan_layout(n_sample, ix->desc.d, by->kind, (long long)n, fetch);
-  if (std::min<long long>(cap, n_items) > cand_max_list(L->chunk))  // (a chunk's survivor lists are one candidate-list search)
+  const int d = ix->desc.d, kind = P->by.kind;
+  P->n_sample = sq8_sampled(form) ? sq8_stream_sample((long long)sample_rows, fetch, n_items) : n_items;
+  if (form == kSq8StreamRange) {
+    P->chunk = sq8_cert_range_chunk((long long)n);
+  } else {
+    P->L = scan_layout(P->n_sample, d, kind, (long long)n, fetch);
+    P->chunk = P->L.chunk;
+  }
+  // a chunk's final lists are one candidate-list search (the streamed form holds what it keeps of cap against it, the others cap)
+  if (form != kSq8Plain && (form == kSq8Stream ? std::min<long long>(cap, n_items) : (long long)cap) > cand_max_list(P->chunk))
     return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": cap beyond the longest list of a candidate-list search, " +
-                                          std::to_string(cand_max_list(L->chunk)) + " at this chunk");
-  *X = sq8_stream_layout(*L, by->kind, ix->desc.d, fetch, (long long)cap, n_items, n_sample);
-  return NANN_OK;
-}
-
-static int flat_all_sq8_stream(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, const float* q, int64_t n,
-                               int32_t fetch, int64_t sample_rows, int32_t cap, int32_t k, int64_t* out_item_ids, float* out_scores,
-                               int32_t* out_index, int32_t* out_complete, int32_t* out_n_survivors, float* out_cut, void* workspace,
-                               int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream, const char* who) {
-  FlatBy by;
-  ScanLayout L;
-  Sq8StreamLayout X;
-  int rc = flat_sq8_stream_check(ix, t, scorer, n, fetch, sample_rows, cap, k, who, &by, &L, &X);
-  if (rc) return rc;
-  if (n == 0 || k == 0) return NANN_OK;
-  if (!q || !out_item_ids || !out_complete) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  rc = check_options(options);
-  if (rc) return rc;
-  rc = flat_workspace(workspace, workspace_bytes, X.total, who, "");
-  if (rc) return rc;
-  DeviceInfo di;
-  rc = device_info(&di);
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  Sq8Args a = {};
-  a.codes = t->codes;
-  a.scales = t->scales;
-  a.norms = t->norms;
-  a.item_ids = ix->desc.item_ids;
-  a.n_items = (long long)ix->desc.n_items;
-  a.d = ix->desc.d;
-  a.metric = by.kind == NANN_SCORER_IP ? MT_IP : MT_L2;
-  Sq8Args sample = a;  // the table's first n_sample rows
-  sample.n_items = X.n_sample;
-  CandArgs ca = {};
-  flat_rows_of(ix, &ca);
-  ca.cus = di.cus;
-  ca.kind = by.kind;
-  ca.row_splits = reinterpret_cast<const int64_t*>(ws + X.off_xsplits);
-  ca.rows = reinterpret_cast<const int32_t*>(ws + X.off_rows);
-  int32_t* status = reinterpret_cast<int32_t*>(ws + X.S.off_status);  // (always 0: the lists are the call's own)
-  for (int64_t c0 = 0; c0 < n; c0 += L.chunk) {
-    const int n_q = (int)std::min<int64_t>(L.chunk, n - c0);
-    const float* qc = q + (size_t)c0 * a.d;
-    // the cut: the fetch stage over the sample; it leaves the chunk's encoded queries and the fetch lists in the workspace
-    rc = launch_sq8_fetch(sample, L, X.S, qc, n_q, fetch, ws, nullptr, nullptr, st);
-    if (rc) return rc;
-    // the survivors of every query over the whole table, as compact lists in ascending row order
-    rc = launch_sq8_stream(a, X, n_q, fetch, ws, out_complete + c0, out_n_survivors ? out_n_survivors + c0 : nullptr,
-                           out_cut ? out_cut + c0 : nullptr, st);
-    if (rc) return rc;
-    // the exact top k of the lists
-    ca.n_cand = (long long)n_q * X.cap;
-    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + X.S.off_cand, out_item_ids + (size_t)c0 * k,
-                     out_scores ? out_scores + (size_t)c0 * k : nullptr, out_index ? out_index + (size_t)c0 * k : nullptr, nullptr,
-                     nullptr, status, st);
-    if (rc) return rc;
+                                          std::to_string(cand_max_list(P->chunk)) + " at this chunk");
+  switch (form) {
+    case kSq8Plain:
+      P->S = sq8_layout(P->L, d, fetch, cand_layout(kind, P->chunk, (long long)P->chunk * fetch).total);
+      P->total = P->S.total;
+      P->off_splits = P->S.off_splits, P->off_rows = P->S.off_sorted, P->width = fetch;
+      break;
+    case kSq8Stream:
+    case kSq8StreamExact:
+      if (form == kSq8Stream) {
+        P->X = sq8_stream_layout(P->L, kind, d, fetch, (long long)cap, n_items, P->n_sample);
+        P->total = P->X.total;
+      } else {
+        P->C = sq8_cert_layout(P->L, kind, d, fetch, (long long)cap, k, n_items, P->n_sample);
+        P->X = P->C.X;
+        P->total = P->C.total;
+        P->off_a_ids = P->C.off_a_ids, P->off_a_scores = P->C.off_a_scores;
+      }
+      P->S = P->X.S;
+      P->off_splits = P->X.off_xsplits, P->off_rows = P->X.off_rows, P->width = P->X.cap;
+      break;
+    case kSq8Exact:
+      P->E = sq8_exact_layout(P->L, kind, d, fetch, (long long)cap, k, n_items);
+      P->S = P->E.S;
+      P->total = P->E.total;
+      P->off_splits = P->E.off_xsplits, P->off_rows = P->E.off_rows, P->width = P->E.cap;
+      P->off_a_ids = P->E.off_a_ids, P->off_a_scores = P->E.off_a_scores;
+      break;
+    case kSq8Range:
+    case kSq8StreamRange:
+      P->R = form == kSq8Range ? sq8_range_layout(P->L, kind, d, (long long)cap, n_items)
+                               : sq8_cert_range_layout(P->chunk, kind, d, (long long)cap, n_items);
+      P->total = P->R.total;
+      P->off_splits = P->R.off_xsplits, P->off_rows = P->R.off_rows, P->width = P->R.cap;
+      break;
   }
   return NANN_OK;
 }
 
-// ---- the certified form (nann_search_all_sq8_exact; nann_sq8.h) -----------------------------------------------
-// Per chunk: flat_all_sq8's two steps with the result kept in the workspace (stage a), the survivor pass over the score buffer
-// the scan has left in the ScanLayout (stage b), and the candidate-list search over the final lists (stage c).
-// workspace: Sq8ExactLayout.  Nothing in it grows with n_queries beyond a chunk.
-static int flat_sq8_exact_check(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer, int64_t n,
-                                int32_t fetch, int64_t cap, int32_t k, const char* who, FlatBy* by, ScanLayout* L, Sq8ExactLayout* X) {
-  if (!b) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  int rc = flat_sq8_check(ix, t, scorer, n, fetch, k, who, by);
+// <who>_workspace_bytes of every form
+static int flat_sq8_size(Sq8Form form, const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                         int64_t n, int32_t fetch, int64_t sample_rows, int64_t cap, int32_t k, int64_t* nbytes, const char* who) {
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  Sq8Plan P;
+  const int rc = flat_sq8_plan(form, ix, t, b, scorer, n, fetch, sample_rows, cap, k, who, &P);
   if (rc) return rc;
-  if (b->uid != ix->uid || b->serial != t->serial || b->n_items != t->n_items)
-    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the bounds were made from another index or code table");
-  if (cap < fetch) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least fetch");
-  *L = scan_layout((long long)ix->desc.n_items, ix->desc.d, by->kind, (long long)n, fetch);
-  if (cap > cand_max_list(L->chunk))  // (a chunk's final lists are one candidate-list search)
-    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": cap beyond the longest list of a candidate-list search, " +
-                                          std::to_string(cand_max_list(L->chunk)) + " at this chunk");
-  *X = sq8_exact_layout(*L, by->kind, ix->desc.d, fetch, (long long)cap, k, (long long)ix->desc.n_items);
+  *nbytes = n == 0 || (!sq8_range(form) && k == 0) ? 0 : (int64_t)P.total;
   return NANN_OK;
 }
 
-static int flat_all_sq8_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
-                              const float* q, int64_t n, int32_t fetch, int64_t cap, int32_t k, int64_t* out_item_ids,
-                              float* out_scores, int32_t* out_index, int32_t* out_certified, int32_t* out_n_survivors,
-                              void* workspace, int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream,
-                              const char* who) {
-  FlatBy by;
-  ScanLayout L;
-  Sq8ExactLayout X;
-  int rc = flat_sq8_exact_check(ix, t, b, scorer, n, fetch, cap, k, who, &by, &L, &X);
-  if (rc) return rc;
-  if (n == 0 || k == 0) return NANN_OK;
-  if (!q || !out_item_ids || !out_certified || !out_n_survivors) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  rc = check_options(options);
-  if (rc) return rc;
-  rc = flat_workspace(workspace, workspace_bytes, X.total, who, "");
-  if (rc) return rc;
-  DeviceInfo di;
-  rc = device_info(&di);
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  const Sq8Layout& S = X.S;
-  Sq8Args a = {};
-  a.codes = t->codes;
-  a.scales = t->scales;
-  a.norms = t->norms;
-  a.item_ids = ix->desc.item_ids;
-  a.n_items = (long long)ix->desc.n_items;
-  a.d = ix->desc.d;
-  a.metric = by.kind == NANN_SCORER_IP ? MT_IP : MT_L2;
-  CandArgs ca = {};
-  flat_rows_of(ix, &ca);
-  ca.cus = di.cus;
-  ca.kind = by.kind;
-  int32_t* status = reinterpret_cast<int32_t*>(ws + S.off_status);  // (always 0: the lists are the call's own)
-  for (int64_t c0 = 0; c0 < n; c0 += L.chunk) {
-    const int n_q = (int)std::min<int64_t>(L.chunk, n - c0);
-    const float* qc = q + (size_t)c0 * a.d;
-    // (a) the fetch stage and its exact re-rank, as nann_search_all_sq8 runs them; the result stays in the workspace
-    rc = launch_sq8_fetch(a, L, S, qc, n_q, fetch, ws, nullptr, nullptr, st);
-    if (rc) return rc;
-    ca.row_splits = reinterpret_cast<const int64_t*>(ws + S.off_splits);
-    ca.rows = reinterpret_cast<const int32_t*>(ws + S.off_sorted);
-    ca.n_cand = (long long)n_q * fetch;
-    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + S.off_cand,
-                     reinterpret_cast<int64_t*>(ws + X.off_a_ids), reinterpret_cast<float*>(ws + X.off_a_scores), nullptr, nullptr,
-                     nullptr, status, st);
-    if (rc) return rc;
-    // (b) the survivors of every query, or its fetch list, as compact lists in ascending row order
-    rc = launch_sq8_survivors(a, L, X, qc, b->err, b->xhat, n_q, fetch, k, ws, out_certified + c0, out_n_survivors + c0, st);
-    if (rc) return rc;
-    // (c) the exact top k of the lists
-    ca.row_splits = reinterpret_cast<const int64_t*>(ws + X.off_xsplits);
-    ca.rows = reinterpret_cast<const int32_t*>(ws + X.off_rows);
-    ca.n_cand = (long long)n_q * X.cap;
-    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + S.off_cand, out_item_ids + (size_t)c0 * k,
-                     out_scores ? out_scores + (size_t)c0 * k : nullptr, out_index ? out_index + (size_t)c0 * k : nullptr, nullptr,
-                     nullptr, status, st);
-    if (rc) return rc;
-  }
-  return NANN_OK;
-}
-
-// ---- the certified range form (nann_search_all_range_sq8_exact; nann_sq8.h) ------------------------------------
-// The caller's threshold is the cut: per chunk the int8 scan and the survivor pass at tau = thresholds[q], the candidate-list
-// search's scorer over the survivor lists, and the ragged selection over those exact scores.  No fetch stage, no top-k.
-// workspace: Sq8RangeLayout behind the ScanLayout at k = 0.  Nothing in it grows with n_queries beyond a chunk.
-static int flat_sq8_range_check(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer, int64_t n,
-                                int64_t cap, const char* who, FlatBy* by, ScanLayout* L, Sq8RangeLayout* R) {
-  if (ix && ix->desc.emb_dtype == NANN_F32) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": 16-bit rows (f16, bf16) only");
-  if (!b) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  int rc = flat_sq8_check(ix, t, scorer, n, 0, 0, who, by);  // (nann_search_all_range's checks of the shape: there is no k)
-  if (rc) return rc;
-  if (b->uid != ix->uid || b->serial != t->serial || b->n_items != t->n_items)
-    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the bounds were made from another index or code table");
-  if (cap < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least 1");
-  *L = scan_layout((long long)ix->desc.n_items, ix->desc.d, by->kind, (long long)n, 0);
-  if (cap > cand_max_list(L->chunk))  // (a chunk's survivor lists are one candidate-list plan)
-    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": cap beyond the longest list of a candidate-list search, " +
-                                          std::to_string(cand_max_list(L->chunk)) + " at this chunk");
-  *R = sq8_range_layout(*L, by->kind, ix->desc.d, (long long)cap, (long long)ix->desc.n_items);
-  return NANN_OK;
-}
-
-static int flat_range_sq8_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
-                                const float* q, int64_t n, const float* thresholds, int64_t cap, int64_t capacity,
-                                int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
-                                int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
-                                const nann_search_options* options, nann_stream_t stream, const char* who) {
-  FlatBy by;
-  ScanLayout L;
-  Sq8RangeLayout R;
-  int rc = flat_sq8_range_check(ix, t, b, scorer, n, cap, who, &by, &L, &R);
-  if (rc) return rc;
-  if (capacity < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": capacity < 0");
-  if (n == 0) return NANN_OK;
-  if (!q || !thresholds || !out_row_splits || !out_certified || !out_n_survivors)
-    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  if (capacity > 0 && !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": out_item_ids is null while capacity > 0");
-  rc = check_options(options);
-  if (rc) return rc;
-  rc = flat_workspace(workspace, workspace_bytes, R.total, who, "");
-  if (rc) return rc;
-  DeviceInfo di;
-  rc = device_info(&di);
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  Sq8Args a = {};
-  a.codes = t->codes;
-  a.scales = t->scales;
-  a.norms = t->norms;
-  a.item_ids = ix->desc.item_ids;
-  a.n_items = (long long)ix->desc.n_items;
-  a.d = ix->desc.d;
-  a.metric = by.kind == NANN_SCORER_IP ? MT_IP : MT_L2;
-  CandArgs ca = {};
-  flat_rows_of(ix, &ca);
-  ca.cus = di.cus;
-  ca.kind = by.kind;
-  ca.row_splits = reinterpret_cast<const int64_t*>(ws + R.off_xsplits);
-  ca.rows = reinterpret_cast<const int32_t*>(ws + R.off_rows);
-  for (int64_t c0 = 0; c0 < n; c0 += L.chunk) {
-    const int n_q = (int)std::min<int64_t>(L.chunk, n - c0);
-    const float* qc = q + (size_t)c0 * a.d;
-    // the survivors of every certified query as compact lists in ascending row order; an uncertified query's list is empty
-    rc = launch_sq8_range_survivors(a, L, R, qc, thresholds + c0, b->err, b->xhat, n_q, ws, out_certified + c0, out_n_survivors + c0, st);
-    if (rc) return rc;
-    // their exact scores, by list position
-    ca.n_cand = (long long)n_q * R.cap;
-    const CandLayout CL = cand_layout(by.kind, n_q, ca.n_cand);
-    rc = launch_cand_scores(ca, CL, qc, n_q, ws + R.off_cand, st);
-    if (rc) return rc;
-    // the rows at or above the threshold, into the caller's ragged outputs
-    rc = launch_sq8_range_select(a, R, R.off_cand + CL.off_scores, thresholds, (long long)c0, n_q, (long long)capacity, ws,
-                                 out_row_splits, out_item_ids, out_scores, out_index, st);
-    if (rc) return rc;
-  }
-  return NANN_OK;
-}
-
-// ---- the certified streamed forms (nann_search_all_sq8_stream_exact, nann_search_all_range_sq8_stream_exact; nann_sq8.h, DESIGN.md
-// 4.26): the two certified forms above with the survivor predicate in the int8 scan's epilogue.  Nothing holds chunk * n_items.
 static Sq8Args flat_sq8_args(const nann_index* ix, const nann_sq8* t, const FlatBy& by) {
   Sq8Args a = {};
   a.codes = t->codes;
@@ -1286,153 +1114,136 @@ static Sq8Args flat_sq8_args(const nann_index* ix, const nann_sq8* t, const Flat
   return a;
 }
 
-// nann_search_all_sq8_exact's checks and the streamed form's sample_rows rule.  workspace: Sq8CertLayout; the chunk is the
-// ScanLayout's at n_sample rows.
-static int flat_sq8_cert_check(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer, int64_t n,
-                               int32_t fetch, int64_t sample_rows, int64_t cap, int32_t k, const char* who, FlatBy* by, ScanLayout* L,
-                               Sq8CertLayout* C) {
-  if (!b) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  int rc = flat_sq8_check(ix, t, scorer, n, fetch, k, who, by);
+// What every form does between its own null checks and its first chunk: the options, the workspace against the plan, and what
+// the launches of a chunk take
+struct Sq8Run {
+  hipStream_t st;
+  unsigned char* ws;
+  Sq8Args a;    // the whole table
+  CandArgs ca;  // the index's rows; flat_sq8_lists names the lists
+};
+static int flat_sq8_begin(const Sq8Plan& P, const nann_index* ix, const nann_sq8* t, void* workspace, int64_t workspace_bytes,
+                          const nann_search_options* options, nann_stream_t stream, const char* who, Sq8Run* r) {
+  int rc = check_options(options);
   if (rc) return rc;
-  if (b->uid != ix->uid || b->serial != t->serial || b->n_items != t->n_items)
-    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the bounds were made from another index or code table");
-  if (cap < fetch) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least fetch");
-  if (sample_rows < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": sample_rows must not be negative");
-  if (n == 0 || k == 0) return NANN_OK;  // (nothing to lay out; fetch >= k >= 1 below)
-  const long long n_items = (long long)ix->desc.n_items;
-  const long long n_sample = sq8_stream_sample((long long)sample_rows, fetch, n_items);
-  *L = scan_layout(n_sample, ix->desc.d, by->kind, (long long)n, fetch);
-  if (cap > cand_max_list(L->chunk))  // (a chunk's final lists are one candidate-list search)
-    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": cap beyond the longest list of a candidate-list search, " +
-                                          std::to_string(cand_max_list(L->chunk)) + " at this chunk");
-  *C = sq8_cert_layout(*L, by->kind, ix->desc.d, fetch, (long long)cap, k, n_items, n_sample);
-  return NANN_OK;
-}
-
-static int flat_all_sq8_stream_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
-                                     const float* q, int64_t n, int32_t fetch, int64_t sample_rows, int64_t cap, int32_t k,
-                                     int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_certified,
-                                     int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
-                                     const nann_search_options* options, nann_stream_t stream, const char* who) {
-  FlatBy by;
-  ScanLayout L;
-  Sq8CertLayout C;
-  int rc = flat_sq8_cert_check(ix, t, b, scorer, n, fetch, sample_rows, cap, k, who, &by, &L, &C);
-  if (rc) return rc;
-  if (n == 0 || k == 0) return NANN_OK;
-  if (!q || !out_item_ids || !out_certified || !out_n_survivors) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  rc = check_options(options);
-  if (rc) return rc;
-  rc = flat_workspace(workspace, workspace_bytes, C.total, who, "");
+  rc = flat_workspace(workspace, workspace_bytes, P.total, who, "");
   if (rc) return rc;
   DeviceInfo di;
   rc = device_info(&di);
   if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  const Sq8StreamLayout& X = C.X;
-  const Sq8Args a = flat_sq8_args(ix, t, by);
-  Sq8Args sample = a;  // the table's first n_sample rows
-  sample.n_items = X.n_sample;
-  CandArgs ca = {};
-  flat_rows_of(ix, &ca);
-  ca.cus = di.cus;
-  ca.kind = by.kind;
-  int32_t* status = reinterpret_cast<int32_t*>(ws + X.S.off_status);  // (always 0: the lists are the call's own)
-  for (int64_t c0 = 0; c0 < n; c0 += L.chunk) {
-    const int n_q = (int)std::min<int64_t>(L.chunk, n - c0);
-    const float* qc = q + (size_t)c0 * a.d;
-    // the cut: the fetch stage over the sample and the exact re-rank of its lists at k; the result stays in the workspace
-    rc = launch_sq8_fetch(sample, L, X.S, qc, n_q, fetch, ws, nullptr, nullptr, st);
-    if (rc) return rc;
-    ca.row_splits = reinterpret_cast<const int64_t*>(ws + X.S.off_splits);
-    ca.rows = reinterpret_cast<const int32_t*>(ws + X.S.off_sorted);
-    ca.n_cand = (long long)n_q * fetch;
-    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + X.S.off_cand,
-                     reinterpret_cast<int64_t*>(ws + C.off_a_ids), reinterpret_cast<float*>(ws + C.off_a_scores), nullptr, nullptr,
-                     nullptr, status, st);
-    if (rc) return rc;
-    // the survivors of every query over the whole table, or its sample's fetch list, as compact lists in ascending row order
-    rc = launch_sq8_cert(a, C, qc, b->err, b->xhat, n_q, fetch, k, ws, out_certified + c0, out_n_survivors + c0, st);
-    if (rc) return rc;
-    // the exact top k of the lists
-    ca.row_splits = reinterpret_cast<const int64_t*>(ws + X.off_xsplits);
-    ca.rows = reinterpret_cast<const int32_t*>(ws + X.off_rows);
-    ca.n_cand = (long long)n_q * X.cap;
-    rc = launch_cand(ca, cand_layout(by.kind, n_q, ca.n_cand), qc, n_q, k, ws + X.S.off_cand, out_item_ids + (size_t)c0 * k,
-                     out_scores ? out_scores + (size_t)c0 * k : nullptr, out_index ? out_index + (size_t)c0 * k : nullptr, nullptr,
-                     nullptr, status, st);
+  r->st = as_stream(stream);
+  r->ws = static_cast<unsigned char*>(workspace);
+  r->a = flat_sq8_args(ix, t, P.by);
+  r->ca = CandArgs{};
+  flat_rows_of(ix, &r->ca);
+  r->ca.cus = di.cus;
+  r->ca.kind = P.by.kind;
+  return NANN_OK;
+}
+
+// step(c0, n_q, qc) over the chunks of a call: queries [c0, c0 + n_q), the first of them at qc
+template <class Step> static int flat_sq8_chunks(const Sq8Plan& P, const float* q, int64_t n, int d, Step step) {
+  for (int64_t c0 = 0; c0 < n; c0 += P.chunk) {
+    const int rc = step(c0, (int)std::min<int64_t>(P.chunk, n - c0), q + (size_t)c0 * d);
     if (rc) return rc;
   }
   return NANN_OK;
 }
 
-// nann_search_all_range_sq8_exact's checks.  workspace: a Sq8RangeLayout with no ScanLayout in front; the chunk is sq8_cert_range_chunk(n).
-static int flat_sq8_cert_range_check(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
-                                     int64_t n, int64_t cap, const char* who, FlatBy* by, int* chunk, Sq8RangeLayout* R) {
-  if (ix && ix->desc.emb_dtype == NANN_F32) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": 16-bit rows (f16, bf16) only");
-  if (!b) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  int rc = flat_sq8_check(ix, t, scorer, n, 0, 0, who, by);  // (nann_search_all_range's checks of the shape: there is no k)
-  if (rc) return rc;
-  if (b->uid != ix->uid || b->serial != t->serial || b->n_items != t->n_items)
-    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the bounds were made from another index or code table");
-  if (cap < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": cap must be at least 1");
-  *chunk = sq8_cert_range_chunk((long long)n);
-  if (cap > cand_max_list(*chunk))  // (a chunk's survivor lists are one candidate-list plan)
-    return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": cap beyond the longest list of a candidate-list search, " +
-                                          std::to_string(cand_max_list(*chunk)) + " at this chunk");
-  *R = sq8_cert_range_layout(*chunk, by->kind, ix->desc.d, (long long)cap, (long long)ix->desc.n_items);
-  return NANN_OK;
+// a chunk's lists in the workspace as the candidate-list search's: row_splits, rows, `width` positions a query
+static void flat_sq8_lists(Sq8Run* r, size_t off_splits, size_t off_rows, int n_q, long long width) {
+  r->ca.row_splits = reinterpret_cast<const int64_t*>(r->ws + off_splits);
+  r->ca.rows = reinterpret_cast<const int32_t*>(r->ws + off_rows);
+  r->ca.n_cand = (long long)n_q * width;
 }
 
-static int flat_range_sq8_stream_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
-                                       const float* q, int64_t n, const float* thresholds, int64_t cap, int64_t capacity,
-                                       int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
-                                       int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
-                                       const nann_search_options* options, nann_stream_t stream, const char* who) {
-  FlatBy by;
-  int chunk = 0;
-  Sq8RangeLayout R;
-  int rc = flat_sq8_cert_range_check(ix, t, b, scorer, n, cap, who, &by, &chunk, &R);
+// the exact top k of those lists, into the caller's outputs at this chunk or into a staging area of the workspace
+static int flat_sq8_topk(const Sq8Plan& P, Sq8Run* r, size_t off_splits, size_t off_rows, long long width, const float* qc, int n_q,
+                         int32_t k, int64_t* ids, float* scores, int32_t* index) {
+  flat_sq8_lists(r, off_splits, off_rows, n_q, width);
+  int32_t* status = reinterpret_cast<int32_t*>(r->ws + P.S.off_status);  // (always 0: the lists are the call's own)
+  return launch_cand(r->ca, cand_layout(P.by.kind, n_q, r->ca.n_cand), qc, n_q, k, r->ws + P.S.off_cand, ids, scores, index, nullptr,
+                     nullptr, status, r->st);
+}
+
+// The four top-k forms.  out_flag: the streamed form's out_complete, the certified forms' out_certified; out_cut, out_fetch_*: the
+// streamed and the plain form's own, else null
+static int flat_all_sq8(Sq8Form form, const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                        const float* q, int64_t n, int32_t fetch, int64_t sample_rows, int64_t cap, int32_t k, int64_t* out_item_ids,
+                        float* out_scores, int32_t* out_index, int32_t* out_flag, int32_t* out_n_survivors, float* out_cut,
+                        int32_t* out_fetch_index, float* out_fetch_scores, void* workspace, int64_t workspace_bytes,
+                        const nann_search_options* options, nann_stream_t stream, const char* who) {
+  Sq8Plan P;
+  int rc = flat_sq8_plan(form, ix, t, b, scorer, n, fetch, sample_rows, cap, k, who, &P);
+  if (rc) return rc;
+  if (n == 0 || k == 0) return NANN_OK;
+  if (!q || !out_item_ids || (form != kSq8Plain && !out_flag) || (sq8_bounded(form) && !out_n_survivors))
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  Sq8Run r;
+  rc = flat_sq8_begin(P, ix, t, workspace, workspace_bytes, options, stream, who, &r);
+  if (rc) return rc;
+  Sq8Args fetched = r.a;  // the rows the fetch stage scans: the table, or its first n_sample rows
+  fetched.n_items = P.n_sample;
+  return flat_sq8_chunks(P, q, n, r.a.d, [&](int64_t c0, int n_q, const float* qc) {
+    // the fetch stage: it leaves the chunk's encoded queries and the sorted fetch lists in the workspace
+    int rc = launch_sq8_fetch(fetched, P.L, P.S, qc, n_q, fetch, r.ws, out_fetch_index ? out_fetch_index + (size_t)c0 * fetch : nullptr,
+                              out_fetch_scores ? out_fetch_scores + (size_t)c0 * fetch : nullptr, r.st);
+    if (rc) return rc;
+    if (sq8_bounded(form)) {  // (a) the exact re-rank of the fetch lists at k, kept in the workspace: its k-th score is the cut
+      rc = flat_sq8_topk(P, &r, P.S.off_splits, P.S.off_sorted, fetch, qc, n_q, k, reinterpret_cast<int64_t*>(r.ws + P.off_a_ids),
+                         reinterpret_cast<float*>(r.ws + P.off_a_scores), nullptr);
+      if (rc) return rc;
+    }
+    // (b) the survivors of every query as compact lists in ascending row order (a certified form: or its fetch list); the plain
+    // form's final lists are the fetch lists
+    if (form == kSq8Stream)
+      rc = launch_sq8_stream(r.a, P.X, n_q, fetch, r.ws, out_flag + c0, out_n_survivors ? out_n_survivors + c0 : nullptr,
+                             out_cut ? out_cut + c0 : nullptr, r.st);
+    else if (form == kSq8Exact)
+      rc = launch_sq8_survivors(r.a, P.L, P.E, qc, b->err, b->xhat, n_q, fetch, k, r.ws, out_flag + c0, out_n_survivors + c0, r.st);
+    else if (form == kSq8StreamExact)
+      rc = launch_sq8_cert(r.a, P.C, qc, b->err, b->xhat, n_q, fetch, k, r.ws, out_flag + c0, out_n_survivors + c0, r.st);
+    if (rc) return rc;
+    // (c) the exact top k of the final lists
+    return flat_sq8_topk(P, &r, P.off_splits, P.off_rows, P.width, qc, n_q, k, out_item_ids + (size_t)c0 * k,
+                         out_scores ? out_scores + (size_t)c0 * k : nullptr, out_index ? out_index + (size_t)c0 * k : nullptr);
+  });
+}
+
+// The two range forms
+static int flat_range_sq8(Sq8Form form, const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
+                          const float* q, int64_t n, const float* thresholds, int64_t cap, int64_t capacity, int64_t* out_row_splits,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_certified, int32_t* out_n_survivors,
+                          void* workspace, int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream,
+                          const char* who) {
+  Sq8Plan P;
+  int rc = flat_sq8_plan(form, ix, t, b, scorer, n, 0, 0, cap, 0, who, &P);  // (there is no fetch and no k)
   if (rc) return rc;
   if (capacity < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": capacity < 0");
   if (n == 0) return NANN_OK;
   if (!q || !thresholds || !out_row_splits || !out_certified || !out_n_survivors)
     return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
   if (capacity > 0 && !out_item_ids) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": out_item_ids is null while capacity > 0");
-  rc = check_options(options);
+  Sq8Run r;
+  rc = flat_sq8_begin(P, ix, t, workspace, workspace_bytes, options, stream, who, &r);
   if (rc) return rc;
-  rc = flat_workspace(workspace, workspace_bytes, R.total, who, "");
-  if (rc) return rc;
-  DeviceInfo di;
-  rc = device_info(&di);
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  const Sq8Args a = flat_sq8_args(ix, t, by);
-  CandArgs ca = {};
-  flat_rows_of(ix, &ca);
-  ca.cus = di.cus;
-  ca.kind = by.kind;
-  ca.row_splits = reinterpret_cast<const int64_t*>(ws + R.off_xsplits);
-  ca.rows = reinterpret_cast<const int32_t*>(ws + R.off_rows);
-  for (int64_t c0 = 0; c0 < n; c0 += chunk) {
-    const int n_q = (int)std::min<int64_t>(chunk, n - c0);
-    const float* qc = q + (size_t)c0 * a.d;
+  const Sq8RangeLayout& R = P.R;
+  return flat_sq8_chunks(P, q, n, r.a.d, [&](int64_t c0, int n_q, const float* qc) {
     // the survivors of every certified query as compact lists in ascending row order; an uncertified query's list is empty
-    rc = launch_sq8_cert_range(a, R, qc, thresholds + c0, b->err, b->xhat, n_q, ws, out_certified + c0, out_n_survivors + c0, st);
+    int rc = form == kSq8Range ? launch_sq8_range_survivors(r.a, P.L, R, qc, thresholds + c0, b->err, b->xhat, n_q, r.ws, out_certified + c0,
+                                                            out_n_survivors + c0, r.st)
+                               : launch_sq8_cert_range(r.a, R, qc, thresholds + c0, b->err, b->xhat, n_q, r.ws, out_certified + c0,
+                                                       out_n_survivors + c0, r.st);
     if (rc) return rc;
     // their exact scores, by list position
-    ca.n_cand = (long long)n_q * R.cap;
-    const CandLayout CL = cand_layout(by.kind, n_q, ca.n_cand);
-    rc = launch_cand_scores(ca, CL, qc, n_q, ws + R.off_cand, st);
+    flat_sq8_lists(&r, P.off_splits, P.off_rows, n_q, P.width);
+    const CandLayout CL = cand_layout(P.by.kind, n_q, r.ca.n_cand);
+    rc = launch_cand_scores(r.ca, CL, qc, n_q, r.ws + R.off_cand, r.st);
     if (rc) return rc;
     // the rows at or above the threshold, into the caller's ragged outputs
-    rc = launch_sq8_range_select(a, R, R.off_cand + CL.off_scores, thresholds, (long long)c0, n_q, (long long)capacity, ws,
-                                 out_row_splits, out_item_ids, out_scores, out_index, st);
-    if (rc) return rc;
-  }
-  return NANN_OK;
+    return launch_sq8_range_select(r.a, R, R.off_cand + CL.off_scores, thresholds, (long long)c0, n_q, (long long)capacity, r.ws,
+                                   out_row_splits, out_item_ids, out_scores, out_index, r.st);
+  });
 }
 
 // ---- the entry points (include/nann_hip.h) -----------------------------------------------------------------------------------
@@ -2040,44 +1851,31 @@ int nann_sq8_encode(const float* x, int64_t n, int32_t d, int8_t* codes, float* 
 }
 int nann_search_all_sq8_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, int64_t n_queries,
                                         int32_t fetch, int32_t k, int64_t* nbytes) {
-  const char* who = "nann_search_all_sq8_workspace_bytes";
-  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  FlatBy by;
-  const int rc = flat_sq8_check(ix, t, scorer, n_queries, fetch, k, who, &by);
-  if (rc) return rc;
-  ScanLayout L;
-  *nbytes = n_queries == 0 || k == 0 ? 0 : (int64_t)flat_sq8_bytes(ix, by, n_queries, fetch, &L).total;
-  return NANN_OK;
+  return flat_sq8_size(kSq8Plain, ix, t, nullptr, scorer, n_queries, fetch, 0, 0, k, nbytes, "nann_search_all_sq8_workspace_bytes");
 }
 int nann_search_all_sq8(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, const float* q, int64_t n_queries,
                         int32_t fetch, int32_t k, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
                         int32_t* out_fetch_index, float* out_fetch_scores, void* workspace, int64_t workspace_bytes,
                         const nann_search_options* options, nann_stream_t stream) {
-  return flat_all_sq8(ix, t, scorer, q, n_queries, fetch, k, out_item_ids, out_scores, out_index, out_fetch_index, out_fetch_scores,
-                      workspace, workspace_bytes, options, stream, "nann_search_all_sq8");
+  return flat_all_sq8(kSq8Plain, ix, t, nullptr, scorer, q, n_queries, fetch, 0, 0, k, out_item_ids, out_scores, out_index, nullptr,
+                      nullptr, nullptr, out_fetch_index, out_fetch_scores, workspace, workspace_bytes, options, stream,
+                      "nann_search_all_sq8");
 }
 
 // ---- the streamed form (nann_sq8.h) ----------------------------------------------------------------------------
 int nann_search_all_sq8_stream_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, int64_t n_queries,
                                                int32_t fetch, int64_t sample_rows, int32_t cap, int32_t k, int64_t* nbytes) {
-  const char* who = "nann_search_all_sq8_stream_workspace_bytes";
-  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  FlatBy by;
-  ScanLayout L;
-  Sq8StreamLayout X;
-  const int rc = flat_sq8_stream_check(ix, t, scorer, n_queries, fetch, sample_rows, cap, k, who, &by, &L, &X);
-  if (rc) return rc;
-  *nbytes = n_queries == 0 || k == 0 ? 0 : (int64_t)X.total;
-  return NANN_OK;
+  return flat_sq8_size(kSq8Stream, ix, t, nullptr, scorer, n_queries, fetch, sample_rows, cap, k, nbytes,
+                       "nann_search_all_sq8_stream_workspace_bytes");
 }
 int nann_search_all_sq8_stream(const nann_index* ix, const nann_sq8* t, const nann_scorer* scorer, const float* q, int64_t n_queries,
                                int32_t fetch, int64_t sample_rows, int32_t cap, int32_t k, int64_t* out_item_ids, float* out_scores,
                                int32_t* out_index, int32_t* out_complete, int32_t* out_n_survivors, float* out_cut, void* workspace,
                                int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream) {
-  return flat_all_sq8_stream(ix, t, scorer, q, n_queries, fetch, sample_rows, cap, k, out_item_ids, out_scores, out_index, out_complete,
-                             out_n_survivors, out_cut, workspace, workspace_bytes, options, stream, "nann_search_all_sq8_stream");
+  return flat_all_sq8(kSq8Stream, ix, t, nullptr, scorer, q, n_queries, fetch, sample_rows, cap, k, out_item_ids, out_scores, out_index,
+                      out_complete, out_n_survivors, out_cut, nullptr, nullptr, workspace, workspace_bytes, options, stream,
+                      "nann_search_all_sq8_stream");
 }
-
 
 // ---- the certified form: the per-row error terms and the search (nann_sq8.h) -------------------------------------
 int nann_sq8_bounds_create(const nann_index* ix, const nann_sq8* t, nann_stream_t stream, nann_sq8_bounds** out) {
@@ -2114,109 +1912,77 @@ int nann_sq8_bounds_view(const nann_sq8_bounds* b, const float** err, const floa
 int nann_search_all_sq8_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
                                               const nann_scorer* scorer, int64_t n_queries, int32_t fetch, int64_t cap, int32_t k,
                                               int64_t* nbytes) {
-  const char* who = "nann_search_all_sq8_exact_workspace_bytes";
-  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  FlatBy by;
-  ScanLayout L;
-  Sq8ExactLayout X;
-  const int rc = flat_sq8_exact_check(ix, t, b, scorer, n_queries, fetch, cap, k, who, &by, &L, &X);
-  if (rc) return rc;
-  *nbytes = n_queries == 0 || k == 0 ? 0 : (int64_t)X.total;
-  return NANN_OK;
+  return flat_sq8_size(kSq8Exact, ix, t, b, scorer, n_queries, fetch, 0, cap, k, nbytes, "nann_search_all_sq8_exact_workspace_bytes");
 }
 int nann_search_all_sq8_exact_layout(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
                                      int64_t n_queries, int32_t fetch, int64_t cap, int32_t k, int64_t out[8]) {
   const char* who = "nann_search_all_sq8_exact_layout";
   if (!out) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  FlatBy by;
-  ScanLayout L;
-  Sq8ExactLayout X;
-  const int rc = flat_sq8_exact_check(ix, t, b, scorer, n_queries, fetch, cap, k, who, &by, &L, &X);
+  Sq8Plan P;
+  const int rc = flat_sq8_plan(kSq8Exact, ix, t, b, scorer, n_queries, fetch, 0, cap, k, who, &P);
   if (rc) return rc;
-  out[0] = L.chunk;
-  out[1] = X.cap;
-  out[2] = (int64_t)X.off_xsplits;
-  out[3] = (int64_t)X.off_rows;
-  out[4] = (int64_t)X.off_terms;
+  out[0] = P.chunk;
+  out[1] = P.E.cap;
+  out[2] = (int64_t)P.E.off_xsplits;
+  out[3] = (int64_t)P.E.off_rows;
+  out[4] = (int64_t)P.E.off_terms;
   out[5] = (int64_t)sizeof(Sq8QTerms);
-  out[6] = (int64_t)X.off_a_scores;
-  out[7] = (int64_t)X.total;
+  out[6] = (int64_t)P.E.off_a_scores;
+  out[7] = (int64_t)P.E.total;
   return NANN_OK;
 }
 int nann_search_all_sq8_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
                               const float* q, int64_t n_queries, int32_t fetch, int64_t cap, int32_t k, int64_t* out_item_ids,
                               float* out_scores, int32_t* out_index, int32_t* out_certified, int32_t* out_n_survivors,
                               void* workspace, int64_t workspace_bytes, const nann_search_options* options, nann_stream_t stream) {
-  return flat_all_sq8_exact(ix, t, b, scorer, q, n_queries, fetch, cap, k, out_item_ids, out_scores, out_index, out_certified,
-                            out_n_survivors, workspace, workspace_bytes, options, stream, "nann_search_all_sq8_exact");
+  return flat_all_sq8(kSq8Exact, ix, t, b, scorer, q, n_queries, fetch, 0, cap, k, out_item_ids, out_scores, out_index, out_certified,
+                      out_n_survivors, nullptr, nullptr, nullptr, workspace, workspace_bytes, options, stream, "nann_search_all_sq8_exact");
 }
 
 // ---- the certified range form (nann_sq8.h) ------------------------------------------------------------------------
 int nann_search_all_range_sq8_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
                                                     const nann_scorer* scorer, int64_t n_queries, int64_t cap, int64_t* nbytes) {
-  const char* who = "nann_search_all_range_sq8_exact_workspace_bytes";
-  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  FlatBy by;
-  ScanLayout L;
-  Sq8RangeLayout R;
-  const int rc = flat_sq8_range_check(ix, t, b, scorer, n_queries, cap, who, &by, &L, &R);
-  if (rc) return rc;
-  *nbytes = n_queries == 0 ? 0 : (int64_t)R.total;
-  return NANN_OK;
+  return flat_sq8_size(kSq8Range, ix, t, b, scorer, n_queries, 0, 0, cap, 0, nbytes, "nann_search_all_range_sq8_exact_workspace_bytes");
 }
 int nann_search_all_range_sq8_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
                                     const float* q, int64_t n_queries, const float* thresholds, int64_t cap, int64_t capacity,
                                     int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
                                     int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
                                     const nann_search_options* options, nann_stream_t stream) {
-  return flat_range_sq8_exact(ix, t, b, scorer, q, n_queries, thresholds, cap, capacity, out_row_splits, out_item_ids, out_scores,
-                              out_index, out_certified, out_n_survivors, workspace, workspace_bytes, options, stream,
-                              "nann_search_all_range_sq8_exact");
+  return flat_range_sq8(kSq8Range, ix, t, b, scorer, q, n_queries, thresholds, cap, capacity, out_row_splits, out_item_ids, out_scores,
+                        out_index, out_certified, out_n_survivors, workspace, workspace_bytes, options, stream,
+                        "nann_search_all_range_sq8_exact");
 }
 
 // ---- the certified streamed forms (nann_sq8.h) ---------------------------------------------------------------------
 int nann_search_all_sq8_stream_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
                                                      const nann_scorer* scorer, int64_t n_queries, int32_t fetch, int64_t sample_rows,
                                                      int64_t cap, int32_t k, int64_t* nbytes) {
-  const char* who = "nann_search_all_sq8_stream_exact_workspace_bytes";
-  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  FlatBy by;
-  ScanLayout L;
-  Sq8CertLayout C;
-  const int rc = flat_sq8_cert_check(ix, t, b, scorer, n_queries, fetch, sample_rows, cap, k, who, &by, &L, &C);
-  if (rc) return rc;
-  *nbytes = n_queries == 0 || k == 0 ? 0 : (int64_t)C.total;
-  return NANN_OK;
+  return flat_sq8_size(kSq8StreamExact, ix, t, b, scorer, n_queries, fetch, sample_rows, cap, k, nbytes,
+                       "nann_search_all_sq8_stream_exact_workspace_bytes");
 }
 int nann_search_all_sq8_stream_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
                                      const float* q, int64_t n_queries, int32_t fetch, int64_t sample_rows, int64_t cap, int32_t k,
                                      int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_certified,
                                      int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
                                      const nann_search_options* options, nann_stream_t stream) {
-  return flat_all_sq8_stream_exact(ix, t, b, scorer, q, n_queries, fetch, sample_rows, cap, k, out_item_ids, out_scores, out_index,
-                                   out_certified, out_n_survivors, workspace, workspace_bytes, options, stream,
-                                   "nann_search_all_sq8_stream_exact");
+  return flat_all_sq8(kSq8StreamExact, ix, t, b, scorer, q, n_queries, fetch, sample_rows, cap, k, out_item_ids, out_scores, out_index,
+                      out_certified, out_n_survivors, nullptr, nullptr, nullptr, workspace, workspace_bytes, options, stream,
+                      "nann_search_all_sq8_stream_exact");
 }
 int nann_search_all_range_sq8_stream_exact_workspace_bytes(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b,
                                                            const nann_scorer* scorer, int64_t n_queries, int64_t cap, int64_t* nbytes) {
-  const char* who = "nann_search_all_range_sq8_stream_exact_workspace_bytes";
-  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
-  FlatBy by;
-  int chunk = 0;
-  Sq8RangeLayout R;
-  const int rc = flat_sq8_cert_range_check(ix, t, b, scorer, n_queries, cap, who, &by, &chunk, &R);
-  if (rc) return rc;
-  *nbytes = n_queries == 0 ? 0 : (int64_t)R.total;
-  return NANN_OK;
+  return flat_sq8_size(kSq8StreamRange, ix, t, b, scorer, n_queries, 0, 0, cap, 0, nbytes,
+                       "nann_search_all_range_sq8_stream_exact_workspace_bytes");
 }
 int nann_search_all_range_sq8_stream_exact(const nann_index* ix, const nann_sq8* t, const nann_sq8_bounds* b, const nann_scorer* scorer,
                                            const float* q, int64_t n_queries, const float* thresholds, int64_t cap, int64_t capacity,
                                            int64_t* out_row_splits, int64_t* out_item_ids, float* out_scores, int32_t* out_index,
                                            int32_t* out_certified, int32_t* out_n_survivors, void* workspace, int64_t workspace_bytes,
                                            const nann_search_options* options, nann_stream_t stream) {
-  return flat_range_sq8_stream_exact(ix, t, b, scorer, q, n_queries, thresholds, cap, capacity, out_row_splits, out_item_ids, out_scores,
-                                     out_index, out_certified, out_n_survivors, workspace, workspace_bytes, options, stream,
-                                     "nann_search_all_range_sq8_stream_exact");
+  return flat_range_sq8(kSq8StreamRange, ix, t, b, scorer, q, n_queries, thresholds, cap, capacity, out_row_splits, out_item_ids,
+                        out_scores, out_index, out_certified, out_n_survivors, workspace, workspace_bytes, options, stream,
+                        "nann_search_all_range_sq8_stream_exact");
 }
 
 }  // extern "C"

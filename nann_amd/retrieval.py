@@ -528,25 +528,41 @@ def search_all_sq8(index, sq8, scorer, q, k, fetch=None, options=None, return_fe
     fetch=None means min(4 * k, 1024, n_items): a convenience default, NOT a tuned one -- recall against search_all grows
     with fetch, and so does the selection's time; measure on your corpus (tools/sq8_rate.py).  k <= fetch <= 1024.
     return_fetch: also return the approximate stage's lists.  Asynchronous on torch's current stream."""
+    fetch = min(4 * int(k), 1024, int(index.n_items)) if fetch is None else int(fetch)
+    lists = [(torch.int32, max(fetch, 0)), (torch.float32, max(fetch, 0))] if return_fetch else [None, None]
+    ids, scores, rows, (f_index, f_scores), ws = _search_all_sq8("search_all_sq8", index, sq8, (), scorer, q, k, (fetch,), lists, options)
+    return Sq8Result(ids, scores, rows, f_index, f_scores, fetch, ws)
+
+
+def _search_all_sq8(name, index, sq8, bounds, scorer, q, k, shape, extras, options, redo=None):
+    """The top-k sq8 calls (nann_<name> and its _workspace_bytes): q to f32 on the device, the [B, k] outputs, the workspace and
+    the call -> (item_ids, scores, index, the extra outputs, workspace).  `bounds`: () for the forms that take none, else
+    (the Sq8Bounds or None,).  `shape`: what the form takes between n_queries and k -- fetch, then sample_rows and cap where it has
+    them.  `extras`: the form's outputs behind out_index, each None (a NULL) or (dtype, width) of a tensor [B, width], [B] at width
+    None; the per-query ones start at 0, and the first is the flag of the fallback.  `redo`: None, or what re-runs the queries it
+    is given and returns their item_ids / scores / index: the flag is read back -- ONE synchronisation -- and the queries it
+    leaves at 0 are re-run."""
     dev = index.device
     q = q.to(device=dev, dtype=torch.float32).contiguous()
     b, k = q.shape[0], int(k)
-    fetch = min(4 * k, 1024, int(index.n_items)) if fetch is None else int(fetch)
-    kk, ff = max(k, 0), max(fetch, 0)
-    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
-    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
-    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
-    f_index = torch.empty((b, ff), dtype=torch.int32, device=dev) if return_fetch else None
-    f_scores = torch.empty((b, ff), dtype=torch.float32, device=dev) if return_fetch else None
+    out = [torch.empty((b, max(k, 0)), dtype=dt, device=dev) for dt in (torch.int64, torch.float32, torch.int32)]
+    def extra(dtype, width):
+        return torch.zeros(b, dtype=dtype, device=dev) if width is None else torch.empty((b, width), dtype=dtype, device=dev)
+
+    extras = [e and extra(*e) for e in extras]
+    head = (index.handle, sq8.handle) + tuple(h.handle if h is not None else None for h in bounds) + (scorer.handle,)
     nbytes = C.c_int64(0)
-    _check(lib().nann_search_all_sq8_workspace_bytes(index.handle, sq8.handle, scorer.handle, b, fetch, k, C.byref(nbytes)),
-           "search_all_sq8")
+    _check(getattr(lib(), "nann_" + name + "_workspace_bytes")(*head, b, *shape, k, C.byref(nbytes)), name)
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _check(lib().nann_search_all_sq8(index.handle, sq8.handle, scorer.handle, _ptr(q), b, fetch, k, _ptr(out_ids),
-                                         _ptr(out_scores), _ptr(out_index), _ptr(f_index), _ptr(f_scores), _ptr(ws), ws.numel(),
-                                         C.byref(options) if options is not None else None, _stream()), "search_all_sq8")
-    return Sq8Result(out_ids, out_scores, out_index, f_index, f_scores, fetch, ws)
+        _check(getattr(lib(), "nann_" + name)(*head, _ptr(q), b, *shape, k, *[_ptr(t) for t in out + extras], _ptr(ws), ws.numel(),
+                                              C.byref(options) if options is not None else None, _stream()), name)
+    if redo is not None and b > 0 and k > 0:
+        todo = torch.nonzero(extras[0] == 0).flatten()  # (the synchronisation)
+        if todo.numel() > 0:
+            r = redo(q[todo])
+            out[0][todo], out[1][todo], out[2][todo] = r.item_ids, r.scores, r.index
+    return out[0], out[1], out[2], extras, ws
 
 
 class Sq8StreamResult:
@@ -572,34 +588,13 @@ def search_all_sq8_stream(index, sq8, scorer, q, k, fetch=None, sample_rows=None
     -- ONE synchronisation of the stream with the host -- and re-runs the incomplete queries through search_all_sq8 at the same
     fetch.  fallback=False: asynchronous on torch's current stream, nothing read back.  fetch=None as in search_all_sq8;
     k <= fetch <= 1024, k <= cap.  return_stats: also return n_survivors and cut."""
-    dev = index.device
-    q = q.to(device=dev, dtype=torch.float32).contiguous()
-    b, k = q.shape[0], int(k)
-    fetch = min(4 * k, 1024, int(index.n_items)) if fetch is None else int(fetch)
-    sample_rows = 0 if sample_rows is None else int(sample_rows)
-    cap = int(cap)
-    kk = max(k, 0)
-    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
-    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
-    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
-    complete = torch.zeros(b, dtype=torch.int32, device=dev)
-    n_surv = torch.zeros(b, dtype=torch.int32, device=dev) if return_stats else None
-    cut = torch.zeros(b, dtype=torch.float32, device=dev) if return_stats else None
-    nbytes = C.c_int64(0)
-    _check(lib().nann_search_all_sq8_stream_workspace_bytes(index.handle, sq8.handle, scorer.handle, b, fetch, sample_rows, cap, k,
-                                                            C.byref(nbytes)), "search_all_sq8_stream")
-    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib().nann_search_all_sq8_stream(index.handle, sq8.handle, scorer.handle, _ptr(q), b, fetch, sample_rows, cap, k,
-                                                _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(complete), _ptr(n_surv),
-                                                _ptr(cut), _ptr(ws), ws.numel(), C.byref(options) if options is not None else None,
-                                                _stream()), "search_all_sq8_stream")
-    if fallback and b > 0 and k > 0:
-        todo = torch.nonzero(complete == 0).flatten()  # (the synchronisation)
-        if todo.numel() > 0:
-            r = search_all_sq8(index, sq8, scorer, q[todo], k, fetch=fetch, options=options)
-            out_ids[todo], out_scores[todo], out_index[todo] = r.item_ids, r.scores, r.index
-    return Sq8StreamResult(out_ids, out_scores, out_index, complete, n_surv, cut, fetch, cap, ws)
+    fetch = min(4 * int(k), 1024, int(index.n_items)) if fetch is None else int(fetch)
+    shape = (fetch, 0 if sample_rows is None else int(sample_rows), int(cap))
+    stats = [(torch.int32, None), (torch.float32, None)] if return_stats else [None, None]
+    redo = (lambda qq: search_all_sq8(index, sq8, scorer, qq, k, fetch=fetch, options=options)) if fallback else None
+    ids, scores, rows, (complete, n_surv, cut), ws = _search_all_sq8("search_all_sq8_stream", index, sq8, (), scorer, q, k, shape,
+                                                                     [(torch.int32, None)] + stats, options, redo)
+    return Sq8StreamResult(ids, scores, rows, complete, n_surv, cut, fetch, shape[2], ws)
 
 
 class Sq8Bounds:
@@ -669,32 +664,17 @@ def search_all_sq8_exact(index, sq8, bounds, scorer, q, k, fetch=None, cap=2048,
     fallback=True: the wrapper reads `certified` back -- ONE synchronisation of the stream with the host -- and re-runs the
     uncertified queries through search_all, so that the result is exact for EVERY query (certified and n_survivors stay as the
     device call left them).  fallback=False: asynchronous on torch's current stream, nothing read back."""
-    dev = index.device
-    q = q.to(device=dev, dtype=torch.float32).contiguous()
-    b, k = q.shape[0], int(k)
-    fetch = min(max(k, 1), 1024, int(index.n_items)) if fetch is None else int(fetch)
-    cap = int(cap)
-    kk = max(k, 0)
-    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
-    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
-    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
-    certified = torch.zeros(b, dtype=torch.int32, device=dev)
-    n_surv = torch.zeros(b, dtype=torch.int32, device=dev)
-    nbytes = C.c_int64(0)
-    bh = bounds.handle if bounds is not None else None
-    _check(lib().nann_search_all_sq8_exact_workspace_bytes(index.handle, sq8.handle, bh, scorer.handle, b, fetch, cap, k,
-                                                           C.byref(nbytes)), "search_all_sq8_exact")
-    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib().nann_search_all_sq8_exact(index.handle, sq8.handle, bh, scorer.handle, _ptr(q), b, fetch, cap, k, _ptr(out_ids),
-                                               _ptr(out_scores), _ptr(out_index), _ptr(certified), _ptr(n_surv), _ptr(ws), ws.numel(),
-                                               C.byref(options) if options is not None else None, _stream()), "search_all_sq8_exact")
-    if fallback and b > 0 and k > 0:
-        todo = torch.nonzero(certified == 0).flatten()  # (the synchronisation)
-        if todo.numel() > 0:
-            r = search_all(index, scorer, q[todo], k, options=options)
-            out_ids[todo], out_scores[todo], out_index[todo] = r.item_ids, r.scores, r.index
-    return Sq8ExactResult(out_ids, out_scores, out_index, certified, n_surv, fetch, cap, ws)
+    fetch = min(max(int(k), 1), 1024, int(index.n_items)) if fetch is None else int(fetch)
+    return _search_all_sq8_certified("search_all_sq8_exact", index, sq8, bounds, scorer, q, k, (fetch, int(cap)), fallback, options)
+
+
+def _search_all_sq8_certified(name, index, sq8, bounds, scorer, q, k, shape, fallback, options):
+    """The two certified top-k calls -> Sq8ExactResult.  `shape`: (fetch, cap) or (fetch, sample_rows, cap); the fallback re-runs
+    the uncertified queries through search_all."""
+    redo = (lambda qq: search_all(index, scorer, qq, k, options=options)) if fallback else None
+    ids, scores, rows, (certified, n_surv), ws = _search_all_sq8(name, index, sq8, (bounds,), scorer, q, k, shape,
+                                                                 [(torch.int32, None)] * 2, options, redo)
+    return Sq8ExactResult(ids, scores, rows, certified, n_surv, shape[0], shape[-1], ws)
 
 
 def search_all_sq8_stream_exact(index, sq8, bounds, scorer, q, k, fetch=None, sample_rows=None, cap=8192, fallback=True, options=None):
@@ -706,35 +686,9 @@ def search_all_sq8_stream_exact(index, sq8, bounds, scorer, q, k, fetch=None, sa
     wrong row.  result.certified[b] == 1 iff at most `cap` rows survived (and the query is finite); an uncertified row of the
     result is the exact top k of the sample's fetch list.  Arguments, fetch=None and fallback as in search_all_sq8_exact;
     k <= fetch <= cap -> Sq8ExactResult."""
-    dev = index.device
-    q = q.to(device=dev, dtype=torch.float32).contiguous()
-    b, k = q.shape[0], int(k)
-    fetch = min(max(k, 1), 1024, int(index.n_items)) if fetch is None else int(fetch)
-    sample_rows = 0 if sample_rows is None else int(sample_rows)
-    cap = int(cap)
-    kk = max(k, 0)
-    out_ids = torch.empty((b, kk), dtype=torch.int64, device=dev)
-    out_scores = torch.empty((b, kk), dtype=torch.float32, device=dev)
-    out_index = torch.empty((b, kk), dtype=torch.int32, device=dev)
-    certified = torch.zeros(b, dtype=torch.int32, device=dev)
-    n_surv = torch.zeros(b, dtype=torch.int32, device=dev)
-    nbytes = C.c_int64(0)
-    bh = bounds.handle if bounds is not None else None
-    _check(lib().nann_search_all_sq8_stream_exact_workspace_bytes(index.handle, sq8.handle, bh, scorer.handle, b, fetch, sample_rows,
-                                                                  cap, k, C.byref(nbytes)), "search_all_sq8_stream_exact")
-    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib().nann_search_all_sq8_stream_exact(index.handle, sq8.handle, bh, scorer.handle, _ptr(q), b, fetch, sample_rows, cap,
-                                                      k, _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(certified),
-                                                      _ptr(n_surv), _ptr(ws), ws.numel(),
-                                                      C.byref(options) if options is not None else None, _stream()),
-               "search_all_sq8_stream_exact")
-    if fallback and b > 0 and k > 0:
-        todo = torch.nonzero(certified == 0).flatten()  # (the synchronisation)
-        if todo.numel() > 0:
-            r = search_all(index, scorer, q[todo], k, options=options)
-            out_ids[todo], out_scores[todo], out_index[todo] = r.item_ids, r.scores, r.index
-    return Sq8ExactResult(out_ids, out_scores, out_index, certified, n_surv, fetch, cap, ws)
+    fetch = min(max(int(k), 1), 1024, int(index.n_items)) if fetch is None else int(fetch)
+    shape = (fetch, 0 if sample_rows is None else int(sample_rows), int(cap))
+    return _search_all_sq8_certified("search_all_sq8_stream_exact", index, sq8, bounds, scorer, q, k, shape, fallback, options)
 
 
 def search_all_model(index, model, comm_seq, k, options=None):

@@ -840,6 +840,44 @@ int nann_search_lists(const nann_index* ix, const nann_partition* partition, con
                       float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status, void* workspace,
                       int64_t workspace_bytes, nann_stream_t stream);
 
+/* nann_search_lists_sq8 (IVF-SQ8): nann_search_lists over the int8 code table of the index (nann_sq8, declared below with the
+ * scalar-quantised exhaustive search) -- the lists are probed on the integer matrix cores by approximate score, the `fetch` best
+ * positions are re-ranked exactly.  The list scan is v_mfma_i32_16x16x64_i8 with a tile's 16 probing queries as one operand and
+ * 16 gathered code rows as the other (csrc/nann_lists.h).  t: nann_sq8_create(ix); the other arguments are
+ * nann_search_lists', with fetch in front of k.
+ * CONTRACT: for query i let C be the concatenation of the lists it names -- slot order, each list in its stored order, exactly
+ * nann_search_lists' -- and len_i its length.
+ *   1. Fetch: the min(fetch, len_i) best positions of C by APPROXIMATE score, the formula under "scalar-quantised exhaustive
+ *      search" below applied to the query's code (nann_sq8_encode's) and the row's code in t: the integer dot is exact, every
+ *      float step one f32 operation.  TopKV2 order, ties -> the lower position.  They go to out_fetch_pos i32 / out_fetch_scores
+ *      f32 [n_queries, fetch] (device; either may be NULL); behind the valid entries: position 0 and -inf (a failed query: the
+ *      whole row).
+ *   2. Result: the min(k, fetch, len_i) best of those positions by EXACT score, nann_score's bits for (query, row); ties -> the
+ *      lower position.  out_item_ids, out_scores, out_index, out_pos, n_out, status, the zeros behind n_out entries and the
+ *      failure of one query alone (a slot >= n_lists: status[i] = NANN_ERR_INDEX_OUT_OF_RANGE, n_out[i] = 0, a zeroed row) are
+ *      nann_search_lists'.
+ *   3. A query's answer does not depend on the batch it is in.
+ *   4. Where fetch >= len_i, query i's result is nann_search_lists' bit for bit.
+ * L2 and inner-product scorers, every d, f16 and bf16 rows (what a code table is made from).
+ * Workspace: device, 256-byte aligned, nann_search_lists_sq8_workspace_bytes(...) bytes.  S = max(fetch, n_probe x max_len) and
+ * the chunk rule are nann_search_lists' with fetch in the place of k; per query of a chunk the workspace holds 4 S bytes of
+ * scores, 8 fetch bytes per 16384 positions of S, d + 8 bytes of the query's code, scale and norm, 20 fetch + 4 k bytes of fetch
+ * lists, sorted positions, rows, exact scores and the selection, and per (query, slot) pair a tile of 152 bytes.
+ * Refusals: nann_search_lists' in its order with fetch in the place of k (so fetch < 0 -> NANN_ERR_BAD_ARGUMENT, fetch > 1024 ->
+ * NANN_ERR_UNSUPPORTED), and: a null handle, k outside [0, fetch] (named in front of the others), a table not made from ix ->
+ * NANN_ERR_BAD_ARGUMENT; an MLP scorer, an index of f32 rows -> NANN_ERR_UNSUPPORTED; fetch == 0, k == 0 or n_queries == 0 ->
+ * NANN_OK, nothing written.  Asynchronous on `stream`, no host read-back, re-entrant on shared handles.  Malformed device contents
+ * (probes) never fault: a slot is validated by the plan, every store is guarded. */
+struct nann_sq8; /* (its typedef stands with nann_sq8_create) */
+int nann_search_lists_sq8_workspace_bytes(const nann_index* ix, const nann_partition* partition, const struct nann_sq8* t,
+                                          const nann_scorer* scorer, int64_t n_queries, int32_t n_probe, int32_t fetch,
+                                          int32_t k, int64_t* nbytes);
+int nann_search_lists_sq8(const nann_index* ix, const nann_partition* partition, const struct nann_sq8* t, const nann_scorer* scorer,
+                          const float* q, int64_t n_queries, const int32_t* probes, int32_t n_probe, int32_t fetch, int32_t k,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out,
+                          int32_t* status, int32_t* out_fetch_pos, float* out_fetch_scores, void* workspace,
+                          int64_t workspace_bytes, nann_stream_t stream);
+
 /* ---- candidate-list search under a model: nann_search_candidates for whatever model the node names ---------------------
  * nann_search_candidates with the serving signature's input, as nann_search_all_model is to nann_search_all: comm_seq_f16 is
  * f16[n_users, seq_len, E] (what nann_search_model_opt and nann_search_all_model take), `cand` the same nann_candidates with

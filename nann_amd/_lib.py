@@ -90,6 +90,7 @@ SYMBOLS = [
     "nann_select_wide_workspace_bytes", "nann_select_wide",
     "nann_partition_create", "nann_partition_destroy", "nann_partition_info", "nann_partition_view",
     "nann_search_lists_workspace_bytes", "nann_search_lists",
+    "nann_search_lists_sq8_workspace_bytes", "nann_search_lists_sq8",
 ]
 
 
@@ -426,6 +427,11 @@ def lib():
         L.nann_search_lists.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + \
                                        [C.c_int64, C.c_void_p]
         L.nann_search_lists.restype = C.c_int
+        L.nann_search_lists_sq8_workspace_bytes.argtypes = [C.c_void_p] * 4 + [C.c_int64] + [C.c_int32] * 3 + [C.POINTER(C.c_int64)]
+        L.nann_search_lists_sq8_workspace_bytes.restype = C.c_int
+        L.nann_search_lists_sq8.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 9 + \
+                                           [C.c_int64, C.c_void_p]
+        L.nann_search_lists_sq8.restype = C.c_int
         L.nann_sq8_encode.argtypes = [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 4
         L.nann_sq8_encode.restype = C.c_int
         L.nann_search_all_sq8_workspace_bytes.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]

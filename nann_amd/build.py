@@ -23,7 +23,7 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 #   nann_attn.o, nann_attn_split.o   the attention model, f32 and split-f16 form
 #   nann_scan.o        the exhaustive search, with the range and wide selections (nann_range.h, nann_wide.h) and the int8 code table, scan and
 #                      streamed and certified survivor passes (nann_sq8.h, nann_sq8_inst.hip), and the shared-list search, whose scans are
-#                      ScanL2's (nann_lists.h, nann_lists_inst.hip); nann_scan_attn.o its scan under the attention model
+#                      ScanL2's and, over the code table, an int8 MFMA scan of its own (nann_lists.h, nann_lists_inst.hip); nann_scan_attn.o its scan under the attention model
 #   nann_filter.o      filtered retrieval, with the group cap (nann_groupcap.h) and the attribute predicates (nann_predicate.h)
 #   nann_cand.o        the candidate-list search, with the union and the fused top-k (nann_union.h, nann_fuse.h), the MMR
 #                      re-ranking (nann_mmr.h) and the user interests (nann_interests.h); nann_cand_attn.o its scorer under the
@@ -171,6 +171,9 @@ RULES = [
     # The list scans of the shared-list search (k_lists_scan_l2 / k_lists_scan_ip, nann_lists.h) stage their rows as k_scan_l2 does,
     # through the same ScanL2, and are held to the same.
     ("lists_scan_scratch", r"k_lists_scan_(l2|ip)", 0, None, "the list scan kernel"),
+    # The int8 list scan (k_lists_scan_sq8, nann_lists.h) keeps the A fragments of a tile's 16 queries, d / 16 registers, from the
+    # head of a work item to its end; spilled, every MFMA of the item would wait for a reload from private memory.
+    ("lists_scan_sq8_scratch", r"k_lists_scan_sq8", 0, None, "the int8 list scan kernel"),
 ]
 
 

@@ -14,7 +14,8 @@
 // kernels in nann_sq8.h), its certified form that returns nann_search_all's bits (nann_sq8_bounds, nann_search_all_sq8_exact) and
 // the certified range form that returns nann_search_all_range's (nann_search_all_range_sq8_exact), and both without a score buffer
 // (nann_search_all_sq8_stream_exact, nann_search_all_range_sq8_stream_exact); the row lists over an index
-// (nann_partition_create, ..) and the shared-list search over them (nann_search_lists; kernels in nann_lists.h).
+// (nann_partition_create, ..) and the shared-list search over them (nann_search_lists; kernels in nann_lists.h), also over the
+// code table with an exact re-rank (nann_search_lists_sq8).
 //
 // A source of nann_core.o.  What it takes from the other host sources, and what the traversal's forms (nann_traverse.hip) take
 // from it -- resolve_filter, resolve_predicates, resolve_groups, resolve_diversity, mmr_index, union_check, fuse_shape_check,
@@ -642,6 +643,53 @@ static int flat_lists(const nann_index* ix, const nann_partition* part, const na
   a.n_probe = n_probe;
   return launch_lists(a, L, q, (long long)n, k, static_cast<unsigned char*>(workspace), out_item_ids, out_scores, out_index, out_pos,
                       n_out, status, as_stream(stream));
+}
+
+// The int8 form (nann_search_lists_sq8): the null handles, k against fetch, then flat_lists_check held against fetch, then the
+// code table against the index.
+static Sq8Args flat_sq8_args(const nann_index* ix, const nann_sq8* t, const FlatBy& by);
+static int flat_lists_sq8_check(const nann_index* ix, const nann_partition* part, const nann_sq8* t, const nann_scorer* scorer,
+                                int64_t n, int32_t n_probe, int32_t fetch, int32_t k, const char* who, FlatBy* by) {
+  if (!ix || !part || !t || !scorer) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  if (fetch >= 0 && (k < 0 || k > fetch)) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": k must lie in [0, fetch]");
+  const int rc = flat_lists_check(ix, part, scorer, n, n_probe, fetch, who, by);
+  if (rc) return rc;
+  if (ix->desc.emb_dtype == NANN_F32) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": 16-bit rows (f16, bf16) only");
+  if (t->uid != ix->uid || t->n_items != ix->desc.n_items || t->d != ix->desc.d)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": the code table was made from another index");
+  return NANN_OK;
+}
+
+static int flat_lists_sq8(const nann_index* ix, const nann_partition* part, const nann_sq8* t, const nann_scorer* scorer,
+                          const float* q, int64_t n, const int32_t* probes, int32_t n_probe, int32_t fetch, int32_t k,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out,
+                          int32_t* status, int32_t* out_fetch_pos, float* out_fetch_scores, void* workspace, int64_t workspace_bytes,
+                          nann_stream_t stream, const char* who) {
+  FlatBy by;
+  int rc = flat_lists_sq8_check(ix, part, t, scorer, n, n_probe, fetch, k, who, &by);
+  if (rc) return rc;
+  if (n > 0 && n_probe > 0 && !probes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": probes is null while there are slots");
+  if (n == 0 || k == 0) return NANN_OK;  // (k <= fetch: fetch == 0 is here too)
+  if (!q || !out_item_ids || !status) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  const ListsSq8Layout X = lists_sq8_layout((long long)part->max_len, ix->desc.d, by.kind, (long long)n, n_probe, fetch, k);
+  rc = flat_workspace(workspace, workspace_bytes, X.total, who, "");
+  if (rc) return rc;
+  DeviceInfo di;
+  rc = device_info(&di);
+  if (rc) return rc;
+  ListsArgs a = {};
+  flat_rows_of(ix, &a);
+  a.kind = by.kind;
+  a.cus = di.cus;
+  a.list_splits = part->list_splits;
+  a.list_rows = part->list_rows;
+  a.n_lists = part->n_lists;
+  a.max_len = (long long)part->max_len;
+  a.probes = probes;
+  a.n_probe = n_probe;
+  return launch_lists_sq8(a, flat_sq8_args(ix, t, by), X, q, (long long)n, fetch, k, static_cast<unsigned char*>(workspace),
+                          out_item_ids, out_scores, out_index, out_pos, n_out, status, out_fetch_pos, out_fetch_scores,
+                          as_stream(stream));
 }
 
 // ---- union top-k (nann_union.h): a user's n_lists result lists -> the k best distinct rows -----------------------------------
@@ -1792,6 +1840,28 @@ int nann_search_lists(const nann_index* ix, const nann_partition* partition, con
                       int64_t workspace_bytes, nann_stream_t stream) {
   return flat_lists(ix, partition, scorer, q, n_queries, probes, n_probe, k, out_item_ids, out_scores, out_index, out_pos, n_out,
                     status, workspace, workspace_bytes, stream, "nann_search_lists");
+}
+int nann_search_lists_sq8_workspace_bytes(const nann_index* ix, const nann_partition* partition, const nann_sq8* t,
+                                          const nann_scorer* scorer, int64_t n_queries, int32_t n_probe, int32_t fetch, int32_t k,
+                                          int64_t* nbytes) {
+  const char* who = "nann_search_lists_sq8_workspace_bytes";
+  if (!nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  FlatBy by;
+  const int rc = flat_lists_sq8_check(ix, partition, t, scorer, n_queries, n_probe, fetch, k, who, &by);
+  if (rc) return rc;
+  *nbytes = n_queries == 0 || k == 0
+                ? 0
+                : (int64_t)lists_sq8_layout((long long)partition->max_len, ix->desc.d, by.kind, (long long)n_queries, n_probe, fetch, k).total;
+  return NANN_OK;
+}
+int nann_search_lists_sq8(const nann_index* ix, const nann_partition* partition, const nann_sq8* t, const nann_scorer* scorer,
+                          const float* q, int64_t n_queries, const int32_t* probes, int32_t n_probe, int32_t fetch, int32_t k,
+                          int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out,
+                          int32_t* status, int32_t* out_fetch_pos, float* out_fetch_scores, void* workspace,
+                          int64_t workspace_bytes, nann_stream_t stream) {
+  return flat_lists_sq8(ix, partition, t, scorer, q, n_queries, probes, n_probe, fetch, k, out_item_ids, out_scores, out_index,
+                        out_pos, n_out, status, out_fetch_pos, out_fetch_scores, workspace, workspace_bytes, stream,
+                        "nann_search_lists_sq8");
 }
 
 // ---- the int8 code table and the search over it (nann_sq8.h) ---------------------------------------------------------------

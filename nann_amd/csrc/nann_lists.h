@@ -30,11 +30,30 @@
 // group's rows in order -- ballots find a row's peers of the same list among the 64, the first of them advances the group's
 // cursor of that list.  Integer counts commute and a cursor has one writer: the layout does not depend on timing, every list
 // comes out in ascending row order.
+//
+// ---- the int8 form (nann_search_lists_sq8): the same plan over the code table of the index (nann_sq8.h), an
+// approximate fetch of the `fetch` best positions of a query's concatenation and their exact re-rank.  Per chunk:
+//   1. k_lists_plan, unchanged; the chunk's queries through the table's encoder (launch_sq8_encode).  No qT.
+//   2. k_lists_scan_sq8 (persistent grid, the same work items): v_mfma_i32_16x16x64_i8 with the tile's 16 QUERIES as A and 16
+//      gathered code ROWS as B.  Operand element j of lane (r = lane & 15, h = lane >> 4) in k-step s is byte 64 s + 16 h + j of
+//      query / row r -- the same bytes on both sides, all an integer dot product needs.  The tile's query fragments are loaded
+//      once per item and stay in registers (d / 16 VGPRs); a code row is never staged: four lanes cover 64 contiguous bytes of
+//      it with one 16-byte load each.  Each wavefront takes 64 rows of the block as 4 groups of 16.  The C/D layout puts the row
+//      on the lane (col = lane & 15) and the query in the register (4 (lane >> 4) + reg): one store of one query covers 16
+//      consecutive positions.  The epilogue is k_scan_sq8's: sq8_score (nann_sq8.h), the same bits.
+//   3. k_lists_pad, k_scan_slab_topk at width fetch.
+//   4. k_lists_fetch_sq8 (one workgroup per query): the merge of the slabs' lists at min(fetch, len_q) -- the fetch lists, to
+//      the caller's arrays --, the fetched positions in ascending order (sq8_sort_i32, the sort of k_sq8_sort_rows) and their
+//      rows, as candidate lists of `fetch` entries a query (behind the fetched ones: row 0, never selected).
+//   5. the candidate-list search's plan and scorer over those lists (launch_cand_scores, nann_cand.h): nann_score's bits.
+//   6. k_lists_finish_sq8 (one workgroup per query): wg_topk over the min(fetch, len_q) exact scores -- list position order is
+//      concatenation order, so ties fall to the lower position --, then the outputs as k_lists_finish writes them.
 #pragma once
 #include <cstddef>
 
 #include "nann_scan.h"
 #include "nann_search.h"
+#include "nann_sq8.h"
 
 namespace nann {
 
@@ -84,6 +103,23 @@ ListsLayout lists_layout(long long max_len, int d, long long n_queries, int n_pr
 int launch_lists(const ListsArgs& a, const ListsLayout& L, const float* q, long long n_queries, int k, unsigned char* ws,
                  int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos, int32_t* n_out, int32_t* status,
                  hipStream_t st);
+
+// the int8 form.  workspace of a call: [the ListsLayout at k = fetch and without qT: scores f32[chunk, S], the slabs' lists, the
+// fetch positions i32[chunk, fetch] (off_pos), the plan | what follows], every part a multiple of 256 bytes
+struct ListsSq8Layout {
+  ListsLayout L;
+  size_t off_qcodes, off_qscales, off_qnorms;  // the chunk's encoded queries
+  size_t off_fscores;                          // the fetch lists' scores f32[chunk, fetch]
+  size_t off_spos, off_rows, off_splits;       // positions ascending and their rows i32[chunk, fetch], row_splits i64[chunk + 1]
+  size_t off_sel;                              // the finish's selection i32[chunk, k]: places in a query's sorted list
+  size_t off_cand;                             // the candidate-list search's workspace (CandLayout) for chunk * fetch positions
+  size_t total;
+};
+ListsSq8Layout lists_sq8_layout(long long max_len, int d, int kind, long long n_queries, int n_probe, int fetch, int k);
+// t: the code table of the index a names.  out_fetch_pos / out_fetch_scores [n_queries, fetch]: may be null.
+int launch_lists_sq8(const ListsArgs& a, const Sq8Args& t, const ListsSq8Layout& X, const float* q, long long n_queries, int fetch,
+                     int k, unsigned char* ws, int64_t* out_item_ids, float* out_scores, int32_t* out_index, int32_t* out_pos,
+                     int32_t* n_out, int32_t* status, int32_t* out_fetch_pos, float* out_fetch_scores, hipStream_t st);
 
 // the partition build.  info i64[4] (device): n_listed_rows, max_len, rows with a value >= n_lists, unused
 size_t lists_build_groups(long long n_items, int n_lists);
@@ -435,19 +471,16 @@ struct ListsFinishArgs {
   int32_t* status;
 };
 
-__global__ __launch_bounds__(kNT) void k_lists_finish(ListsFinishArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned char scratch[sizeof(TopkScratch)];
-  __shared__ long long sbegin[kListsMaxProbe];
-  __shared__ int32_t soff[kListsMaxProbe];
-  const size_t qi = blockIdx.x;
+// The slots' offsets of query qi again, by the first wavefront: an exclusive prefix of the lengths over the lanes.  sbegin, soff:
+// LDS, kListsMaxProbe entries each; a barrier publishes them.
+__device__ __forceinline__ void lists_slot_offsets(const int32_t* __restrict__ probes, size_t qi, int n_probe, int n_lists,
+                                                   const int64_t* __restrict__ list_splits, long long* sbegin, int32_t* soff) {
   const int tid = threadIdx.x;
-  const ListsQuery Q = a.queries[qi];
-  const int kk = Q.status != 0 ? 0 : min(a.k, Q.len);
-  if (tid < 64) {  // the slots' offsets again: an exclusive prefix of the lengths over the lanes
-    const int32_t l = tid < a.n_probe ? a.probes[qi * a.n_probe + tid] : -1;
-    const bool named = l >= 0 && l < a.n_lists;
-    const long long b = named ? a.list_splits[l] : 0;
-    int32_t len = named ? (int32_t)(a.list_splits[l + 1] - b) : 0, at = len;
+  if (tid < 64) {
+    const int32_t l = tid < n_probe ? probes[qi * n_probe + tid] : -1;
+    const bool named = l >= 0 && l < n_lists;
+    const long long b = named ? list_splits[l] : 0;
+    int32_t len = named ? (int32_t)(list_splits[l + 1] - b) : 0, at = len;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
       const int32_t t = __shfl_up(at, o);
@@ -456,6 +489,29 @@ __global__ __launch_bounds__(kNT) void k_lists_finish(ListsFinishArgs a) {
     sbegin[tid] = b;
     soff[tid] = at - len;
   }
+}
+
+// position of a query's concatenation -> row of the table
+__device__ __forceinline__ int32_t lists_row_at(int32_t pos, int32_t len_q, int n_probe, const long long* sbegin, const int32_t* soff,
+                                                const int32_t* __restrict__ list_rows) {
+  int lo = 0, hi = n_probe;  // soff[lo] <= pos < soff[hi]: the last slot that starts at or before pos holds it
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (soff[mid] <= pos) lo = mid; else hi = mid;
+  }
+  // (pos < len_q unless a NaN score outranked the padding -- outside the contract, as for nann_topk, but never out of bounds)
+  return pos < len_q ? list_rows[sbegin[lo] + (pos - soff[lo])] : 0;
+}
+
+__global__ __launch_bounds__(kNT) void k_lists_finish(ListsFinishArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char scratch[sizeof(TopkScratch)];
+  __shared__ long long sbegin[kListsMaxProbe];
+  __shared__ int32_t soff[kListsMaxProbe];
+  const size_t qi = blockIdx.x;
+  const int tid = threadIdx.x;
+  const ListsQuery Q = a.queries[qi];
+  const int kk = Q.status != 0 ? 0 : min(a.k, Q.len);
+  lists_slot_offsets(a.probes, qi, a.n_probe, a.n_lists, a.list_splits, sbegin, soff);
   __syncthreads();
   if (kk > 0) {
     wg_topk(a.cand_rows + qi * a.n_in, a.cand_scores + qi * a.n_in, nullptr, a.n_in, kk, nullptr, a.pos + qi * a.k,
@@ -468,13 +524,208 @@ __global__ __launch_bounds__(kNT) void k_lists_finish(ListsFinishArgs a) {
     int64_t id = 0;
     if (i < kk) {
       pos = a.pos[at];
-      int lo = 0, hi = a.n_probe;  // soff[lo] <= pos < soff[hi]: the last slot that starts at or before pos holds it
-      while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (soff[mid] <= pos) lo = mid; else hi = mid;
-      }
-      // (pos < len_q unless a NaN score outranked the padding -- outside the contract, as for nann_topk, but never out of bounds)
-      row = pos < Q.len ? a.list_rows[sbegin[lo] + (pos - soff[lo])] : 0;
+      row = lists_row_at(pos, Q.len, a.n_probe, sbegin, soff, a.list_rows);
+      id = a.item_ids[row];
+    } else if (a.out_scores) {
+      a.out_scores[at] = 0.0f;
+    }
+    a.out_item_ids[at] = id;
+    if (a.out_index) a.out_index[at] = row;
+    if (a.out_pos) a.out_pos[at] = pos;
+  }
+  if (tid == 0) {
+    if (a.n_out) a.n_out[qi] = kk;
+    a.status[qi] = Q.status;
+  }
+}
+
+// ---- the int8 form ------------------------------------------------------------------------------------------------------------
+// Work item w as in lists_scan.  LDS: the block's 256 row numbers (behind the list's end: its last row again; a number outside the
+// table becomes row 0) and, per query of the tile, its scale term, its norm term (sq8_scan_front's qs and qa) and where its
+// run of the score buffer starts.  Wavefront v takes rows [64 v, +64) of the block as 4 groups of 16; per k-step the four
+// groups' 16-byte loads are issued, then the four MFMAs.  No row of the table passes through LDS.
+template <int NS, int METRIC>  // NS = d / 64 k-steps
+__global__ __launch_bounds__(kScanRows) void k_lists_scan_sq8(const int8_t* __restrict__ codes, const float* __restrict__ scales,
+                                                              const int32_t* __restrict__ norms, long long n_items,
+                                                              const int32_t* __restrict__ list_rows, const ListsHead* __restrict__ head,
+                                                              const long long* __restrict__ blk, const ListsTile* __restrict__ tiles,
+                                                              const int8_t* __restrict__ qcodes, const float* __restrict__ qscales,
+                                                              const int32_t* __restrict__ qnorms, float* __restrict__ scores,
+                                                              long long stride /* S */) {
+  constexpr int D = NS * 64, TQ = kScanTileQueries, G = 4;  // G groups of 16 rows per wavefront
+  static_assert(TQ == 16 && kScanRows == 4 * 16 * G, "a tile is the A operand; four wavefronts of 64 rows");
+  __shared__ int32_t ids[kScanRows];
+  __shared__ float qs[TQ], qa[TQ];
+  __shared__ long long dst[TQ];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, h = lane >> 4;
+  const long long n_work = head->n_work;
+  const int n_tiles = head->n_tiles;
+  for (long long w = blockIdx.x; w < n_work; w += gridDim.x) {
+    int lo = 0, hi = n_tiles;  // blk[lo] <= w < blk[hi]
+    while (hi - lo > 1) {
+      const int mid = lo + (hi - lo) / 2;
+      if (blk[mid] <= w) lo = mid; else hi = mid;
+    }
+    const ListsTile* __restrict__ t = tiles + lo;
+    const int len = t->len, nq = t->nq;
+    const int row0 = (int)(w - blk[lo]) * kScanRows;  // the block's first row of the list
+    __syncthreads();  // (every wavefront has left the item before: its row numbers and query terms may go)
+    {
+      const int32_t id = list_rows[t->begin + min(row0 + tid, len - 1)];
+      ids[tid] = id >= 0 && id < n_items ? id : 0;
+    }
+    if (tid < TQ) {
+      const int qi = t->q[tid];
+      const float sq = qscales[qi];
+      qs[tid] = METRIC == MT_IP ? sq : __fmul_rn(2.0f, sq);
+      qa[tid] = __fmul_rn(__fmul_rn(sq, sq), (float)qnorms[qi]);
+      dst[tid] = (long long)qi * stride + t->off[tid];
+    }
+    __syncthreads();
+    const int wrow0 = row0 + wave * (16 * G);
+    if (wrow0 >= len) continue;  // (uniform over the wavefront; the barriers stand at the head of an item)
+    // A: query r of the tile, bytes [64 s + 16 h, +16) of k-step s -- once per item, in registers to its end
+    i32x4v a[NS];
+    {
+      const int8_t* qrow = qcodes + (size_t)t->q[r] * D + h * 16;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) a[s] = *reinterpret_cast<const i32x4v*>(qrow + s * 64);
+    }
+    // B: row r of group g, the same bytes
+    const int8_t* xrow[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) xrow[g] = codes + (size_t)ids[wave * (16 * G) + 16 * g + r] * D + h * 16;
+    i32x4v acc[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) acc[g] = i32x4v{0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      i32x4v b[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) b[g] = *reinterpret_cast<const i32x4v*>(xrow[g] + s * 64);
+#pragma unroll
+      for (int g = 0; g < G; ++g) acc[g] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], b[g], acc[g], 0, 0, 0);
+    }
+    // C/D: register i of lane (r, h) is query 4 h + i against row r of the group
+    float my_qs[4], my_qa[4];
+    long long my_dst[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      my_qs[i] = qs[4 * h + i];
+      my_qa[i] = qa[4 * h + i];
+      my_dst[i] = dst[4 * h + i];
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const int row = wrow0 + 16 * g + r;  // this lane's row of the list
+      if (row >= len) continue;
+      const int32_t id = ids[wave * (16 * G) + 16 * g + r];
+      const float sx = scales[id];
+      const float bx = __fmul_rn(__fmul_rn(sx, sx), (float)norms[id]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (4 * h + i < nq) scores[my_dst[i] + row] = sq8_score<METRIC>(my_qs[i], my_qa[i], sx, bx, acc[g][i]);
+    }
+  }
+}
+
+struct ListsFetchSq8Args {
+  const float* cand_scores;   // [n_q][n_in]: the slabs' lists at width fetch, end to end
+  const int32_t* cand_rows;   // positions in the concatenation
+  int n_in, fetch;
+  const ListsQuery* queries;
+  const int32_t* probes;      // the chunk's
+  int n_probe, n_lists;
+  const int64_t* list_splits;
+  const int32_t* list_rows;
+  long long n_items;
+  int32_t* fpos;              // workspace [n_q, fetch]: the fetch lists, TopKV2 order
+  float* fscores;
+  int32_t* spos;              // workspace [n_q, fetch]: the fetched positions ascending (behind them: 0),
+  int32_t* rows;              // and their rows (behind them: row 0): the candidate lists,
+  long long* splits;          // and their row_splits i64[n_q + 1]
+  int32_t* out_fetch_pos;     // the chunk's rows of the caller's arrays, or null
+  float* out_fetch_scores;
+};
+
+__global__ __launch_bounds__(kNT) void k_lists_fetch_sq8(ListsFetchSq8Args a) {
+  __shared__ __attribute__((aligned(16))) unsigned char scratch[sizeof(TopkScratch)];
+  __shared__ long long sbegin[kListsMaxProbe];
+  __shared__ int32_t soff[kListsMaxProbe];
+  __shared__ int32_t v[kMaxK];
+  const size_t qi = blockIdx.x, base = qi * (size_t)a.fetch;
+  const int tid = threadIdx.x;
+  const ListsQuery Q = a.queries[qi];
+  const int ff = Q.status != 0 ? 0 : min(a.fetch, Q.len);
+  lists_slot_offsets(a.probes, qi, a.n_probe, a.n_lists, a.list_splits, sbegin, soff);
+  __syncthreads();
+  if (ff > 0) {
+    wg_topk(a.cand_rows + qi * a.n_in, a.cand_scores + qi * a.n_in, nullptr, a.n_in, ff, nullptr, a.fpos + base, a.fscores + base,
+            nullptr, nullptr, scratch);
+    __syncthreads();
+  }
+  int n2 = 1;
+  while (n2 < a.fetch) n2 <<= 1;
+  for (int i = tid; i < n2; i += kNT) {
+    const int32_t pos = i < ff ? a.fpos[base + i] : 0x7fffffff;
+    v[i] = pos;
+    if (i < a.fetch) {
+      if (a.out_fetch_pos) a.out_fetch_pos[base + i] = i < ff ? pos : 0;
+      if (a.out_fetch_scores) a.out_fetch_scores[base + i] = i < ff ? a.fscores[base + i] : -__builtin_inff();
+    }
+  }
+  sq8_sort_i32<kNT>(v, n2);
+  for (int i = tid; i < a.fetch; i += kNT) {
+    int32_t pos = 0, row = 0;
+    if (i < ff) {
+      pos = v[i];
+      row = lists_row_at(pos, Q.len, a.n_probe, sbegin, soff, a.list_rows);
+      if (row < 0 || row >= a.n_items) row = 0;
+    }
+    a.spos[base + i] = pos;
+    a.rows[base + i] = row;
+  }
+  if (tid == 0) {  // (neighbours write the same value to the split they share)
+    a.splits[qi] = (long long)base;
+    a.splits[qi + 1] = (long long)(base + a.fetch);
+  }
+}
+
+struct ListsFinishSq8Args {
+  const float* exact;         // the candidate-list scorer's buffer: query qi's list at [qi * fetch, +fetch), position order
+  const int32_t* spos;        // [n_q, fetch]
+  const int32_t* rows;
+  int fetch, k;
+  const ListsQuery* queries;
+  const int64_t* item_ids;
+  int32_t* sel;               // workspace i32[n_q, k]
+  int64_t* out_item_ids;      // the chunk's rows of the outputs
+  float* out_scores;
+  int32_t* out_index;
+  int32_t* out_pos;
+  int32_t* n_out;
+  int32_t* status;
+};
+
+__global__ __launch_bounds__(kNT) void k_lists_finish_sq8(ListsFinishSq8Args a) {
+  __shared__ __attribute__((aligned(16))) unsigned char scratch[sizeof(TopkScratch)];
+  const size_t qi = blockIdx.x, base = qi * (size_t)a.fetch;
+  const int tid = threadIdx.x;
+  const ListsQuery Q = a.queries[qi];
+  const int ff = Q.status != 0 ? 0 : min(a.fetch, Q.len), kk = min(a.k, ff);
+  if (kk > 0) {  // (a place in the sorted list is a rank among the fetched positions: ties -> the lower position)
+    wg_topk(nullptr, a.exact + base, nullptr, ff, kk, a.sel + qi * a.k, nullptr, a.out_scores ? a.out_scores + qi * a.k : nullptr,
+            nullptr, nullptr, scratch);
+    __syncthreads();
+  }
+  for (int i = tid; i < a.k; i += kNT) {
+    const size_t at = qi * (size_t)a.k + i;
+    int32_t pos = 0, row = 0;
+    int64_t id = 0;
+    if (i < kk) {
+      const int32_t j = a.sel[at];
+      pos = a.spos[base + j];
+      row = a.rows[base + j];
       id = a.item_ids[row];
     } else if (a.out_scores) {
       a.out_scores[at] = 0.0f;

@@ -381,6 +381,27 @@ __global__ __launch_bounds__(kSq8NT) void k_scan_sq8(const int8_t* __restrict__ 
   });
 }
 
+// v[0, n2) in LDS, n2 a power of two, into ascending order by the NT threads of the workgroup: a bitonic sort between two barriers
+template <int NT>
+__device__ __forceinline__ void sq8_sort_i32(int32_t* v, int n2) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  for (int size = 2; size <= n2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < (n2 >> 1); i += NT) {
+        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+        const bool up = (lo & size) == 0;
+        const int32_t x = v[lo], y = v[hi];
+        if ((x > y) == up) {
+          v[lo] = y;
+          v[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // one workgroup per query: the fetched rows (all distinct) in ascending order by a bitonic sort in LDS; thread 0 of every
 // workgroup writes its query's two row_splits (neighbours write the same value to the shared one); the fetch lists as the merge
 // left them go to the caller's arrays.
@@ -400,21 +421,7 @@ __global__ __launch_bounds__(kSq8NT) void k_sq8_sort_rows(const int32_t* __restr
       if (out_fetch_scores) out_fetch_scores[qi * fetch + i] = fscores[qi * fetch + i];
     }
   }
-  __syncthreads();
-  for (int size = 2; size <= n2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < (n2 >> 1); i += kSq8NT) {
-        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-        const bool up = (lo & size) == 0;
-        const int32_t x = v[lo], y = v[hi];
-        if ((x > y) == up) {
-          v[lo] = y;
-          v[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  sq8_sort_i32<kSq8NT>(v, n2);
   for (int i = tid; i < fetch; i += kSq8NT) sorted[qi * fetch + i] = v[i];
   if (tid == 0) {
     splits[qi] = (long long)qi * fetch;

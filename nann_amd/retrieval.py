@@ -1194,6 +1194,52 @@ def search_lists(index, partition, scorer, q, probes, k):
     return CandidateResult(out_ids, out_scores, out_index, out_pos, n_out, status, ws, (probes, partition))
 
 
+class ListsSq8Result(CandidateResult):
+    """Outputs of search_lists_sq8: a CandidateResult, and with return_fetch the approximate stage's lists -- fetch_pos i32[B, fetch]
+    (positions in the query's concatenation) and fetch_scores f32[B, fetch] (approximate), best first, min(fetch, len_b) valid
+    entries at the head of row b and position 0 / -inf behind -- else None."""
+    __slots__ = ("fetch_pos", "fetch_scores", "fetch")
+
+    def __init__(self, *result, fetch_pos=None, fetch_scores=None, fetch=0):
+        super().__init__(*result)
+        self.fetch_pos, self.fetch_scores, self.fetch = fetch_pos, fetch_scores, fetch
+
+
+def search_lists_sq8(index, partition, sq8, scorer, q, probes, k, fetch=None, return_fetch=False):
+    """IVF-SQ8 (nann_search_lists_sq8): search_lists over the int8 code table sq8 = make_sq8(index).  The lists a query names are
+    scanned on the integer matrix cores, the `fetch` best positions of their concatenation by approximate score are re-ranked by
+    the EXACT score, top k of those -> ListsSq8Result, a CandidateResult whose scores are search_lists' bits for the rows
+    returned; where fetch covers a query's whole concatenation the result IS search_lists'.  fetch=None means min(4 * k, 1024):
+    a convenience default, NOT a tuned one (tools/lists_sq8_rate.py measures recall against search_lists).  k <= fetch <= 1024;
+    f16 / bf16 rows, an L2 or inner-product ops.Scorer.  Asynchronous on torch's current stream."""
+    dev = index.device
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    b, k = q.shape[0], int(k)
+    fetch = min(4 * k, 1024) if fetch is None else int(fetch)
+    probes = torch.as_tensor(probes).to(device=dev, dtype=torch.int32).reshape(b, -1).contiguous()
+    n_probe = int(probes.shape[1])
+    kk, ff = max(k, 0), max(fetch, 0)
+    out_ids = torch.zeros((b, kk), dtype=torch.int64, device=dev)
+    out_scores = torch.zeros((b, kk), dtype=torch.float32, device=dev)
+    out_index = torch.zeros((b, kk), dtype=torch.int32, device=dev)
+    out_pos = torch.zeros((b, kk), dtype=torch.int32, device=dev)
+    n_out = torch.zeros(b, dtype=torch.int32, device=dev)
+    status = torch.zeros(b, dtype=torch.int32, device=dev)
+    f_pos = torch.zeros((b, ff), dtype=torch.int32, device=dev) if return_fetch else None
+    f_scores = torch.full((b, ff), float("-inf"), dtype=torch.float32, device=dev) if return_fetch else None
+    head = (index.handle, partition.handle, sq8.handle, scorer.handle)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_search_lists_sq8_workspace_bytes(*head, b, n_probe, fetch, k, C.byref(nbytes)), "search_lists_sq8")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_search_lists_sq8(*head, _ptr(q), b, _ptr(probes) if probes.numel() else None, n_probe, fetch, k,
+                                           _ptr(out_ids), _ptr(out_scores), _ptr(out_index), _ptr(out_pos), _ptr(n_out), _ptr(status),
+                                           _ptr(f_pos) if return_fetch else None, _ptr(f_scores) if return_fetch else None,
+                                           _ptr(ws), ws.numel(), _stream()), "search_lists_sq8")
+    return ListsSq8Result(out_ids, out_scores, out_index, out_pos, n_out, status, ws, (probes, partition, sq8),
+                          fetch_pos=f_pos, fetch_scores=f_scores, fetch=fetch)
+
+
 def train_partition(index, n_lists, iters=10, seed=0):
     """A coarse (IVF) partition of `index`: Lloyd's k-means on its rows, plain torch on the device -- plumbing around
     make_partition, not a hot path.  Returns (partition, centroids f32[n_lists, d]); every row is in the list of its nearest centroid (L2)."""
@@ -1218,15 +1264,18 @@ def _nearest_centroid(x, cent, block=65536):
     return out
 
 
-def search_partitioned(index, partition, centroids, scorer, q, k, n_probe):
+def search_partitioned(index, partition, centroids, scorer, q, k, n_probe, sq8=None, fetch=None):
     """IVF search in one line: rank the centroids for every query in plain torch (by L2 distance, or by inner product under an
-    inner-product scorer), probe the n_probe best lists with search_lists -> CandidateResult."""
+    inner-product scorer), probe the n_probe best lists with search_lists -> CandidateResult.  With sq8 = make_sq8(index) the
+    lists are probed over the int8 codes (search_lists_sq8 at `fetch`) -> ListsSq8Result."""
     qf = q.to(device=index.device, dtype=torch.float32)
     cent = centroids.to(device=index.device, dtype=torch.float32)
     sim = qf @ cent.T
     if getattr(scorer, "kind", "l2") != "ip":
         sim = 2.0 * sim - (cent * cent).sum(1)[None, :]
     probes = sim.topk(min(int(n_probe), cent.shape[0]), dim=1).indices.to(torch.int32)
+    if sq8 is not None:
+        return search_lists_sq8(index, partition, sq8, scorer, qf, probes, k, fetch=fetch)
     return search_lists(index, partition, scorer, qf, probes, k)
 
 

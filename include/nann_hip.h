@@ -878,6 +878,38 @@ int nann_search_lists_sq8(const nann_index* ix, const nann_partition* partition,
                           int32_t* status, int32_t* out_fetch_pos, float* out_fetch_scores, void* workspace,
                           int64_t workspace_bytes, nann_stream_t stream);
 
+/* ---- the coarse quantiser: nearest centroid of every row, and deterministic k-means ---------------------
+ * What makes the lists of an IVF partition, on the device: list_of_row for nann_partition_create, and the cell of a row
+ * appended later.  The reference has no such call.
+ * nann_kmeans_assign: rows [row_begin, row_begin + n_rows) of ix against centroids f32[n_lists, d] (device, row-major);
+ * out_list i32[n_rows] (device) gets the number of each row's nearest centroid by L2, ties -> the lower number; out_dist
+ * f32[n_rows] (device, may be NULL) the winner's |c|^2 - 2 <x, c> + |x|^2, each term as the kernel computed it (it can be a
+ * few ulps of |x|^2 below zero).  The rows are exact; a centroid enters <x, c> as the sum of two f16 (f16 rows) or three bf16
+ * (bf16 rows) terms on v_mfma_f32_32x32x16_{f16,bf16} with an f32 accumulator, |c|^2 and |x|^2 are f32 sums in element order:
+ * the assigned centroid is the nearest up to the bound of DESIGN.md 4.28, and exactly the nearest where every product and sum
+ * is exact in f32.  Centroids must be finite and, for f16 rows, within f16's range.  Nothing of size n_rows x n_lists is written.
+ * nann_kmeans_train: Lloyd's algorithm over all rows.  centroids f32[n_lists, d] (device) holds the seeds on entry and the
+ * result on return.  n_iter rounds of (assign, mean), then a final assign: out_list i32[n_items] and out_counts i32[n_lists]
+ * (device) are consistent with the centroids returned.  A mean is the f32 sum of the list's rows -- over segments of 1024 rows
+ * of the list in ascending row order, the segment sums added in segment order -- divided by the count in one f32 operation; a
+ * list that receives no row keeps its centroid.  out_inertia f64[n_iter + 1] (device, may be NULL): entry i is the sum of
+ * out_dist after the i-th assign, in f64 and in a fixed order.  No float atomics anywhere: the same call on the same inputs
+ * returns the same bits every time.
+ * f16 and bf16 rows, d in {64, 128, 256, 512}, 1 <= n_lists <= min(n_items, NANN_KMEANS_MAX_LISTS), n_iter >= 0.
+ * Workspace: device, 256-byte aligned, *_workspace_bytes(...) bytes: the split centroids (4 or 6 bytes an element) and, for
+ * training, 8 bytes a row, the counts of the CSR build and d floats per 1024 rows and per list.
+ * Refusals, in this order: a null pointer, n_lists < 1, n_iter < 0 -> NANN_ERR_BAD_ARGUMENT (no device needed); f32 rows
+ * ("16-bit rows (f16, bf16) only"), another d, n_lists > NANN_KMEANS_MAX_LISTS -> NANN_ERR_UNSUPPORTED; n_lists > n_items, a
+ * row range outside the index -> NANN_ERR_BAD_ARGUMENT; n_rows == 0 -> NANN_OK, nothing written; then the workspace.
+ * Asynchronous on `stream`, no host read-back, re-entrant on a shared index. */
+#define NANN_KMEANS_MAX_LISTS 65536
+int nann_kmeans_assign_workspace_bytes(const nann_index* ix, int32_t n_lists, int64_t n_rows, int64_t* nbytes);
+int nann_kmeans_assign(const nann_index* ix, const float* centroids, int32_t n_lists, int64_t row_begin, int64_t n_rows,
+                       int32_t* out_list, float* out_dist, void* workspace, int64_t workspace_bytes, nann_stream_t stream);
+int nann_kmeans_train_workspace_bytes(const nann_index* ix, int32_t n_lists, int64_t* nbytes);
+int nann_kmeans_train(const nann_index* ix, float* centroids, int32_t n_lists, int32_t n_iter, int32_t* out_list,
+                      int32_t* out_counts, double* out_inertia, void* workspace, int64_t workspace_bytes, nann_stream_t stream);
+
 /* ---- candidate-list search under a model: nann_search_candidates for whatever model the node names ---------------------
  * nann_search_candidates with the serving signature's input, as nann_search_all_model is to nann_search_all: comm_seq_f16 is
  * f16[n_users, seq_len, E] (what nann_search_model_opt and nann_search_all_model take), `cand` the same nann_candidates with

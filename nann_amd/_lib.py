@@ -91,6 +91,7 @@ SYMBOLS = [
     "nann_partition_create", "nann_partition_destroy", "nann_partition_info", "nann_partition_view",
     "nann_search_lists_workspace_bytes", "nann_search_lists",
     "nann_search_lists_sq8_workspace_bytes", "nann_search_lists_sq8",
+    "nann_kmeans_assign_workspace_bytes", "nann_kmeans_assign", "nann_kmeans_train_workspace_bytes", "nann_kmeans_train",
 ]
 
 
@@ -432,6 +433,16 @@ def lib():
         L.nann_search_lists_sq8.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 9 + \
                                            [C.c_int64, C.c_void_p]
         L.nann_search_lists_sq8.restype = C.c_int
+        # (ix, n_lists, n_rows, *nbytes) / (ix, centroids, n_lists, row_begin, n_rows, out_list, out_dist, workspace, bytes, stream) /
+        # (ix, n_lists, *nbytes) / (ix, centroids, n_lists, n_iter, out_list, out_counts, out_inertia, workspace, bytes, stream)
+        L.nann_kmeans_assign_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
+        L.nann_kmeans_assign_workspace_bytes.restype = C.c_int
+        L.nann_kmeans_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]
+        L.nann_kmeans_assign.restype = C.c_int
+        L.nann_kmeans_train_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
+        L.nann_kmeans_train_workspace_bytes.restype = C.c_int
+        L.nann_kmeans_train.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]
+        L.nann_kmeans_train.restype = C.c_int
         L.nann_sq8_encode.argtypes = [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 4
         L.nann_sq8_encode.restype = C.c_int
         L.nann_search_all_sq8_workspace_bytes.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]

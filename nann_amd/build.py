@@ -19,7 +19,8 @@ LIB = os.path.join(OUT_DIR, "libnann_hip.so")
 #                      longest to build)
 #   nann_eval*.o       the evaluation traversal: slot form and attention model; LDS form; LDS form in windows.  These three
 #                      bound a build from scratch
-#   nann_mlp_d*.o      the MLP traversal per embedding dim; the resident-layer-2 kernels ride with d = 64
+#   nann_mlp_d*.o      the MLP traversal per embedding dim; the resident-layer-2 kernels ride with d = 64, the coarse quantiser
+#                      (nann_kmeans.h, nann_kmeans_inst.hip: seconds to compile) with d = 256, the quickest of the three
 #   nann_attn.o, nann_attn_split.o   the attention model, f32 and split-f16 form
 #   nann_scan.o        the exhaustive search, with the range and wide selections (nann_range.h, nann_wide.h) and the int8 code table, scan and
 #                      streamed and certified survivor passes (nann_sq8.h, nann_sq8_inst.hip), and the shared-list search, whose scans are
@@ -43,7 +44,7 @@ UNITS = [("nann_core.o", [("nann_ops.hip", {}), ("nann_hip.hip", {}), ("nann_sco
          ("nann_l2_f32.o", [("nann_l2_inst.hip", {"NANN_L2_DT": "2", "NANN_L2_NAME": "f32"})]),
          ("nann_mlp_d64_res.o", [("nann_mlp_inst.hip", {"NANN_MLP_D": "64"}), ("nann_mlp_res_inst.hip", {})]),
          ("nann_mlp_d128.o", [("nann_mlp_inst.hip", {"NANN_MLP_D": "128"}), _lean("NANN_SCORER_L2", "2", "l2_f32")]),
-         ("nann_mlp_d256.o", [("nann_mlp_inst.hip", {"NANN_MLP_D": "256"})]),
+         ("nann_mlp_d256.o", [("nann_mlp_inst.hip", {"NANN_MLP_D": "256"}), ("nann_kmeans_inst.hip", {})]),
          ("nann_attn.o", [("nann_attn_inst.hip", {})]),
          ("nann_attn_split.o", [("nann_attn_split_inst.hip", {}), _lean("kScorerIp", "2", "ip_f32")]),
          ("nann_eval.o", [("nann_eval_inst.hip", {})]),
@@ -174,6 +175,9 @@ RULES = [
     # The int8 list scan (k_lists_scan_sq8, nann_lists.h) keeps the A fragments of a tile's 16 queries, d / 16 registers, from the
     # head of a work item to its end; spilled, every MFMA of the item would wait for a reload from private memory.
     ("lists_scan_sq8_scratch", r"k_lists_scan_sq8", 0, None, "the int8 list scan kernel"),
+    # The nearest-centroid sweep (k_kmeans_assign, nann_kmeans.h) keeps the A fragments of a wavefront's rows, up to 128 registers,
+    # from its first centroid tile to its last; spilled, every MFMA of the sweep would wait for a reload from private memory.
+    ("kmeans_assign_scratch", r"k_kmeans_assign", 0, None, "the nearest-centroid kernel"),
 ]
 
 

@@ -15,7 +15,8 @@
 // the certified range form that returns nann_search_all_range's (nann_search_all_range_sq8_exact), and both without a score buffer
 // (nann_search_all_sq8_stream_exact, nann_search_all_range_sq8_stream_exact); the row lists over an index
 // (nann_partition_create, ..) and the shared-list search over them (nann_search_lists; kernels in nann_lists.h), also over the
-// code table with an exact re-rank (nann_search_lists_sq8).
+// code table with an exact re-rank (nann_search_lists_sq8); the coarse quantiser that makes such lists (nann_kmeans_assign,
+// nann_kmeans_train; kernels in nann_kmeans.h).
 //
 // A source of nann_core.o.  What it takes from the other host sources, and what the traversal's forms (nann_traverse.hip) take
 // from it -- resolve_filter, resolve_predicates, resolve_groups, resolve_diversity, mmr_index, union_check, fuse_shape_check,
@@ -41,6 +42,7 @@
 #include "nann_scan.h"
 #include "nann_cand.h"
 #include "nann_lists.h"
+#include "nann_kmeans.h"
 #include "nann_union.h"
 #include "nann_fuse.h"
 #include "nann_groupcap.h"
@@ -1862,6 +1864,74 @@ int nann_search_lists_sq8(const nann_index* ix, const nann_partition* partition,
   return flat_lists_sq8(ix, partition, t, scorer, q, n_queries, probes, n_probe, fetch, k, out_item_ids, out_scores, out_index,
                         out_pos, n_out, status, out_fetch_pos, out_fetch_scores, workspace, workspace_bytes, stream,
                         "nann_search_lists_sq8");
+}
+
+// ---- the coarse quantiser (nann_kmeans.h): nearest centroid of every row, and Lloyd rounds around it ------------------------
+// What needs no device comes first: the null pointers, n_lists < 1, n_iter < 0; then the index against the kernels' limits.
+static int flat_kmeans_check(const nann_index* ix, int32_t n_lists, int32_t n_iter, const char* who, KmeansArgs* a) {
+  if (n_lists < 1) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_lists < 1");
+  if (n_iter < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_iter < 0");
+  const int dt = ix->desc.emb_dtype, d = ix->desc.d;
+  if (dt != NANN_F16 && dt != NANN_BF16) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": 16-bit rows (f16, bf16) only");
+  if (d != 64 && d != 128 && d != 256 && d != 512) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": d must be 64, 128, 256 or 512");
+  if (n_lists > kKmeansMaxLists) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": n_lists <= " + std::to_string(kKmeansMaxLists));
+  if (n_lists > ix->desc.n_items) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": more lists than the index has rows");
+  if (ix->desc.n_items > 0x7fffffffll) return fail(NANN_ERR_UNSUPPORTED, std::string(who) + ": row numbers are 32-bit");
+  a->emb = ix->desc.item_embs;
+  a->n_items = (long long)ix->desc.n_items;
+  a->d = d;
+  a->dt = dt;
+  a->n_lists = n_lists;
+  return NANN_OK;
+}
+
+int nann_kmeans_assign_workspace_bytes(const nann_index* ix, int32_t n_lists, int64_t n_rows, int64_t* nbytes) {
+  const char* who = "nann_kmeans_assign_workspace_bytes";
+  if (!ix || !nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  KmeansArgs a;
+  const int rc = flat_kmeans_check(ix, n_lists, 0, who, &a);
+  if (rc) return rc;
+  if (n_rows < 0) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": n_rows < 0");
+  *nbytes = n_rows == 0 ? 0 : (int64_t)kmeans_layout(a.d, a.dt, n_lists).total;
+  return NANN_OK;
+}
+int nann_kmeans_assign(const nann_index* ix, const float* centroids, int32_t n_lists, int64_t row_begin, int64_t n_rows,
+                       int32_t* out_list, float* out_dist, void* workspace, int64_t workspace_bytes, nann_stream_t stream) {
+  const char* who = "nann_kmeans_assign";
+  if (!ix || !centroids || !out_list) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  KmeansArgs a;
+  int rc = flat_kmeans_check(ix, n_lists, 0, who, &a);
+  if (rc) return rc;
+  if (row_begin < 0 || n_rows < 0 || row_begin > ix->desc.n_items - n_rows)
+    return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": [row_begin, row_begin + n_rows) must lie within the index");
+  if (n_rows == 0) return NANN_OK;
+  const KmeansLayout L = kmeans_layout(a.d, a.dt, n_lists);
+  rc = flat_workspace(workspace, workspace_bytes, L.total, who, "");
+  if (rc) return rc;
+  return launch_kmeans_assign(a, L, centroids, (long long)row_begin, (long long)n_rows, out_list, out_dist,
+                              static_cast<unsigned char*>(workspace), as_stream(stream));
+}
+int nann_kmeans_train_workspace_bytes(const nann_index* ix, int32_t n_lists, int64_t* nbytes) {
+  const char* who = "nann_kmeans_train_workspace_bytes";
+  if (!ix || !nbytes) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  KmeansArgs a;
+  const int rc = flat_kmeans_check(ix, n_lists, 0, who, &a);
+  if (rc) return rc;
+  *nbytes = (int64_t)kmeans_train_layout(a.n_items, a.d, a.dt, n_lists).total;
+  return NANN_OK;
+}
+int nann_kmeans_train(const nann_index* ix, float* centroids, int32_t n_lists, int32_t n_iter, int32_t* out_list,
+                      int32_t* out_counts, double* out_inertia, void* workspace, int64_t workspace_bytes, nann_stream_t stream) {
+  const char* who = "nann_kmeans_train";
+  if (!ix || !centroids || !out_list || !out_counts) return fail(NANN_ERR_BAD_ARGUMENT, std::string(who) + ": null argument");
+  KmeansArgs a;
+  int rc = flat_kmeans_check(ix, n_lists, n_iter, who, &a);
+  if (rc) return rc;
+  const KmeansTrainLayout L = kmeans_train_layout(a.n_items, a.d, a.dt, n_lists);
+  rc = flat_workspace(workspace, workspace_bytes, L.total, who, "");
+  if (rc) return rc;
+  return launch_kmeans_train(a, L, centroids, n_iter, out_list, out_counts, out_inertia, static_cast<unsigned char*>(workspace),
+                             as_stream(stream));
 }
 
 // ---- the int8 code table and the search over it (nann_sq8.h) ---------------------------------------------------------------

@@ -1240,9 +1240,19 @@ def search_lists_sq8(index, partition, sq8, scorer, q, probes, k, fetch=None, re
                           fetch_pos=f_pos, fetch_scores=f_scores, fetch=fetch)
 
 
-def train_partition(index, n_lists, iters=10, seed=0):
-    """A coarse (IVF) partition of `index`: Lloyd's k-means on its rows, plain torch on the device -- plumbing around
-    make_partition, not a hot path.  Returns (partition, centroids f32[n_lists, d]); every row is in the list of its nearest centroid (L2)."""
+def train_partition(index, n_lists, iters=10, seed=0, method="torch"):
+    """A coarse (IVF) partition of `index`: Lloyd's k-means on its rows, seeded with n_lists rows drawn by a seeded randperm.
+    method="torch": plain torch on the device -- plumbing around make_partition, not a hot path.  method="device": the same seeds
+    and the same schedule through nann_kmeans_train -- nearest centroids on the matrix cores, deterministic means; f16 / bf16
+    rows.  Returns (partition, centroids f32[n_lists, d]); every row is in the list of its nearest centroid (L2)."""
+    if method not in ("torch", "device"):
+        raise ValueError("train_partition: method must be 'torch' or 'device'")
+    if method == "device":
+        g = torch.Generator(device="cpu").manual_seed(int(seed))
+        seeds = torch.randperm(index.n_items, generator=g)[:n_lists].to(index.device)  # (the torch path's draw, below)
+        cent = index.item_embs[seeds].to(torch.float32).contiguous()
+        assign, _, _ = kmeans_train(index, cent, max(int(iters), 1))
+        return make_partition(index, assign, n_lists), cent
     x = index.item_embs.to(torch.float32)
     g = torch.Generator(device="cpu").manual_seed(int(seed))
     cent = x[torch.randperm(x.shape[0], generator=g)[:n_lists].to(x.device)].clone()
@@ -1254,6 +1264,47 @@ def train_partition(index, n_lists, iters=10, seed=0):
         cent = torch.where(cnt[:, None] > 0, sums / cnt.clamp(min=1)[:, None], cent)
     assign = _nearest_centroid(x, cent)
     return make_partition(index, assign.to(torch.int32), n_lists), cent
+
+
+def kmeans_assign(index, centroids, rows=None):
+    """The nearest of centroids f32[n_lists, d] by L2 for rows [rows[0], rows[1]) of `index` (None: every row), on the matrix
+    cores (nann_kmeans_assign) -> (list i32[n_rows], dist f32[n_rows]); ties go to the lower centroid number.  The cell of rows
+    appended to a live index: kmeans_assign(index, centroids, (n_before, index.n_items)).  Asynchronous on torch's current stream."""
+    dev = index.device
+    cent = centroids.to(device=dev, dtype=torch.float32).contiguous()
+    begin, end = (0, index.n_items) if rows is None else (int(rows[0]), int(rows[1]))
+    n = max(end - begin, 0)
+    out_list = torch.zeros(n, dtype=torch.int32, device=dev)
+    out_dist = torch.zeros(n, dtype=torch.float32, device=dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_kmeans_assign_workspace_bytes(index.handle, int(cent.shape[0]), end - begin, C.byref(nbytes)), "kmeans_assign")
+    if n == 0:
+        return out_list, out_dist
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_kmeans_assign(index.handle, _ptr(cent), int(cent.shape[0]), begin, end - begin, _ptr(out_list), _ptr(out_dist),
+                                        _ptr(ws), ws.numel(), _stream()), "kmeans_assign")
+    return out_list, out_dist
+
+
+def kmeans_train(index, centroids, n_iter):
+    """Lloyd's k-means over every row of `index` on the device (nann_kmeans_train): centroids f32[n_lists, d], a contiguous
+    device tensor, holds the seeds and is UPDATED IN PLACE by n_iter rounds of (assign, mean); a list that receives no row
+    keeps its centroid -> (list i32[n_items], counts i32[n_lists], inertia f64[n_iter + 1]), the final assignment under the
+    centroids returned and the sum of squared distances after every assign.  Deterministic: the same inputs give the same bits."""
+    dev = index.device
+    assert centroids.dtype == torch.float32 and centroids.is_contiguous() and centroids.device == dev, "centroids: contiguous f32 on the index's device"
+    n_lists, n_iter = int(centroids.shape[0]), int(n_iter)
+    out_list = torch.zeros(index.n_items, dtype=torch.int32, device=dev)
+    counts = torch.zeros(n_lists, dtype=torch.int32, device=dev)
+    inertia = torch.zeros(max(n_iter, 0) + 1, dtype=torch.float64, device=dev)
+    nbytes = C.c_int64(0)
+    _check(lib().nann_kmeans_train_workspace_bytes(index.handle, n_lists, C.byref(nbytes)), "kmeans_train")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nann_kmeans_train(index.handle, _ptr(centroids), n_lists, n_iter, _ptr(out_list), _ptr(counts), _ptr(inertia),
+                                       _ptr(ws), ws.numel(), _stream()), "kmeans_train")
+    return out_list, counts, inertia
 
 
 def _nearest_centroid(x, cent, block=65536):
